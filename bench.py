@@ -5,7 +5,7 @@ Workload (BASELINE config 2): 4096x4096 synthetic stereo pair, 7x7 SAD, +-64 px 
 (search_volume 129x1), one call of vw::stereo::calc_disparity per step, inputs (float32 PixelGray images)
 already resident in HBM, output (PixelMask<Vector2i>, 12 B/px) left in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   N > 1: one rank per GPU.  Either launched by torch.distributed.run (RANK / WORLD_SIZE in the environment), or typed as
   above: bench.py then re-executes itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
   --master-addr 127.0.0.1 --master-port <free port>`.  The pair is split into N row strips (output rows
@@ -38,7 +38,7 @@ sys.path.insert(0, ROOT)
 W = H = 4096
 KERNEL = (7, 7)
 SEARCH = (129, 1)
-HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0          # MI355X: HBM3E 8.0 TB/s spec
 FCLK_HZ = 2.4e9                # max shader clock
 LANES = 256 * 4 * 16           # CUs x SIMDs x lanes/clk of an ordinary VOP3 op (profiles/r01_ubench_valu.txt)
 
@@ -835,10 +835,35 @@ def run_config5(args, torch, dist, vwa, core, stereo, synth, partition, rank, wo
         dist.destroy_process_group()
 
 
+DUMP_ROWS, DUMP_SEED = 512, 20261015      # --dump-outputs: a fixed, seeded sample of output rows (512 x 4090 x 3 float64 = 50 MB)
+
+
+def dump_outputs(torch, dist, dump_dir, out, oh, r0, r1, rank, world):
+    """`--dump-outputs DIR`: the result of the LAST timed step — calc_disparity's (rows, cols, 3) int32 {dx, dy, valid} image — as
+    DIR/disparity.npy, restricted to DUMP_ROWS output rows drawn with a fixed seed (DIR/disparity_rows.npy holds their indices).
+    float64 holds every int32 exactly.  Each rank contributes the sampled rows of its strip; rank 0 writes the files.  Returns the
+    file names (rank 0) or None."""
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(oh, size=min(DUMP_ROWS, oh), replace=False))
+    mine = rows[(rows >= r0) & (rows < r1)]
+    part = out[torch.from_numpy(mine - r0).to(out.device)].cpu().numpy().astype(np.float64)
+    parts = [part]
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, part)
+    if rank != 0:
+        return None
+    disp = np.concatenate(parts, axis=0)
+    assert disp.shape[0] == rows.shape[0]
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "disparity.npy"), disp)
+    np.save(os.path.join(dump_dir, "disparity_rows.npy"), rows.astype(np.float64))
+    return ["disparity.npy", "disparity_rows.npy"]
+
+
 def measure_traffic():
     """HBM bytes per launch of the headline kernel from the PMC counters, measured NOW: two rocprofv3 passes of this very command (short:
     8 steps, no CPU leg, no extras), one per counter — FETCH_SIZE and WRITE_SIZE do not fit one pass — read back from the rocpd database.
-    gfx950 correction of /opt/skills/guides/MI355X_MICROARCH.md (HBM section): FETCH_SIZE counts the 128-byte requests of wide
+    gfx950 correction (HBM counters): FETCH_SIZE counts the 128-byte requests of wide
     coalesced reads at 64 bytes -> x2; WRITE_SIZE as is; both in KiB.  Returns (bytes per launch or None, how it was obtained)."""
     import glob
     import shutil
@@ -938,7 +963,14 @@ def main():
                          "written (SGM.cc:1651-1738; unreachable upstream, explicit opt-in here)")
     ap.add_argument("--workload", default="config2", choices=["config2", "config4", "config5"],
                     help="config2 (default, the headline metric): 4096^2 7x7 SAD; config4: 16384^2 census SGM in 8 strips + collar")
+    ap.add_argument("--dump-outputs", default=None, dest="dump_outputs", metavar="DIR",
+                    help="config2 only: after the timed steps, write what the last step computed to DIR/*.npy (a fixed, seeded sample of "
+                         "%d output rows, float64; see dump_outputs)" % DUMP_ROWS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "config2":
+        ap.error("--dump-outputs covers the headline workload (config2) only")
 
     maybe_self_launch(args.gpus)              # `python bench.py --gpus N` as typed: re-executes under torch.distributed.run (never returns)
     # the host driver supports dmabuf IPC only: without this RCCL's peer mappings fail (hipIpcGetMemHandle: invalid argument)
@@ -1078,6 +1110,7 @@ def main():
     assert got.shape == (8, 64, 3) and (got[..., 0] >= 0).all() and (got[..., 0] < sx).all()
     assert ctx.last_path() == path, "the kernel family changed during the timed region"
     ctx.set_option(core.OPT_DEFER_EXACTNESS, 0)
+    dumped = dump_outputs(torch, dist, args.dump_outputs, out, oh, r0, r1, rank, world) if args.dump_outputs else None
 
     if rank == 0:
         per_kernel = {}
@@ -1136,6 +1169,8 @@ def main():
                                  "step since round 4 (validity sweep folded into the matcher); avg_us_per_launch comes from HIP events around the "
                                  "kernel on every 4th step, whose two event records cost ~1.5 us that the other steps do not pay"},
         }
+        if dumped:
+            res["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped, "rows_sampled": DUMP_ROWS, "seed": DUMP_SEED}
         if not args.no_cpu_baseline:
             # rank 0, for every N: the same leg (the other ranks wait at the final barrier)
             res["cpu_baseline"] = cpu_baseline(left, right)

@@ -1,7 +1,7 @@
 // vw_sgm_oracle.cc — CPU restatement of the reference's semi-global matching path.  TEST INFRASTRUCTURE ONLY: loaded by
 // tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg, never by the product.
 //
-// Follows, function by function (all paths relative to /root/reference):
+// Follows, function by function (all paths relative to the Vision Workbench source tree):
 //   u8_convert                          src/vw/Image/ImageThresh.h:275-286 (+ find_image_min_max Statistics.h:114-127,
 //                                       ChannelNormalizeFunctor Algorithms.h:105-126)
 //   get_census_value_* / ternary        src/vw/Image/CensusTransform.h:64-340

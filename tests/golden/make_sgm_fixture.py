@@ -1,18 +1,16 @@
 """Generates tests/golden/sgm_fixture.npz from the reference's own SGM test images
 (src/vw/Stereo/tests/left.tif, left_const_offset.tif — uncompressed 8-bit strip TIFFs read with the 40-line parser
-below).  Run in the build container, where /root/reference exists; the GPU box only sees the committed .npz.
+below).  Needs a Vision Workbench source tree; the tests only read the committed .npz.
 
-    python tests/golden/make_sgm_fixture.py
+    python tests/golden/make_sgm_fixture.py <vision workbench source tree>
 
 Stored: the crops TestSGM.cxx:33-45 takes — left = [0,400)^2, right = rightRoi = [-4, 405)^2 with the out-of-image
 border (4 px at the top/left) zero-filled."""
 import os
 import struct
+import sys
 
 import numpy as np
-
-REF = "/root/reference/src/vw/Stereo/tests"
-
 
 def read_tiff_u8(path):
     d = open(path, "rb").read()
@@ -41,8 +39,11 @@ def read_tiff_u8(path):
 
 
 def main():
-    left = read_tiff_u8(os.path.join(REF, "left.tif"))
-    right = read_tiff_u8(os.path.join(REF, "left_const_offset.tif"))
+    if len(sys.argv) != 2:
+        sys.exit("usage: python tests/golden/make_sgm_fixture.py <vision workbench source tree>")
+    ref = os.path.join(sys.argv[1], "src", "vw", "Stereo", "tests")
+    left = read_tiff_u8(os.path.join(ref, "left.tif"))
+    right = read_tiff_u8(os.path.join(ref, "left_const_offset.tif"))
     l = left[:400, :400]
     r = np.zeros((409, 409), np.uint8)
     r[4:, 4:] = right[:405, :405]

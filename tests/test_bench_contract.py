@@ -119,3 +119,31 @@ def test_oracle_is_only_the_checker_in_bench():
     # every mention sits in the docstrings / the cpu_baseline leg, none in the timed step
     step = src[src.index("def step():"):src.index("def barrier():")]
     assert "oracle" not in step
+
+
+def test_dump_outputs_is_a_fixed_sample_of_the_last_step(tmp_path):
+    """bench.py --dump-outputs: the seeded row sample of the (4090, 4090, 3) int32 result as float64 — exact, the same rows in every
+    run, under 64 MB in all."""
+    import numpy as np
+    import torch
+    import bench
+    oh = ow = 4090
+    out = torch.arange(oh, dtype=torch.int32)[:, None, None].expand(oh, ow, 3).contiguous()
+    out[..., 2] = np.iinfo(np.int32).max
+    files = bench.dump_outputs(torch, None, str(tmp_path / "a"), out, oh, 0, oh, 0, 1)
+    bench.dump_outputs(torch, None, str(tmp_path / "b"), out, oh, 0, oh, 0, 1)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    d, rows = np.load(tmp_path / "a" / "disparity.npy"), np.load(tmp_path / "a" / "disparity_rows.npy")
+    assert d.dtype == np.float64 and rows.dtype == np.float64 and d.shape == (bench.DUMP_ROWS, ow, 3)
+    assert (np.diff(rows) > 0).all() and rows[0] >= 0 and rows[-1] < oh
+    assert (d[:, :, 0] == rows[:, None]).all() and (d[:, :, 2] == np.iinfo(np.int32).max).all()
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "disparity_rows.npy"))
+    assert np.array_equal(d, np.load(tmp_path / "b" / "disparity.npy"))
+
+
+def test_dump_outputs_refused_outside_the_headline_workload():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "config4", "--dump-outputs", "x"], capture_output=True,
+                       text=True, timeout=300)
+    assert p.returncode == 2 and "config2" in p.stderr
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and "--steps" in p.stderr

@@ -48,6 +48,7 @@
 //
 // Limits (else the generic path): SAD only; kernel sizes in kLaunch; 4*ceil(kx/4)*ky*255 < 65536;
 // sx*sy <= 65535; LDS footprint <= 80 KiB.
+#include <climits>
 #include <cstdlib>
 #include <type_traits>
 
@@ -152,7 +153,7 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
                  const float* __restrict__ R, ptrdiff_t rs, int rcw, int rch,
                  int sx, int sy, int ne, int32_t* __restrict__ out, ptrdiff_t os, int ow, int oh,
                  int* __restrict__ flag_set, int* __restrict__ flag_clear,
-                 int gxt, int ntiles) {
+                 int gxt, int ntiles, int last_round) {
   typedef Cfg<KX, KY, TY, WV> C;
   constexpr bool SPLIT = GR > 1;
   constexpr int NW = C::NW, EW = C::EW, NR = C::NR;
@@ -225,6 +226,13 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
   constexpr int NPROBE = 4;
   const u32 zero = 0;
 
+  // End balance (one-group grids of two rounds or more; `last_round` = first workgroup of the last round of dispatch, see the launcher).
+  // Each slot of a CU ends on a last-round workgroup, and oldest-first arbitration lets the older of the two finish tens of us before
+  // the younger, which then runs alone (one wave per SIMD issues at ~2/3 of the rate of two).  So earlier workgroups — whose remaining
+  // work includes a successor's — keep the top priority, and last-round workgroups take priority by the byte phases they have left:
+  // the one that started later catches up, and the two slots of a CU finish together.
+  const bool late = !SPLIT && (int)blockIdx.x >= last_round;
+  if (!SPLIT) { if (late) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3); }
   typedef std::true_type T;
   typedef std::false_type F;
 
@@ -238,6 +246,10 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
       for (int t = 0; t < 4; ++t) {
         const int a_last = (sx + 2 - t) >> 2;       // last step with any valid slot
         __syncthreads();                            // base staged / previous phase's readers done
+        if (!MAXSWEEP && !SPLIT && dy == 0 && late) {
+          if (t == 2) __builtin_amdgcn_s_setprio(1);
+          else if (t == 3) __builtin_amdgcn_s_setprio(0);
+        }
         {
           auto build = [&](int r, int m) __attribute__((always_inline)) {
             const u32* bp = base + (size_t)r * bpitch + m;
@@ -420,6 +432,7 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
     }
   };
   sweep(F{});
+  if (!SPLIT) __builtin_amdgcn_s_setprio(3);          // vote, output (and the rare validity sweep): the slot's successor waits on them
 
   if (bad_acc != 0u) atomicOr(flag_set, 1);
   // ---- SPLIT: merge the two wave groups.  Group 0 finishes rows [0,TY/2), group 1 rows [TY/2,TY): each hands the
@@ -547,7 +560,7 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
 }
 
 typedef void (*KernelFn)(const float*, ptrdiff_t, int, int, const float*, ptrdiff_t, int, int, int, int, int,
-                         int32_t*, ptrdiff_t, int, int, int*, int*, int, int);
+                         int32_t*, ptrdiff_t, int, int, int*, int*, int, int, int);
 struct Launch {
   int kx, ky, ty;
   int threads, twb, nr, ew, nw;
@@ -665,6 +678,10 @@ int vwgpu_launch_bm_sad_u8(vwgpu_ctx* ctx,
   const size_t shmem = lds_bytes(*l, sx, split ? l->split_groups : 1) + (split ? 64 : 0);   // + the item counters of the split variant
   const KernelFn main_fn = split ? l->split_fn : l->fn;
   const unsigned grid1 = (unsigned)((gx * gy + 7) / 8 * 8);   // one tile per workgroup, see the XCD note in the kernel
+  // the end balance of the one-group matcher (see the kernel): workgroups are dispatched in index order, and the last `slots` of a grid
+  // of two rounds or more are its last round; INT_MAX turns it off (one round: the slots start together, nothing to balance)
+  const int slots = ctx->num_cu * ((l->ty <= 8 && l->kx <= 8) ? 3 : 2);
+  const int last_round = (!split && (int)grid1 >= 2 * slots) ? (int)grid1 - slots : INT_MAX;
   if (shmem > 64 * 1024)
     VWGPU_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(main_fn),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
@@ -672,7 +689,7 @@ int vwgpu_launch_bm_sad_u8(vwgpu_ctx* ctx,
     vwgpu_prof_scope ps(ctx, "bm_sad_u8");
     hipLaunchKernelGGL(main_fn, dim3(grid1), dim3(split ? l->split_groups * l->threads : l->threads), shmem, ctx->stream,
                        left, ls, lw, lh, right, rs, rcw, rch, sx, sy, ne, out, os, ow, oh,
-                       flag_set, flag_clear, gx, gx * gy);
+                       flag_set, flag_clear, gx, gx * gy, last_round);
   }
   VWGPU_HIP(ctx, hipGetLastError());
   return VWGPU_OK;

@@ -20,6 +20,7 @@ SYMBOLS = [
     "vwgpu_subsample_mask_by_two_dev", "vwgpu_subsample_mask_by_two",
     "vwgpu_prefilter_image_dev", "vwgpu_prefilter_image",
     "vwgpu_parabola_subpixel_dev", "vwgpu_parabola_subpixel",
+    "vwgpu_pyramid_subpixel_dev", "vwgpu_pyramid_subpixel",
     "vwgpu_disparity_filter_dev", "vwgpu_disparity_filter",
     "vwgpu_disparity_mask_dev", "vwgpu_disparity_mask",
     "vwgpu_subdivide_regions",
@@ -140,6 +141,9 @@ def load():
     ps = [P, P, I, I, PD, P, PD, P, I, I, PD, I, F, I, I, P, PD]
     lib.vwgpu_parabola_subpixel_dev.argtypes = ps
     lib.vwgpu_parabola_subpixel.argtypes = ps
+    pys = [P, P, I, I, PD, P, PD, P, I, I, PD, I, F, I, I, I, I, P, I, P, PD, P]
+    lib.vwgpu_pyramid_subpixel_dev.argtypes = pys
+    lib.vwgpu_pyramid_subpixel.argtypes = pys
     D = ctypes.c_double
     df = [P, P, I, I, I, I, D, D, I, P]
     lib.vwgpu_disparity_filter_dev.argtypes = df

@@ -185,6 +185,68 @@ def parabola_subpixel(disparity, left_image, right_image, prefilter_mode, prefil
     return out
 
 
+SUBPIXEL_LUCAS_KANADE, SUBPIXEL_FAST_AFFINE, SUBPIXEL_BAYES_EM, SUBPIXEL_PHASE = 0, 1, 2, 3   # SubpixelView.h:28-33
+
+
+def subpixel_tiles(cols, rows, block_size=None):
+    """The prerasterize boxes {x, y, w, h}: the whole image, or the blocks of block_write_image / block_rasterize,
+    aligned to multiples of block_size = (bw, bh) from (0, 0)."""
+    if block_size is None:
+        return np.array([[0, 0, cols, rows]], np.int32)
+    bw, bh = int(block_size[0]), int(block_size[1])
+    if bw <= 0 or bh <= 0:
+        raise ArgumentErr("affine_subpixel: block_size must be positive")
+    return np.array([[x, y, min(bw, cols - x), min(bh, rows - y)] for y in range(0, rows, bh) for x in range(0, cols, bw)],
+                    np.int32).reshape(-1, 4)
+
+
+def affine_subpixel(disparity, left, right, prefilter_mode, prefilter_width, kernel_size, max_pyramid_levels=2,
+                    block_size=None, ctx=None, algorithm=SUBPIXEL_FAST_AFFINE, stats=None):
+    """vw::stereo::affine_subpixel (src/vw/Stereo/SubpixelView.h:120-126): PyramidSubpixelView with SUBPIXEL_FAST_AFFINE,
+    rasterised one prerasterize(bbox) per tile (SubpixelView.cc:33-224).
+
+    disparity: (rows, cols, 3) float32 PixelMask<Vector2f> {dx, dy, valid}, the left image's size; stored values of invalid
+    pixels count in each tile's disparity range, as in the reference.  left / right: 2-D float32 (any sizes).
+    block_size None = one tile, the whole image (ImageView out = affine_subpixel(...)); (bw, bh) = the blocks of
+    block_write_image.  Returns refined {dx, dy, 1}, invalid {0, 0, 0}.  stats (optional list) receives
+    [fixpoint rounds summed over tiles and levels, most rounds of one tile level, window-loop iterations]."""
+    kx, ky = int(kernel_size[0]), int(kernel_size[1])
+    if disparity.ndim != 3 or disparity.shape[2] != 3 or left.ndim != 2 or right.ndim != 2 \
+            or tuple(disparity.shape[:2]) != tuple(left.shape):
+        raise ArgumentErr("PyramidSubpixelView::PyramidSubpixelView(): Disparity image must match left image.")
+    if kx < 1 or ky < 1 or kx % 2 != 1 or ky % 2 != 1:
+        raise ArgumentErr("affine_subpixel: Kernel input not sized with odd values.")
+    if int(algorithm) != SUBPIXEL_FAST_AFFINE:
+        raise core.NoImplErr("PyramidSubpixelView: algorithm %d is not implemented (FAST_AFFINE only)" % int(algorithm))
+    h, w = left.shape
+    rh, rw = right.shape
+    tiles = subpixel_tiles(w, h, block_size)
+    st = (ctypes.c_longlong * 3)()
+    ctx = _ctx_for(left, ctx)
+    lib = ctx._lib
+    if _is_tensor(left):
+        d, l, r = disparity.contiguous(), left.contiguous(), right.contiguous()
+        if not (d.is_cuda and l.is_cuda and r.is_cuda) or d.dtype != torch.float32 or l.dtype != torch.float32 \
+                or r.dtype != torch.float32:
+            raise ArgumentErr("affine_subpixel: float32 CUDA tensors required")
+        out = torch.zeros_like(d)
+        ctx.set_stream(torch.cuda.current_stream(l.device).cuda_stream)
+        ctx.check(lib.vwgpu_pyramid_subpixel_dev(ctx._h, d.data_ptr(), w, h, 0, l.data_ptr(), 0, r.data_ptr(), rw, rh, 0,
+                                                 int(prefilter_mode), float(prefilter_width), kx, ky, int(max_pyramid_levels),
+                                                 int(algorithm), tiles.ctypes.data, len(tiles), out.data_ptr(), 0, st))
+    else:
+        d = np.ascontiguousarray(disparity, np.float32)
+        l = np.ascontiguousarray(left, np.float32)
+        r = np.ascontiguousarray(right, np.float32)
+        out = np.zeros_like(d)
+        ctx.check(lib.vwgpu_pyramid_subpixel(ctx._h, d.ctypes.data, w, h, 0, l.ctypes.data, 0, r.ctypes.data, rw, rh, 0,
+                                             int(prefilter_mode), float(prefilter_width), kx, ky, int(max_pyramid_levels),
+                                             int(algorithm), tiles.ctypes.data, len(tiles), out.ctypes.data, 0, st))
+    if stats is not None:
+        stats[:] = list(st)
+    return out
+
+
 def _filter_call(name, disparity, hh, hv, pthr, rthr, cleanup, ctx):
     if disparity.ndim != 3 or disparity.shape[2] != 3:
         raise ArgumentErr("%s: disparity must be (rows, cols, 3) int32" % name)
@@ -502,6 +564,6 @@ def calc_disparity_sgm(cost_type, left_in, right_in, left_region, search_volume,
     return (res, sub[:n].reshape(oh.value, ow.value, 3).copy()) if with_subpixel else res
 
 
-__all__ = ["calc_disparity", "calc_disparity_sgm", "cross_corr_consistency_check", "parabola_subpixel", "rm_outliers_using_thresh",
+__all__ = ["affine_subpixel", "calc_disparity", "calc_disparity_sgm", "cross_corr_consistency_check", "parabola_subpixel", "rm_outliers_using_thresh",
            "disparity_cleanup_using_thresh", "disparity_mask", "disparity_blob_filter", "subdivide_regions", "pyramid_correlate", "pyramid_correlate_batch",
            "BBox2i", "CostFunctionType"]

@@ -8,6 +8,7 @@
 //                                src/vw/Stereo/tests/TestCorrelationView.cxx:79-82,213-215
 //   pyramid_correlate            src/vw/Stereo/CorrelationView.h:195-230 (PyramidCorrelationView :35-190, BM algorithm)
 //   parabola_subpixel            src/vw/Stereo/ParabolaSubpixelView.h:112-117
+//   PyramidSubpixelView, affine_subpixel   src/vw/Stereo/SubpixelView.h:28-126 (SUBPIXEL_FAST_AFFINE)
 //   prefilter_image              src/vw/Stereo/PreFilter.h:76-95
 //   rm_outliers_using_thresh / disparity_cleanup_using_thresh / disparity_mask
 //                                src/vw/Stereo/DisparityMap.h:387-441, 236-253
@@ -578,6 +579,82 @@ pyramid_correlate(ImageViewBase<Image1T> const& left, ImageViewBase<Image2T> con
   p.memory_limit_mb = memory_limit_mb; p.sgm_num_threads = 1;
   return PyramidCorrelationView(detail::gray_float_ref(left.impl()), detail::gray_float_ref(right.impl()),
                                 detail::mask_ref(left_mask.impl()), detail::mask_ref(right_mask.impl()), p, collar_size, lr_disp_diff, region_ul);
+}
+
+enum PyramidSubpixelView_Algorithm {     // src/vw/Stereo/SubpixelView.h:28-33
+  SUBPIXEL_LUCAS_KANADE = 0, SUBPIXEL_FAST_AFFINE = 1, SUBPIXEL_BAYES_EM = 2, SUBPIXEL_PHASE = 3
+};
+
+/// PyramidSubpixelView (src/vw/Stereo/SubpixelView.h:36-108): lazy; rasterize(dest, bbox) runs one
+/// prerasterize(bbox) of the reference (SubpixelView.cc:33-224) on the engine (vwgpu_pyramid_subpixel).  The result of a
+/// pixel depends on the tile it is rasterised in, as in the reference.  Only SUBPIXEL_FAST_AFFINE is implemented; the
+/// engine reports the others as NoImplErr.
+class PyramidSubpixelView : public ImageViewBase<PyramidSubpixelView> {
+  ImageViewRef<PixelMask<Vector2f>> m_disparity_map;
+  ImageViewRef<PixelGray<float>> m_left_image, m_right_image;
+  Vector2i m_kernel_size;
+  int32 m_max_pyramid_levels;
+  PyramidSubpixelView_Algorithm m_algorithm;
+  PrefilterModeType m_prefilter_mode;
+  float m_prefilter_width;
+public:
+  typedef PixelMask<Vector2f> pixel_type;
+  typedef pixel_type result_type;
+  typedef CropView<ImageView<pixel_type>> prerasterize_type;
+
+  PyramidSubpixelView(ImageViewRef<PixelMask<Vector2f>> const& disparity_map, ImageViewRef<PixelGray<float>> const& left_image,
+                      ImageViewRef<PixelGray<float>> const& right_image, PrefilterModeType prefilter_mode, float prefilter_width,
+                      Vector2i const& kernel_size, int32 max_pyramid_levels, PyramidSubpixelView_Algorithm algorithm)
+      : m_disparity_map(disparity_map), m_left_image(left_image), m_right_image(right_image), m_kernel_size(kernel_size),
+        m_max_pyramid_levels(max_pyramid_levels < 0 ? 0 : max_pyramid_levels), m_algorithm(algorithm),
+        m_prefilter_mode(prefilter_mode), m_prefilter_width(prefilter_width) {
+    VW_ASSERT(m_disparity_map.cols() == m_left_image.cols() && m_disparity_map.rows() == m_left_image.rows(),
+              ArgumentErr() << "PyramidSubpixelView::PyramidSubpixelView(): Disparity image must match left image.\n");
+  }
+  int32 cols() const { return m_left_image.cols(); }
+  int32 rows() const { return m_left_image.rows(); }
+  int32 planes() const { return 1; }
+  pixel_type operator()(int32 /*i*/, int32 /*j*/, int32 /*p*/ = 0) const {
+    vw_throw(NoImplErr() << "PyramidSubpixelView::operator() is not yet implemented.");   // SubpixelView.h:93-96
+    return pixel_type();
+  }
+  /// The tile at bbox, indexed from the tile's own origin.  The operands are rasterised whole (the tile's patch depends on
+  /// its disparity range), and the engine writes into an image of the full size of which the tile is copied out.
+  ImageView<pixel_type> refine_tile(BBox2i const& bbox) const {
+    ImageView<pixel_type> tile(bbox.width(), bbox.height());
+    if (bbox.empty()) return tile;
+    const BBox2i all(0, 0, cols(), rows()), rall(0, 0, m_right_image.cols(), m_right_image.rows());
+    ImageView<pixel_type> d = m_disparity_map.prerasterize(all), full(cols(), rows());
+    ImageView<PixelGray<float>> l = m_left_image.prerasterize(all), r = m_right_image.prerasterize(rall);
+    const int box[4] = {bbox.min().x(), bbox.min().y(), bbox.width(), bbox.height()};
+    vwgpu_ctx* ctx = detail::thread_context();
+    detail::check(ctx, vwgpu_pyramid_subpixel(ctx, reinterpret_cast<const float*>(d.data()), d.cols(), d.rows(), 0,
+                                              reinterpret_cast<const float*>(l.data()), 0,
+                                              reinterpret_cast<const float*>(r.data()), r.cols(), r.rows(), 0,
+                                              (int)m_prefilter_mode, m_prefilter_width, m_kernel_size[0], m_kernel_size[1],
+                                              m_max_pyramid_levels, (int)m_algorithm, box, 1,
+                                              reinterpret_cast<float*>(full.data()), 0, NULL));
+    for (int32 y = 0; y < bbox.height(); ++y)
+      for (int32 x = 0; x < bbox.width(); ++x) tile(x, y) = full(bbox.min().x() + x, bbox.min().y() + y);
+    return tile;
+  }
+  prerasterize_type prerasterize(BBox2i const& bbox) const {
+    return prerasterize_type(refine_tile(bbox), -bbox.min().x(), -bbox.min().y(), cols(), rows());
+  }
+  template <class DestT> void rasterize(DestT const& dest, BBox2i const& bbox) const {
+    ImageView<pixel_type> t = refine_tile(bbox);
+    for (int32 y = 0; y < bbox.height(); ++y)
+      for (int32 x = 0; x < bbox.width(); ++x) dest(x, y) = t(x, y);
+  }
+};
+
+/// affine_subpixel (src/vw/Stereo/SubpixelView.h:120-126, SubpixelView.cc:242-254).
+inline PyramidSubpixelView
+affine_subpixel(ImageViewRef<PixelMask<Vector2f>> const& disparity_map, ImageViewRef<PixelGray<float>> const& left_image,
+                ImageViewRef<PixelGray<float>> const& right_image, PrefilterModeType prefilter_mode, float prefilter_width,
+                Vector2i const& kernel_size, int max_pyramid_levels = 2) {
+  return PyramidSubpixelView(disparity_map, left_image, right_image, prefilter_mode, prefilter_width, kernel_size,
+                             max_pyramid_levels, SUBPIXEL_FAST_AFFINE);
 }
 
 }  // namespace stereo

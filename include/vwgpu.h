@@ -332,14 +332,16 @@ int vwgpu_parabola_subpixel(vwgpu_ctx* ctx, const float* disp, int w, int h, ptr
 
 /* ---- pyramid (affine-adaptive) sub-pixel refinement ---------------------------------------------------- */
 
-/* PyramidSubpixelView_Algorithm, src/vw/Stereo/SubpixelView.h:28-33.  Only FAST_AFFINE is implemented. */
+/* PyramidSubpixelView_Algorithm, src/vw/Stereo/SubpixelView.h:28-33.  PHASE is not implemented. */
 typedef enum vwgpu_subpixel_algorithm {
   VWGPU_SUBPIXEL_LUCAS_KANADE = 0, VWGPU_SUBPIXEL_FAST_AFFINE = 1, VWGPU_SUBPIXEL_BAYES_EM = 2, VWGPU_SUBPIXEL_PHASE = 3
 } vwgpu_subpixel_algorithm;
 
-/* Replaces rasterising vw::stereo::affine_subpixel(disparity, left, right, prefilter_mode, prefilter_width, kernel_size,
- * max_pyramid_levels) (src/vw/Stereo/SubpixelView.h:120-126) tile by tile: one PyramidSubpixelView::prerasterize(bbox)
- * per box (src/vw/Stereo/SubpixelView.cc:33-224, subpixel_optimized_affine_2d src/vw/Stereo/Correlate.cc:848-1200).
+/* Replaces rasterising vw::stereo::lk_subpixel / affine_subpixel / bayes_em_subpixel(disparity, left, right,
+ * prefilter_mode, prefilter_width, kernel_size, max_pyramid_levels) (src/vw/Stereo/SubpixelView.h:111-133) tile by tile:
+ * one PyramidSubpixelView::prerasterize(bbox) per box (src/vw/Stereo/SubpixelView.cc:33-224; subpixel_optimized_LK_2d,
+ * subpixel_optimized_affine_2d and subpixel_optimized_affine_2d_EM, src/vw/Stereo/Correlate.cc:1203-1391, 848-1200,
+ * 500-845).
  * The result of a pixel depends on its tile, as in the reference.
  *   disp   w x h x {dx, dy, valid (!= 0)} float, the left image's size; the stored values of invalid pixels count in the
  *          tile's disparity range, as in the reference (DisparityMap.h:52-64).  Strides of disp / out in PIXELS.
@@ -347,15 +349,17 @@ typedef enum vwgpu_subpixel_algorithm {
  *          constant edge extension of the source wherever a crop leaves an image (as vwgpu_parabola_subpixel).
  *          A non-finite disparity (valid or not) inside a tile: VWGPU_ERR_ARGUMENT.
  *   kx, ky odd (even sizes: VWGPU_ERR_ARGUMENT); max_pyramid_levels < 0 counts as 0.
- *   algorithm  VWGPU_SUBPIXEL_FAST_AFFINE; the others return VWGPU_ERR_NOIMPL.
+ *   algorithm  VWGPU_SUBPIXEL_LUCAS_KANADE, VWGPU_SUBPIXEL_FAST_AFFINE or VWGPU_SUBPIXEL_BAYES_EM; VWGPU_SUBPIXEL_PHASE
+ *          returns VWGPU_ERR_NOIMPL.
  *   tiles  HOST array of ntiles boxes {x, y, w, h} inside the left image; pixels outside every box are not written.
  *   out    refined {dx, dy, 1}, invalid {0, 0, 0}.  Must not alias disp.
  *   stats  optional HOST array of 3: {fixpoint rounds summed over tiles and levels, the most rounds of one tile level,
- *          window-loop iterations run (re-evaluations included)}; NULL skips the iteration counter.
- * Bit-identical to the reference's sequential in-place order (the 6 x 6 solve follows the
- * LAPACK reference SPOTRF2 / SPOTRS).  The device entry synchronises the context's stream (data-dependent patch sizes
- * and fixpoint rounds).  VWGPU_ERR_NOMEM when one tile's patch (tile + disparity range + 2 kernels per axis) cannot be
- * held. */
+ *          window-loop iterations run (re-evaluations included; BAYES_EM counts every EM pass over a window)}; NULL
+ *          skips the iteration counter.
+ * Bit-identical to the reference's sequential in-place order (DESIGN.md sections 4.11, 4.12; the 2 x 2 and 6 x 6 solves
+ * follow the LAPACK reference SPOTRF2 / SPOTRS; BAYES_EM's float k * exp(e) is the double form of the host libm).
+ * The device entry synchronises the context's stream (data-dependent patch sizes and fixpoint rounds).  VWGPU_ERR_NOMEM
+ * when one tile's patch (tile + disparity range + 2 kernels per axis) cannot be held. */
 int vwgpu_pyramid_subpixel_dev(vwgpu_ctx* ctx, const float* d_disp, int w, int h, ptrdiff_t dstride,
                                const float* d_left, ptrdiff_t lstride,
                                const float* d_right, int rw, int rh, ptrdiff_t rstride,

@@ -1,6 +1,8 @@
-// affine_subpixel.hip — affine-adaptive sub-pixel refinement: vw::stereo::PyramidSubpixelView::prerasterize with
-// SUBPIXEL_FAST_AFFINE (src/vw/Stereo/SubpixelView.cc:33-224) and subpixel_optimized_affine_2d
-// (src/vw/Stereo/Correlate.cc:848-1200), tile by tile, bit-identical to the reference's sequential order.
+// affine_subpixel.hip — pyramid sub-pixel refinement: vw::stereo::PyramidSubpixelView::prerasterize
+// (src/vw/Stereo/SubpixelView.cc:33-224) with SUBPIXEL_FAST_AFFINE (subpixel_optimized_affine_2d,
+// src/vw/Stereo/Correlate.cc:848-1200), SUBPIXEL_LUCAS_KANADE (subpixel_optimized_LK_2d, :1203-1391) and SUBPIXEL_BAYES_EM
+// (subpixel_optimized_affine_2d_EM, :500-845), tile by tile, bit-identical to the reference's sequential order.  The
+// algorithms share everything but the refinement kernel launched in the fixpoint loop.
 //
 // Per call: one kernel reduces the disparity range of every tile, one readback sizes the tile patches.  Per tile:
 // prefiltered crops (the prefilter of the edge-extended image, as vwgpu_parabola_subpixel), the zero-extended
@@ -9,7 +11,7 @@
 // and the final write of the tile's box.
 //
 // The reference updates the disparity map in place, in raster order: a pixel it invalidates is missing from the
-// weight window (adjust_weight_image, Correlate.cc:1393-1440) of every later pixel.  affine_refine_kernel evaluates
+// weight window (adjust_weight_image, Correlate.cc:1393-1440) of every later pixel.  the refinement kernel evaluates
 // the pixels of one level in parallel, each with the window validity "earlier pixels as of the previous round, the
 // pixel itself and later pixels as on entry"; a round re-evaluates only pixels whose causal window (rows above, and
 // the same row to the left) holds a pixel whose state changed in the previous round, and the rounds stop when none
@@ -19,6 +21,7 @@
 #include <cstring>
 #include <vector>
 
+#include "em_exp.h"
 #include "vwgpu_internal.h"
 
 namespace {
@@ -403,6 +406,261 @@ affine_refine_kernel(aff_level_args a) {
   if (a.iters) atomicAdd(a.iters, (unsigned long long)iters);
 }
 
+// ---- SUBPIXEL_LUCAS_KANADE and SUBPIXEL_BAYES_EM: the same launch shape, rounds and commit ---------
+
+// The part before the window loop shared by lk_refine_kernel and em_refine_kernel (as in affine_refine_kernel): the
+// dirty test of rounds > 0 and adjust_weight_image.  Returns false when the lane is done.
+__device__ inline bool pyr_prologue(const aff_level_args& a, int x, int y, size_t p, float& sum, int& good) {
+  if (!a.v0[p]) return false;
+  const int w = a.w, khw = a.kx / 2, khh = a.ky / 2;
+  if (a.round > 0) {
+    bool dirty = false;
+    for (int jj = -khh; jj <= 0 && !dirty; ++jj) {
+      const int iend = jj < 0 ? khw : -1;
+      const uint8_t* c = a.cprev + (size_t)(y + jj) * w + x;
+      for (int ii = -khw; ii <= iend; ++ii)
+        if (c[ii]) { dirty = true; break; }
+    }
+    if (!dirty) {
+      a.scur[p] = a.sprev[p];
+      a.ccur[p] = 0;
+      return false;
+    }
+  }
+  sum = 0.0f;
+  good = 0;
+  for (int jj = -khh; jj <= khh; ++jj) {
+    const size_t r = (size_t)(y + jj) * w + x;
+    for (int ii = -khw; ii <= khw; ++ii) {
+      const bool earlier = jj < 0 || (jj == 0 && ii < 0);
+      if (earlier ? a.sprev[r + ii] : a.v0[r + ii]) {
+        sum = __fadd_rn(sum, a.tmpl[(jj + khh) * a.kx + ii + khw]);
+        ++good;
+      }
+    }
+  }
+  return true;
+}
+
+// w(0, 0) after adjust_weight_image: the weight every window pixel gets (the accessor is never advanced)
+__device__ inline float pyr_top_left_weight(const aff_level_args& a, int x, int y, size_t p, float sum) {
+  const int khw = a.kx / 2, khh = a.ky / 2;
+  const bool tl_valid = (khh > 0 || khw > 0) ? a.sprev[(size_t)(y - khh) * a.w + x - khw] : a.v0[p];
+  return tl_valid ? __fdiv_rn(a.tmpl[0], sum) : __fdiv_rn(0.0f, sum);
+}
+
+__device__ inline void pyr_epilogue(const aff_level_args& a, size_t p, uint8_t ns, float ux, float uy, unsigned iters) {
+  a.rdx[p] = __fadd_rn(a.dx[p], ux);
+  a.rdy[p] = __fadd_rn(a.dy[p], uy);
+  const uint8_t old = a.round > 0 ? a.sprev[p] : a.v0[p];
+  a.scur[p] = ns;
+  a.ccur[p] = ns != old;
+  if (ns != old) atomicAdd(a.changes, 1);
+  if (a.iters) atomicAdd(a.iters, (unsigned long long)iters);
+}
+
+// SPOSV('L', 2, 1) = SPOTRF2 (n1 = n2 = 1) + SPOTRS; b untouched when the factorisation fails
+__device__ inline void pyr_posv2(float a00, float a10, float a11, float& b0, float& b1) {
+  if (!(a00 > 0.0f)) return;
+  a00 = aff_sqrt_rn(a00);
+  a10 = __fmul_rn(__fdiv_rn(1.0f, a00), a10);                        // STRSM('R', 'L', 'T', 'N')
+  if (a10 != 0.0f) a11 = __fadd_rn(a11, __fmul_rn(-a10, a10));       // SSYRK
+  if (!(a11 > 0.0f)) return;
+  a11 = aff_sqrt_rn(a11);
+  if (b0 != 0.0f) {                                                  // STRSM('L', 'L', 'N', 'N')
+    b0 = __fdiv_rn(b0, a00);
+    b1 = __fsub_rn(b1, __fmul_rn(b0, a10));
+  }
+  if (b1 != 0.0f) b1 = __fdiv_rn(b1, a11);
+  b1 = __fdiv_rn(b1, a11);                                           // STRSM('L', 'L', 'T', 'N')
+  b0 = __fdiv_rn(__fsub_rn(b0, __fmul_rn(a10, b1)), a00);
+}
+
+// subpixel_optimized_LK_2d (Correlate.cc:1203-1391): a translation, at most 10 Gauss-Newton steps, a 2 x 2 solve.
+__global__ void __launch_bounds__(AFF_BX * AFF_BY)
+lk_refine_kernel(aff_level_args a) {
+  const int x = a.x0 + blockIdx.x * AFF_BX + threadIdx.x, y = a.y0 + blockIdx.y * AFF_BY + threadIdx.y;
+  if (x >= a.x1 || y >= a.y1) return;
+  const int w = a.w;
+  const size_t p = (size_t)y * w + x;
+  float sum;
+  int good;
+  if (!pyr_prologue(a, x, y, p, sum, good)) return;
+  const int khw = a.kx / 2, khh = a.ky / 2;
+  uint8_t ns = 1;
+  float d0 = 0.0f, d1 = 0.0f;
+  unsigned iters = 0;
+  if (good < (a.kx * a.ky) / 2) {
+    ns = 0;
+  } else {
+    const float max_translation = (float)(a.kx / 2);
+    const float x_base = __fadd_rn((float)x, a.dx[p]), y_base = __fadd_rn((float)y, a.dy[p]);
+    const float wt = pyr_top_left_weight(a, x, y, p, sum);          // robust_weight (1) * w(0, 0)
+    for (unsigned iter = 0; iter < 10; ++iter) {
+      if (aff_norm2_2(d0, d1) > (double)max_translation) break;
+      ++iters;
+      float r00 = 0.0f, r01 = 0.0f, r11 = 0.0f, l0 = 0.0f, l1 = 0.0f;
+      const float xx_partial = __fadd_rn(x_base, d0);
+      for (int jj = -khh; jj <= khh; ++jj) {
+        const float yy = __fadd_rn(__fadd_rn(y_base, (float)jj), d1);
+        const size_t r = (size_t)(y + jj) * w + x;
+        for (int ii = -khw; ii <= khw; ++ii) {
+          const float xx = __fadd_rn((float)ii, xx_partial);
+          const float I_e = __fsub_rn(aff_bilinear(a.R, w, a.h, xx, yy), a.L[r + ii]);
+          const float ix = a.Ix[r + ii], iy = a.Iy[r + ii];
+          const float Ixv = __fmul_rn(wt, ix), Iyv = __fmul_rn(wt, iy);
+          l0 = __fsub_rn(l0, __fmul_rn(Ixv, I_e));
+          l1 = __fsub_rn(l1, __fmul_rn(Iyv, I_e));
+          r00 = __fadd_rn(r00, __fmul_rn(Ixv, ix));
+          r01 = __fadd_rn(r01, __fmul_rn(Ixv, iy));
+          r11 = __fadd_rn(r11, __fmul_rn(Iyv, iy));
+        }
+      }
+      pyr_posv2(r00, r01, r11, l0, l1);
+      d0 = __fadd_rn(d0, l0);
+      d1 = __fadd_rn(d1, l1);
+      if (aff_norm2_2(l0, l1) < 0.05) break;
+    }
+    if (aff_norm2_2(d0, d1) > (double)max_translation || isnan(d0) || isnan(d1)) ns = 0;
+  }
+  pyr_epilogue(a, p, ns, d0, d1, iters);
+}
+
+// subpixel_optimized_affine_2d_EM (Correlate.cc:500-845): up to 10 outer steps of up to 2 EM passes, each a 6 x 6 solve.
+// plane_nf / noise_nf are plane_norm_factor / noise_norm_factor (constant: the variances are never updated).
+__global__ void __launch_bounds__(AFF_BX * AFF_BY)
+em_refine_kernel(aff_level_args a, float plane_nf, float noise_nf) {
+  const int x = a.x0 + blockIdx.x * AFF_BX + threadIdx.x, y = a.y0 + blockIdx.y * AFF_BY + threadIdx.y;
+  if (x >= a.x1 || y >= a.y1) return;
+  const int w = a.w;
+  const size_t p = (size_t)y * w + x;
+  float sum;
+  int good;
+  if (!pyr_prologue(a, x, y, p, sum, good)) return;
+  const int khw = a.kx / 2, khh = a.ky / 2, kern_pixels = a.kx * a.ky;
+  constexpr float two_var2_plane = 2 * 1e-3f, two_var2_noise = 2 * 1e-2f;
+  uint8_t ns = 1;
+  float d[6] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f};
+  unsigned iters = 0;
+  if (good < kern_pixels / 2) {
+    ns = 0;
+  } else {
+    const float max_translation = (float)(a.kx / 2);
+    const float x_base = __fadd_rn((float)x, a.dx[p]), y_base = __fadd_rn((float)y, a.dy[p]);
+    const float wt = pyr_top_left_weight(a, x, y, p, sum);
+    float curr_sum_I_e = 0.0f, prev_sum_I_e = 0.0f;
+    for (unsigned iter = 0; iter < 10; ++iter) {
+      if (aff_norm2_2(d[2], d[5]) > (double)max_translation) break;
+      float lhs[6], prev_lhs[6], d_em[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) { lhs[k] = 0.0f; prev_lhs[k] = 0.0f; d_em[k] = d[k]; }
+      float mean_noise = 0.0f, w_plane = 0.8f, w_noise = 0.2f;
+      for (unsigned em_iter = 0; em_iter < 2; ++em_iter) {
+        ++iters;
+        float rhs[36];
+#pragma unroll
+        for (int k = 0; k < 36; ++k) rhs[k] = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) lhs[k] = 0.0f;
+        float in_curr_sum_I_e = 0.0f, mean_noise_tmp = 0.0f, sum_gamma_noise = 0.0f, sum_gamma_plane = 0.0f;
+        int skip = 0;
+        for (int jj = -khh; jj <= khh; ++jj) {
+          const float fj = (float)jj;
+          const float xx_partial = __fadd_rn(__fadd_rn(x_base, __fmul_rn(d[1], fj)), d[2]);
+          const float yy_partial = __fadd_rn(__fadd_rn(y_base, __fmul_rn(d[4], fj)), d[5]);
+          const float delta_x_partial = __fadd_rn(__fmul_rn(d_em[1], fj), d_em[2]);
+          const float delta_y_partial = __fadd_rn(__fmul_rn(d_em[4], fj), d_em[5]);
+          const size_t r = (size_t)(y + jj) * w + x;
+          for (int ii = -khw; ii <= khw; ++ii) {
+            const float fi = (float)ii;
+            const float xx = __fadd_rn(__fmul_rn(d[0], fi), xx_partial);
+            const float yy = __fadd_rn(__fmul_rn(d[3], fi), yy_partial);
+            const float delta_x = __fadd_rn(__fmul_rn(d_em[0], fi), delta_x_partial);
+            const float delta_y = __fadd_rn(__fmul_rn(d_em[3], fi), delta_y_partial);
+            const float px = aff_bilinear(a.R, w, a.h, xx, yy);
+            const float I_e = __fsub_rn(px, a.L[r + ii]);
+            in_curr_sum_I_e = __fadd_rn(in_curr_sum_I_e, I_e);
+            const float ix = a.Ix[r + ii], iy = a.Iy[r + ii];
+            const float temp_plane = __fsub_rn(__fsub_rn(I_e, __fmul_rn(delta_x, ix)), __fmul_rn(delta_y, iy));
+            const float temp_noise = __fsub_rn(px, mean_noise);
+            const float plane_e = __fdiv_rn(-__fmul_rn(temp_plane, temp_plane), two_var2_plane);
+            const float plane_prob = plane_e < -75.0f ? 0.0f : em_scaled_exp(plane_nf, plane_e);
+            const float noise_e = __fdiv_rn(-__fmul_rn(temp_noise, temp_noise), two_var2_noise);
+            const float noise_prob = noise_e < -75.0f ? 0.0f : em_scaled_exp(noise_nf, noise_e);
+            const float pw = __fmul_rn(plane_prob, w_plane), nw = __fmul_rn(noise_prob, w_noise);
+            const float psum = __fadd_rn(pw, nw);
+            const float gamma_plane = __fdiv_rn(pw, psum), gamma_noise = __fdiv_rn(nw, psum);
+            mean_noise_tmp = __fadd_rn(mean_noise_tmp, __fmul_rn(px, gamma_noise));
+            sum_gamma_plane = __fadd_rn(sum_gamma_plane, gamma_plane);
+            sum_gamma_noise = __fadd_rn(sum_gamma_noise, gamma_noise);
+            const float weight = __fmul_rn(gamma_plane, wt);
+            if ((double)weight < 1e-26) {                            // NaN is not: it enters the sums
+              ++skip;
+              continue;
+            }
+            const float Ixv = __fmul_rn(weight, ix), Iyv = __fmul_rn(weight, iy);
+            const float Ixx = __fmul_rn(Ixv, ix), Iyy = __fmul_rn(Iyv, iy), Ixy = __fmul_rn(Ixv, iy);
+            lhs[0] = __fsub_rn(lhs[0], __fmul_rn(__fmul_rn(fi, Ixv), I_e));
+            lhs[1] = __fsub_rn(lhs[1], __fmul_rn(__fmul_rn(fj, Ixv), I_e));
+            lhs[2] = __fsub_rn(lhs[2], __fmul_rn(Ixv, I_e));
+            lhs[3] = __fsub_rn(lhs[3], __fmul_rn(__fmul_rn(fi, Iyv), I_e));
+            lhs[4] = __fsub_rn(lhs[4], __fmul_rn(__fmul_rn(fj, Iyv), I_e));
+            lhs[5] = __fsub_rn(lhs[5], __fmul_rn(Iyv, I_e));
+            const float m0 = (float)(ii * ii), m1 = (float)(ii * jj), m2 = (float)(jj * jj);
+            rhs[0] = __fadd_rn(rhs[0], __fmul_rn(m0, Ixx));
+            rhs[1] = __fadd_rn(rhs[1], __fmul_rn(m1, Ixx));
+            rhs[2] = __fadd_rn(rhs[2], __fmul_rn(fi, Ixx));
+            rhs[7] = __fadd_rn(rhs[7], __fmul_rn(m2, Ixx));
+            rhs[8] = __fadd_rn(rhs[8], __fmul_rn(fj, Ixx));
+            rhs[14] = __fadd_rn(rhs[14], Ixx);
+            rhs[3] = __fadd_rn(rhs[3], __fmul_rn(m0, Ixy));
+            rhs[4] = __fadd_rn(rhs[4], __fmul_rn(m1, Ixy));
+            rhs[5] = __fadd_rn(rhs[5], __fmul_rn(fi, Ixy));
+            rhs[10] = __fadd_rn(rhs[10], __fmul_rn(m2, Ixy));
+            rhs[11] = __fadd_rn(rhs[11], __fmul_rn(fj, Ixy));
+            rhs[17] = __fadd_rn(rhs[17], Ixy);
+            rhs[21] = __fadd_rn(rhs[21], __fmul_rn(m0, Iyy));
+            rhs[22] = __fadd_rn(rhs[22], __fmul_rn(m1, Iyy));
+            rhs[23] = __fadd_rn(rhs[23], __fmul_rn(fi, Iyy));
+            rhs[28] = __fadd_rn(rhs[28], __fmul_rn(m2, Iyy));
+            rhs[29] = __fadd_rn(rhs[29], __fmul_rn(fj, Iyy));
+            rhs[35] = __fadd_rn(rhs[35], Iyy);
+          }
+        }
+        if (skip == kern_pixels) break;                              // before the solve: lhs stays zero
+        rhs[9] = rhs[4]; rhs[15] = rhs[5]; rhs[16] = rhs[11];
+#pragma unroll
+        for (int rr = 1; rr < 6; ++rr)
+#pragma unroll
+          for (int c = 0; c < rr; ++c) rhs[rr * 6 + c] = rhs[c * 6 + rr];
+        aff_posv6(rhs, lhs);
+        mean_noise = __fdiv_rn(mean_noise_tmp, sum_gamma_noise);
+        w_plane = __fdiv_rn(sum_gamma_plane, (float)kern_pixels);
+        w_noise = __fdiv_rn(sum_gamma_noise, (float)kern_pixels);
+        double s2 = 0.0;                                             // norm_2(prev_lhs - lhs), stored as float
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          const float t = __fsub_rn(prev_lhs[k], lhs[k]);
+          s2 = __dadd_rn(s2, (double)__fmul_rn(t, t));
+        }
+        const float conv_error = (float)__dsqrt_rn((double)(float)s2);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) { d_em[k] = __fadd_rn(d[k], lhs[k]); prev_lhs[k] = lhs[k]; }
+        if (in_curr_sum_I_e < 0.0f) in_curr_sum_I_e = -in_curr_sum_I_e;
+        curr_sum_I_e = in_curr_sum_I_e;
+        if ((double)conv_error < 1e-3 && em_iter > 0) break;
+      }
+#pragma unroll
+      for (int k = 0; k < 6; ++k) d[k] = __fadd_rn(d[k], lhs[k]);
+      if (curr_sum_I_e < 0.0f) curr_sum_I_e = -curr_sum_I_e;
+      if (prev_sum_I_e < curr_sum_I_e && iter > 0) break;
+      prev_sum_I_e = curr_sum_I_e;
+    }
+    if (aff_norm2_2(d[2], d[5]) > (double)max_translation || isnan(d[2]) || isnan(d[5])) ns = 0;
+  }
+  pyr_epilogue(a, p, ns, d[2], d[5], iters);
+}
+
 // the converged state back into the level's map (ROI + ring only)
 __global__ void affine_commit_kernel(float* __restrict__ dx, float* __restrict__ dy, uint8_t* __restrict__ v,
                                      const uint8_t* __restrict__ s, const float* __restrict__ rdx, const float* __restrict__ rdy,
@@ -461,7 +719,7 @@ struct aff_level {
 // The tile loop of vwgpu_pyramid_subpixel_dev (include/vwgpu.h); arguments are checked by the caller.
 static int vwgpu_affine_subpixel_tiles(vwgpu_ctx* ctx, const float* d_disp, int w, int h, ptrdiff_t dstride,
                                 const float* d_left, ptrdiff_t lstride, const float* d_right, int rw, int rh, ptrdiff_t rstride,
-                                int mode, float width, int kx, int ky, int levels, const int* tiles, int ntiles,
+                                int mode, float width, int kx, int ky, int levels, int algorithm, const int* tiles, int ntiles,
                                 float* d_out, ptrdiff_t ostride, long long* stats) {
   // ranges of all tiles: one launch, one readback
   const size_t tb = vwgpu_align_up((size_t)ntiles * 16, 256);
@@ -511,6 +769,10 @@ static int vwgpu_affine_subpixel_tiles(vwgpu_ctx* ctx, const float* d_disp, int 
   }
   const float lap[9] = {0, 1, 0, 1, -4, 1, 0, 1, 0};
   int total_rounds = 0, max_rounds = 0;
+  // BAYES_EM: plane_norm_factor / noise_norm_factor as the reference forms them (Correlate.cc:634-635), 1.0 / sqrt(2 pi
+  // var2) in double stored to float; var2_plane = 1e-3 and var2_noise = 1e-2 are never updated.
+  const float var2_plane = 1e-3f, var2_noise = 1e-2f;
+  const float plane_nf = 1.0 / std::sqrt(2 * M_PI * var2_plane), noise_nf = 1.0 / std::sqrt(2 * M_PI * var2_noise);
 
   for (int t = 0; t < ntiles; ++t) {
     const int bx = tiles[4 * t], by = tiles[4 * t + 1], bw = tiles[4 * t + 2], bh = tiles[4 * t + 3];
@@ -613,7 +875,13 @@ static int vwgpu_affine_subpixel_tiles(vwgpu_ctx* ctx, const float* d_disp, int 
           if (round > cap) return vwgpu_fail(ctx, VWGPU_ERR_LOGIC, "pyramid_subpixel: invalidation fixpoint did not converge");
           a.round = round; a.sprev = sp; a.cprev = cp; a.scur = sc; a.ccur = cc;
           VWGPU_HIP(ctx, hipMemsetAsync(d_changes, 0, 4, ctx->stream));
-          hipLaunchKernelGGL(affine_refine_kernel, aff_grid(x1 - x0, y1 - y0), dim3(AFF_BX, AFF_BY), 0, ctx->stream, a);
+          if (algorithm == VWGPU_SUBPIXEL_FAST_AFFINE)
+            hipLaunchKernelGGL(affine_refine_kernel, aff_grid(x1 - x0, y1 - y0), dim3(AFF_BX, AFF_BY), 0, ctx->stream, a);
+          else if (algorithm == VWGPU_SUBPIXEL_LUCAS_KANADE)
+            hipLaunchKernelGGL(lk_refine_kernel, aff_grid(x1 - x0, y1 - y0), dim3(AFF_BX, AFF_BY), 0, ctx->stream, a);
+          else
+            hipLaunchKernelGGL(em_refine_kernel, aff_grid(x1 - x0, y1 - y0), dim3(AFF_BX, AFF_BY), 0, ctx->stream, a, plane_nf,
+                               noise_nf);
           int changes = 0;
           VWGPU_HIP(ctx, hipMemcpyAsync(&changes, d_changes, 4, hipMemcpyDeviceToHost, ctx->stream));
           VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -666,8 +934,8 @@ int aff_check(vwgpu_ctx* ctx, const void* disp, int w, int h, ptrdiff_t& dstride
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "pyramid_subpixel: unknown prefilter mode %d", mode);
   if (algorithm < VWGPU_SUBPIXEL_LUCAS_KANADE || algorithm > VWGPU_SUBPIXEL_PHASE)
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "pyramid_subpixel: unknown algorithm %d", algorithm);
-  if (algorithm != VWGPU_SUBPIXEL_FAST_AFFINE)
-    return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "pyramid_subpixel: algorithm %d is not implemented (FAST_AFFINE only)", algorithm);
+  if (algorithm == VWGPU_SUBPIXEL_PHASE)
+    return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "pyramid_subpixel: algorithm %d (PHASE) is not implemented", algorithm);
   if (dstride == 0) dstride = w;
   if (ostride == 0) ostride = w;
   if (lstride == 0) lstride = w;
@@ -698,7 +966,7 @@ int vwgpu_pyramid_subpixel_dev(vwgpu_ctx* ctx, const float* d_disp, int w, int h
   if (ntiles == 0) return VWGPU_OK;
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
   return vwgpu_affine_subpixel_tiles(ctx, d_disp, w, h, dstride, d_left, lstride, d_right, rw, rh, rstride, mode, width, kx, ky,
-                                     levels < 0 ? 0 : levels, tiles, ntiles, d_out, ostride, stats);
+                                     levels < 0 ? 0 : levels, algorithm, tiles, ntiles, d_out, ostride, stats);
 }
 
 int vwgpu_pyramid_subpixel(vwgpu_ctx* ctx, const float* disp, int w, int h, ptrdiff_t dstride,
@@ -724,8 +992,8 @@ int vwgpu_pyramid_subpixel(vwgpu_ctx* ctx, const float* disp, int w, int h, ptrd
   VWGPU_HIP(ctx, hipMemcpy2DAsync(so, (size_t)w * 12, out, (size_t)ostride * 12, (size_t)w * 12, h, hipMemcpyHostToDevice, ctx->stream));
   VWGPU_HIP(ctx, hipMemcpy2DAsync(sl, (size_t)w * 4, left, (size_t)lstride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
   VWGPU_HIP(ctx, hipMemcpy2DAsync(sr, (size_t)rw * 4, right, (size_t)rstride * 4, (size_t)rw * 4, rh, hipMemcpyHostToDevice, ctx->stream));
-  rc = vwgpu_affine_subpixel_tiles(ctx, sd, w, h, w, sl, w, sr, rw, rh, rw, mode, width, kx, ky, levels < 0 ? 0 : levels, tiles, ntiles,
-                                   so, w, stats);
+  rc = vwgpu_affine_subpixel_tiles(ctx, sd, w, h, w, sl, w, sr, rw, rh, rw, mode, width, kx, ky, levels < 0 ? 0 : levels, algorithm,
+                                   tiles, ntiles, so, w, stats);
   if (rc) return rc;
   VWGPU_HIP(ctx, hipMemcpy2DAsync(out, (size_t)ostride * 12, so, (size_t)w * 12, (size_t)w * 12, h, hipMemcpyDeviceToHost, ctx->stream));
   VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -195,29 +195,19 @@ def subpixel_tiles(cols, rows, block_size=None):
         return np.array([[0, 0, cols, rows]], np.int32)
     bw, bh = int(block_size[0]), int(block_size[1])
     if bw <= 0 or bh <= 0:
-        raise ArgumentErr("affine_subpixel: block_size must be positive")
+        raise ArgumentErr("PyramidSubpixelView: block_size must be positive")
     return np.array([[x, y, min(bw, cols - x), min(bh, rows - y)] for y in range(0, rows, bh) for x in range(0, cols, bw)],
                     np.int32).reshape(-1, 4)
 
 
-def affine_subpixel(disparity, left, right, prefilter_mode, prefilter_width, kernel_size, max_pyramid_levels=2,
-                    block_size=None, ctx=None, algorithm=SUBPIXEL_FAST_AFFINE, stats=None):
-    """vw::stereo::affine_subpixel (src/vw/Stereo/SubpixelView.h:120-126): PyramidSubpixelView with SUBPIXEL_FAST_AFFINE,
-    rasterised one prerasterize(bbox) per tile (SubpixelView.cc:33-224).
-
-    disparity: (rows, cols, 3) float32 PixelMask<Vector2f> {dx, dy, valid}, the left image's size; stored values of invalid
-    pixels count in each tile's disparity range, as in the reference.  left / right: 2-D float32 (any sizes).
-    block_size None = one tile, the whole image (ImageView out = affine_subpixel(...)); (bw, bh) = the blocks of
-    block_write_image.  Returns refined {dx, dy, 1}, invalid {0, 0, 0}.  stats (optional list) receives
-    [fixpoint rounds summed over tiles and levels, most rounds of one tile level, window-loop iterations]."""
+def _pyramid_subpixel(name, disparity, left, right, prefilter_mode, prefilter_width, kernel_size, max_pyramid_levels,
+                      algorithm, block_size, ctx, stats):
     kx, ky = int(kernel_size[0]), int(kernel_size[1])
     if disparity.ndim != 3 or disparity.shape[2] != 3 or left.ndim != 2 or right.ndim != 2 \
             or tuple(disparity.shape[:2]) != tuple(left.shape):
         raise ArgumentErr("PyramidSubpixelView::PyramidSubpixelView(): Disparity image must match left image.")
     if kx < 1 or ky < 1 or kx % 2 != 1 or ky % 2 != 1:
-        raise ArgumentErr("affine_subpixel: Kernel input not sized with odd values.")
-    if int(algorithm) != SUBPIXEL_FAST_AFFINE:
-        raise core.NoImplErr("PyramidSubpixelView: algorithm %d is not implemented (FAST_AFFINE only)" % int(algorithm))
+        raise ArgumentErr("%s: Kernel input not sized with odd values." % name)
     h, w = left.shape
     rh, rw = right.shape
     tiles = subpixel_tiles(w, h, block_size)
@@ -228,7 +218,7 @@ def affine_subpixel(disparity, left, right, prefilter_mode, prefilter_width, ker
         d, l, r = disparity.contiguous(), left.contiguous(), right.contiguous()
         if not (d.is_cuda and l.is_cuda and r.is_cuda) or d.dtype != torch.float32 or l.dtype != torch.float32 \
                 or r.dtype != torch.float32:
-            raise ArgumentErr("affine_subpixel: float32 CUDA tensors required")
+            raise ArgumentErr("%s: float32 CUDA tensors required" % name)
         out = torch.zeros_like(d)
         ctx.set_stream(torch.cuda.current_stream(l.device).cuda_stream)
         ctx.check(lib.vwgpu_pyramid_subpixel_dev(ctx._h, d.data_ptr(), w, h, 0, l.data_ptr(), 0, r.data_ptr(), rw, rh, 0,
@@ -245,6 +235,54 @@ def affine_subpixel(disparity, left, right, prefilter_mode, prefilter_width, ker
     if stats is not None:
         stats[:] = list(st)
     return out
+
+
+def pyramid_subpixel(disparity, left, right, prefilter_mode, prefilter_width, kernel_size, max_pyramid_levels=2,
+                     algorithm=SUBPIXEL_FAST_AFFINE, block_size=None, ctx=None, stats=None):
+    """vw::stereo::PyramidSubpixelView (src/vw/Stereo/SubpixelView.h:36-108) with any implemented algorithm
+    (SUBPIXEL_LUCAS_KANADE, SUBPIXEL_FAST_AFFINE, SUBPIXEL_BAYES_EM; SUBPIXEL_PHASE raises NoImplErr), rasterised one
+    prerasterize(bbox) per tile (SubpixelView.cc:33-224).
+
+    disparity: (rows, cols, 3) float32 PixelMask<Vector2f> {dx, dy, valid}, the left image's size; stored values of invalid
+    pixels count in each tile's disparity range, as in the reference.  left / right: 2-D float32 (any sizes), numpy arrays
+    (host entry) or CUDA tensors (device entry, result on the device).  block_size None = one tile, the whole image
+    (ImageView out = view); (bw, bh) = the blocks of block_write_image.  Returns refined {dx, dy, 1}, invalid {0, 0, 0}.
+    stats (optional list) receives [fixpoint rounds summed over tiles and levels, most rounds of one tile level, window
+    passes (BAYES_EM: every EM pass)]."""
+    if int(algorithm) not in (SUBPIXEL_LUCAS_KANADE, SUBPIXEL_FAST_AFFINE, SUBPIXEL_BAYES_EM, SUBPIXEL_PHASE):
+        raise ArgumentErr("PyramidSubpixelView: unknown algorithm %d" % int(algorithm))
+    if int(algorithm) == SUBPIXEL_PHASE:
+        raise core.NoImplErr("PyramidSubpixelView: SUBPIXEL_PHASE is not implemented")
+    return _pyramid_subpixel("pyramid_subpixel", disparity, left, right, prefilter_mode, prefilter_width, kernel_size,
+                             max_pyramid_levels, algorithm, block_size, ctx, stats)
+
+
+def affine_subpixel(disparity, left, right, prefilter_mode, prefilter_width, kernel_size, max_pyramid_levels=2,
+                    block_size=None, ctx=None, algorithm=SUBPIXEL_FAST_AFFINE, stats=None):
+    """vw::stereo::affine_subpixel (src/vw/Stereo/SubpixelView.h:120-126): PyramidSubpixelView with SUBPIXEL_FAST_AFFINE
+    (see pyramid_subpixel for the arguments).  algorithm must stay SUBPIXEL_FAST_AFFINE; the other refiners are
+    lk_subpixel, bayes_em_subpixel and pyramid_subpixel."""
+    if int(algorithm) != SUBPIXEL_FAST_AFFINE:
+        raise core.NoImplErr("affine_subpixel: algorithm %d is not FAST_AFFINE (use lk_subpixel, bayes_em_subpixel or "
+                             "pyramid_subpixel)" % int(algorithm))
+    return _pyramid_subpixel("affine_subpixel", disparity, left, right, prefilter_mode, prefilter_width, kernel_size,
+                             max_pyramid_levels, algorithm, block_size, ctx, stats)
+
+
+def lk_subpixel(disparity, left, right, prefilter_mode, prefilter_width, kernel_size, max_pyramid_levels=2,
+                block_size=None, ctx=None, stats=None):
+    """vw::stereo::lk_subpixel (src/vw/Stereo/SubpixelView.h:111-117): PyramidSubpixelView with SUBPIXEL_LUCAS_KANADE
+    (see pyramid_subpixel for the arguments)."""
+    return _pyramid_subpixel("lk_subpixel", disparity, left, right, prefilter_mode, prefilter_width, kernel_size,
+                             max_pyramid_levels, SUBPIXEL_LUCAS_KANADE, block_size, ctx, stats)
+
+
+def bayes_em_subpixel(disparity, left, right, prefilter_mode, prefilter_width, kernel_size, max_pyramid_levels=2,
+                      block_size=None, ctx=None, stats=None):
+    """vw::stereo::bayes_em_subpixel (src/vw/Stereo/SubpixelView.h:127-133): PyramidSubpixelView with SUBPIXEL_BAYES_EM
+    (see pyramid_subpixel for the arguments)."""
+    return _pyramid_subpixel("bayes_em_subpixel", disparity, left, right, prefilter_mode, prefilter_width, kernel_size,
+                             max_pyramid_levels, SUBPIXEL_BAYES_EM, block_size, ctx, stats)
 
 
 def _filter_call(name, disparity, hh, hv, pthr, rthr, cleanup, ctx):
@@ -564,6 +602,6 @@ def calc_disparity_sgm(cost_type, left_in, right_in, left_region, search_volume,
     return (res, sub[:n].reshape(oh.value, ow.value, 3).copy()) if with_subpixel else res
 
 
-__all__ = ["affine_subpixel", "calc_disparity", "calc_disparity_sgm", "cross_corr_consistency_check", "parabola_subpixel", "rm_outliers_using_thresh",
+__all__ = ["affine_subpixel", "bayes_em_subpixel", "lk_subpixel", "pyramid_subpixel", "calc_disparity", "calc_disparity_sgm", "cross_corr_consistency_check", "parabola_subpixel", "rm_outliers_using_thresh",
            "disparity_cleanup_using_thresh", "disparity_mask", "disparity_blob_filter", "subdivide_regions", "pyramid_correlate", "pyramid_correlate_batch",
            "BBox2i", "CostFunctionType"]

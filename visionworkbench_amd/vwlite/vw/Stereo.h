@@ -8,7 +8,8 @@
 //                                src/vw/Stereo/tests/TestCorrelationView.cxx:79-82,213-215
 //   pyramid_correlate            src/vw/Stereo/CorrelationView.h:195-230 (PyramidCorrelationView :35-190, BM algorithm)
 //   parabola_subpixel            src/vw/Stereo/ParabolaSubpixelView.h:112-117
-//   PyramidSubpixelView, affine_subpixel   src/vw/Stereo/SubpixelView.h:28-126 (SUBPIXEL_FAST_AFFINE)
+//   PyramidSubpixelView, lk_subpixel, affine_subpixel, bayes_em_subpixel
+//                                src/vw/Stereo/SubpixelView.h:28-134 (SUBPIXEL_PHASE: NoImplErr)
 //   prefilter_image              src/vw/Stereo/PreFilter.h:76-95
 //   rm_outliers_using_thresh / disparity_cleanup_using_thresh / disparity_mask
 //                                src/vw/Stereo/DisparityMap.h:387-441, 236-253
@@ -587,8 +588,8 @@ enum PyramidSubpixelView_Algorithm {     // src/vw/Stereo/SubpixelView.h:28-33
 
 /// PyramidSubpixelView (src/vw/Stereo/SubpixelView.h:36-108): lazy; rasterize(dest, bbox) runs one
 /// prerasterize(bbox) of the reference (SubpixelView.cc:33-224) on the engine (vwgpu_pyramid_subpixel).  The result of a
-/// pixel depends on the tile it is rasterised in, as in the reference.  Only SUBPIXEL_FAST_AFFINE is implemented; the
-/// engine reports the others as NoImplErr.
+/// pixel depends on the tile it is rasterised in, as in the reference.  SUBPIXEL_LUCAS_KANADE, SUBPIXEL_FAST_AFFINE and
+/// SUBPIXEL_BAYES_EM are implemented; the engine reports SUBPIXEL_PHASE as NoImplErr.
 class PyramidSubpixelView : public ImageViewBase<PyramidSubpixelView> {
   ImageViewRef<PixelMask<Vector2f>> m_disparity_map;
   ImageViewRef<PixelGray<float>> m_left_image, m_right_image;
@@ -647,6 +648,24 @@ public:
       for (int32 x = 0; x < bbox.width(); ++x) dest(x, y) = t(x, y);
   }
 };
+
+/// lk_subpixel (src/vw/Stereo/SubpixelView.h:111-117).
+inline PyramidSubpixelView
+lk_subpixel(ImageViewRef<PixelMask<Vector2f>> const& disparity_map, ImageViewRef<PixelGray<float>> const& left_image,
+            ImageViewRef<PixelGray<float>> const& right_image, PrefilterModeType prefilter_mode, float prefilter_width,
+            Vector2i const& kernel_size, int max_pyramid_levels = 2) {
+  return PyramidSubpixelView(disparity_map, left_image, right_image, prefilter_mode, prefilter_width, kernel_size,
+                             max_pyramid_levels, SUBPIXEL_LUCAS_KANADE);
+}
+
+/// bayes_em_subpixel (src/vw/Stereo/SubpixelView.h:127-133).
+inline PyramidSubpixelView
+bayes_em_subpixel(ImageViewRef<PixelMask<Vector2f>> const& disparity_map, ImageViewRef<PixelGray<float>> const& left_image,
+                  ImageViewRef<PixelGray<float>> const& right_image, PrefilterModeType prefilter_mode, float prefilter_width,
+                  Vector2i const& kernel_size, int max_pyramid_levels = 2) {
+  return PyramidSubpixelView(disparity_map, left_image, right_image, prefilter_mode, prefilter_width, kernel_size,
+                             max_pyramid_levels, SUBPIXEL_BAYES_EM);
+}
 
 /// affine_subpixel (src/vw/Stereo/SubpixelView.h:120-126, SubpixelView.cc:242-254).
 inline PyramidSubpixelView

@@ -5,7 +5,7 @@ Workload (BASELINE config 2): 4096x4096 synthetic stereo pair, 7x7 SAD, +-64 px 
 (search_volume 129x1), one call of vw::stereo::calc_disparity per step, inputs (float32 PixelGray images)
 already resident in HBM, output (PixelMask<Vector2i>, 12 B/px) left in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N > 1: one rank per GPU.  Either launched by torch.distributed.run (RANK / WORLD_SIZE in the environment), or typed as
   above: bench.py then re-executes itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
   --master-addr 127.0.0.1 --master-port <free port>`.  The pair is split into N row strips (output rows
@@ -15,14 +15,17 @@ already resident in HBM, output (PixelMask<Vector2i>, 12 B/px) left in HBM.
   fallback; the choice is made collectively (an all-reduced flag), never per rank.  Block matching needs no exchange
   step inside the timed region: no data-path collective.  Total work is fixed: scaling = "strong".
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with three extra objects:
-  roofline     HBM roofline of the hot path's kernels: algorithmic bytes / HIP-event time
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs and prints the line; its `roofline` comes from the HIP events recorded inside the timed steps, and `cpu_baseline`
+is null.  --full adds everything else, after the timed steps:
+  roofline     traffic measured in the same run (two rocprofv3 --pmc child passes, see measure_traffic)
   cpu_baseline the CPU oracle (restated reference, tile-threaded like the reference) on a bounded sample; its full-image
                pass is also the checker of the timed result (every one of the 4090^2 pixels must be identical)
   extra        (N = 1) the other measured points of the path, each with its algorithmic bytes, kernel time and roofline
                fraction: the same pair at +-16 px (33 disparities: where the HBM bound is arithmetically in reach), BASELINE
                config 3 (11x11 NCC, then parabola_subpixel) and the SGM building block of config 4 (2048^2, census 7x7,
-               129 disparities).  They are not part of `value`.
+               129 disparities), and configs 4 and 5 as child runs.  They are not part of `value`.
+The --workload config4 / config5 modes likewise run their CPU baselines and oracle checks only with --full.
 """
 import argparse
 import json
@@ -616,7 +619,7 @@ def run_config4(args, torch, dist, vwa, core, stereo, synth, partition, rank, wo
     ok = float((got[..., 0].cpu().numpy() == tr).mean())
     if rank == 0:
         per_px = 20 + 11 * D
-        cpu = None if args.no_cpu_baseline else cpu_baseline_sgm(synth, cost_type, k, D)
+        cpu = cpu_baseline_sgm(synth, cost_type, k, D) if args.full and not args.no_cpu_baseline else None
         print(json.dumps({
             "metric": "disparity Mpix/s, 16384x16384 pair, %s SGM, 129 disparities, 8 row strips + collar" % ("census 7x7" if cost_type == 3 else "7x7 MAD block cost"),
             "value": npx * steps / dt / 1e6, "unit": "Mpix/s", "n_gpus": world, "steps": steps, "warmup": 1,
@@ -726,10 +729,10 @@ def run_config5(args, torch, dist, vwa, core, stereo, synth, partition, rank, wo
     ctxs = [vwa.Context(dev.index) for _ in range(T)]
     streams = [torch.cuda.Stream(device=dev) for _ in range(T)]
     keep = {}
-    # tiles compared with the oracle after the clock has stopped: corners, the four borders, interior (rank 0's strip; VWGPU_BENCH_CONFIG5_CHECK
-    # = how many, default 16 at full size, 6 below; 0 = none); one of them also for SGM
+    # tiles compared with the oracle after the clock has stopped (--full only): corners, the four borders, interior (rank 0's strip;
+    # VWGPU_BENCH_CONFIG5_CHECK = how many, default 16 at full size, 6 below; 0 = none); one of them also for SGM
     ntx, nty = W // TILE, (b - a) // TILE
-    ncheck = int(os.environ.get("VWGPU_BENCH_CONFIG5_CHECK", "16" if W >= 32768 else "6"))
+    ncheck = int(os.environ.get("VWGPU_BENCH_CONFIG5_CHECK", "16" if W >= 32768 else "6")) if args.full else 0
     cand = [(0, 0), (ntx - 1, nty - 1), (ntx - 1, 0), (0, nty - 1), (ntx // 2, 0), (0, nty // 2), (ntx - 1, nty // 2), (ntx // 2, nty - 1),
             (ntx // 2, nty // 2), (1, 1), (ntx // 3, nty // 4), (ntx - 2, nty // 3), (ntx // 4, nty - 2), (2 * ntx // 3, 2 * nty // 3), (ntx // 5, nty // 2), (3 * ntx // 4, nty // 5)]
     sample = []
@@ -808,7 +811,7 @@ def run_config5(args, torch, dist, vwa, core, stereo, synth, partition, rank, wo
         if sample_xy:
             checked = check_config5_tiles(synth, keep, sorted(sample_xy), sorted(sgm_xy), modes, W, H, D, TILE, LEVELS)
             assert checked["bm_identical"] == checked["bm_checked"] and checked["sgm_identical"] == checked["sgm_checked"], checked
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             l0, r0, _ = synth.stereo_pair_rows(W, H, D, 0, 2 * TILE)
             cpu = cpu_baseline_pyramid(np.ascontiguousarray(l0[:, :8 * TILE]), np.ascontiguousarray(r0[:, 64:64 + 8 * TILE]), modes, (-64, -1, 64, 1), LEVELS)
         print(json.dumps({
@@ -947,9 +950,7 @@ def halo_probe(spec):
     sys.exit(0 if ok else 4)
 
 
-def main():
-    if len(sys.argv) == 3 and sys.argv[1] == "--halo-probe":
-        return halo_probe(sys.argv[2])
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)     # 0.36 ms each: long enough to amortise the ~1.3 ms of barrier + first-launch latency
@@ -966,11 +967,22 @@ def main():
     ap.add_argument("--dump-outputs", default=None, dest="dump_outputs", metavar="DIR",
                     help="config2 only: after the timed steps, write what the last step computed to DIR/*.npy (a fixed, seeded sample of "
                          "%d output rows, float64; see dump_outputs)" % DUMP_ROWS)
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: the CPU baselines and oracle checks, the "
+                         "rocprofv3 traffic passes and the extra points with the config 4 / 5 child runs (--no-cpu-baseline, --no-traffic "
+                         "and --no-extra still drop their part)")
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.workload != "config2":
         ap.error("--dump-outputs covers the headline workload (config2) only")
+    return args
+
+
+def main():
+    if len(sys.argv) == 3 and sys.argv[1] == "--halo-probe":
+        return halo_probe(sys.argv[2])
+    args = parse_args()
 
     maybe_self_launch(args.gpus)              # `python bench.py --gpus N` as typed: re-executes under torch.distributed.run (never returns)
     # the host driver supports dmabuf IPC only: without this RCCL's peer mappings fail (hipIpcGetMemHandle: invalid argument)
@@ -1125,9 +1137,11 @@ def main():
         achieved = strip_bytes / (t_hot_us * 1e-6) / 1e9 if t_hot_us > 0 else 0.0
         evals = (r1 - r0) * ow * sx * sy
         traffic = traffic_src = None
-        if world == 1 and not args.no_traffic:
+        if not args.full:
+            traffic_src = "not measured (bench.py --full measures it)"
+        elif world == 1 and not args.no_traffic:
             traffic, traffic_src = measure_traffic()
-        if traffic is None:
+        if traffic is None and args.full:
             why = traffic_src
             tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")
             if os.path.exists(tfile):
@@ -1171,7 +1185,7 @@ def main():
         }
         if dumped:
             res["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped, "rows_sampled": DUMP_ROWS, "seed": DUMP_SEED}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0, for every N: the same leg (the other ranks wait at the final barrier)
             res["cpu_baseline"] = cpu_baseline(left, right)
             # the checker: one full-image pass of the oracle against the result of the timed work — every pixel of this rank's strip
@@ -1183,7 +1197,7 @@ def main():
             assert same, "the timed result differs from the CPU oracle"
         else:
             res["cpu_baseline"] = None
-        if world == 1 and not args.no_extra:
+        if world == 1 and args.full and not args.no_extra:
             try:                                  # the headline line must not depend on the side measurements
                 res["extra"] = extra_points(ctx, torch, stereo, core, vwa, synth, l_strip, r_strip, left, right, with_cpu=not args.no_cpu_baseline)
                 # BASELINE configs[3] and configs[4] themselves on this GPU: config 4 at full size (one pair = 0.45 s), config 5 on an
@@ -1196,7 +1210,7 @@ def main():
                 c5 = {"VWGPU_BENCH_CONFIG5_SIZE": os.environ["VWGPU_BENCH_CONFIG5_SIZE"]} if os.environ.get("VWGPU_BENCH_CONFIG5_SIZE") else {}
                 res["extra"].append(sub_workload("BASELINE configs[4] on one GPU at full size: 32768^2 pair (1024 tiles of 1024^2), pyramid_correlate tile loop, "
                                                  "LoG 1.4 + NCC 11x11 and census SGM; 16 + 1 tiles compared with the oracle",
-                                                 ["--workload", "config5", "--no-cpu-baseline"], c5, ckeys, timeout=1500))
+                                                 ["--workload", "config5", "--full", "--no-cpu-baseline"], c5, ckeys, timeout=1500))
             except Exception as e:  # noqa: BLE001
                 res["extra"] = [{"name": "extra points failed", "error": "%s: %s" % (type(e).__name__, str(e)[:300])}]
             # Every point once more in a dozen short entries: inside `config` (the part of the line the driver's record keeps whole) and as the

@@ -141,6 +141,15 @@ def test_dump_outputs_is_a_fixed_sample_of_the_last_step(tmp_path):
     assert np.array_equal(d, np.load(tmp_path / "b" / "disparity.npy"))
 
 
+def test_full_is_opt_in():
+    """A plain run does only what the headline needs; the CPU legs, traffic passes and extra points wait for --full."""
+    import bench
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert plain.full is False and (plain.steps, plain.warmup) == (3, 1)
+    assert bench.parse_args(["--full"]).full is True
+    assert bench.parse_args(["--workload", "config5", "--full", "--no-cpu-baseline"]).full is True
+
+
 def test_dump_outputs_refused_outside_the_headline_workload():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "config4", "--dump-outputs", "x"], capture_output=True,
                        text=True, timeout=300)

@@ -332,7 +332,8 @@ int vwgpu_parabola_subpixel(vwgpu_ctx* ctx, const float* disp, int w, int h, ptr
 
 /* ---- pyramid (affine-adaptive) sub-pixel refinement ---------------------------------------------------- */
 
-/* PyramidSubpixelView_Algorithm, src/vw/Stereo/SubpixelView.h:28-33.  PHASE is not implemented. */
+/* PyramidSubpixelView_Algorithm, src/vw/Stereo/SubpixelView.h:28-33.  vwgpu_pyramid_subpixel[_dev] does not run PHASE:
+ * phase refinement is reached through vwgpu_phase_subpixel[_dev] below, which takes its accuracy argument. */
 typedef enum vwgpu_subpixel_algorithm {
   VWGPU_SUBPIXEL_LUCAS_KANADE = 0, VWGPU_SUBPIXEL_FAST_AFFINE = 1, VWGPU_SUBPIXEL_BAYES_EM = 2, VWGPU_SUBPIXEL_PHASE = 3
 } vwgpu_subpixel_algorithm;
@@ -350,7 +351,7 @@ typedef enum vwgpu_subpixel_algorithm {
  *          A non-finite disparity (valid or not) inside a tile: VWGPU_ERR_ARGUMENT.
  *   kx, ky odd (even sizes: VWGPU_ERR_ARGUMENT); max_pyramid_levels < 0 counts as 0.
  *   algorithm  VWGPU_SUBPIXEL_LUCAS_KANADE, VWGPU_SUBPIXEL_FAST_AFFINE or VWGPU_SUBPIXEL_BAYES_EM; VWGPU_SUBPIXEL_PHASE
- *          returns VWGPU_ERR_NOIMPL.
+ *          returns VWGPU_ERR_NOIMPL (use vwgpu_phase_subpixel[_dev]).
  *   tiles  HOST array of ntiles boxes {x, y, w, h} inside the left image; pixels outside every box are not written.
  *   out    refined {dx, dy, 1}, invalid {0, 0, 0}.  Must not alias disp.
  *   stats  optional HOST array of 3: {fixpoint rounds summed over tiles and levels, the most rounds of one tile level,
@@ -370,6 +371,33 @@ int vwgpu_pyramid_subpixel(vwgpu_ctx* ctx, const float* disp, int w, int h, ptrd
                            const float* right, int rw, int rh, ptrdiff_t rstride,
                            int prefilter_mode, float prefilter_width, int kx, int ky, int max_pyramid_levels,
                            int algorithm, const int* tiles, int ntiles, float* out, ptrdiff_t ostride, long long* stats);
+
+/* Replaces rasterising vw::stereo::phase_subpixel(disparity, left, right, prefilter_mode, prefilter_width, kernel_size,
+ * max_pyramid_levels = 0, phase_subpixel_accuracy = 20) (src/vw/Stereo/SubpixelView.h:136-144): PyramidSubpixelView with
+ * SUBPIXEL_PHASE, one prerasterize(bbox) per box, whose refiner is subpixel_phase_2d (src/vw/Stereo/PhaseSubpixelView.cc:
+ * 231-326): two phase correlations per valid pixel (accuracy / 2, then accuracy on the bicubic-shifted right crop); a
+ * pixel whose total offset d has norm_2(d) > 3 or is NaN is invalidated, any other gets disparity -= d.
+ * Arguments, tiles, error codes and the out layout as vwgpu_pyramid_subpixel[_dev], without `algorithm`, plus
+ *   phase_subpixel_accuracy  the pad factor of the second call (the first gets accuracy / 2); a call whose factor is <= 2
+ *          stops after the first pass, as in the reference (so 2, 1, 0 and negative values are accepted).
+ * Limits: kx, ky <= 41 and phase_subpixel_accuracy <= 64; larger values return VWGPU_ERR_NOIMPL.
+ *   stats  optional HOST array of 3: {pixels refined, pixels invalidated by the 3-pixel / NaN rule, tiles}.
+ * The reference's OpenCV DFTs have no reproducible order; the transforms follow the order defined in DESIGN.md section 4.13
+ * (direct sums, one fmaf chain per output) and are bit-identical to tests/refimpl/phase_ref.cc.  As the reference's get_dft,
+ * every patch is first converted to 8 bits with percentile_scale_convert (2 % / 98 %, 256 bins).
+ * The device entry synchronises the context's stream. */
+int vwgpu_phase_subpixel_dev(vwgpu_ctx* ctx, const float* d_disp, int w, int h, ptrdiff_t dstride,
+                             const float* d_left, ptrdiff_t lstride,
+                             const float* d_right, int rw, int rh, ptrdiff_t rstride,
+                             int prefilter_mode, float prefilter_width, int kx, int ky, int max_pyramid_levels,
+                             int phase_subpixel_accuracy, const int* tiles, int ntiles, float* d_out, ptrdiff_t ostride,
+                             long long* stats);
+int vwgpu_phase_subpixel(vwgpu_ctx* ctx, const float* disp, int w, int h, ptrdiff_t dstride,
+                         const float* left, ptrdiff_t lstride,
+                         const float* right, int rw, int rh, ptrdiff_t rstride,
+                         int prefilter_mode, float prefilter_width, int kx, int ky, int max_pyramid_levels,
+                         int phase_subpixel_accuracy, const int* tiles, int ntiles, float* out, ptrdiff_t ostride,
+                         long long* stats);
 
 /* ---- disparity clean-up filters and the zone scheduler ------------------------------------------------- */
 

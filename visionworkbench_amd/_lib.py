@@ -21,6 +21,7 @@ SYMBOLS = [
     "vwgpu_prefilter_image_dev", "vwgpu_prefilter_image",
     "vwgpu_parabola_subpixel_dev", "vwgpu_parabola_subpixel",
     "vwgpu_pyramid_subpixel_dev", "vwgpu_pyramid_subpixel",
+    "vwgpu_phase_subpixel_dev", "vwgpu_phase_subpixel",
     "vwgpu_disparity_filter_dev", "vwgpu_disparity_filter",
     "vwgpu_disparity_mask_dev", "vwgpu_disparity_mask",
     "vwgpu_subdivide_regions",
@@ -144,6 +145,9 @@ def load():
     pys = [P, P, I, I, PD, P, PD, P, I, I, PD, I, F, I, I, I, I, P, I, P, PD, P]
     lib.vwgpu_pyramid_subpixel_dev.argtypes = pys
     lib.vwgpu_pyramid_subpixel.argtypes = pys
+    phs = pys    # the same layout: phase_subpixel_accuracy where vwgpu_pyramid_subpixel takes algorithm
+    lib.vwgpu_phase_subpixel_dev.argtypes = phs
+    lib.vwgpu_phase_subpixel.argtypes = phs
     D = ctypes.c_double
     df = [P, P, I, I, I, I, D, D, I, P]
     lib.vwgpu_disparity_filter_dev.argtypes = df

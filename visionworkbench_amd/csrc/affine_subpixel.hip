@@ -716,11 +716,13 @@ struct aff_level {
 
 }  // namespace
 
-// The tile loop of vwgpu_pyramid_subpixel_dev (include/vwgpu.h); arguments are checked by the caller.
-static int vwgpu_affine_subpixel_tiles(vwgpu_ctx* ctx, const float* d_disp, int w, int h, ptrdiff_t dstride,
-                                const float* d_left, ptrdiff_t lstride, const float* d_right, int rw, int rh, ptrdiff_t rstride,
-                                int mode, float width, int kx, int ky, int levels, int algorithm, const int* tiles, int ntiles,
-                                float* d_out, ptrdiff_t ostride, long long* stats) {
+// The tile loop of vwgpu_pyramid_subpixel_dev (include/vwgpu.h) and vwgpu_phase_subpixel_dev (phase_subpixel.hip, through
+// `refiner`); arguments are checked by the caller.
+int vwgpu_pyramid_subpixel_tiles(vwgpu_ctx* ctx, const float* d_disp, int w, int h, ptrdiff_t dstride,
+                                 const float* d_left, ptrdiff_t lstride, const float* d_right, int rw, int rh, ptrdiff_t rstride,
+                                 int mode, float width, int kx, int ky, int levels, int algorithm, const vwgpu_pyr_refiner* refiner,
+                                 const int* tiles, int ntiles, float* d_out, ptrdiff_t ostride, long long* stats) {
+  if (refiner) stats = nullptr;
   // ranges of all tiles: one launch, one readback
   const size_t tb = vwgpu_align_up((size_t)ntiles * 16, 256);
   int rc = vwgpu_arena_reserve(ctx, &ctx->misc, 2 * tb + 256 + vwgpu_align_up((size_t)kx * ky * 4, 256));
@@ -857,7 +859,10 @@ static int vwgpu_affine_subpixel_tiles(vwgpu_ctx* ctx, const float* d_disp, int 
       (void)div;
       x0 = std::max(x0 - 1, kx / 2); y0 = std::max(y0 - 1, ky / 2);
       x1 = std::min(L.w - kx / 2, x1 + 1); y1 = std::min(L.h - ky / 2, y1 + 1);
-      if (x1 > x0 && y1 > y0) {
+      if (x1 > x0 && y1 > y0 && refiner) {
+        const vwgpu_pyr_level_view view{L.w, L.h, L.L, L.R, L.dx, L.dy, L.v};
+        if ((rc = refiner->refine(ctx, view, kx, ky, x0, y0, x1, y1, refiner->user))) return rc;
+      } else if (x1 > x0 && y1 > y0) {
         hipLaunchKernelGGL(affine_deriv_kernel, aff_grid(L.w, L.h), dim3(AFF_BX, AFF_BY), 0, ctx->stream, L.L, L.w, L.h, L.Ix, L.Iy);
         const size_t n = (size_t)L.w * L.h;
         VWGPU_HIP(ctx, hipMemcpyAsync(sA, L.v, n, hipMemcpyDeviceToDevice, ctx->stream));
@@ -965,8 +970,8 @@ int vwgpu_pyramid_subpixel_dev(vwgpu_ctx* ctx, const float* d_disp, int w, int h
   if (stats) stats[0] = stats[1] = stats[2] = 0;
   if (ntiles == 0) return VWGPU_OK;
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  return vwgpu_affine_subpixel_tiles(ctx, d_disp, w, h, dstride, d_left, lstride, d_right, rw, rh, rstride, mode, width, kx, ky,
-                                     levels < 0 ? 0 : levels, algorithm, tiles, ntiles, d_out, ostride, stats);
+  return vwgpu_pyramid_subpixel_tiles(ctx, d_disp, w, h, dstride, d_left, lstride, d_right, rw, rh, rstride, mode, width, kx, ky,
+                                      levels < 0 ? 0 : levels, algorithm, nullptr, tiles, ntiles, d_out, ostride, stats);
 }
 
 int vwgpu_pyramid_subpixel(vwgpu_ctx* ctx, const float* disp, int w, int h, ptrdiff_t dstride,
@@ -992,8 +997,8 @@ int vwgpu_pyramid_subpixel(vwgpu_ctx* ctx, const float* disp, int w, int h, ptrd
   VWGPU_HIP(ctx, hipMemcpy2DAsync(so, (size_t)w * 12, out, (size_t)ostride * 12, (size_t)w * 12, h, hipMemcpyHostToDevice, ctx->stream));
   VWGPU_HIP(ctx, hipMemcpy2DAsync(sl, (size_t)w * 4, left, (size_t)lstride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
   VWGPU_HIP(ctx, hipMemcpy2DAsync(sr, (size_t)rw * 4, right, (size_t)rstride * 4, (size_t)rw * 4, rh, hipMemcpyHostToDevice, ctx->stream));
-  rc = vwgpu_affine_subpixel_tiles(ctx, sd, w, h, w, sl, w, sr, rw, rh, rw, mode, width, kx, ky, levels < 0 ? 0 : levels, algorithm,
-                                   tiles, ntiles, so, w, stats);
+  rc = vwgpu_pyramid_subpixel_tiles(ctx, sd, w, h, w, sl, w, sr, rw, rh, rw, mode, width, kx, ky, levels < 0 ? 0 : levels, algorithm,
+                                    nullptr, tiles, ntiles, so, w, stats);
   if (rc) return rc;
   VWGPU_HIP(ctx, hipMemcpy2DAsync(out, (size_t)ostride * 12, so, (size_t)w * 12, (size_t)w * 12, h, hipMemcpyDeviceToHost, ctx->stream));
   VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -231,6 +231,28 @@ int vwgpu_launch_parabola(vwgpu_ctx* ctx, const float* disp3f, int w, int h, ptr
                           const float* lras, int lrw, const float* rras, int rrw, int range_minx, int range_miny,
                           int kx, int ky, float* out3f, ptrdiff_t ostride_px, int integer_class = 0);
 
+// affine_subpixel.hip — the PyramidSubpixelView tile loop (tile ranges, prefiltered crops, pyramids, disparity_subsample /
+// disparity_upsample, the final write of each box).  One level of one tile, as a refiner sees it: the level's left and
+// right patches and its disparity map {dx, dy, v}, updated in place on the ROI plus its 1-pixel ring [x0, x1) x [y0, y1).
+struct vwgpu_pyr_level_view {
+  int w, h;
+  const float *L, *R;
+  float *dx, *dy;
+  uint8_t* v;
+};
+// A refiner of pixels that do not depend on each other (SUBPIXEL_PHASE): called for every level of every tile instead
+// of the raster-order fixpoint of the other algorithms.  Returns a vwgpu_status.
+struct vwgpu_pyr_refiner {
+  int (*refine)(vwgpu_ctx* ctx, const vwgpu_pyr_level_view& lv, int kx, int ky, int x0, int y0, int x1, int y1, void* user);
+  void* user;
+};
+// Arguments as vwgpu_pyramid_subpixel_dev, checked by the caller.  refiner == nullptr: `algorithm` runs in the fixpoint
+// and stats receives its three counters; otherwise `algorithm` is ignored and stats is not touched.
+int vwgpu_pyramid_subpixel_tiles(vwgpu_ctx* ctx, const float* d_disp, int w, int h, ptrdiff_t dstride,
+                                 const float* d_left, ptrdiff_t lstride, const float* d_right, int rw, int rh, ptrdiff_t rstride,
+                                 int mode, float width, int kx, int ky, int levels, int algorithm, const vwgpu_pyr_refiner* refiner,
+                                 const int* tiles, int ntiles, float* d_out, ptrdiff_t ostride, long long* stats);
+
 // bm_zones.hip — one row per search zone (or per R->L zone image); see the kernels for the field meaning
 struct vwgpu_zone_task {
   int ax, ay;          // origin of the zone's input crop in image A (may lie outside: coordinates are clamped)

@@ -201,13 +201,19 @@ def subpixel_tiles(cols, rows, block_size=None):
 
 
 def _pyramid_subpixel(name, disparity, left, right, prefilter_mode, prefilter_width, kernel_size, max_pyramid_levels,
-                      algorithm, block_size, ctx, stats):
+                      algorithm, block_size, ctx, stats, phase_accuracy=None):
+    # phase_accuracy given: vwgpu_phase_subpixel[_dev], which takes the accuracy where the generic entry takes algorithm
+    entry = "pyramid_subpixel" if phase_accuracy is None else "phase_subpixel"
+    selector = int(algorithm) if phase_accuracy is None else int(phase_accuracy)
     kx, ky = int(kernel_size[0]), int(kernel_size[1])
     if disparity.ndim != 3 or disparity.shape[2] != 3 or left.ndim != 2 or right.ndim != 2 \
             or tuple(disparity.shape[:2]) != tuple(left.shape):
         raise ArgumentErr("PyramidSubpixelView::PyramidSubpixelView(): Disparity image must match left image.")
     if kx < 1 or ky < 1 or kx % 2 != 1 or ky % 2 != 1:
         raise ArgumentErr("%s: Kernel input not sized with odd values." % name)
+    if phase_accuracy is not None and (kx > PHASE_MAX_KERNEL or ky > PHASE_MAX_KERNEL or selector > PHASE_MAX_ACCURACY):
+        raise core.NoImplErr("phase_subpixel: kernel %d x %d or accuracy %d above the limits %d x %d, %d"
+                             % (kx, ky, selector, PHASE_MAX_KERNEL, PHASE_MAX_KERNEL, PHASE_MAX_ACCURACY))
     h, w = left.shape
     rh, rw = right.shape
     tiles = subpixel_tiles(w, h, block_size)
@@ -221,17 +227,17 @@ def _pyramid_subpixel(name, disparity, left, right, prefilter_mode, prefilter_wi
             raise ArgumentErr("%s: float32 CUDA tensors required" % name)
         out = torch.zeros_like(d)
         ctx.set_stream(torch.cuda.current_stream(l.device).cuda_stream)
-        ctx.check(lib.vwgpu_pyramid_subpixel_dev(ctx._h, d.data_ptr(), w, h, 0, l.data_ptr(), 0, r.data_ptr(), rw, rh, 0,
+        ctx.check(getattr(lib, "vwgpu_%s_dev" % entry)(ctx._h, d.data_ptr(), w, h, 0, l.data_ptr(), 0, r.data_ptr(), rw, rh, 0,
                                                  int(prefilter_mode), float(prefilter_width), kx, ky, int(max_pyramid_levels),
-                                                 int(algorithm), tiles.ctypes.data, len(tiles), out.data_ptr(), 0, st))
+                                                 selector, tiles.ctypes.data, len(tiles), out.data_ptr(), 0, st))
     else:
         d = np.ascontiguousarray(disparity, np.float32)
         l = np.ascontiguousarray(left, np.float32)
         r = np.ascontiguousarray(right, np.float32)
         out = np.zeros_like(d)
-        ctx.check(lib.vwgpu_pyramid_subpixel(ctx._h, d.ctypes.data, w, h, 0, l.ctypes.data, 0, r.ctypes.data, rw, rh, 0,
+        ctx.check(getattr(lib, "vwgpu_" + entry)(ctx._h, d.ctypes.data, w, h, 0, l.ctypes.data, 0, r.ctypes.data, rw, rh, 0,
                                              int(prefilter_mode), float(prefilter_width), kx, ky, int(max_pyramid_levels),
-                                             int(algorithm), tiles.ctypes.data, len(tiles), out.ctypes.data, 0, st))
+                                             selector, tiles.ctypes.data, len(tiles), out.ctypes.data, 0, st))
     if stats is not None:
         stats[:] = list(st)
     return out
@@ -240,7 +246,8 @@ def _pyramid_subpixel(name, disparity, left, right, prefilter_mode, prefilter_wi
 def pyramid_subpixel(disparity, left, right, prefilter_mode, prefilter_width, kernel_size, max_pyramid_levels=2,
                      algorithm=SUBPIXEL_FAST_AFFINE, block_size=None, ctx=None, stats=None):
     """vw::stereo::PyramidSubpixelView (src/vw/Stereo/SubpixelView.h:36-108) with any implemented algorithm
-    (SUBPIXEL_LUCAS_KANADE, SUBPIXEL_FAST_AFFINE, SUBPIXEL_BAYES_EM; SUBPIXEL_PHASE raises NoImplErr), rasterised one
+    (SUBPIXEL_LUCAS_KANADE, SUBPIXEL_FAST_AFFINE, SUBPIXEL_BAYES_EM; SUBPIXEL_PHASE raises NoImplErr: phase refinement is
+    phase_subpixel, which takes its accuracy argument), rasterised one
     prerasterize(bbox) per tile (SubpixelView.cc:33-224).
 
     disparity: (rows, cols, 3) float32 PixelMask<Vector2f> {dx, dy, valid}, the left image's size; stored values of invalid
@@ -283,6 +290,23 @@ def bayes_em_subpixel(disparity, left, right, prefilter_mode, prefilter_width, k
     (see pyramid_subpixel for the arguments)."""
     return _pyramid_subpixel("bayes_em_subpixel", disparity, left, right, prefilter_mode, prefilter_width, kernel_size,
                              max_pyramid_levels, SUBPIXEL_BAYES_EM, block_size, ctx, stats)
+
+
+PHASE_MAX_KERNEL, PHASE_MAX_ACCURACY = 41, 64   # include/vwgpu.h: larger sizes raise NoImplErr
+
+
+def phase_subpixel(disparity, left, right, prefilter_mode, prefilter_width, kernel_size, max_pyramid_levels=0,
+                   phase_subpixel_accuracy=20, block_size=None, ctx=None, stats=None):
+    """vw::stereo::phase_subpixel (src/vw/Stereo/SubpixelView.h:136-144): PyramidSubpixelView with SUBPIXEL_PHASE, refined
+    by subpixel_phase_2d (src/vw/Stereo/PhaseSubpixelView.cc:231-326).  Arguments and result as pyramid_subpixel, plus
+    phase_subpixel_accuracy (the pad factor of the second phase correlation; the first gets accuracy // 2 rounded toward
+    zero, and a factor <= 2 stops after the coarse pass).  Kernels up to 41 x 41 and accuracies up to 64; larger values
+    raise NoImplErr.  stats (optional list) receives [pixels refined, pixels invalidated (|d| > 3 or NaN), tiles].
+    Each patch is converted to 8 bits as the reference's get_dft does; the transforms follow the order defined in
+    DESIGN.md section 4.13, not OpenCV's."""
+    return _pyramid_subpixel("phase_subpixel", disparity, left, right, prefilter_mode, prefilter_width, kernel_size,
+                             max_pyramid_levels, SUBPIXEL_PHASE, block_size, ctx, stats,
+                             phase_accuracy=int(phase_subpixel_accuracy))
 
 
 def _filter_call(name, disparity, hh, hv, pthr, rthr, cleanup, ctx):
@@ -602,6 +626,6 @@ def calc_disparity_sgm(cost_type, left_in, right_in, left_region, search_volume,
     return (res, sub[:n].reshape(oh.value, ow.value, 3).copy()) if with_subpixel else res
 
 
-__all__ = ["affine_subpixel", "bayes_em_subpixel", "lk_subpixel", "pyramid_subpixel", "calc_disparity", "calc_disparity_sgm", "cross_corr_consistency_check", "parabola_subpixel", "rm_outliers_using_thresh",
+__all__ = ["affine_subpixel", "bayes_em_subpixel", "lk_subpixel", "phase_subpixel", "pyramid_subpixel", "calc_disparity", "calc_disparity_sgm", "cross_corr_consistency_check", "parabola_subpixel", "rm_outliers_using_thresh",
            "disparity_cleanup_using_thresh", "disparity_mask", "disparity_blob_filter", "subdivide_regions", "pyramid_correlate", "pyramid_correlate_batch",
            "BBox2i", "CostFunctionType"]

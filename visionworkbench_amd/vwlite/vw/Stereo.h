@@ -10,6 +10,7 @@
 //   parabola_subpixel            src/vw/Stereo/ParabolaSubpixelView.h:112-117
 //   PyramidSubpixelView, lk_subpixel, affine_subpixel, bayes_em_subpixel
 //                                src/vw/Stereo/SubpixelView.h:28-134 (SUBPIXEL_PHASE: NoImplErr)
+//   phase_subpixel               src/vw/Stereo/SubpixelView.h:136-144 (vwgpu_phase_subpixel)
 //   prefilter_image              src/vw/Stereo/PreFilter.h:76-95
 //   rm_outliers_using_thresh / disparity_cleanup_using_thresh / disparity_mask
 //                                src/vw/Stereo/DisparityMap.h:387-441, 236-253
@@ -589,7 +590,8 @@ enum PyramidSubpixelView_Algorithm {     // src/vw/Stereo/SubpixelView.h:28-33
 /// PyramidSubpixelView (src/vw/Stereo/SubpixelView.h:36-108): lazy; rasterize(dest, bbox) runs one
 /// prerasterize(bbox) of the reference (SubpixelView.cc:33-224) on the engine (vwgpu_pyramid_subpixel).  The result of a
 /// pixel depends on the tile it is rasterised in, as in the reference.  SUBPIXEL_LUCAS_KANADE, SUBPIXEL_FAST_AFFINE and
-/// SUBPIXEL_BAYES_EM are implemented; the engine reports SUBPIXEL_PHASE as NoImplErr.
+/// SUBPIXEL_BAYES_EM are implemented; the engine reports SUBPIXEL_PHASE as NoImplErr through this constructor: phase
+/// refinement is reached through phase_subpixel(...), which takes the accuracy argument (vwgpu_phase_subpixel).
 class PyramidSubpixelView : public ImageViewBase<PyramidSubpixelView> {
   ImageViewRef<PixelMask<Vector2f>> m_disparity_map;
   ImageViewRef<PixelGray<float>> m_left_image, m_right_image;
@@ -598,6 +600,11 @@ class PyramidSubpixelView : public ImageViewBase<PyramidSubpixelView> {
   PyramidSubpixelView_Algorithm m_algorithm;
   PrefilterModeType m_prefilter_mode;
   float m_prefilter_width;
+  bool m_phase_entry = false;        // built by phase_subpixel: vwgpu_phase_subpixel with m_phase_accuracy
+  int32 m_phase_accuracy = 20;
+  friend PyramidSubpixelView phase_subpixel(ImageViewRef<PixelMask<Vector2f>> const&, ImageViewRef<PixelGray<float>> const&,
+                                            ImageViewRef<PixelGray<float>> const&, PrefilterModeType, float, Vector2i const&,
+                                            int, int);
 public:
   typedef PixelMask<Vector2f> pixel_type;
   typedef pixel_type result_type;
@@ -629,12 +636,20 @@ public:
     ImageView<PixelGray<float>> l = m_left_image.prerasterize(all), r = m_right_image.prerasterize(rall);
     const int box[4] = {bbox.min().x(), bbox.min().y(), bbox.width(), bbox.height()};
     vwgpu_ctx* ctx = detail::thread_context();
-    detail::check(ctx, vwgpu_pyramid_subpixel(ctx, reinterpret_cast<const float*>(d.data()), d.cols(), d.rows(), 0,
+    if (m_phase_entry)
+      detail::check(ctx, vwgpu_phase_subpixel(ctx, reinterpret_cast<const float*>(d.data()), d.cols(), d.rows(), 0,
                                               reinterpret_cast<const float*>(l.data()), 0,
                                               reinterpret_cast<const float*>(r.data()), r.cols(), r.rows(), 0,
                                               (int)m_prefilter_mode, m_prefilter_width, m_kernel_size[0], m_kernel_size[1],
-                                              m_max_pyramid_levels, (int)m_algorithm, box, 1,
+                                              m_max_pyramid_levels, m_phase_accuracy, box, 1,
                                               reinterpret_cast<float*>(full.data()), 0, NULL));
+    else
+      detail::check(ctx, vwgpu_pyramid_subpixel(ctx, reinterpret_cast<const float*>(d.data()), d.cols(), d.rows(), 0,
+                                                reinterpret_cast<const float*>(l.data()), 0,
+                                                reinterpret_cast<const float*>(r.data()), r.cols(), r.rows(), 0,
+                                                (int)m_prefilter_mode, m_prefilter_width, m_kernel_size[0], m_kernel_size[1],
+                                                m_max_pyramid_levels, (int)m_algorithm, box, 1,
+                                                reinterpret_cast<float*>(full.data()), 0, NULL));
     for (int32 y = 0; y < bbox.height(); ++y)
       for (int32 x = 0; x < bbox.width(); ++x) tile(x, y) = full(bbox.min().x() + x, bbox.min().y() + y);
     return tile;
@@ -674,6 +689,19 @@ affine_subpixel(ImageViewRef<PixelMask<Vector2f>> const& disparity_map, ImageVie
                 Vector2i const& kernel_size, int max_pyramid_levels = 2) {
   return PyramidSubpixelView(disparity_map, left_image, right_image, prefilter_mode, prefilter_width, kernel_size,
                              max_pyramid_levels, SUBPIXEL_FAST_AFFINE);
+}
+
+/// phase_subpixel (src/vw/Stereo/SubpixelView.h:136-144, SubpixelView.cc:275-289): PyramidSubpixelView with SUBPIXEL_PHASE
+/// and the phase accuracy, rasterised through vwgpu_phase_subpixel (kernels up to 41 x 41, accuracy up to 64).
+inline PyramidSubpixelView
+phase_subpixel(ImageViewRef<PixelMask<Vector2f>> const& disparity_map, ImageViewRef<PixelGray<float>> const& left_image,
+               ImageViewRef<PixelGray<float>> const& right_image, PrefilterModeType prefilter_mode, float prefilter_width,
+               Vector2i const& kernel_size, int max_pyramid_levels = 0, int phase_subpixel_accuracy = 20) {
+  PyramidSubpixelView v(disparity_map, left_image, right_image, prefilter_mode, prefilter_width, kernel_size,
+                        max_pyramid_levels, SUBPIXEL_PHASE);
+  v.m_phase_entry = true;
+  v.m_phase_accuracy = phase_subpixel_accuracy;
+  return v;
 }
 
 }  // namespace stereo

@@ -399,6 +399,73 @@ int vwgpu_phase_subpixel(vwgpu_ctx* ctx, const float* disp, int w, int h, ptrdif
                          int phase_subpixel_accuracy, const int* tiles, int ntiles, float* out, ptrdiff_t ostride,
                          long long* stats);
 
+/* ---- disparity quality evaluation ------------------------------------------------------------------------- */
+
+/* CorrEval's metric strings, src/vw/Stereo/CorrEval.h:88-90: "ncc", "stddev", "parabola_curvature", "cramer_rao". */
+typedef enum vwgpu_corr_eval_metric {
+  VWGPU_CORR_EVAL_NCC = 0, VWGPU_CORR_EVAL_STDDEV = 1, VWGPU_CORR_EVAL_PARABOLA_CURVATURE = 2, VWGPU_CORR_EVAL_CRAMER_RAO = 3
+} vwgpu_corr_eval_metric;
+
+/* Replaces rasterising vw::stereo::corr_eval(left, right, disp, kernel_size, metric, sample_rate, round_to_int,
+ * prefilter_mode, prefilter_kernel_width) (src/vw/Stereo/CorrEval.h:117-128): one CorrEval::prerasterize(bbox) per box
+ * (src/vw/Stereo/CorrEval.cc:139-317).  For each sampled valid pixel p of a box: the NCC of the left kx x ky patch around
+ * p against the bilinearly resampled right patch around p + d(p) (NCC), the mean of the two patches' standard
+ * deviations (STDDEV), or sigma = sqrt(1 / k_x + 1 / k_y) from the NCC curvature k_x = 2 C - ncc(d + (1, 0)) -
+ * ncc(d - (1, 0)), k_y alike (PARABOLA_CURVATURE), times sqrt(max(1 - C, 0)) (CRAMER_RAO).
+ *   disp   w x h x {dx, dy, valid (!= 0)} float (PixelMask<Vector2f>), the left image's size.
+ *   left   w x h float; left_valid optional w x h uint8 (!= 0 valid; NULL: all valid) with the left image's stride.
+ *   right  rw x rh float (any size); right_valid optional, with the right image's stride.  Strides in ELEMENTS (pixels
+ *          for disp / out); 0 = packed.
+ *   kx, ky positive and odd (VWGPU_ERR_ARGUMENT otherwise); at most 63 x 63 (a workgroup's staged left block then fits
+ *          64 KB of LDS at sample rates up to 3); larger kernels return VWGPU_ERR_NOIMPL.
+ *   metric a vwgpu_corr_eval_metric (others: VWGPU_ERR_ARGUMENT).  sample_rate >= 1 (the reference divides by zero).
+ *   prefilter_mode  accepted and unused, as in the reference; prefilter_kernel_width only sets the right crop's padding
+ *          (int)ceil(width) + 5, which must lie in [0, INT_MAX] (a negative padding makes the reference throw when a
+ *          patch leaves its left crop): VWGPU_ERR_ARGUMENT otherwise.
+ *   tiles  HOST array of ntiles boxes {x, y, w, h} inside the left image; pixels outside every box are not written.
+ *          The boxes must not overlap: a pixel inside two boxes receives the result of one of them, unspecified which
+ *          (the reference's sequential prerasterize calls would leave the last one's).
+ *   out    w x h x {value, valid in {0.f, 1.f}} (PixelMask<float>); every pixel of a box is written, invalid = {0, 0}.
+ *   stats  optional HOST array of 4: {sampled valid pixels evaluated, valid results, boxes, boxes whose right box is
+ *          degenerate (see below)}.
+ * What the reference computes, and the port reproduces bit for bit (tests/refimpl/corr_eval_ref.cc):
+ *   - a result depends on its box: a pixel is evaluated only if its column and row inside the box are multiples of
+ *     sample_rate, and the right image is read through the box's crop right_box: floor and ceil of bbox.min + (col, row)
+ *     + d over the box's sampled valid pixels, expanded by the half kernel, 1, 2, the padding and, for the two curvature
+ *     metrics, 1 more.  Interpolation takes coordinates relative to right_box.min, formed in double as
+ *     (double(x) + double(dx)) - right_box.min; its integer shortcut compares the double coordinates, its weights are
+ *     float(i) - float(floor(i)), and the blend follows BilinearInterpolationImpl's float operation order;
+ *   - BBox::expand does nothing on an empty box (min >= max on an axis): when every sampled valid pixel of a box lands on
+ *     one integer coordinate in an axis (one sampled row with dy = 0, say), the crop is empty and every right sample is
+ *     nodata, so NCC is -1 and the box's results are invalid.  With round_to_int the reference then reads an empty image
+ *     out of bounds (undefined); here such reads are nodata too.  A box without sampled valid pixels is all invalid;
+ *   - NCC = num / sqrt(den1 den2) in double, c outer, r inner, over the STORED value of every sample: the reference's
+ *     validity test is misparenthesised and always passes, so masked left pixels, bilinear blends of invalid right
+ *     neighbourhoods and nodata (0) all count; -1 unless den1 > 0 and den2 > 0; a result is valid when >= 0.  No mean
+ *     is subtracted.  STDDEV skips invalid samples (two passes in double, sqrt(sum / n));
+ *   - the neighbour disparities of the curvature metrics are d + shift in float, so fl32(dx + 1) need not be dx + 1;
+ *     sigma is valid when C and the four neighbour NCCs are >= 0 and k_x, k_y > 0;
+ *   - round_to_int rounds d half away from zero (roundf) before the box is built and reads the crop without
+ *     interpolation;
+ *   - the result is the double value cast to float.
+ * A non-finite sampled valid disparity (after rounding), a right coordinate outside int32 or a right box that does not
+ * fit int32: VWGPU_ERR_ARGUMENT (undefined in the reference); values at invalid or unsampled pixels are never read.
+ * Two launches on the context's stream (per-box right boxes, then the evaluation).  Both entries synchronise the
+ * context's stream once, after the evaluation, to report the box pass's argument checks; stats add no synchronisation
+ * of their own. */
+int vwgpu_corr_eval_dev(vwgpu_ctx* ctx, const float* d_disp, int w, int h, ptrdiff_t dstride,
+                        const float* d_left, const uint8_t* d_left_valid, ptrdiff_t lstride,
+                        const float* d_right, const uint8_t* d_right_valid, int rw, int rh, ptrdiff_t rstride,
+                        int kx, int ky, int metric, int sample_rate, int round_to_int,
+                        int prefilter_mode, float prefilter_kernel_width, const int* tiles, int ntiles,
+                        float* d_out, ptrdiff_t ostride, long long* stats);
+int vwgpu_corr_eval(vwgpu_ctx* ctx, const float* disp, int w, int h, ptrdiff_t dstride,
+                    const float* left, const uint8_t* left_valid, ptrdiff_t lstride,
+                    const float* right, const uint8_t* right_valid, int rw, int rh, ptrdiff_t rstride,
+                    int kx, int ky, int metric, int sample_rate, int round_to_int,
+                    int prefilter_mode, float prefilter_kernel_width, const int* tiles, int ntiles,
+                    float* out, ptrdiff_t ostride, long long* stats);
+
 /* ---- disparity clean-up filters and the zone scheduler ------------------------------------------------- */
 
 /* Replaces rasterising vw::stereo::rm_outliers_using_thresh (cleanup == 0) or

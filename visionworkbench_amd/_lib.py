@@ -22,6 +22,7 @@ SYMBOLS = [
     "vwgpu_parabola_subpixel_dev", "vwgpu_parabola_subpixel",
     "vwgpu_pyramid_subpixel_dev", "vwgpu_pyramid_subpixel",
     "vwgpu_phase_subpixel_dev", "vwgpu_phase_subpixel",
+    "vwgpu_corr_eval_dev", "vwgpu_corr_eval",
     "vwgpu_disparity_filter_dev", "vwgpu_disparity_filter",
     "vwgpu_disparity_mask_dev", "vwgpu_disparity_mask",
     "vwgpu_subdivide_regions",
@@ -148,6 +149,9 @@ def load():
     phs = pys    # the same layout: phase_subpixel_accuracy where vwgpu_pyramid_subpixel takes algorithm
     lib.vwgpu_phase_subpixel_dev.argtypes = phs
     lib.vwgpu_phase_subpixel.argtypes = phs
+    ce = [P, P, I, I, PD, P, P, PD, P, P, I, I, PD, I, I, I, I, I, I, F, P, I, P, PD, P]
+    lib.vwgpu_corr_eval_dev.argtypes = ce
+    lib.vwgpu_corr_eval.argtypes = ce
     D = ctypes.c_double
     df = [P, P, I, I, I, I, D, D, I, P]
     lib.vwgpu_disparity_filter_dev.argtypes = df

@@ -309,6 +309,78 @@ def phase_subpixel(disparity, left, right, prefilter_mode, prefilter_width, kern
                              phase_accuracy=int(phase_subpixel_accuracy))
 
 
+CORR_EVAL_METRICS = {"ncc": 0, "stddev": 1, "parabola_curvature": 2, "cramer_rao": 3}   # CorrEval.h:88-90
+CORR_EVAL_MAX_KERNEL = 63   # include/vwgpu.h: larger kernels raise NoImplErr
+
+
+def corr_eval(left, right, disparity, kernel_size, metric, sample_rate=1, round_to_int=False, prefilter_mode=0,
+              prefilter_kernel_width=0.0, left_valid=None, right_valid=None, block_size=None, ctx=None, stats=None):
+    """vw::stereo::corr_eval (src/vw/Stereo/CorrEval.h:117-128), rasterised one CorrEval::prerasterize(bbox) per tile
+    (CorrEval.cc:139-317); the tiles follow block_size as in pyramid_subpixel (the whole image when None).
+
+    left: (rows, cols) float32, right: any (rrows, rcols) float32; left_valid / right_valid: optional masks of the same
+    shapes (nonzero = valid; None = all valid), the PixelMask<float> validity of the images.  disparity: (rows, cols, 3)
+    float32 PixelMask<Vector2f> {dx, dy, valid}.  metric: "ncc", "stddev", "parabola_curvature" or "cramer_rao".
+    Returns (rows, cols, 2) float32 PixelMask<float> {value, valid}; pixels outside every tile stay 0.  numpy inputs run
+    the host entry, CUDA tensors the device entry (which synchronises the stream once to report argument errors).
+    The quirks the result keeps (the right crop per tile, the NCC that counts invalid samples, the float neighbour
+    disparities of the curvature metrics) are listed at vwgpu_corr_eval in include/vwgpu.h.  Kernels up to 63 x 63.
+    stats (optional list) receives [pixels evaluated, valid results, tiles, tiles with a degenerate right box]."""
+    kx, ky = int(kernel_size[0]), int(kernel_size[1])
+    if disparity.ndim != 3 or disparity.shape[2] != 3 or left.ndim != 2 or right.ndim != 2 \
+            or tuple(disparity.shape[:2]) != tuple(left.shape):
+        raise ArgumentErr("CorrEval: Left image and disparity must have the same dimensions.")
+    if kx <= 0 or ky <= 0 or kx % 2 != 1 or ky % 2 != 1:
+        raise ArgumentErr("CorrEval: The kernel dimensions must be positive and odd.")
+    if metric not in CORR_EVAL_METRICS:
+        raise ArgumentErr("CorrEval: Invalid metric: %s." % metric)
+    if (left_valid is not None and tuple(left_valid.shape) != tuple(left.shape)) \
+            or (right_valid is not None and tuple(right_valid.shape) != tuple(right.shape)):
+        raise ArgumentErr("corr_eval: a validity mask does not match its image")
+    if kx > CORR_EVAL_MAX_KERNEL or ky > CORR_EVAL_MAX_KERNEL:
+        raise core.NoImplErr("corr_eval: kernel %d x %d is larger than %d x %d"
+                             % (kx, ky, CORR_EVAL_MAX_KERNEL, CORR_EVAL_MAX_KERNEL))
+    h, w = left.shape
+    rh, rw = right.shape
+    tiles = subpixel_tiles(w, h, block_size)
+    st = (ctypes.c_longlong * 4)()
+    if _is_tensor(left):
+        # every operand, the masks included, must live on the left image's device: the kernels read them all
+        operands = [(disparity, True), (left, True), (right, True), (left_valid, False), (right_valid, False)]
+        for x, is_float in operands:
+            if x is not None and (not _is_tensor(x) or not x.is_cuda or x.device != left.device
+                                  or (is_float and x.dtype != torch.float32)):
+                raise ArgumentErr("corr_eval: float32 images and disparity, and masks, as CUDA tensors on %s" % left.device)
+    elif any(_is_tensor(x) for x in (disparity, right, left_valid, right_valid)):
+        raise ArgumentErr("corr_eval: with a numpy left image every operand must be a numpy array")
+    ctx = _ctx_for(left, ctx)
+    lib = ctx._lib
+    args = (CORR_EVAL_METRICS[metric], int(sample_rate), 1 if round_to_int else 0, int(prefilter_mode),
+            float(prefilter_kernel_width), tiles.ctypes.data, len(tiles))
+    if _is_tensor(left):
+        d, l, r = disparity.contiguous(), left.contiguous(), right.contiguous()
+        lv = None if left_valid is None else (left_valid != 0).to(torch.uint8).contiguous()
+        rv = None if right_valid is None else (right_valid != 0).to(torch.uint8).contiguous()
+        out = torch.zeros((h, w, 2), dtype=torch.float32, device=l.device)
+        ctx.set_stream(torch.cuda.current_stream(l.device).cuda_stream)
+        ctx.check(lib.vwgpu_corr_eval_dev(ctx._h, d.data_ptr(), w, h, 0, l.data_ptr(), None if lv is None else lv.data_ptr(), 0,
+                                          r.data_ptr(), None if rv is None else rv.data_ptr(), rw, rh, 0, kx, ky, *args,
+                                          out.data_ptr(), 0, st))
+    else:
+        d = np.ascontiguousarray(disparity, np.float32)
+        l = np.ascontiguousarray(left, np.float32)
+        r = np.ascontiguousarray(right, np.float32)
+        lv = None if left_valid is None else np.ascontiguousarray(np.asarray(left_valid) != 0, np.uint8)
+        rv = None if right_valid is None else np.ascontiguousarray(np.asarray(right_valid) != 0, np.uint8)
+        out = np.zeros((h, w, 2), np.float32)
+        ctx.check(lib.vwgpu_corr_eval(ctx._h, d.ctypes.data, w, h, 0, l.ctypes.data, None if lv is None else lv.ctypes.data, 0,
+                                      r.ctypes.data, None if rv is None else rv.ctypes.data, rw, rh, 0, kx, ky, *args,
+                                      out.ctypes.data, 0, st))
+    if stats is not None:
+        stats[:] = list(st)
+    return out
+
+
 def _filter_call(name, disparity, hh, hv, pthr, rthr, cleanup, ctx):
     if disparity.ndim != 3 or disparity.shape[2] != 3:
         raise ArgumentErr("%s: disparity must be (rows, cols, 3) int32" % name)
@@ -626,6 +698,6 @@ def calc_disparity_sgm(cost_type, left_in, right_in, left_region, search_volume,
     return (res, sub[:n].reshape(oh.value, ow.value, 3).copy()) if with_subpixel else res
 
 
-__all__ = ["affine_subpixel", "bayes_em_subpixel", "lk_subpixel", "phase_subpixel", "pyramid_subpixel", "calc_disparity", "calc_disparity_sgm", "cross_corr_consistency_check", "parabola_subpixel", "rm_outliers_using_thresh",
+__all__ = ["affine_subpixel", "bayes_em_subpixel", "corr_eval", "lk_subpixel", "phase_subpixel", "pyramid_subpixel", "calc_disparity", "calc_disparity_sgm", "cross_corr_consistency_check", "parabola_subpixel", "rm_outliers_using_thresh",
            "disparity_cleanup_using_thresh", "disparity_mask", "disparity_blob_filter", "subdivide_regions", "pyramid_correlate", "pyramid_correlate_batch",
            "BBox2i", "CostFunctionType"]

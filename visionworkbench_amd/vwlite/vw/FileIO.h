@@ -5,7 +5,8 @@
 // DiskImageResource plug-ins; none of those libraries exist here, so the on-disk formats are the two header-plus-raster
 // ones that need no library: PGM "P5" (8- or 16-bit grey, big-endian, rows top to bottom) and PFM "Pf" / "PF" (1 or 3
 // float32 channels, little-endian when the scale line is negative, rows BOTTOM to top).  A 3-channel PFM is exactly a
-// PixelMask<Vector2f> disparity image {dx, dy, valid}.
+// PixelMask<Vector2f> disparity image {dx, dy, valid}; a PixelMask<float> image (a masked image, corr_eval's result) has
+// two channels {value, valid}, stored as a 3-channel PFM {value, valid, 0} (PFM has no 2-channel form).
 #ifndef VWLITE_FILEIO_H
 #define VWLITE_FILEIO_H
 
@@ -71,15 +72,23 @@ inline Header read_header(std::string const& path) {
 // pixel <-> channel helpers for the pixel types the stereo path stores
 template <class PixelT> struct Channels { static const int n = 1; };
 template <class T> struct Channels<PixelMask<Vector<T, 2>>> { static const int n = 3; };
+template <> struct Channels<PixelMask<float>> { static const int n = 3; };
 inline void put(float* dst, float v) { dst[0] = v; }
 inline void put(float* dst, PixelGray<float> const& v) { dst[0] = v.v(); }
 inline void put(float* dst, PixelMask<Vector2f> const& v) { dst[0] = v.child()[0]; dst[1] = v.child()[1]; dst[2] = is_valid(v) ? 1.0f : 0.0f; }
+inline void put(float* dst, PixelMask<float> const& v) { dst[0] = v.child(); dst[1] = is_valid(v) ? 1.0f : 0.0f; dst[2] = 0.0f; }
 inline void get(const float* src, float& v) { v = src[0]; }
 inline void get(const float* src, PixelGray<float>& v) { v = PixelGray<float>(src[0]); }
 inline void get(const float* src, uint8& v) { v = (uint8)src[0]; }
 inline void get(const float* src, PixelMask<Vector2f>& v) {
   v = PixelMask<Vector2f>(Vector2f(src[0], src[1]));
   if (src[2] == 0.0f) v.invalidate();
+}
+// a pixel from `nch` file channels: a PixelMask<float> read from a 1-channel file is valid everywhere
+template <class PixelT> void get(const float* src, int, PixelT& v) { get(src, v); }
+inline void get(const float* src, int nch, PixelMask<float>& v) {
+  v = PixelMask<float>(src[0]);
+  if (nch == 3 && src[1] == 0.0f) v.invalidate();
 }
 }  // namespace fileio
 
@@ -135,7 +144,7 @@ public:
       }
       for (int32 c = 0; c < w; ++c) {
         PixelT px;
-        fileio::get(&rowf[(size_t)c * nch], px);
+        fileio::get(&rowf[(size_t)c * nch], nch, px);
         dest(c, r) = px;
       }
     }

@@ -11,6 +11,7 @@
 //   PyramidSubpixelView, lk_subpixel, affine_subpixel, bayes_em_subpixel
 //                                src/vw/Stereo/SubpixelView.h:28-134 (SUBPIXEL_PHASE: NoImplErr)
 //   phase_subpixel               src/vw/Stereo/SubpixelView.h:136-144 (vwgpu_phase_subpixel)
+//   CorrEval, corr_eval          src/vw/Stereo/CorrEval.h:56-128 (vwgpu_corr_eval)
 //   prefilter_image              src/vw/Stereo/PreFilter.h:76-95
 //   rm_outliers_using_thresh / disparity_cleanup_using_thresh / disparity_mask
 //                                src/vw/Stereo/DisparityMap.h:387-441, 236-253
@@ -27,6 +28,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -702,6 +704,95 @@ phase_subpixel(ImageViewRef<PixelMask<Vector2f>> const& disparity_map, ImageView
   v.m_phase_entry = true;
   v.m_phase_accuracy = phase_subpixel_accuracy;
   return v;
+}
+
+/// CorrEval (src/vw/Stereo/CorrEval.h:56-115): lazy; prerasterize(bbox) is one vwgpu_corr_eval call with the one box
+/// (CorrEval.cc:139-317).  The result of a pixel depends on the tile it is rasterised in, as in the reference (the right
+/// crop is built per tile, and only pixels whose column and row inside the tile are multiples of sample_rate are
+/// evaluated).  Kernels up to 63 x 63 (NoImplErr above).
+static_assert(sizeof(PixelMask<float>) == 8, "PixelMask<float> is the engine's {value, valid} pair");
+class CorrEval : public ImageViewBase<CorrEval> {
+  ImageViewRef<PixelMask<float>> m_left, m_right;
+  ImageViewRef<PixelMask<Vector2f>> m_disp;
+  Vector2i m_kernel_size;
+  std::string m_metric;
+  int m_sample_rate;
+  bool m_round_to_int;
+  int m_prefilter_mode;
+  float m_prefilter_kernel_width;
+public:
+  typedef PixelMask<float> pixel_type;
+  typedef PixelMask<float> result_type;
+  typedef CropView<ImageView<pixel_type>> prerasterize_type;
+
+  CorrEval(ImageViewRef<PixelMask<float>> left, ImageViewRef<PixelMask<float>> right, ImageViewRef<PixelMask<Vector2f>> disp,
+           Vector2i const& kernel_size, std::string const& metric, int sample_rate, bool round_to_int, int prefilter_mode = 0,
+           float prefilter_kernel_width = 0.0)
+      : m_left(left), m_right(right), m_disp(disp), m_kernel_size(kernel_size), m_metric(metric), m_sample_rate(sample_rate),
+        m_round_to_int(round_to_int), m_prefilter_mode(prefilter_mode), m_prefilter_kernel_width(prefilter_kernel_width) {
+    VW_ASSERT(m_left.cols() == m_disp.cols() && m_left.rows() == m_disp.rows(),
+              ArgumentErr() << "CorrEval: Left image and disparity must have the same dimensions.\n");
+    VW_ASSERT(m_kernel_size[0] > 0 && m_kernel_size[0] % 2 == 1 && m_kernel_size[1] > 0 && m_kernel_size[1] % 2 == 1,
+              ArgumentErr() << "CorrEval: The kernel dimensions must be positive and odd.\n");
+    VW_ASSERT(metric_code() >= 0, ArgumentErr() << "CorrEval: Invalid metric: " << m_metric << ".\n");
+  }
+  int metric_code() const {
+    return m_metric == "ncc" ? VWGPU_CORR_EVAL_NCC : m_metric == "stddev" ? VWGPU_CORR_EVAL_STDDEV
+         : m_metric == "parabola_curvature" ? VWGPU_CORR_EVAL_PARABOLA_CURVATURE
+         : m_metric == "cramer_rao" ? VWGPU_CORR_EVAL_CRAMER_RAO : -1;
+  }
+  int32 cols() const { return m_left.cols(); }
+  int32 rows() const { return m_left.rows(); }
+  int32 planes() const { return 1; }
+  pixel_type operator()(int32 /*i*/, int32 /*j*/, int32 /*p*/ = 0) const {
+    vw_throw(NoImplErr() << "CorrEval::operator() is not implemented.");   // CorrEval.h:103-106
+    return pixel_type();
+  }
+  /// The tile at bbox, indexed from the tile's own origin.  The operands are rasterised whole (the right crop depends on
+  /// the tile's disparities), and the engine writes into an image of the full size of which the tile is copied out.
+  ImageView<pixel_type> evaluate_tile(BBox2i const& bbox) const {
+    ImageView<pixel_type> tile(bbox.width(), bbox.height());
+    if (bbox.empty()) return tile;
+    const BBox2i all(0, 0, cols(), rows()), rall(0, 0, m_right.cols(), m_right.rows());
+    ImageView<PixelMask<Vector2f>> d = m_disp.prerasterize(all);
+    ImageView<pixel_type> l = m_left.prerasterize(all), r = m_right.prerasterize(rall), full(cols(), rows());
+    std::vector<float> lv((size_t)l.cols() * l.rows()), rv((size_t)r.cols() * r.rows());
+    std::vector<uint8_t> lm(lv.size()), rm(rv.size());
+    for (int32 y = 0; y < l.rows(); ++y)
+      for (int32 x = 0; x < l.cols(); ++x) {
+        lv[(size_t)y * l.cols() + x] = l(x, y).child();
+        lm[(size_t)y * l.cols() + x] = is_valid(l(x, y)) ? 1 : 0;
+      }
+    for (int32 y = 0; y < r.rows(); ++y)
+      for (int32 x = 0; x < r.cols(); ++x) {
+        rv[(size_t)y * r.cols() + x] = r(x, y).child();
+        rm[(size_t)y * r.cols() + x] = is_valid(r(x, y)) ? 1 : 0;
+      }
+    const int box[4] = {bbox.min().x(), bbox.min().y(), bbox.width(), bbox.height()};
+    vwgpu_ctx* ctx = detail::thread_context();
+    detail::check(ctx, vwgpu_corr_eval(ctx, reinterpret_cast<const float*>(d.data()), d.cols(), d.rows(), 0, lv.data(), lm.data(), 0,
+                                       rv.data(), rm.data(), r.cols(), r.rows(), 0, m_kernel_size[0], m_kernel_size[1],
+                                       metric_code(), m_sample_rate, m_round_to_int ? 1 : 0, m_prefilter_mode,
+                                       m_prefilter_kernel_width, box, 1, reinterpret_cast<float*>(full.data()), 0, NULL));
+    for (int32 y = 0; y < bbox.height(); ++y)
+      for (int32 x = 0; x < bbox.width(); ++x) tile(x, y) = full(bbox.min().x() + x, bbox.min().y() + y);
+    return tile;
+  }
+  prerasterize_type prerasterize(BBox2i const& bbox) const {
+    return prerasterize_type(evaluate_tile(bbox), -bbox.min().x(), -bbox.min().y(), cols(), rows());
+  }
+  template <class DestT> void rasterize(DestT const& dest, BBox2i const& bbox) const {
+    ImageView<pixel_type> t = evaluate_tile(bbox);
+    for (int32 y = 0; y < bbox.height(); ++y)
+      for (int32 x = 0; x < bbox.width(); ++x) dest(x, y) = t(x, y);
+  }
+};
+
+/// corr_eval (src/vw/Stereo/CorrEval.h:117-128).
+inline CorrEval corr_eval(ImageViewRef<PixelMask<float>> left, ImageViewRef<PixelMask<float>> right,
+                          ImageViewRef<PixelMask<Vector2f>> disp, Vector2i const& kernel_size, std::string const& metric,
+                          int sample_rate, bool round_to_int, int prefilter_mode = 0, float prefilter_kernel_width = 0.0) {
+  return CorrEval(left, right, disp, kernel_size, metric, sample_rate, round_to_int, prefilter_mode, prefilter_kernel_width);
 }
 
 }  // namespace stereo

@@ -466,6 +466,79 @@ int vwgpu_corr_eval(vwgpu_ctx* ctx, const float* disp, int w, int h, ptrdiff_t d
                     int prefilter_mode, float prefilter_kernel_width, const int* tiles, int ntiles,
                     float* out, ptrdiff_t ostride, long long* stats);
 
+/* ---- disparity post-filters of Stereo/Algorithms.h ------------------------------------------------------- */
+
+/* The reference's three disparity filters begin with `disparity_out = disparity_in`, a shallow ImageView copy
+ * (src/vw/Image/ImageView.h:72, 95-103, 136-148: no user-written copy assignment, the buffer is shared), and then read
+ * disparity_in while they write disparity_out in raster order: they run IN PLACE.  A window sees filtered values in the
+ * rows above and to the left in its own row, unfiltered values elsewhere.
+ *   VWGPU_FILTER_REFERENCE  that recursion, bit for bit; `out` may be the same image as `in` (same pointer and stride).
+ *   VWGPU_FILTER_SNAPSHOT   every window reads the unmodified input (what the functions' comments describe); `out`
+ *                           must be a different image. */
+typedef enum vwgpu_filter_semantics { VWGPU_FILTER_REFERENCE = 0, VWGPU_FILTER_SNAPSHOT = 1 } vwgpu_filter_semantics;
+
+/* Common to the entries below (tests/refimpl/disparity_filters_ref.cc):
+ *   in / out  w x h x {dx, dy, valid (!= 0)}, float (PixelMask<Vector2f>) or int32 (PixelMask<Vector2i>); strides in
+ *          PIXELS, 0 = packed.  A pixel the filter replaces becomes {dx, dy, 1}; every other pixel of `out` is a copy.
+ *   boxes  HOST array of nboxes boxes {x, y, w, h} inside the image that do not overlap (VWGPU_ERR_ARGUMENT otherwise).
+ *          Every box is filtered as an image of its own: its own untouched border, edge extension and raster order, as
+ *          a caller filtering tile by tile gets.  Pixels outside every box are copied.  One box {0, 0, w, h} is the
+ *          reference's call on the whole image.
+ *   stats  optional HOST array of 1: pixels whose dx, dy or validity changed (asking for it synchronises the stream).
+ * The device entries run on the context's stream and synchronise it once, for the box table. */
+
+/* Replaces vw::stereo::disparity_median_filter (src/vw/Stereo/Algorithms.cc:26-67; math::destructive_median,
+ * src/vw/Math/Functors.h:393-398): per channel the median of the valid disparities of the kernel window as doubles, the
+ * mean of the two middle ones ((a + b) / 2.0) for an even count, narrowed to float.  half = (kernel_size - 1) / 2 (an
+ * even size uses the next smaller odd window); a border of `half` pixels and invalid centres are untouched;
+ * kernel_size < 3 copies; negative: VWGPU_ERR_ARGUMENT; above 31: VWGPU_ERR_NOIMPL.  A window with a NaN among its valid
+ * disparities (std::sort is undefined there) leaves its pixel unchanged; the sign of a zero median is unspecified. */
+int vwgpu_disparity_median_filter_dev(vwgpu_ctx* ctx, const float* d_in, int w, int h, ptrdiff_t istride, int kernel_size,
+                                      int semantics, const int* boxes, int nboxes, float* d_out, ptrdiff_t ostride,
+                                      long long* stats);
+int vwgpu_disparity_median_filter(vwgpu_ctx* ctx, const float* in, int w, int h, ptrdiff_t istride, int kernel_size,
+                                  int semantics, const int* boxes, int nboxes, float* out, ptrdiff_t ostride,
+                                  long long* stats);
+
+/* Replaces vw::stereo::disparity_neighbor_filter (src/vw/Stereo/Algorithms.cc:69-110): among the 8 neighbours in the
+ * reference's order, each valid one counts the neighbours equal to it in dx, dy and validity; the first strictly larger
+ * count wins and, at 5 or more, replaces the centre whatever the centre's own validity.  A 1-pixel border is untouched. */
+int vwgpu_disparity_neighbor_filter_dev(vwgpu_ctx* ctx, const int32_t* d_in, int w, int h, ptrdiff_t istride, int semantics,
+                                        const int* boxes, int nboxes, int32_t* d_out, ptrdiff_t ostride, long long* stats);
+int vwgpu_disparity_neighbor_filter(vwgpu_ctx* ctx, const int32_t* in, int w, int h, ptrdiff_t istride, int semantics,
+                                    const int* boxes, int nboxes, int32_t* out, ptrdiff_t ostride, long long* stats);
+
+/* Replaces vw::stereo::texture_measure on a plain float image (src/vw/Stereo/Algorithms.h:144-209): per pixel, over the
+ * (2 half + 1)^2 window (half = (kernel_size - 1) / 2) of the edge-extended image, score = float(gradient_weight *
+ * sum(|dx| + |dy|) / (2 n) + stddev_weight * sqrt(sum((v - mean)^2) / n)), with dx, dy = derivative_filter (kernel
+ * {0.5, 0, -0.5}, constant edge extension, the derivative images edge-extended again), |dx| + |dy| a float add, all
+ * sums in double in the reference's order (r outer, c inner).  out: w x h float, written inside the boxes only (a box
+ * is an image of its own, see above); strides in elements.  kernel_size < 1: VWGPU_ERR_ARGUMENT; above 31:
+ * VWGPU_ERR_NOIMPL.  max_score: optional HOST float, the largest score written (0 when none is positive; the
+ * reference's caller scales texture_max from it; asking for it synchronises the stream). */
+int vwgpu_texture_measure_dev(vwgpu_ctx* ctx, const float* d_image, int w, int h, ptrdiff_t stride, int kernel_size,
+                              double gradient_weight, double stddev_weight, const int* boxes, int nboxes, float* d_out,
+                              ptrdiff_t ostride, float* max_score);
+int vwgpu_texture_measure(vwgpu_ctx* ctx, const float* image, int w, int h, ptrdiff_t stride, int kernel_size,
+                          double gradient_weight, double stddev_weight, const int* boxes, int nboxes, float* out,
+                          ptrdiff_t ostride, float* max_score);
+
+/* Replaces vw::stereo::texture_preserving_disparity_filter<float> (src/vw/Stereo/Algorithms.h:215-281): a valid pixel
+ * with texture t >= 0 gets the window size floor(max(texture_max - t, 0) * (max_kernel_size / texture_max)) (float
+ * arithmetic), made odd; sizes below 3 or above max_kernel_size leave the pixel; otherwise the pixel becomes the mean,
+ * summed in double and narrowed to float, of the valid pixels of that window of the edge-extended (clamped) disparity.
+ * texture: w x h float (tstride in elements, 0 = packed).  max_kernel_size < 3 or texture_max <= 0 copies; negative
+ * max_kernel_size or NaN texture_max: VWGPU_ERR_ARGUMENT; max_kernel_size above 31: VWGPU_ERR_NOIMPL.  A pixel whose
+ * texture or window-size product is not finite (undefined in the reference) is left unchanged. */
+int vwgpu_texture_preserving_disparity_filter_dev(vwgpu_ctx* ctx, const float* d_in, int w, int h, ptrdiff_t istride,
+                                                  const float* d_texture, ptrdiff_t tstride, float texture_max,
+                                                  int max_kernel_size, int semantics, const int* boxes, int nboxes,
+                                                  float* d_out, ptrdiff_t ostride, long long* stats);
+int vwgpu_texture_preserving_disparity_filter(vwgpu_ctx* ctx, const float* in, int w, int h, ptrdiff_t istride,
+                                              const float* texture, ptrdiff_t tstride, float texture_max,
+                                              int max_kernel_size, int semantics, const int* boxes, int nboxes,
+                                              float* out, ptrdiff_t ostride, long long* stats);
+
 /* ---- disparity clean-up filters and the zone scheduler ------------------------------------------------- */
 
 /* Replaces rasterising vw::stereo::rm_outliers_using_thresh (cleanup == 0) or

@@ -23,6 +23,10 @@ SYMBOLS = [
     "vwgpu_pyramid_subpixel_dev", "vwgpu_pyramid_subpixel",
     "vwgpu_phase_subpixel_dev", "vwgpu_phase_subpixel",
     "vwgpu_corr_eval_dev", "vwgpu_corr_eval",
+    "vwgpu_disparity_median_filter_dev", "vwgpu_disparity_median_filter",
+    "vwgpu_disparity_neighbor_filter_dev", "vwgpu_disparity_neighbor_filter",
+    "vwgpu_texture_measure_dev", "vwgpu_texture_measure",
+    "vwgpu_texture_preserving_disparity_filter_dev", "vwgpu_texture_preserving_disparity_filter",
     "vwgpu_disparity_filter_dev", "vwgpu_disparity_filter",
     "vwgpu_disparity_mask_dev", "vwgpu_disparity_mask",
     "vwgpu_subdivide_regions",
@@ -153,6 +157,18 @@ def load():
     lib.vwgpu_corr_eval_dev.argtypes = ce
     lib.vwgpu_corr_eval.argtypes = ce
     D = ctypes.c_double
+    med = [P, P, I, I, PD, I, I, P, I, P, PD, P]
+    lib.vwgpu_disparity_median_filter_dev.argtypes = med
+    lib.vwgpu_disparity_median_filter.argtypes = med
+    nbf = [P, P, I, I, PD, I, P, I, P, PD, P]
+    lib.vwgpu_disparity_neighbor_filter_dev.argtypes = nbf
+    lib.vwgpu_disparity_neighbor_filter.argtypes = nbf
+    txm = [P, P, I, I, PD, I, D, D, P, I, P, PD, P]
+    lib.vwgpu_texture_measure_dev.argtypes = txm
+    lib.vwgpu_texture_measure.argtypes = txm
+    tpf = [P, P, I, I, PD, P, PD, F, I, I, P, I, P, PD, P]
+    lib.vwgpu_texture_preserving_disparity_filter_dev.argtypes = tpf
+    lib.vwgpu_texture_preserving_disparity_filter.argtypes = tpf
     df = [P, P, I, I, I, I, D, D, I, P]
     lib.vwgpu_disparity_filter_dev.argtypes = df
     lib.vwgpu_disparity_filter.argtypes = df

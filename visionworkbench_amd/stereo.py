@@ -698,6 +698,137 @@ def calc_disparity_sgm(cost_type, left_in, right_in, left_region, search_volume,
     return (res, sub[:n].reshape(oh.value, ow.value, 3).copy()) if with_subpixel else res
 
 
-__all__ = ["affine_subpixel", "bayes_em_subpixel", "corr_eval", "lk_subpixel", "phase_subpixel", "pyramid_subpixel", "calc_disparity", "calc_disparity_sgm", "cross_corr_consistency_check", "parabola_subpixel", "rm_outliers_using_thresh",
+FILTER_SEMANTICS = {"reference": 0, "snapshot": 1}   # vwgpu_filter_semantics
+MEDIAN_FILTER_MAX_KERNEL = TEXTURE_MEASURE_MAX_KERNEL = TEXTURE_FILTER_MAX_KERNEL = 31
+
+
+def _filter_boxes(name, cols, rows, block_size, tiles):
+    if tiles is not None:
+        return np.ascontiguousarray(tiles, np.int32).reshape(-1, 4)
+    if block_size is not None and (int(block_size[0]) <= 0 or int(block_size[1]) <= 0):
+        raise ArgumentErr("%s: block_size must be positive" % name)
+    return subpixel_tiles(cols, rows, block_size)
+
+
+def _post_filter(name, disparity, dtype, semantics, block_size, tiles, ctx, stats, head, texture=None):
+    """One of the three disparity filters of Algorithms.h through vwgpu_<name>[_dev]: `head` are the arguments between
+    the input's stride and `semantics`, the texture image (if any) is passed in front of them."""
+    if semantics not in FILTER_SEMANTICS:
+        raise ArgumentErr("%s: semantics must be 'reference' or 'snapshot', not %r" % (name, semantics))
+    if disparity.ndim != 3 or disparity.shape[2] != 3:
+        raise ArgumentErr("%s: disparity must be (rows, cols, 3) {dx, dy, valid}" % name)
+    h, w = int(disparity.shape[0]), int(disparity.shape[1])
+    if texture is not None and (texture.ndim != 2 or tuple(texture.shape) != (h, w)):
+        raise ArgumentErr("%s: the texture image and the disparity differ in size" % name)
+    boxes = _filter_boxes(name, w, h, block_size, tiles)
+    st = (ctypes.c_longlong * 1)()
+    ctx = _ctx_for(disparity, ctx)
+    lib = ctx._lib
+    sem = FILTER_SEMANTICS[semantics]
+    want_stats = st if stats is not None else None
+    if _is_tensor(disparity):
+        tdt = torch.float32 if dtype == np.float32 else torch.int32
+        if not disparity.is_cuda or disparity.dtype != tdt:
+            raise ArgumentErr("%s: the disparity must be a %s CUDA tensor" % (name, tdt))
+        if texture is not None and (not _is_tensor(texture) or texture.device != disparity.device
+                                    or texture.dtype != torch.float32):
+            raise ArgumentErr("%s: the texture image must be a float32 CUDA tensor on %s" % (name, disparity.device))
+        d = disparity.contiguous()
+        out = torch.empty_like(d)
+        tex = () if texture is None else (texture.contiguous(),)
+        ctx.set_stream(torch.cuda.current_stream(d.device).cuda_stream)
+        fn = getattr(lib, "vwgpu_%s_dev" % name)
+        targs = () if texture is None else (tex[0].data_ptr(), 0)
+        ctx.check(fn(ctx._h, d.data_ptr(), w, h, 0, *targs, *head, sem, boxes.ctypes.data, len(boxes), out.data_ptr(), 0,
+                     want_stats))
+    else:
+        if _is_tensor(texture):
+            raise ArgumentErr("%s: with a numpy disparity the texture image must be a numpy array" % name)
+        d = np.ascontiguousarray(disparity, dtype)
+        out = np.empty_like(d)
+        tex = None if texture is None else np.ascontiguousarray(texture, np.float32)
+        targs = () if tex is None else (tex.ctypes.data, 0)
+        fn = getattr(lib, "vwgpu_%s" % name)
+        ctx.check(fn(ctx._h, d.ctypes.data, w, h, 0, *targs, *head, sem, boxes.ctypes.data, len(boxes), out.ctypes.data, 0,
+                     want_stats))
+    if stats is not None:
+        stats[:] = list(st)
+    return out
+
+
+def disparity_median_filter(disparity, kernel_size, semantics="reference", block_size=None, tiles=None, ctx=None,
+                            stats=None):
+    """vw::stereo::disparity_median_filter (src/vw/Stereo/Algorithms.cc:26-67) on a (rows, cols, 3) float32
+    PixelMask<Vector2f> image {dx, dy, valid}; returns the filtered image (the input is not modified).
+
+    semantics="reference" (default) is the reference's result: its loops run in place (`disparity_out = disparity_in`
+    shares the buffer), so a window sees the filtered values above and to its left.  "snapshot" filters every pixel from
+    the unmodified input.  Every box (block_size as in pyramid_subpixel, or tiles = [[x, y, w, h], ...], which must not
+    overlap) is filtered as an image of its own.  numpy in -> numpy out (host entry); CUDA tensor in -> CUDA tensor out
+    on the current stream, no pixel leaves the device.  kernel_size up to 31 (NoImplErr above).  stats (optional list)
+    receives [pixels changed]."""
+    if int(kernel_size) > MEDIAN_FILTER_MAX_KERNEL:
+        raise core.NoImplErr("disparity_median_filter: kernel_size %d is larger than %d"
+                             % (int(kernel_size), MEDIAN_FILTER_MAX_KERNEL))
+    return _post_filter("disparity_median_filter", disparity, np.float32, semantics, block_size, tiles, ctx, stats,
+                        (int(kernel_size),))
+
+
+def disparity_neighbor_filter(disparity, semantics="reference", block_size=None, tiles=None, ctx=None, stats=None):
+    """vw::stereo::disparity_neighbor_filter (src/vw/Stereo/Algorithms.cc:69-110) on a (rows, cols, 3) int32
+    PixelMask<Vector2i> image: a pixel five or more of whose 8 neighbours agree takes their value, whatever its own
+    validity.  semantics, boxes, devices and stats as disparity_median_filter."""
+    return _post_filter("disparity_neighbor_filter", disparity, np.int32, semantics, block_size, tiles, ctx, stats, ())
+
+
+def texture_preserving_disparity_filter(disparity, texture, texture_max=0.15, max_kernel_size=11, semantics="reference",
+                                        block_size=None, tiles=None, ctx=None, stats=None):
+    """vw::stereo::texture_preserving_disparity_filter<float> (src/vw/Stereo/Algorithms.h:215-281): every valid pixel is
+    replaced by the mean of the valid pixels of a window whose size grows as the texture (a (rows, cols) float32 image,
+    see texture_measure) falls below texture_max, up to max_kernel_size (at most 31, NoImplErr above).  semantics,
+    boxes, devices and stats as disparity_median_filter."""
+    if int(max_kernel_size) > TEXTURE_FILTER_MAX_KERNEL:
+        raise core.NoImplErr("texture_preserving_disparity_filter: max_kernel_size %d is larger than %d"
+                             % (int(max_kernel_size), TEXTURE_FILTER_MAX_KERNEL))
+    return _post_filter("texture_preserving_disparity_filter", disparity, np.float32, semantics, block_size, tiles, ctx,
+                        stats, (float(texture_max), int(max_kernel_size)), texture=texture)
+
+
+def texture_measure(image, kernel_size=9, gradient_weight=0.5, stddev_weight=0.5, block_size=None, tiles=None, ctx=None,
+                    stats=None):
+    """vw::stereo::texture_measure (src/vw/Stereo/Algorithms.h:144-209) of a plain (rows, cols) float32 image: per pixel
+    gradient_weight * mean(|dx| + |dy|) / 2 + stddev_weight * stddev over the kernel window of the edge-extended image.
+    Returns a (rows, cols) float32 image (zero outside the boxes); numpy or CUDA tensor as the input.  kernel_size up to
+    31 (NoImplErr above).  stats (optional list) receives [largest score], from which the reference's caller scales
+    texture_max."""
+    if image.ndim != 2:
+        raise ArgumentErr("texture_measure: the image must be (rows, cols)")
+    if int(kernel_size) > TEXTURE_MEASURE_MAX_KERNEL:
+        raise core.NoImplErr("texture_measure: kernel_size %d is larger than %d" % (int(kernel_size), TEXTURE_MEASURE_MAX_KERNEL))
+    h, w = int(image.shape[0]), int(image.shape[1])
+    boxes = _filter_boxes("texture_measure", w, h, block_size, tiles)
+    mx = ctypes.c_float(0)
+    want = ctypes.addressof(mx) if stats is not None else None
+    ctx = _ctx_for(image, ctx)
+    lib = ctx._lib
+    args = (int(kernel_size), float(gradient_weight), float(stddev_weight), boxes.ctypes.data, len(boxes))
+    if _is_tensor(image):
+        if not image.is_cuda or image.dtype != torch.float32:
+            raise ArgumentErr("texture_measure: the image must be a float32 CUDA tensor")
+        img = image.contiguous()
+        out = torch.zeros((h, w), dtype=torch.float32, device=img.device)
+        ctx.set_stream(torch.cuda.current_stream(img.device).cuda_stream)
+        ctx.check(lib.vwgpu_texture_measure_dev(ctx._h, img.data_ptr(), w, h, 0, *args, out.data_ptr(), 0, want))
+    else:
+        img = np.ascontiguousarray(image, np.float32)
+        out = np.zeros((h, w), np.float32)
+        ctx.check(lib.vwgpu_texture_measure(ctx._h, img.ctypes.data, w, h, 0, *args, out.ctypes.data, 0, want))
+    if stats is not None:
+        stats[:] = [mx.value]
+    return out
+
+
+__all__ = ["affine_subpixel", "bayes_em_subpixel", "corr_eval", "disparity_median_filter", "disparity_neighbor_filter",
+           "texture_measure", "texture_preserving_disparity_filter","lk_subpixel", "phase_subpixel", "pyramid_subpixel", "calc_disparity", "calc_disparity_sgm", "cross_corr_consistency_check", "parabola_subpixel", "rm_outliers_using_thresh",
            "disparity_cleanup_using_thresh", "disparity_mask", "disparity_blob_filter", "subdivide_regions", "pyramid_correlate", "pyramid_correlate_batch",
            "BBox2i", "CostFunctionType"]

@@ -12,6 +12,8 @@
 //                                src/vw/Stereo/SubpixelView.h:28-134 (SUBPIXEL_PHASE: NoImplErr)
 //   phase_subpixel               src/vw/Stereo/SubpixelView.h:136-144 (vwgpu_phase_subpixel)
 //   CorrEval, corr_eval          src/vw/Stereo/CorrEval.h:56-128 (vwgpu_corr_eval)
+//   disparity_median_filter, disparity_neighbor_filter, texture_measure, texture_preserving_disparity_filter
+//                                src/vw/Stereo/Algorithms.h:132-281, Algorithms.cc:26-110 (vwgpu_disparity_median_filter ...)
 //   prefilter_image              src/vw/Stereo/PreFilter.h:76-95
 //   rm_outliers_using_thresh / disparity_cleanup_using_thresh / disparity_mask
 //                                src/vw/Stereo/DisparityMap.h:387-441, 236-253
@@ -793,6 +795,83 @@ inline CorrEval corr_eval(ImageViewRef<PixelMask<float>> left, ImageViewRef<Pixe
                           ImageViewRef<PixelMask<Vector2f>> disp, Vector2i const& kernel_size, std::string const& metric,
                           int sample_rate, bool round_to_int, int prefilter_mode = 0, float prefilter_kernel_width = 0.0) {
   return CorrEval(left, right, disp, kernel_size, metric, sample_rate, round_to_int, prefilter_mode, prefilter_kernel_width);
+}
+
+// ---- the disparity post-filters of Stereo/Algorithms.h -------------------------------------------------------------
+// The reference's three disparity filters start with `disparity_out = disparity_in`, a shallow copy, and then filter in
+// place in raster order (include/vwgpu.h, vwgpu_filter_semantics).  By default these functions do the same: the engine
+// filters disparity_in's buffer in place and disparity_out shares it afterwards.  snapshot = true filters every pixel
+// from the unmodified input into a fresh image and leaves disparity_in alone.
+namespace detail {
+static_assert(sizeof(PixelMask<Vector2f>) == 12 && sizeof(PixelMask<Vector2i>) == 12, "{dx, dy, valid} pixels");
+// call(in, out, box): the engine entry on one whole-image box
+template <class PixelT, class CallT>
+void post_filter(ImageView<PixelT> const& disparity_in, ImageView<PixelT>& disparity_out, bool snapshot, CallT call) {
+  if (disparity_in.cols() == 0 || disparity_in.rows() == 0) {
+    disparity_out = disparity_in;
+    return;
+  }
+  const int box[4] = {0, 0, disparity_in.cols(), disparity_in.rows()};
+  if (!snapshot) {
+    call(disparity_in.data(), disparity_in.data(), box, (int)VWGPU_FILTER_REFERENCE);
+    disparity_out = disparity_in;
+    return;
+  }
+  ImageView<PixelT> fresh(disparity_in.cols(), disparity_in.rows());
+  call(disparity_in.data(), fresh.data(), box, (int)VWGPU_FILTER_SNAPSHOT);
+  disparity_out = fresh;
+}
+}  // namespace detail
+
+/// disparity_median_filter (Algorithms.h:132-135, Algorithms.cc:26-67); kernel sizes up to 31 (NoImplErr above).
+inline void disparity_median_filter(ImageView<PixelMask<Vector2f>> const& disparity_in,
+                                    ImageView<PixelMask<Vector2f>>& disparity_out, int kernel_size, bool snapshot = false) {
+  detail::post_filter(disparity_in, disparity_out, snapshot,
+                      [&](PixelMask<Vector2f>* in, PixelMask<Vector2f>* out, const int* box, int semantics) {
+    vwgpu_ctx* ctx = detail::thread_context();
+    detail::check(ctx, vwgpu_disparity_median_filter(ctx, reinterpret_cast<const float*>(in), box[2], box[3], 0, kernel_size,
+                                                     semantics, box, 1, reinterpret_cast<float*>(out), 0, NULL));
+  });
+}
+
+/// disparity_neighbor_filter (Algorithms.h:137-139, Algorithms.cc:69-110).
+inline void disparity_neighbor_filter(ImageView<PixelMask<Vector2i>> const& disparity_in,
+                                      ImageView<PixelMask<Vector2i>>& disparity_out, bool snapshot = false) {
+  detail::post_filter(disparity_in, disparity_out, snapshot,
+                      [&](PixelMask<Vector2i>* in, PixelMask<Vector2i>* out, const int* box, int semantics) {
+    vwgpu_ctx* ctx = detail::thread_context();
+    detail::check(ctx, vwgpu_disparity_neighbor_filter(ctx, reinterpret_cast<const int32_t*>(in), box[2], box[3], 0, semantics,
+                                                       box, 1, reinterpret_cast<int32_t*>(out), 0, NULL));
+  });
+}
+
+/// texture_measure (Algorithms.h:144-209) of a plain float image (masked inputs: not implemented); kernel sizes up to 31.
+template <class ImageT>
+inline void texture_measure(ImageViewBase<ImageT> const& input_image, ImageView<float>& output_image, int kernel_size = 9,
+                            double gradient_weight = 0.5, double stddev_weight = 0.5) {
+  ImageView<float> in = pixel_cast<float>(input_image.impl());
+  output_image.set_size(in.cols(), in.rows());
+  if (in.cols() == 0 || in.rows() == 0) return;
+  const int box[4] = {0, 0, in.cols(), in.rows()};
+  vwgpu_ctx* ctx = detail::thread_context();
+  detail::check(ctx, vwgpu_texture_measure(ctx, in.data(), in.cols(), in.rows(), 0, kernel_size, gradient_weight, stddev_weight,
+                                           box, 1, output_image.data(), 0, NULL));
+}
+
+/// texture_preserving_disparity_filter<float> (Algorithms.h:215-281); max_kernel_size up to 31 (NoImplErr above).
+inline void texture_preserving_disparity_filter(ImageView<PixelMask<Vector2f>> const& disparity_in,
+                                                ImageView<PixelMask<Vector2f>>& disparity_out,
+                                                ImageView<float> const& texture_image, float texture_max = 0.15,
+                                                int max_kernel_size = 11, bool snapshot = false) {
+  VW_ASSERT(texture_image.cols() == disparity_in.cols() && texture_image.rows() == disparity_in.rows(),
+            ArgumentErr() << "texture_preserving_disparity_filter: texture image and disparity must have the same dimensions.");
+  detail::post_filter(disparity_in, disparity_out, snapshot,
+                      [&](PixelMask<Vector2f>* in, PixelMask<Vector2f>* out, const int* box, int semantics) {
+    vwgpu_ctx* ctx = detail::thread_context();
+    detail::check(ctx, vwgpu_texture_preserving_disparity_filter(ctx, reinterpret_cast<const float*>(in), box[2], box[3], 0,
+                                                                 texture_image.data(), 0, texture_max, max_kernel_size,
+                                                                 semantics, box, 1, reinterpret_cast<float*>(out), 0, NULL));
+  });
 }
 
 }  // namespace stereo

@@ -304,3 +304,59 @@ def batch_cases(n, seed):
             boxes = [boxes[i] for i in sorted(rng.choice(len(boxes), 12, replace=False))]
         c["boxes"] = boxes
         yield c
+
+
+PARABOLA_KINDS = ("u8", "i16", "i20", "f01", "f12")
+
+
+def parabola_cases(n, seed):
+    """parabola_subpixel: random sizes (1 x 1 included), windows 1 ... 23 on a side (mostly the widths that have compile-time forms, a
+    third of them square), input classes (bytes / negative 16-bit / 20-bit integers / floats in [0, 1] / floats on a 2^-12 grid), prefilters on
+    the float classes, blocky fractional disparity fields, 0 ... 100 % invalid pixels, a right image larger than, equal to or smaller than the
+    left one.  Only ORDER-FREE scenes (integers, or floats of one binade range: no partial sum of the reference's running box sums rounds), so
+    the oracle, the direct-sum restatement (tests/refimpl/parabola_direct.py) and the kernel agree bit for bit; tests/test_subpixel_cpu.py
+    checks the first two on a sample of this generator."""
+    rng = np.random.default_rng([seed, 0x9A7AB01A])
+    for it in range(n):
+        h = int(rng.choice([1, 2, 3, 4, 5, int(rng.integers(6, 70))]))
+        w = int(rng.choice([1, 3, 63, 64, 65, int(rng.integers(2, 150)), int(rng.integers(2, 150))]))
+        kx = int(rng.choice([3, 5, 7, 9, 11, 13, 15, int(rng.integers(0, 12)) * 2 + 1]))
+        ky = kx if rng.random() < 0.35 else int(rng.integers(0, 12)) * 2 + 1
+        kind = PARABOLA_KINDS[int(rng.integers(len(PARABOLA_KINDS)))]
+        pf, pfw = 0, 0.0
+        if kind in ("f01", "f12") and rng.random() < 0.5:
+            pf = int(rng.integers(1, 3))
+            pfw = float(rng.choice([1.4, 2.0, 3.0]))
+        relation = int(rng.integers(3))                                # right image larger / equal / smaller
+        rh = max(1, h + (int(rng.integers(1, 6)), 0, -int(rng.integers(1, 6)))[relation])
+        rw = max(1, w + (int(rng.integers(1, 20)), 0, -int(rng.integers(1, 20)))[relation])
+        H, W = max(h, rh), max(w, rw) + 8
+        tex = rng.random((H, W))
+        yy, xx = np.mgrid[0:H, 0:W]
+        tex = 0.5 * tex + 0.25 * (1 + np.sin(xx / 2.7 + yy / 3.9))      # in [0, 1): noise on a smooth wave
+        if kind == "u8":
+            img = np.floor(tex * 256)
+            if rng.random() < 0.3:
+                img[rng.random((H, W)) < 0.2] = float(rng.choice([0, 255]))       # saturated / nodata pixels
+        elif kind == "i16":
+            img = np.floor(tex * 32768) - 32768
+        elif kind == "i20":
+            img = np.floor((tex - 0.5) * (2 ** 22 - 2))
+        elif kind == "f01":
+            img = tex
+        else:
+            img = np.floor(tex * 4096) / 4096
+        img = img.astype(np.float32)
+        sh = int(rng.integers(0, 8))
+        left, right = img[:h, :w].copy(), img[:rh, sh:sh + rw].copy()
+        if kind == "i20" and rng.random() < 0.5:
+            left.flat[int(rng.integers(left.size))] = float(rng.choice([-1, 1]) * (2 ** 21 - 1))
+        by, bx = int(rng.integers(1, 12)), int(rng.integers(1, 12))
+        nby, nbx = (h + by - 1) // by, (w + bx - 1) // bx
+        lox, hix = sorted(int(v) for v in rng.integers(-9, 10, 2))
+        loy, hiy = sorted(int(v) for v in rng.integers(-4, 5, 2))
+        d = np.zeros((h, w, 3), np.float32)
+        d[..., 0] = (rng.integers(lox, hix + 1, (nby, nbx)) + rng.choice([0.0, 0.6, -0.3, -0.7])).repeat(by, 0).repeat(bx, 1)[:h, :w]
+        d[..., 1] = (rng.integers(loy, hiy + 1, (nby, nbx)) + rng.choice([0.0, 0.4, -0.3])).repeat(by, 0).repeat(bx, 1)[:h, :w]
+        d[..., 2] = rng.random((h, w)) >= float(rng.choice([0.0, 0.1, 0.5, 0.98, 1.0]))
+        yield dict(it=it, disp=d, left=left, right=right, mode=pf, width=pfw, kernel=(kx, ky), kind=kind)

@@ -2,7 +2,8 @@
   * packed SAD / SSD / NCC matchers vs the generic float64 kernel (itself pinned to the oracle in test_bm_gpu.py),
   * pyramid_correlate vs the oracle (tiles, masks, thresholds, filters, level counts; integer scenes, float scenes and
     LoG / mean-subtracted prefilters — the inputs on which the reference's running box sums are order dependent),
-  * calc_disparity_sgm vs the oracle (masks, previous-level bounds, memory levels, every sub-pixel mode).
+  * calc_disparity_sgm vs the oracle (masks, previous-level bounds, memory levels, every sub-pixel mode),
+  * parabola_subpixel vs the oracle (sizes from 1 x 1, windows 1 ... 23, every input class and prefilter, host and device entry).
 Every case must be IDENTICAL; a failure prints (generator, seed, index) for tools/replay_pyramid_case.py."""
 import os
 
@@ -199,3 +200,20 @@ def test_fuzz_batch_identical_to_oracle(ctx, oracle, n, seed):
             if not np.array_equal(g, o):
                 bad.append((c["it"], b, int((g != o).any(-1).sum())))
     assert not bad, "batch_cases(seed=%d): (index, tile, differing pixels) %s" % (seed, bad)
+
+
+@pytest.mark.parametrize("n,seed", [(1000, 701), (1000, 702)])
+def test_fuzz_parabola_identical_to_oracle(ctx, oracle, n, seed):
+    """parabola_subpixel on fuzz_cases.parabola_cases (order-free scenes only: tests/test_subpixel_cpu.py checks a sample of seed 701
+    against the direct-sum restatement), through the host and the device entry."""
+    import torch
+    bad = []
+    for c in fuzz_cases.parabola_cases(n, seed):
+        want = oracle.parabola_subpixel(c["disp"], c["left"], c["right"], c["mode"], c["width"], c["kernel"])
+        got_h = stereo.parabola_subpixel(c["disp"], c["left"], c["right"], c["mode"], c["width"], c["kernel"], ctx=ctx)
+        got_d = stereo.parabola_subpixel(torch.from_numpy(c["disp"]).cuda(), torch.from_numpy(c["left"]).cuda(), torch.from_numpy(c["right"]).cuda(),
+                                         c["mode"], c["width"], c["kernel"], ctx=ctx).cpu().numpy()
+        if not (np.array_equal(got_h, want) and np.array_equal(got_d, want)):
+            bad.append((c["it"], c["kind"], c["mode"], c["kernel"], c["left"].shape, c["right"].shape,
+                        int((got_h != want).any(-1).sum()), int((got_d != want).any(-1).sum())))
+    assert not bad, "parabola_cases(seed=%d): (index, class, prefilter, kernel, left, right, differing host / device) %s" % (seed, bad)

@@ -9,8 +9,12 @@
 // per-pixel quantities, so this kernel computes them directly: one thread per pixel, nine windowed SADs in float64
 // over pre-filtered, pre-cropped rasters (the same `left_raster` / `right_raster` the reference rasterises, :44-45).
 // The float solve below is the reference's expression order with contraction off.
-// Exact on integer-valued imagery with PREFILTER_NONE (all sums exact); after LoG / mean-subtraction the reference's
-// running sums are position dependent and agreement is to float rounding (tests: 1e-5 abs).
+// Parity: bit-identical to the reference wherever no partial sum of its running box sums rounds — all integer imagery, and
+// ordinary float imagery with or without LoG / mean-subtraction (a float64 sum of a few thousand float32 terms of similar
+// magnitude is exact, so the order cannot show).  Where they do round (one pixel of 1e12, a 3e38 nodata value, NaN, Inf) the
+// reference's running column / row sums keep the residue for the rest of the zone and this kernel's per-window sums do not: the
+// results then differ by up to several pixels, and the kernel is held to tests/refimpl/parabola_direct.py (these sums in this
+// order) instead.  tests/test_subpixel_cpu.py, tests/test_subpixel_gpu.py; DESIGN.md section 2.
 //
 // Roofline: 9*kx*ky abs-diffs per pixel against 36 B of compulsory traffic per pixel (disparity in, two images,
 // disparity out) — VALU / L1 bound; the windows of neighbouring pixels overlap and are served by the vector L1.
@@ -137,8 +141,8 @@ parabola_prepass_kernel(const float* __restrict__ d, int w, int h, ptrdiff_t str
 // the right neighbourhood: every right value is loaded once (kx + 2 per row) and every left value once (three rows kept in
 // registers), instead of 9 * kx * ky loads of each.  The float64 accumulation order of each of the nine sums is unchanged
 // (rows outer, columns inner).  KX == 0: any width, the plain loops.
-// INT: every pixel of both rasters is an integer of magnitude < 2^21 (measured by the caller): the nine sums are then exact
-// integers below 2^31 in any arithmetic, so they are formed with v_sad_u32 (one instruction per abs-diff instead of
+// INT: every pixel of both rasters is an integer of magnitude < 2^21 (measured by the caller) and the window is small enough that
+// kx * ky * 2^22 < 2^32: the nine sums are then exact integers below 2^32 in any arithmetic, so they are formed UNSIGNED with v_sad_u32 (one instruction per abs-diff instead of
 // subtract + widen + float64 add) and converted once — the same float the reference's float64 sum rounds to.
 __device__ __forceinline__ unsigned sad_u32(unsigned a, unsigned b, unsigned c) {
   unsigned r;

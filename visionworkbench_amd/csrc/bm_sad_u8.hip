@@ -34,7 +34,12 @@
 //   LDS       RIGHT words at byte phase t = j mod 4 are unaligned, so the step loop runs t-outer: the
 //             float tile is converted to a u8 base tile in LDS once, and for each t the workgroup derives
 //             one array of pre-shifted, pre-masked word groups (v_alignbyte_b32), then walks a = 0..A with
-//             one 8/16-byte LDS read per row.
+//             one 8/16-byte LDS read per row.  The array is entry-major, [entry][row][EW] with the row count padded to odd:
+//             a lane reads one entry column per step, so every row is an immediate offset of the LDS read (and the second
+//             step of a pair the other offset of a ds_read2_b64) instead of a v_add_u32 per row on a loop that is bound by
+//             VALU issue; the odd column stride keeps consecutive lanes on distinct banks.  The pad costs 1/NR of the array,
+//             so the widest searches (7x7: 174 .. 209 disparities) run the row-major instantiation [row][entry][EW] — the
+//             layout of rounds 1-6 — rather than leave the packed path (profiles/sad_step_trim.md).
 //   validity  invalid <=> all sx*sy costs equal.  Instead of tracking the worst cost everywhere, four cost pairs are
 //             compared during the first sweep (one bit per lane and row: "some pixel of the row had equal costs in every
 //             probe"); only a workgroup with a surviving row (never on textured data, always on flat data) runs the
@@ -147,7 +152,10 @@ __host__ __device__ constexpr size_t ent_words(int nr, int ne, int ew, int gr, i
 //        is not split: group 0 walks its items alone, group 1 only helps to build the word groups.)
 // GR = number of wave groups on the tile (1, 2, 4); SPLIT = GR > 1.  GR = 4 (round 6) exists for the 512-column tile: two wave columns x
 // four groups = the same eight wavefronts per CU as the two-group 1024-column tile.
-template <int KX, int KY, int TY, int GR, int WV = 0>
+// EM = entry-major word groups ([entry][row][EW], rows padded to an odd count): a row of a step is an immediate offset from the lane's
+//      entry.  EM = false is the row-major array ([row][entry][EW], row pitch in a register): the launcher takes it only for searches
+//      so wide that the padded array would not fit the LDS budget.
+template <int KX, int KY, int TY, int GR, int WV = 0, bool EM = true>
 __global__ void __launch_bounds__((GR * (Cfg<KX, KY, TY, WV>::THREADS)), (GR > 1 ? 1 : (TY <= 8 && KX <= 8 ? 3 : 2)))
 bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
                  const float* __restrict__ R, ptrdiff_t rs, int rcw, int rch,
@@ -157,14 +165,17 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
   typedef Cfg<KX, KY, TY, WV> C;
   constexpr bool SPLIT = GR > 1;
   constexpr int NW = C::NW, EW = C::EW, NR = C::NR;
+  // rows per entry column.  Odd: consecutive lanes read consecutive entries, and an even column stride would put lanes l and l + 16
+  // (EW = 2: a 64-bit read is served in halves of 32 lanes over 64 banks) or l and l + 8 (EW = 4) on the same banks.
+  constexpr int NRP = EM ? (NR | 1) : NR;
   extern __shared__ __attribute__((aligned(16))) u32 lds[];
-  u32* ent = lds;                                   // [NR][ne][EW]   word groups of the current byte phase
+  u32* ent = lds;                                   // EM: [ne][NRP][EW], else [NR][ne][EW]: word groups of the current byte phase
   const int bpitch = ne + NW + 1;                   // dwords per row of the RIGHT u8 base tile
   // The entry array is borrowed twice after the sweep: by the merge of the wave groups ((GR - 1) x TY / GR x 4 x PT keys + GR x PT equality
   // words) and by the epilogue's per-wave transposition buffers (768 dwords each).  With a narrow search both can exceed NR x ne x EW — and
   // the RIGHT base tile behind it is still needed by the validity sweep (found by the round-6 campaign: constant images, search 2 .. 8 on the
   // 512-column four-group tile).  ent_words() is the size both sides use.
-  u32* base = lds + ent_words(NR, ne, EW, GR, TY, C::THREADS);           // [NR][bpitch]
+  u32* base = lds + ent_words(NRP, ne, EW, GR, TY, C::THREADS);           // [NR][bpitch]
   u32* item_ctr = base + (size_t)NR * bpitch;       // SPLIT: one work item counter per wave pair
 
   constexpr int PT = C::THREADS;                    // threads that map to pixels
@@ -262,7 +273,7 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
 #pragma unroll
             for (int n = 0; n < NW; ++n) w[n] = __builtin_amdgcn_alignbyte(b[n + 1], b[n], t);
             w[NW - 1] &= C::LAST_MASK;
-            u32* e = ent + ((size_t)r * ne + m) * EW;
+            u32* e = ent + (EM ? (size_t)m * NRP + r : (size_t)r * ne + m) * EW;
             if (EW == 2) *reinterpret_cast<uint2*>(e) = make_uint2(w[0], w[1]);
             else *reinterpret_cast<uint4*>(e) = make_uint4(w[0], w[1], w[2 % EW], w[3 % EW]);
           };
@@ -302,7 +313,7 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
               if (d < 0 || d >= sx) orA[i >> 1] |= (i & 1) ? 0xffff0000u : 0x0000ffffu;
             }
           }
-          const u32* ep = ent + (size_t)(ltid + a) * EW;
+          const u32* ep = ent + (size_t)(ltid + a) * (EM ? NRP * EW : EW);
           u64 accA = 0, accB = 0;
           u64 PA[NR], PB[NR];
           // LDS reads are issued PF rows ahead by hand: the volatile asm statements below are scheduling barriers
@@ -310,15 +321,16 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
           constexpr int PF = 4;
           u32 wa[NR][EW], wb[NR][EW];
           auto fetch = [&](int r) __attribute__((always_inline)) {
-            const u32* e = ep + (size_t)r * ne * EW;
+            const u32* e = ep + (EM ? (size_t)r * EW : (size_t)r * ne * EW);
+            constexpr int NX = EM ? NRP * EW : EW;     // the next entry: the second step of a pair
             if (EW == 2) {
               const uint2 v = *reinterpret_cast<const uint2*>(e);
               wa[r][0] = v.x; wa[r][1] = v.y;
-              if (PAIR) { const uint2 u = *reinterpret_cast<const uint2*>(e + EW); wb[r][0] = u.x; wb[r][1] = u.y; }
+              if (PAIR) { const uint2 u = *reinterpret_cast<const uint2*>(e + NX); wb[r][0] = u.x; wb[r][1] = u.y; }
             } else {
               const uint4 v = *reinterpret_cast<const uint4*>(e);
               wa[r][0] = v.x; wa[r][1] = v.y; wa[r][2 % EW] = v.z; wa[r][3 % EW] = v.w;
-              if (PAIR) { const uint4 u = *reinterpret_cast<const uint4*>(e + EW); wb[r][0] = u.x; wb[r][1] = u.y; wb[r][2 % EW] = u.z; wb[r][3 % EW] = u.w; }
+              if (PAIR) { const uint4 u = *reinterpret_cast<const uint4*>(e + NX); wb[r][0] = u.x; wb[r][1] = u.y; wb[r][2 % EW] = u.z; wb[r][3 % EW] = u.w; }
             }
           };
 #pragma unroll
@@ -567,14 +579,24 @@ struct Launch {
   int split_groups;          // wave groups of split_fn
   KernelFn fn;
   KernelFn split_fn;         // the two-wave-group matcher for small grids (nullptr: not instantiated for this size)
+  KernelFn fn_rm, split_fn_rm;   // the same two with the row-major entry array (searches too wide for the padded entry-major one)
 };
+
+// the kernel, instantiated only where kLaunch can reach it
+template <bool ON, int KX, int KY, int TY, int GR, int WV, bool EM>
+constexpr KernelFn kernel_if() {
+  if constexpr (ON) return bm_sad_u8_kernel<KX, KY, TY, GR, WV, EM>;
+  else return nullptr;
+}
 
 template <int KX, int KY, int TY, bool WITH_SPLIT = false, int WV = 0>
 constexpr Launch make_launch() {
   typedef Cfg<KX, KY, TY, WV> C;
   return Launch{KX, KY, TY, C::THREADS, C::TWB, C::NR, C::EW, C::NW, WV ? 4 : 2,
-                WV ? nullptr : bm_sad_u8_kernel<KX, KY, TY, 1, WV>,              // (the narrow tile exists as the four-group matcher only)
-                WITH_SPLIT ? bm_sad_u8_kernel<KX, KY, TY, (WV ? 4 : 2), WV> : nullptr};
+                kernel_if<WV == 0, KX, KY, TY, 1, WV, true>(),                   // (the narrow tile exists as the four-group matcher only)
+                kernel_if<WITH_SPLIT, KX, KY, TY, (WV ? 4 : 2), WV, true>(),
+                kernel_if<WV == 0, KX, KY, TY, 1, WV, false>(),
+                kernel_if<WITH_SPLIT, KX, KY, TY, (WV ? 4 : 2), WV, false>()};
 }
 
 // Instantiated kernel sizes.  Others fall back to the generic path.
@@ -601,6 +623,8 @@ const Launch* find_launch(int kx, int ky) {
 //   steps    one group : rows * 0.5 * n when >= 2 tiles share the SIMDs, rows * 0.74 for a lone 4-wave workgroup (one wave
 //                        per SIMD reaches ~2/3 of the issue rate);  two groups: rows * 0.55 * n (8 waves on one tile)
 //   rounds   sequential staging / output phases: ceil(n / resident) for one group, n for two; ~4.5 row-units each
+// (The entry-major word groups made every flavour faster by a similar share — 2.5 % one group at 4096^2, 2.6 / 2.8 / 2.0 % on the 1/2, 1/4
+// and 1/8 strips — so the ratios above, which are all the model uses, stand: profiles/sad_step_trim.md.)
 // 4096^2: 16-row tiles, one group (4 per CU).  1/4 strip: 16-row tiles, two groups (exactly one per CU; 8-row tiles would
 // put a third tile on a few CUs).  1/8 strip: 512-column tiles of 16 rows, four groups (round 6; 8-row tiles with two groups before).
 const Launch* pick_launch(int kx, int ky, int ow, int oh, int num_cu, int groups, bool* split) {
@@ -637,9 +661,10 @@ constexpr size_t kMaxLds = 80 * 1024;   // two workgroups per CU
 
 int entries_per_row(const Launch& l, int sx) { return l.twb / 4 + ((sx + 2) >> 2) + 1; }
 
-size_t lds_bytes(const Launch& l, int sx, int groups) {
+// em: the entry-major array (rows padded to an odd count), else the row-major one
+size_t lds_bytes(const Launch& l, int sx, int groups, bool em) {
   const int ne = entries_per_row(l, sx);
-  const size_t ent = ent_words(l.nr, ne, l.ew, groups, l.ty, l.threads);
+  const size_t ent = ent_words(em ? (l.nr | 1) : l.nr, ne, l.ew, groups, l.ty, l.threads);
   const size_t left = (size_t)l.nr * (l.twb / 4 + l.nw + 1);        // borrowed from the entry array
   const size_t base = (size_t)l.nr * (ne + l.nw + 1);
   return ((ent > left ? ent : left) + base) * sizeof(u32);
@@ -652,7 +677,7 @@ bool vwgpu_bm_sad_u8_supported(int cost_type, int kx, int ky, int sx, int sy) {
   const Launch* l = find_launch(kx, ky);
   if (!l) return false;
   if ((long long)sx * sy > 65535) return false;
-  return lds_bytes(*l, sx, l->split_fn ? l->split_groups : 1) <= kMaxLds;
+  return lds_bytes(*l, sx, l->split_fn ? l->split_groups : 1, false) <= kMaxLds;    // (the row-major array is the smaller one)
 }
 
 int vwgpu_launch_bm_sad_u8(vwgpu_ctx* ctx,
@@ -675,8 +700,16 @@ int vwgpu_launch_bm_sad_u8(vwgpu_ctx* ctx,
   int rc = vwgpu_next_flags(ctx, 0, &flag_set, &flag_clear, nullptr);
   if (rc) return rc;
   *d_fallback_flag = flag_set;
-  const size_t shmem = lds_bytes(*l, sx, split ? l->split_groups : 1) + (split ? 64 : 0);   // + the item counters of the split variant
-  const KernelFn main_fn = split ? l->split_fn : l->fn;
+  // entry-major word groups wherever the padded array fits the budget the size was admitted with (7x7 at 1024 x 16: up to 173 disparities with one group, 169 with two, of the
+  // 209 the kernel serves); VWGPU_OPT_SAD_LAYOUT = 1 pins the row-major array (same results)
+  const int groups = split ? l->split_groups : 1;
+  const size_t ctr_bytes = split ? 64 : 0;            // the item counters of the split variant
+  // (the counters count against the padded array; the row-major one was admitted without them by vwgpu_bm_sad_u8_supported and
+  // may exceed the constant by those 64 bytes, as it always could: a split workgroup has its CU to itself)
+  const bool em = ctx->sad_layout == 0 && lds_bytes(*l, sx, groups, true) + ctr_bytes <= kMaxLds;
+  const size_t shmem = lds_bytes(*l, sx, groups, em) + ctr_bytes;
+  ctx->sad_last_launch = l->ty | (l->twb / 256) << 8 | groups << 12 | (em ? 1 : 0) << 16;      // VWGPU_OPT_SAD_LAST_LAUNCH
+  const KernelFn main_fn = em ? (split ? l->split_fn : l->fn) : (split ? l->split_fn_rm : l->fn_rm);
   const unsigned grid1 = (unsigned)((gx * gy + 7) / 8 * 8);   // one tile per workgroup, see the XCD note in the kernel
   // the end balance of the one-group matcher (see the kernel): workgroups are dispatched in index order, and the last `slots` of a grid
   // of two rounds or more are its last round; INT_MAX turns it off (one round: the slots start together, nothing to balance)

@@ -74,6 +74,8 @@ struct vwgpu_ctx {
   bool measure_first = false; // the previous calc_disparity was refused by the packed-u8 kernels: measure the input class first
   bool defer_exact = false;   // VWGPU_OPT_DEFER_EXACTNESS: calc_disparity_dev never waits for the input-class flags
   int sad_groups = 0;         // VWGPU_OPT_SAD_GROUPS
+  int sad_layout = 0;         // VWGPU_OPT_SAD_LAYOUT
+  int sad_last_launch = 0;    // VWGPU_OPT_SAD_LAST_LAUNCH
   int exact_scratch_mb = 4096;// VWGPU_OPT_EXACT_SCRATCH_MB
   int exact_split = 0;        // VWGPU_OPT_EXACT_SPLIT: 0 by the longest chain, 1 always the split pass 2, 2 always the fused one
   int trace = 0;              // VWGPU_OPT_TRACE

@@ -520,33 +520,15 @@ int vwgpu_corr_eval(vwgpu_ctx* ctx, const float* disp, int w, int h, ptrdiff_t d
   if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
   if (ntiles == 0) return VWGPU_OK;
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t db = vwgpu_align_up((size_t)w * h * 12, 256), ob = vwgpu_align_up((size_t)w * h * 8, 256),
-               lb = vwgpu_align_up((size_t)w * h * 4, 256), rb = vwgpu_align_up((size_t)rw * rh * 4, 256),
-               lvb = left_valid ? vwgpu_align_up((size_t)w * h, 256) : 0,
-               rvb = right_valid ? vwgpu_align_up((size_t)rw * rh, 256) : 0;
-  rc = vwgpu_arena_reserve(ctx, &ctx->staging, db + ob + lb + rb + lvb + rvb);
+  vwgpu_stage st(ctx);
+  const int pd = st.add(disp, w, h, 12, dstride, VWGPU_STAGE_IN), po = st.add(out, w, h, 8, ostride, VWGPU_STAGE_INOUT);
+  const int pl = st.add(left, w, h, 4, lstride, VWGPU_STAGE_IN), pr = st.add(right, rw, rh, 4, rstride, VWGPU_STAGE_IN);
+  const int plv = st.add(left_valid, w, h, 1, lstride, VWGPU_STAGE_IN), prv = st.add(right_valid, rw, rh, 1, rstride, VWGPU_STAGE_IN);
+  if ((rc = st.commit())) return rc;
+  rc = ce_run(ctx, st.dev<float>(pd), w, h, w, st.dev<float>(pl), st.dev<uint8_t>(plv), w, st.dev<float>(pr), st.dev<uint8_t>(prv), rw, rh, rw,
+              kx, ky, metric, sample_rate, round_to_int, prefilter_kernel_width, tiles, ntiles, st.dev<float>(po), w, stats);
   if (rc) return rc;
-  char* base = static_cast<char*>(ctx->staging.base);
-  float* sd = reinterpret_cast<float*>(base);
-  float* so = reinterpret_cast<float*>(base + db);
-  float* sl = reinterpret_cast<float*>(base + db + ob);
-  float* sr = reinterpret_cast<float*>(base + db + ob + lb);
-  uint8_t* slv = left_valid ? reinterpret_cast<uint8_t*>(base + db + ob + lb + rb) : nullptr;
-  uint8_t* srv = right_valid ? reinterpret_cast<uint8_t*>(base + db + ob + lb + rb + lvb) : nullptr;
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(sd, (size_t)w * 12, disp, (size_t)dstride * 12, (size_t)w * 12, h, hipMemcpyHostToDevice, ctx->stream));
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(so, (size_t)w * 8, out, (size_t)ostride * 8, (size_t)w * 8, h, hipMemcpyHostToDevice, ctx->stream));
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(sl, (size_t)w * 4, left, (size_t)lstride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(sr, (size_t)rw * 4, right, (size_t)rstride * 4, (size_t)rw * 4, rh, hipMemcpyHostToDevice, ctx->stream));
-  if (slv)
-    VWGPU_HIP(ctx, hipMemcpy2DAsync(slv, (size_t)w, left_valid, (size_t)lstride, (size_t)w, h, hipMemcpyHostToDevice, ctx->stream));
-  if (srv)
-    VWGPU_HIP(ctx, hipMemcpy2DAsync(srv, (size_t)rw, right_valid, (size_t)rstride, (size_t)rw, rh, hipMemcpyHostToDevice, ctx->stream));
-  rc = ce_run(ctx, sd, w, h, w, sl, slv, w, sr, srv, rw, rh, rw, kx, ky, metric, sample_rate, round_to_int,
-              prefilter_kernel_width, tiles, ntiles, so, w, stats);
-  if (rc) return rc;
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(out, (size_t)ostride * 8, so, (size_t)w * 8, (size_t)w * 8, h, hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VWGPU_OK;
+  return st.finish();
 }
 
 }  // extern "C"

@@ -547,26 +547,21 @@ int df_host(vwgpu_ctx* ctx, df_call c, const void* in, int w, int h, ptrdiff_t i
   int rc = df_check(ctx, c, in, w, h, istride, semantics, boxes, nboxes, out, ostride);
   if (rc) return rc;
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t db = vwgpu_align_up((size_t)w * h * 12, 256), tb = c.tex ? vwgpu_align_up((size_t)w * h * 4, 256) : 0;
-  rc = vwgpu_arena_reserve(ctx, &ctx->staging, 2 * db + tb);
-  if (rc) return rc;
-  char* base = static_cast<char*>(ctx->staging.base);
-  uint32_t* si = reinterpret_cast<uint32_t*>(base);
-  // reference semantics run in place on the staged copy
-  uint32_t* so = semantics == VWGPU_FILTER_REFERENCE ? si : reinterpret_cast<uint32_t*>(base + db);
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(si, (size_t)w * 12, in, (size_t)istride * 12, (size_t)w * 12, h, hipMemcpyHostToDevice, ctx->stream));
+  vwgpu_stage st(ctx);
+  // reference semantics run in place on the staged copy (the second piece is reserved all the same)
+  const bool in_place = semantics == VWGPU_FILTER_REFERENCE;
+  const int pi = st.add(in, w, h, 12, istride, VWGPU_STAGE_IN);
+  const int po = st.add(out, w, h, 12, ostride, in_place ? VWGPU_STAGE_NONE : VWGPU_STAGE_OUT);
+  const int pt = st.add(c.tex, w, h, 4, c.tstride ? c.tstride : w, VWGPU_STAGE_IN);
+  if ((rc = st.commit())) return rc;
   if (c.tex) {
-    float* st = reinterpret_cast<float*>(base + 2 * db);
-    const size_t ts = c.tstride ? (size_t)c.tstride : (size_t)w;
-    VWGPU_HIP(ctx, hipMemcpy2DAsync(st, (size_t)w * 4, c.tex, ts * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
-    c.tex = st;
+    c.tex = st.dev<float>(pt);
     c.tstride = w;
   }
-  rc = df_run(ctx, c, si, w, h, w, semantics, boxes, nboxes, so, w, stats);
+  rc = df_run(ctx, c, st.dev<uint32_t>(pi), w, h, w, semantics, boxes, nboxes, st.dev<uint32_t>(in_place ? pi : po), w, stats);
   if (rc) return rc;
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(out, (size_t)ostride * 12, so, (size_t)w * 12, (size_t)w * 12, h, hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VWGPU_OK;
+  if (in_place && (rc = st.download(pi, out, w, h, ostride))) return rc;
+  return st.finish();
 }
 
 int tm_check(vwgpu_ctx* ctx, const void* img, int w, int h, ptrdiff_t& stride, int kernel_size, double gw, double sw,
@@ -681,18 +676,12 @@ int vwgpu_texture_measure(vwgpu_ctx* ctx, const float* image, int w, int h, ptrd
   int rc = tm_check(ctx, image, w, h, stride, kernel_size, gradient_weight, stddev_weight, boxes, nboxes, out, ostride);
   if (rc) return rc;
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t ib = vwgpu_align_up((size_t)w * h * 4, 256);
-  rc = vwgpu_arena_reserve(ctx, &ctx->staging, 2 * ib);
+  vwgpu_stage st(ctx);
+  const int pi = st.add(image, w, h, 4, stride, VWGPU_STAGE_IN), po = st.add(out, w, h, 4, ostride, VWGPU_STAGE_INOUT);
+  if ((rc = st.commit())) return rc;
+  rc = tm_run(ctx, st.dev<float>(pi), w, h, w, kernel_size, gradient_weight, stddev_weight, boxes, nboxes, st.dev<float>(po), w, max_score);
   if (rc) return rc;
-  float* si = static_cast<float*>(ctx->staging.base);
-  float* so = reinterpret_cast<float*>(static_cast<char*>(ctx->staging.base) + ib);
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(si, (size_t)w * 4, image, (size_t)stride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(so, (size_t)w * 4, out, (size_t)ostride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
-  rc = tm_run(ctx, si, w, h, w, kernel_size, gradient_weight, stddev_weight, boxes, nboxes, so, w, max_score);
-  if (rc) return rc;
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(out, (size_t)ostride * 4, so, (size_t)w * 4, (size_t)w * 4, h, hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VWGPU_OK;
+  return st.finish();
 }
 
 }  // extern "C"

@@ -603,25 +603,14 @@ int vwgpu_phase_subpixel(vwgpu_ctx* ctx, const float* disp, int w, int h, ptrdif
   if (stats) stats[0] = stats[1] = stats[2] = 0;
   if (ntiles == 0) return VWGPU_OK;
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t db = vwgpu_align_up((size_t)w * h * 12, 256), lb = vwgpu_align_up((size_t)w * h * 4, 256),
-               rb = vwgpu_align_up((size_t)rw * rh * 4, 256);
-  rc = vwgpu_arena_reserve(ctx, &ctx->staging, 2 * db + lb + rb);
+  vwgpu_stage st(ctx);
+  const int pd = st.add(disp, w, h, 12, dstride, VWGPU_STAGE_IN), po = st.add(out, w, h, 12, ostride, VWGPU_STAGE_INOUT);
+  const int pl = st.add(left, w, h, 4, lstride, VWGPU_STAGE_IN), pr = st.add(right, rw, rh, 4, rstride, VWGPU_STAGE_IN);
+  if ((rc = st.commit())) return rc;
+  rc = ph_run(ctx, st.dev<float>(pd), w, h, w, st.dev<float>(pl), w, st.dev<float>(pr), rw, rh, rw, mode, width, kx, ky, levels < 0 ? 0 : levels,
+              accuracy, tiles, ntiles, st.dev<float>(po), w, stats);
   if (rc) return rc;
-  char* base = static_cast<char*>(ctx->staging.base);
-  float* sd = reinterpret_cast<float*>(base);
-  float* so = reinterpret_cast<float*>(base + db);
-  float* sl = reinterpret_cast<float*>(base + 2 * db);
-  float* sr = reinterpret_cast<float*>(base + 2 * db + lb);
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(sd, (size_t)w * 12, disp, (size_t)dstride * 12, (size_t)w * 12, h, hipMemcpyHostToDevice, ctx->stream));
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(so, (size_t)w * 12, out, (size_t)ostride * 12, (size_t)w * 12, h, hipMemcpyHostToDevice, ctx->stream));
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(sl, (size_t)w * 4, left, (size_t)lstride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(sr, (size_t)rw * 4, right, (size_t)rstride * 4, (size_t)rw * 4, rh, hipMemcpyHostToDevice, ctx->stream));
-  rc = ph_run(ctx, sd, w, h, w, sl, w, sr, rw, rh, rw, mode, width, kx, ky, levels < 0 ? 0 : levels, accuracy, tiles, ntiles, so, w,
-              stats);
-  if (rc) return rc;
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(out, (size_t)ostride * 12, so, (size_t)w * 12, (size_t)w * 12, h, hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VWGPU_OK;
+  return st.finish();
 }
 
 }  // extern "C"

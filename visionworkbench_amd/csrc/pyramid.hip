@@ -1851,19 +1851,16 @@ int vwgpu_disparity_filter_dev(vwgpu_ctx* ctx, const int32_t* d_src, int w, int 
 int vwgpu_disparity_filter(vwgpu_ctx* ctx, const int32_t* src, int w, int h, int hh, int hv,
                            double pthr, double rthr, int cleanup, int32_t* dst) {
   if (!ctx) return VWGPU_ERR_ARGUMENT;
+  ctx->err.clear();
   if (!src || !dst || w <= 0 || h <= 0) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "rm_outliers_using_thresh: bad image arguments");
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t nb = vwgpu_align_up((size_t)w * h * 12, 256);
-  int rc = vwgpu_arena_reserve(ctx, &ctx->staging, 2 * nb);
+  vwgpu_stage st(ctx);
+  const int ps = st.add(src, w, h, 12, w, VWGPU_STAGE_IN), pd = st.add(dst, w, h, 12, w, VWGPU_STAGE_OUT);
+  int rc = st.commit();
   if (rc) return rc;
-  int32_t* a = static_cast<int32_t*>(ctx->staging.base);
-  int32_t* b = reinterpret_cast<int32_t*>(static_cast<char*>(ctx->staging.base) + nb);
-  VWGPU_HIP(ctx, hipMemcpyAsync(a, src, (size_t)w * h * 12, hipMemcpyHostToDevice, ctx->stream));
-  rc = vwgpu_disparity_filter_dev(ctx, a, w, h, hh, hv, pthr, rthr, cleanup, b);
+  rc = vwgpu_disparity_filter_dev(ctx, st.dev<int32_t>(ps), w, h, hh, hv, pthr, rthr, cleanup, st.dev<int32_t>(pd));
   if (rc) return rc;
-  VWGPU_HIP(ctx, hipMemcpyAsync(dst, b, (size_t)w * h * 12, hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VWGPU_OK;
+  return st.finish();
 }
 
 int vwgpu_disparity_mask_dev(vwgpu_ctx* ctx, int32_t* d_disp, int w, int h, const uint8_t* m1, const uint8_t* m2, int rmw, int rmh) {
@@ -1876,23 +1873,16 @@ int vwgpu_disparity_mask_dev(vwgpu_ctx* ctx, int32_t* d_disp, int w, int h, cons
 
 int vwgpu_disparity_mask(vwgpu_ctx* ctx, int32_t* disp, int w, int h, const uint8_t* m1, const uint8_t* m2, int rmw, int rmh) {
   if (!ctx) return VWGPU_ERR_ARGUMENT;
+  ctx->err.clear();
   if (!disp || !m1 || !m2 || w <= 0 || h <= 0 || rmw <= 0 || rmh <= 0) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "disparity_mask: bad image arguments");
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t db = vwgpu_align_up((size_t)w * h * 12, 256), ab = vwgpu_align_up((size_t)w * h, 256), bb = vwgpu_align_up((size_t)rmw * rmh, 256);
-  int rc = vwgpu_arena_reserve(ctx, &ctx->staging, db + ab + bb);
+  vwgpu_stage st(ctx);
+  const int pd = st.add(disp, w, h, 12, w, VWGPU_STAGE_INOUT), pa = st.add(m1, w, h, 1, w, VWGPU_STAGE_IN), pb = st.add(m2, rmw, rmh, 1, rmw, VWGPU_STAGE_IN);
+  int rc = st.commit();
   if (rc) return rc;
-  char* base = static_cast<char*>(ctx->staging.base);
-  int32_t* d = reinterpret_cast<int32_t*>(base);
-  uint8_t* a = reinterpret_cast<uint8_t*>(base + db);
-  uint8_t* b = reinterpret_cast<uint8_t*>(base + db + ab);
-  VWGPU_HIP(ctx, hipMemcpyAsync(d, disp, (size_t)w * h * 12, hipMemcpyHostToDevice, ctx->stream));
-  VWGPU_HIP(ctx, hipMemcpyAsync(a, m1, (size_t)w * h, hipMemcpyHostToDevice, ctx->stream));
-  VWGPU_HIP(ctx, hipMemcpyAsync(b, m2, (size_t)rmw * rmh, hipMemcpyHostToDevice, ctx->stream));
-  rc = vwgpu_launch_disparity_mask(ctx, d, w, h, a, b, rmw, rmh);
+  rc = vwgpu_launch_disparity_mask(ctx, st.dev<int32_t>(pd), w, h, st.dev<uint8_t>(pa), st.dev<uint8_t>(pb), rmw, rmh);
   if (rc) return rc;
-  VWGPU_HIP(ctx, hipMemcpyAsync(disp, d, (size_t)w * h * 12, hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VWGPU_OK;
+  return st.finish();
 }
 
 int vwgpu_disparity_blob_filter_dev(vwgpu_ctx* ctx, int32_t* d_disp, int w, int h, int max_blob_area) {
@@ -1907,17 +1897,16 @@ int vwgpu_disparity_blob_filter_dev(vwgpu_ctx* ctx, int32_t* d_disp, int w, int 
 
 int vwgpu_disparity_blob_filter(vwgpu_ctx* ctx, int32_t* disp, int w, int h, int max_blob_area) {
   if (!ctx) return VWGPU_ERR_ARGUMENT;
+  ctx->err.clear();
   if (!disp || w <= 0 || h <= 0) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "disparity_blob_filter: bad image arguments");
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = vwgpu_arena_reserve(ctx, &ctx->staging, (size_t)w * h * 12);
+  vwgpu_stage st(ctx);
+  const int pd = st.add(disp, w, h, 12, w, VWGPU_STAGE_INOUT);
+  int rc = st.commit();
   if (rc) return rc;
-  int32_t* d = static_cast<int32_t*>(ctx->staging.base);
-  VWGPU_HIP(ctx, hipMemcpyAsync(d, disp, (size_t)w * h * 12, hipMemcpyHostToDevice, ctx->stream));
-  rc = vwgpu_disparity_blob_filter_dev(ctx, d, w, h, max_blob_area);
+  rc = vwgpu_disparity_blob_filter_dev(ctx, st.dev<int32_t>(pd), w, h, max_blob_area);
   if (rc) return rc;
-  VWGPU_HIP(ctx, hipMemcpyAsync(disp, d, (size_t)w * h * 12, hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VWGPU_OK;
+  return st.finish();
 }
 
 static int check_pyramid_args(vwgpu_ctx* ctx, const void* l, int lw, int lh, const void* r, int rw, int rh,
@@ -2025,58 +2014,63 @@ int vwgpu_pyramid_correlate_batch_dev(vwgpu_ctx* ctx, const float* d_left, int l
   return VWGPU_OK;
 }
 
-// One run of tiles of the host batch entry: ONE staged window (the union of what the run's tiles can touch), one device batch call.
-static int pyramid_batch_host_run(vwgpu_ctx* ctx, const float* left, int lw, int lh, ptrdiff_t ls, const float* right, int rw, int rh, ptrdiff_t rs,
-                                  const uint8_t* lmask, ptrdiff_t lms, const uint8_t* rmask, ptrdiff_t rms, const vwgpu_pyramid_params* P, int n_tiles,
-                                  const int* bx, const int* by, const int* bw, const int* bh, float* const* outs, const ptrdiff_t* os) {
-  // the window of the sources the tiles can touch (see vwgpu_pyramid_correlate): the union over the run's tiles, one origin for both images and masks
+// Only the window of the sources a tile can touch goes to the device — the reference's prerasterize also pulls just
+// its padded ROIs through the views (CorrelationView.cc:89-97) — not the whole images: a 1024^2 tile of a 32768^2 pair
+// stages ~2000^2 pixels per image.  Window = the box [x0, x1) x [y0, y1) (a tile, or the union of a run of tiles) grown by
+// half_kernel * 2^max_levels (pyramid padding), twice the search extent (R->L runs of the SGM branch) and the search
+// range itself, cut at the image borders; both images and masks share the window origin, so disparities and the edge
+// extension at true image borders are unchanged.
+struct pyr_window {
+  int ox, oy, lww, lwh, rww, rwh;   // origin; sizes of the left and the right window
+  long long gx, gy;                 // the growth of a side, border cuts aside, with the whole search range on either side (the run heuristic's measure)
+};
+static pyr_window pyramid_window(const vwgpu_pyramid_params* P, long long x0, long long y0, long long x1, long long y1, int lw, int lh, int rw, int rh) {
   const int upb = 1 << std::max(0, std::min(P->max_pyramid_levels, 12));
   const int sdx = P->search_max_x - P->search_min_x, sdy = P->search_max_y - P->search_min_y;
   const long long padx = (long long)(P->kernel_x / 2) * upb + 2LL * std::max(sdx, 0) + 8;
   const long long pady = (long long)(P->kernel_y / 2) * upb + 2LL * std::max(sdy, 0) + 8;
-  long long ux0 = LLONG_MAX, uy0 = LLONG_MAX, ux1 = LLONG_MIN, uy1 = LLONG_MIN;
-  size_t out_bytes = 0;
-  for (int t = 0; t < n_tiles; ++t) {
-    ux0 = std::min<long long>(ux0, bx[t]); uy0 = std::min<long long>(uy0, by[t]);
-    ux1 = std::max<long long>(ux1, (long long)bx[t] + bw[t]); uy1 = std::max<long long>(uy1, (long long)by[t] + bh[t]);
-    out_bytes += vwgpu_align_up((size_t)bw[t] * bh[t] * 12, 256);
-  }
-  const long long wx0 = std::max<long long>(0, ux0 - padx + std::min(P->search_min_x, 0)), wy0 = std::max<long long>(0, uy0 - pady + std::min(P->search_min_y, 0));
-  const long long wx1 = ux1 + padx + std::max(P->search_max_x, 0), wy1 = uy1 + pady + std::max(P->search_max_y, 0);
-  const int ox = (int)std::min<long long>(wx0, std::min(lw, rw)), oy = (int)std::min<long long>(wy0, std::min(lh, rh));
-  const int lww = (int)(std::min<long long>(wx1, lw) - ox), lwh = (int)(std::min<long long>(wy1, lh) - oy);
-  const int rww = (int)(std::min<long long>(wx1, rw) - ox), rwh = (int)(std::min<long long>(wy1, rh) - oy);
-  if (lww <= 0 || lwh <= 0 || rww <= 0 || rwh <= 0) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "pyramid_correlate: the tiles lie outside the images");
-  const size_t lb = vwgpu_align_up((size_t)lww * lwh * 4, 256), rb = vwgpu_align_up((size_t)rww * rwh * 4, 256);
-  const size_t lmb = vwgpu_align_up((size_t)lww * lwh, 256), rmb = vwgpu_align_up((size_t)rww * rwh, 256);
-  int rc = vwgpu_arena_reserve(ctx, &ctx->staging, lb + rb + lmb + rmb + out_bytes);
+  const long long sx0 = std::min(P->search_min_x, 0), sy0 = std::min(P->search_min_y, 0);
+  const long long sx1 = std::max(P->search_max_x, 0), sy1 = std::max(P->search_max_y, 0);
+  const long long wx0 = std::max<long long>(0, x0 - padx + sx0), wy0 = std::max<long long>(0, y0 - pady + sy0);
+  const long long wx1 = x1 + padx + sx1, wy1 = y1 + pady + sy1;
+  pyr_window W;
+  W.ox = (int)std::min<long long>(wx0, std::min(lw, rw)); W.oy = (int)std::min<long long>(wy0, std::min(lh, rh));
+  W.lww = (int)(std::min<long long>(wx1, lw) - W.ox); W.lwh = (int)(std::min<long long>(wy1, lh) - W.oy);
+  W.rww = (int)(std::min<long long>(wx1, rw) - W.ox); W.rwh = (int)(std::min<long long>(wy1, rh) - W.oy);
+  W.gx = padx + sx1 - sx0; W.gy = pady + sy1 - sy0;
+  return W;
+}
+
+// The two images and the two masks of a window: pieces 0 .. 3 of a plan.  The mask pieces are reserved whether or not there are masks.
+static void stage_window(vwgpu_stage& st, const pyr_window& W, const float* left, ptrdiff_t ls, const float* right, ptrdiff_t rs,
+                         const uint8_t* lmask, ptrdiff_t lms, const uint8_t* rmask, ptrdiff_t rms) {
+  st.add(left + (ptrdiff_t)W.oy * ls + W.ox, W.lww, W.lwh, 4, ls, VWGPU_STAGE_IN);
+  st.add(right + (ptrdiff_t)W.oy * rs + W.ox, W.rww, W.rwh, 4, rs, VWGPU_STAGE_IN);
+  st.add(lmask ? lmask + (ptrdiff_t)W.oy * lms + W.ox : nullptr, W.lww, W.lwh, 1, lms, lmask ? VWGPU_STAGE_IN : VWGPU_STAGE_NONE);
+  st.add(rmask ? rmask + (ptrdiff_t)W.oy * rms + W.ox : nullptr, W.rww, W.rwh, 1, rms, rmask ? VWGPU_STAGE_IN : VWGPU_STAGE_NONE);
+}
+
+// One run of tiles of the host batch entry: ONE staged window W (the union of what the run's tiles can touch), one device batch call.
+static_assert(4 + VWGPU_MAX_GROUP <= vwgpu_stage::MAX_PIECES, "a run's window and outputs must fit one staging plan");
+static int pyramid_batch_host_run(vwgpu_ctx* ctx, const pyr_window& W, const float* left, ptrdiff_t ls, const float* right, ptrdiff_t rs,
+                                  const uint8_t* lmask, ptrdiff_t lms, const uint8_t* rmask, ptrdiff_t rms, const vwgpu_pyramid_params* P, int n_tiles,
+                                  const int* bx, const int* by, const int* bw, const int* bh, float* const* outs, const ptrdiff_t* os) {
+  if (W.lww <= 0 || W.lwh <= 0 || W.rww <= 0 || W.rwh <= 0) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "pyramid_correlate: the tiles lie outside the images");
+  vwgpu_stage st(ctx);
+  stage_window(st, W, left, ls, right, rs, lmask, lms, rmask, rms);
+  for (int t = 0; t < n_tiles; ++t) st.add(outs[t], bw[t], bh[t], 12, (os && os[t]) ? os[t] : bw[t], VWGPU_STAGE_OUT);
+  int rc = st.commit();
   if (rc) return rc;
-  char* base = static_cast<char*>(ctx->staging.base);
-  float* d_l = reinterpret_cast<float*>(base);
-  float* d_r = reinterpret_cast<float*>(base + lb);
-  uint8_t* d_lm = reinterpret_cast<uint8_t*>(base + lb + rb);
-  uint8_t* d_rm = reinterpret_cast<uint8_t*>(base + lb + rb + lmb);
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(d_l, (size_t)lww * 4, left + (ptrdiff_t)oy * ls + ox, (size_t)ls * 4, (size_t)lww * 4, lwh, hipMemcpyHostToDevice, ctx->stream));
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(d_r, (size_t)rww * 4, right + (ptrdiff_t)oy * rs + ox, (size_t)rs * 4, (size_t)rww * 4, rwh, hipMemcpyHostToDevice, ctx->stream));
-  if (lmask) VWGPU_HIP(ctx, hipMemcpy2DAsync(d_lm, (size_t)lww, lmask + (ptrdiff_t)oy * lms + ox, (size_t)lms, (size_t)lww, lwh, hipMemcpyHostToDevice, ctx->stream));
-  if (rmask) VWGPU_HIP(ctx, hipMemcpy2DAsync(d_rm, (size_t)rww, rmask + (ptrdiff_t)oy * rms + ox, (size_t)rms, (size_t)rww, rwh, hipMemcpyHostToDevice, ctx->stream));
-  std::vector<int> wbx((size_t)n_tiles), wby((size_t)n_tiles);
-  std::vector<float*> d_outs((size_t)n_tiles);
-  char* q = base + lb + rb + lmb + rmb;
+  int wbx[VWGPU_MAX_GROUP], wby[VWGPU_MAX_GROUP];
+  float* d_outs[VWGPU_MAX_GROUP];
   for (int t = 0; t < n_tiles; ++t) {
-    wbx[t] = bx[t] - ox; wby[t] = by[t] - oy;
-    d_outs[t] = reinterpret_cast<float*>(q);
-    q += vwgpu_align_up((size_t)bw[t] * bh[t] * 12, 256);
+    wbx[t] = bx[t] - W.ox; wby[t] = by[t] - W.oy;
+    d_outs[t] = st.dev<float>(4 + t);
   }
-  rc = vwgpu_pyramid_correlate_batch_dev(ctx, d_l, lww, lwh, lww, d_r, rww, rwh, rww, lmask ? d_lm : nullptr, lww, rmask ? d_rm : nullptr, rww, P, n_tiles,
-                                         wbx.data(), wby.data(), bw, bh, d_outs.data(), nullptr);
+  rc = vwgpu_pyramid_correlate_batch_dev(ctx, st.dev<float>(0), W.lww, W.lwh, W.lww, st.dev<float>(1), W.rww, W.rwh, W.rww, lmask ? st.dev<uint8_t>(2) : nullptr, W.lww,
+                                         rmask ? st.dev<uint8_t>(3) : nullptr, W.rww, P, n_tiles, wbx, wby, bw, bh, d_outs, nullptr);
   if (rc) return rc;
-  for (int t = 0; t < n_tiles; ++t) {
-    const ptrdiff_t o = (os && os[t]) ? os[t] : bw[t];
-    VWGPU_HIP(ctx, hipMemcpy2DAsync(outs[t], (size_t)o * 12, d_outs[t], (size_t)bw[t] * 12, (size_t)bw[t] * 12, bh[t], hipMemcpyDeviceToHost, ctx->stream));
-  }
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VWGPU_OK;
+  return st.finish();
 }
 
 int vwgpu_pyramid_correlate_batch(vwgpu_ctx* ctx, const float* left, int lw, int lh, ptrdiff_t ls,
@@ -2108,23 +2102,20 @@ int vwgpu_pyramid_correlate_batch(vwgpu_ctx* ctx, const float* left, int lw, int
   // Staged per RUN of tiles (consecutive tiles of equal size, at most VWGPU_MAX_GROUP: what one device group takes), not per call: tiles
   // scattered over a large pair would otherwise upload nearly the whole pair.  A run whose union window is more than three
   // times the windows of its tiles taken one by one (tiles far apart inside the run) goes through the single-tile entry.
-  const int upb_ = 1 << std::max(0, std::min(P->max_pyramid_levels, 12));
-  const long long padx_ = (long long)(P->kernel_x / 2) * upb_ + 2LL * std::max(P->search_max_x - P->search_min_x, 0) + 8 + std::max(P->search_max_x, 0) - std::min(P->search_min_x, 0);
-  const long long pady_ = (long long)(P->kernel_y / 2) * upb_ + 2LL * std::max(P->search_max_y - P->search_min_y, 0) + 8 + std::max(P->search_max_y, 0) - std::min(P->search_min_y, 0);
   int t0 = 0;
   while (t0 < n_tiles) {
     int t1 = t0 + 1;
     while (t1 < n_tiles && t1 - t0 < VWGPU_MAX_GROUP && bw[t1] == bw[t0] && bh[t1] == bh[t0]) ++t1;
     long long ux0 = LLONG_MAX, uy0 = LLONG_MAX, ux1 = LLONG_MIN, uy1 = LLONG_MIN;
-    double each = 0.0;
     for (int t = t0; t < t1; ++t) {
       ux0 = std::min<long long>(ux0, bx[t]); uy0 = std::min<long long>(uy0, by[t]);
       ux1 = std::max<long long>(ux1, (long long)bx[t] + bw[t]); uy1 = std::max<long long>(uy1, (long long)by[t] + bh[t]);
-      each += (double)(bw[t] + 2 * padx_) * (double)(bh[t] + 2 * pady_);
     }
-    const double uni = (double)(ux1 - ux0 + 2 * padx_) * (double)(uy1 - uy0 + 2 * pady_);
+    const pyr_window W = pyramid_window(P, ux0, uy0, ux1, uy1, lw, lh, rw, rh);
+    const double each = (double)(t1 - t0) * ((double)(bw[t0] + 2 * W.gx) * (double)(bh[t0] + 2 * W.gy));      // (the tiles of a run are equal in size)
+    const double uni = (double)(ux1 - ux0 + 2 * W.gx) * (double)(uy1 - uy0 + 2 * W.gy);
     if (t1 - t0 > 1 && uni <= 3.0 * each) {
-      int rc = pyramid_batch_host_run(ctx, left, lw, lh, ls, right, rw, rh, rs, lmask, lms, rmask, rms, P, t1 - t0, bx + t0, by + t0, bw + t0, bh + t0, outs + t0, os ? os + t0 : nullptr);
+      int rc = pyramid_batch_host_run(ctx, W, left, ls, right, rs, lmask, lms, rmask, rms, P, t1 - t0, bx + t0, by + t0, bw + t0, bh + t0, outs + t0, os ? os + t0 : nullptr);
       if (rc) return rc;
     } else {
       for (int t = t0; t < t1; ++t) {
@@ -2149,63 +2140,28 @@ int vwgpu_pyramid_correlate(vwgpu_ctx* ctx, const float* left, int lw, int lh, p
   if (rms == 0) rms = rw;
   if (os == 0) os = bw;
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  // Only the window of the sources this tile can touch goes to the device — the reference's prerasterize also pulls just
-  // its padded ROIs through the views (CorrelationView.cc:89-97) — not the whole images: a 1024^2 tile of a 32768^2 pair
-  // stages ~2000^2 pixels per image.  Window = tile grown by half_kernel * 2^max_levels (pyramid padding), twice the
-  // search extent (R->L runs of the SGM branch) and the search range itself, cut at the image borders; both images and
-  // masks share the window origin, so disparities and the edge extension at true image borders are unchanged.
-  const int upb = 1 << std::max(0, std::min(P->max_pyramid_levels, 12));
-  const int sdx = P->search_max_x - P->search_min_x, sdy = P->search_max_y - P->search_min_y;
-  const long long padx = (long long)(P->kernel_x / 2) * upb + 2LL * std::max(sdx, 0) + 8;
-  const long long pady = (long long)(P->kernel_y / 2) * upb + 2LL * std::max(sdy, 0) + 8;
-  const long long wx0 = std::max<long long>(0, (long long)bx - padx + std::min(P->search_min_x, 0));
-  const long long wy0 = std::max<long long>(0, (long long)by - pady + std::min(P->search_min_y, 0));
-  const long long wx1 = (long long)bx + bw + padx + std::max(P->search_max_x, 0);
-  const long long wy1 = (long long)by + bh + pady + std::max(P->search_max_y, 0);
-  const int ox = (int)std::min<long long>(wx0, std::min(lw, rw)), oy = (int)std::min<long long>(wy0, std::min(lh, rh));
-  const int lww = (int)(std::min<long long>(wx1, lw) - ox), lwh = (int)(std::min<long long>(wy1, lh) - oy);
-  const int rww = (int)(std::min<long long>(wx1, rw) - ox), rwh = (int)(std::min<long long>(wy1, rh) - oy);
-  if (lww <= 0 || lwh <= 0 || rww <= 0 || rwh <= 0)
+  const pyr_window W = pyramid_window(P, bx, by, (long long)bx + bw, (long long)by + bh, lw, lh, rw, rh);
+  if (W.lww <= 0 || W.lwh <= 0 || W.rww <= 0 || W.rwh <= 0)
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "pyramid_correlate: the tile lies outside the images");
-  const size_t lb = vwgpu_align_up((size_t)lww * lwh * 4, 256), rb = vwgpu_align_up((size_t)rww * rwh * 4, 256);
-  const size_t lmb = vwgpu_align_up((size_t)lww * lwh, 256), rmb = vwgpu_align_up((size_t)rww * rwh, 256), ob = vwgpu_align_up((size_t)bw * bh * 12, 256);
   if (P->lr_disp_diff && (bx < P->region_ul_x || by < P->region_ul_y || bx + bw > P->region_ul_x + P->lr_disp_diff_cols ||
                           by + bh > P->region_ul_y + P->lr_disp_diff_rows))
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "The L-R to R-L difference image domain does not contain the current tile.");
   // The discrepancy image is shared by the tile threads (each writes its own pixels, CorrelationView.cc:683-694): only the
   // tile's rectangle of it is staged, so that concurrent tiles never write back each other's stale pixels.
   const ptrdiff_t hdst = P->lr_disp_diff_stride ? P->lr_disp_diff_stride : P->lr_disp_diff_cols;
-  const size_t db = P->lr_disp_diff ? vwgpu_align_up((size_t)bw * bh * 8, 256) : 0;
   float* h_diff = P->lr_disp_diff ? P->lr_disp_diff + ((ptrdiff_t)(by - P->region_ul_y) * hdst + (bx - P->region_ul_x)) * 2 : nullptr;
-  rc = vwgpu_arena_reserve(ctx, &ctx->staging, lb + rb + lmb + rmb + ob + db);
-  if (rc) return rc;
-  char* base = static_cast<char*>(ctx->staging.base);
-  float* d_l = reinterpret_cast<float*>(base);
-  float* d_r = reinterpret_cast<float*>(base + lb);
-  uint8_t* d_lm = reinterpret_cast<uint8_t*>(base + lb + rb);
-  uint8_t* d_rm = reinterpret_cast<uint8_t*>(base + lb + rb + lmb);
-  float* d_o = reinterpret_cast<float*>(base + lb + rb + lmb + rmb);
-  const float* lsrc = left + (ptrdiff_t)oy * ls + ox;
-  const float* rsrc = right + (ptrdiff_t)oy * rs + ox;
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(d_l, (size_t)lww * 4, lsrc, (size_t)ls * 4, (size_t)lww * 4, lwh, hipMemcpyHostToDevice, ctx->stream));
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(d_r, (size_t)rww * 4, rsrc, (size_t)rs * 4, (size_t)rww * 4, rwh, hipMemcpyHostToDevice, ctx->stream));
-  if (lmask) VWGPU_HIP(ctx, hipMemcpy2DAsync(d_lm, (size_t)lww, lmask + (ptrdiff_t)oy * lms + ox, (size_t)lms, (size_t)lww, lwh, hipMemcpyHostToDevice, ctx->stream));
-  if (rmask) VWGPU_HIP(ctx, hipMemcpy2DAsync(d_rm, (size_t)rww, rmask + (ptrdiff_t)oy * rms + ox, (size_t)rms, (size_t)rww, rwh, hipMemcpyHostToDevice, ctx->stream));
-  float* d_d = reinterpret_cast<float*>(base + lb + rb + lmb + rmb + ob);
+  vwgpu_stage st(ctx);
+  stage_window(st, W, left, ls, right, rs, lmask, lms, rmask, rms);
+  const int pd = st.add(h_diff, bw, bh, 8, hdst, VWGPU_STAGE_INOUT), po = st.add(out, bw, bh, 12, os, VWGPU_STAGE_OUT);
+  if ((rc = st.commit())) return rc;
   vwgpu_pyramid_params Pd = *P;                     // the device-side discrepancy image is the tile's rectangle, dense
   Pd.lr_disp_diff_cols = bw; Pd.lr_disp_diff_rows = bh; Pd.lr_disp_diff_stride = bw;
-  Pd.region_ul_x = bx - ox;                         // everything below runs in window coordinates
-  Pd.region_ul_y = by - oy;
-  if (P->lr_disp_diff)
-    VWGPU_HIP(ctx, hipMemcpy2DAsync(d_d, (size_t)bw * 8, h_diff, (size_t)hdst * 8, (size_t)bw * 8, bh, hipMemcpyHostToDevice, ctx->stream));
-  rc = vwgpu_pyramid_correlate_impl(ctx, d_l, lww, lwh, lww, d_r, rww, rwh, rww, lmask ? d_lm : nullptr, lww, rmask ? d_rm : nullptr, rww,
-                                    &Pd, bx - ox, by - oy, bw, bh, d_o, bw, P->lr_disp_diff ? d_d : nullptr);
+  Pd.region_ul_x = bx - W.ox;                       // everything below runs in window coordinates
+  Pd.region_ul_y = by - W.oy;
+  rc = vwgpu_pyramid_correlate_impl(ctx, st.dev<float>(0), W.lww, W.lwh, W.lww, st.dev<float>(1), W.rww, W.rwh, W.rww, lmask ? st.dev<uint8_t>(2) : nullptr, W.lww,
+                                    rmask ? st.dev<uint8_t>(3) : nullptr, W.rww, &Pd, bx - W.ox, by - W.oy, bw, bh, st.dev<float>(po), bw, st.dev<float>(pd));
   if (rc) return rc;
-  if (P->lr_disp_diff)
-    VWGPU_HIP(ctx, hipMemcpy2DAsync(h_diff, (size_t)hdst * 8, d_d, (size_t)bw * 8, (size_t)bw * 8, bh, hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(out, (size_t)os * 12, d_o, (size_t)bw * 12, (size_t)bw * 12, bh, hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VWGPU_OK;
+  return st.finish();
 }
 
 }  // extern "C"

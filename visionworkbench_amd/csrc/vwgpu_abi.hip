@@ -48,6 +48,43 @@ int vwgpu_arena_reserve(vwgpu_ctx* ctx, vwgpu_arena* a, size_t bytes) {
   return VWGPU_OK;
 }
 
+int vwgpu_stage::add(const void* host, int w, int h, size_t elem, ptrdiff_t host_stride, int dir) {
+  if (n == MAX_PIECES) { total = SIZE_MAX; return 0; }             // commit refuses
+  const bool present = host || dir == VWGPU_STAGE_NONE;
+  p[n] = piece{const_cast<void*>(host), nullptr, total, elem, host_stride, w, h, dir, present};
+  if (present) total += vwgpu_align_up((size_t)w * h * elem, 256);
+  return n++;
+}
+
+int vwgpu_stage::commit() {
+  if (total == SIZE_MAX) return vwgpu_fail(ctx, VWGPU_ERR_LOGIC, "vwgpu_stage: more than %d pieces", MAX_PIECES);
+  int rc = vwgpu_arena_reserve(ctx, &ctx->staging, total);
+  if (rc) return rc;
+  for (piece* q = p; q < p + n; ++q) {
+    if (!q->present) continue;
+    q->dev = static_cast<char*>(ctx->staging.base) + q->off;
+    if ((q->dir & VWGPU_STAGE_IN) && q->w > 0 && q->h > 0)
+      VWGPU_HIP(ctx, hipMemcpy2DAsync(q->dev, q->w * q->elem, q->host, q->stride * q->elem, q->w * q->elem, q->h, hipMemcpyHostToDevice, ctx->stream));
+  }
+  return VWGPU_OK;
+}
+
+int vwgpu_stage::download(int piece, void* host, int w, int h, ptrdiff_t host_stride) {
+  const size_t e = p[piece].elem;
+  if (w > 0 && h > 0) VWGPU_HIP(ctx, hipMemcpy2DAsync(host, host_stride * e, p[piece].dev, w * e, w * e, h, hipMemcpyDeviceToHost, ctx->stream));
+  return VWGPU_OK;
+}
+
+int vwgpu_stage::finish() {
+  for (int i = 0; i < n; ++i)
+    if (p[i].present && (p[i].dir & VWGPU_STAGE_OUT)) {
+      int rc = download(i, p[i].host, p[i].w, p[i].h, p[i].stride);
+      if (rc) return rc;
+    }
+  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return VWGPU_OK;
+}
+
 // The pinned ring is two halves.  Pieces are handed out in address order; when the cursor leaves a half, an event recorded on the
 // stream marks "every copy that reads this half has been queued before here", and the cursor enters the other half only after the
 // event recorded when IT was last left has completed.  So a piece is never rewritten while a copy that reads it is still pending,
@@ -235,29 +272,38 @@ int vwgpu_force_path(vwgpu_ctx* ctx, int path) {
   return VWGPU_OK;
 }
 
+// The integer options that are a field of the context: set accepts [lo, hi] where `settable`, get reads every one of them.  The options
+// that are not a plain int field (a bool, derived or device-wide values) are spelled out in the two functions.
+static const struct { int id; int vwgpu_ctx::* field; int lo, hi; bool settable; } k_options[] = {
+  // these select between variants that return identical results; out-of-range values are refused
+  {VWGPU_OPT_SAD_GROUPS, &vwgpu_ctx::sad_groups, 0, 3, true},
+  {VWGPU_OPT_SAD_LAYOUT, &vwgpu_ctx::sad_layout, 0, 1, true},
+  {VWGPU_OPT_SAD_LAST_LAUNCH, &vwgpu_ctx::sad_last_launch, 0, 0, false},
+  {VWGPU_OPT_EXACT_SCRATCH_MB, &vwgpu_ctx::exact_scratch_mb, 16, 65536, true},
+  {VWGPU_OPT_TRACE, &vwgpu_ctx::trace, 0, 7, true},
+  {VWGPU_OPT_CERTIFY, &vwgpu_ctx::certify, 0, 1, true},
+  {VWGPU_OPT_CERT_F32, &vwgpu_ctx::cert_f32, 0, 1, true},
+  {VWGPU_OPT_ZONE_TILE16, &vwgpu_ctx::zone_tile16, 0, 2, true},
+  {VWGPU_OPT_ZONE_SXC, &vwgpu_ctx::zone_sxc, 0, 4096, true},
+  {VWGPU_OPT_SGM_SWEEP, &vwgpu_ctx::sgm_sweep, 0, 15, true},
+  {VWGPU_OPT_MGM_SWEEP, &vwgpu_ctx::mgm_sweep, 0, 15, true},
+  {VWGPU_OPT_SGM_PATH_MODE, &vwgpu_ctx::sgm_path_mode, 0, 4095, true},
+  {VWGPU_OPT_EXACT_SPLIT, &vwgpu_ctx::exact_split, 0, 3, true},
+  {VWGPU_OPT_HOST_RING_KB, &vwgpu_ctx::host_ring_kb, 16, 1 << 20, true},
+};
+
 int vwgpu_set_option(vwgpu_ctx* ctx, int option, int value) {
   if (!ctx) return VWGPU_ERR_ARGUMENT;
   if (option == VWGPU_OPT_DEFER_EXACTNESS) { ctx->defer_exact = value != 0; return VWGPU_OK; }
-  // the options below select between variants that return identical results; out-of-range values are refused
-  if (option == VWGPU_OPT_SAD_GROUPS && value >= 0 && value <= 3) { ctx->sad_groups = value; return VWGPU_OK; }
-  if (option == VWGPU_OPT_SAD_LAYOUT && (value == 0 || value == 1)) { ctx->sad_layout = value; return VWGPU_OK; }
-  if (option == VWGPU_OPT_EXACT_SCRATCH_MB && value >= 16 && value <= 65536) { ctx->exact_scratch_mb = value; return VWGPU_OK; }
-  if (option == VWGPU_OPT_TRACE && value >= 0 && value <= 7) { ctx->trace = value; ctx->cert_px[0] = ctx->cert_px[1] = ctx->cert_px[2] = 0; return VWGPU_OK; }
-  if (option == VWGPU_OPT_CERTIFY && (value == 0 || value == 1)) { ctx->certify = value; return VWGPU_OK; }
-  if (option == VWGPU_OPT_CERT_F32 && (value == 0 || value == 1)) { ctx->cert_f32 = value; return VWGPU_OK; }
-  if (option == VWGPU_OPT_ZONE_TILE16 && value >= 0 && value <= 2) { ctx->zone_tile16 = value; return VWGPU_OK; }
-  if (option == VWGPU_OPT_ZONE_SXC && value >= 0 && value <= 4096) { ctx->zone_sxc = value; return VWGPU_OK; }
-  if (option == VWGPU_OPT_SGM_SWEEP && value >= 0 && value <= 15) { ctx->sgm_sweep = value; return VWGPU_OK; }
-  if (option == VWGPU_OPT_MGM_SWEEP && value >= 0 && value <= 15) { ctx->mgm_sweep = value; return VWGPU_OK; }
-  if (option == VWGPU_OPT_SGM_PATH_MODE && value >= 0 && value <= 4095) { ctx->sgm_path_mode = value; return VWGPU_OK; }
-  if (option == VWGPU_OPT_EXACT_SPLIT && value >= 0 && value <= 3) { ctx->exact_split = value; return VWGPU_OK; }
-  if (option == VWGPU_OPT_HOST_RING_KB && value >= 16 && value <= (1 << 20)) {
-    if (value != ctx->host_ring_kb && ctx->host_ring) {            // pending copies read the old ring
+  for (const auto& o : k_options) {
+    if (o.id != option || !o.settable || value < o.lo || value > o.hi) continue;
+    if (option == VWGPU_OPT_TRACE) ctx->cert_px[0] = ctx->cert_px[1] = ctx->cert_px[2] = 0;
+    if (option == VWGPU_OPT_HOST_RING_KB && value != ctx->host_ring_kb && ctx->host_ring) {            // pending copies read the old ring
       VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
       (void)hipHostFree(ctx->host_ring);
       ctx->host_ring = nullptr; ctx->host_cap = ctx->host_pos = 0;
     }
-    ctx->host_ring_kb = value;
+    ctx->*o.field = value;
     return VWGPU_OK;
   }
   return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "vwgpu_set_option: unknown or read-only option %d, or value %d out of range", option, value);
@@ -272,29 +318,13 @@ int vwgpu_get_option(const vwgpu_ctx* ctx, int option, int* value) {
     return VWGPU_OK;
   }
   if (!ctx) return VWGPU_ERR_ARGUMENT;
+  for (const auto& o : k_options)
+    if (o.id == option) { *value = ctx->*o.field; return VWGPU_OK; }
   if (option == VWGPU_OPT_DEFER_EXACTNESS) { *value = ctx->defer_exact ? 1 : 0; return VWGPU_OK; }
-  if (option == VWGPU_OPT_SAD_GROUPS) { *value = ctx->sad_groups; return VWGPU_OK; }
-  if (option == VWGPU_OPT_SAD_LAYOUT) { *value = ctx->sad_layout; return VWGPU_OK; }
-  if (option == VWGPU_OPT_SAD_LAST_LAUNCH) { *value = ctx->sad_last_launch; return VWGPU_OK; }
-  if (option == VWGPU_OPT_EXACT_SCRATCH_MB) { *value = ctx->exact_scratch_mb; return VWGPU_OK; }
-  if (option == VWGPU_OPT_TRACE) { *value = ctx->trace; return VWGPU_OK; }
-  if (option == VWGPU_OPT_SGM_SWEEP) { *value = ctx->sgm_sweep; return VWGPU_OK; }
-  if (option == VWGPU_OPT_MGM_SWEEP) { *value = ctx->mgm_sweep; return VWGPU_OK; }
-  if (option == VWGPU_OPT_SGM_PATH_MODE) { *value = ctx->sgm_path_mode; return VWGPU_OK; }
-  if (option == VWGPU_OPT_EXACT_SPLIT) { *value = ctx->exact_split; return VWGPU_OK; }
-  if (option == VWGPU_OPT_HOST_RING_KB) { *value = ctx->host_ring_kb; return VWGPU_OK; }
-  if (option == VWGPU_OPT_CERTIFY) { *value = ctx->certify; return VWGPU_OK; }
-  if (option == VWGPU_OPT_ZONE_SXC) { *value = ctx->zone_sxc; return VWGPU_OK; }
-  if (option == VWGPU_OPT_CERT_PERMILLE) {          // share of the pixels (per mille) that were certified since VWGPU_OPT_TRACE was last set; -1: none counted
+  // shares (per mille) of the pixels counted since VWGPU_OPT_TRACE was last set: certified / passed on to float64 by the fp32 tier; -1: none counted
+  if (option == VWGPU_OPT_CERT_PERMILLE || option == VWGPU_OPT_CERT_F64_PERMILLE) {
     const unsigned long long all = ctx->cert_px[0] + ctx->cert_px[1];
-    *value = all ? (int)((ctx->cert_px[0] * 1000ull) / all) : -1;
-    return VWGPU_OK;
-  }
-  if (option == VWGPU_OPT_CERT_F32) { *value = ctx->cert_f32; return VWGPU_OK; }
-  if (option == VWGPU_OPT_ZONE_TILE16) { *value = ctx->zone_tile16; return VWGPU_OK; }
-  if (option == VWGPU_OPT_CERT_F64_PERMILLE) {
-    const unsigned long long all = ctx->cert_px[0] + ctx->cert_px[1];
-    *value = all ? (int)((ctx->cert_px[2] * 1000ull) / all) : -1;
+    *value = all ? (int)((ctx->cert_px[option == VWGPU_OPT_CERT_PERMILLE ? 0 : 2] * 1000ull) / all) : -1;
     return VWGPU_OK;
   }
   if (option == VWGPU_OPT_HOST_RING_WRAPS) { *value = (int)(ctx->ring_wraps & 0x7fffffff); return VWGPU_OK; }
@@ -561,22 +591,13 @@ int vwgpu_calc_disparity(vwgpu_ctx* ctx, int cost_type,
   if (os == 0) os = ow;
   // Only the part of the right raster the search can reach is staged (Correlation.cc:356-359).
   const int rcw = lw + sx - 1, rch = lh + sy - 1;
-  const size_t lb = vwgpu_align_up((size_t)lw * lh * sizeof(float), 256);
-  const size_t rb = vwgpu_align_up((size_t)rcw * rch * sizeof(float), 256);
-  const size_t ob = vwgpu_align_up((size_t)ow * oh * 3 * sizeof(int32_t), 256);
-  rc = vwgpu_arena_reserve(ctx, &ctx->staging, lb + rb + ob);
+  vwgpu_stage st(ctx);
+  const int pl = st.add(left, lw, lh, 4, ls, VWGPU_STAGE_IN), pr = st.add(right, rcw, rch, 4, rs, VWGPU_STAGE_IN);
+  const int po = st.add(out, ow, oh, 12, os, VWGPU_STAGE_OUT);
+  if ((rc = st.commit())) return rc;
+  rc = vwgpu_calc_disparity_dev(ctx, cost_type, st.dev<float>(pl), lw, lh, lw, st.dev<float>(pr), rcw, rch, rcw, kx, ky, sx, sy, st.dev<int32_t>(po), ow);
   if (rc) return rc;
-  char* base = static_cast<char*>(ctx->staging.base);
-  float* d_l = reinterpret_cast<float*>(base);
-  float* d_r = reinterpret_cast<float*>(base + lb);
-  int32_t* d_o = reinterpret_cast<int32_t*>(base + lb + rb);
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(d_l, (size_t)lw * 4, left, (size_t)ls * 4, (size_t)lw * 4, lh, hipMemcpyHostToDevice, ctx->stream));
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(d_r, (size_t)rcw * 4, right, (size_t)rs * 4, (size_t)rcw * 4, rch, hipMemcpyHostToDevice, ctx->stream));
-  rc = vwgpu_calc_disparity_dev(ctx, cost_type, d_l, lw, lh, lw, d_r, rcw, rch, rcw, kx, ky, sx, sy, d_o, ow);
-  if (rc) return rc;
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(out, (size_t)os * 12, d_o, (size_t)ow * 12, (size_t)ow * 12, oh, hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VWGPU_OK;
+  return st.finish();
 }
 
 // ---- fast_box_sum -------------------------------------------------------------------------------------------
@@ -617,17 +638,12 @@ int vwgpu_fast_box_sum(vwgpu_ctx* ctx, const float* img, int w, int h, ptrdiff_t
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
   const int ow = w - kx + 1, oh = h - ky + 1;
   if (os == 0) os = ow;
-  const size_t ib = vwgpu_align_up((size_t)w * h * sizeof(float), 256), ob = (size_t)ow * oh * sizeof(double);
-  rc = vwgpu_arena_reserve(ctx, &ctx->staging, ib + ob);
+  vwgpu_stage st(ctx);
+  const int pi = st.add(img, w, h, 4, stride, VWGPU_STAGE_IN), po = st.add(out, ow, oh, 8, os, VWGPU_STAGE_OUT);
+  if ((rc = st.commit())) return rc;
+  rc = vwgpu_launch_box_sum_exact(ctx, st.dev<float>(pi), w, h, w, kx, ky, st.dev<double>(po));
   if (rc) return rc;
-  float* d_i = static_cast<float*>(ctx->staging.base);
-  double* d_o = reinterpret_cast<double*>(static_cast<char*>(ctx->staging.base) + ib);
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(d_i, (size_t)w * 4, img, (size_t)stride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
-  rc = vwgpu_launch_box_sum_exact(ctx, d_i, w, h, w, kx, ky, d_o);
-  if (rc) return rc;
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(out, (size_t)os * 8, d_o, (size_t)ow * 8, (size_t)ow * 8, oh, hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VWGPU_OK;
+  return st.finish();
 }
 
 // ---- left/right consistency check -----------------------------------------------------------------------
@@ -651,26 +667,20 @@ int vwgpu_cross_corr_consistency_check_dev(vwgpu_ctx* ctx, int32_t* d_l2r, int l
 int vwgpu_cross_corr_consistency_check(vwgpu_ctx* ctx, int32_t* l2r, int lw, int lh, ptrdiff_t ls,
                                        const int32_t* r2l, int rw, int rh, ptrdiff_t rs, float thr) {
   if (!ctx) return VWGPU_ERR_ARGUMENT;
+  ctx->err.clear();
   if (!l2r || !r2l || lw < 0 || lh < 0 || rw < 0 || rh < 0)
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "cross_corr_consistency_check: bad image");
   if (ls == 0) ls = lw;
   if (rs == 0) rs = rw;
   if (lw == 0 || lh == 0) return VWGPU_OK;
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t lb = vwgpu_align_up((size_t)lw * lh * 12, 256), rb = vwgpu_align_up((size_t)rw * rh * 12, 256);
-  int rc = vwgpu_arena_reserve(ctx, &ctx->staging, lb + rb);
+  vwgpu_stage st(ctx);
+  const int pl = st.add(l2r, lw, lh, 12, ls, VWGPU_STAGE_INOUT), pr = st.add(r2l, rw, rh, 12, rs, VWGPU_STAGE_IN);
+  int rc = st.commit();
   if (rc) return rc;
-  char* base = static_cast<char*>(ctx->staging.base);
-  int32_t* d_l = reinterpret_cast<int32_t*>(base);
-  int32_t* d_r = reinterpret_cast<int32_t*>(base + lb);
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(d_l, (size_t)lw * 12, l2r, (size_t)ls * 12, (size_t)lw * 12, lh, hipMemcpyHostToDevice, ctx->stream));
-  if (rw > 0 && rh > 0)
-    VWGPU_HIP(ctx, hipMemcpy2DAsync(d_r, (size_t)rw * 12, r2l, (size_t)rs * 12, (size_t)rw * 12, rh, hipMemcpyHostToDevice, ctx->stream));
-  rc = vwgpu_cross_corr_consistency_check_dev(ctx, d_l, lw, lh, lw, d_r, rw, rh, rw, thr);
+  rc = vwgpu_cross_corr_consistency_check_dev(ctx, st.dev<int32_t>(pl), lw, lh, lw, st.dev<int32_t>(pr), rw, rh, rw, thr);
   if (rc) return rc;
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(l2r, (size_t)ls * 12, d_l, (size_t)lw * 12, (size_t)lw * 12, lh, hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VWGPU_OK;
+  return st.finish();
 }
 
 int vwgpu_cross_corr_consistency_check_diff_dev(vwgpu_ctx* ctx, int32_t* d_l2r, int lw, int lh, ptrdiff_t ls,
@@ -696,6 +706,7 @@ int vwgpu_cross_corr_consistency_check_diff(vwgpu_ctx* ctx, int32_t* l2r, int lw
                                             const int32_t* r2l, int rw, int rh, ptrdiff_t rs, float thr,
                                             float* diff, int dcols, int drows, ptrdiff_t dstride, int ulx, int uly) {
   if (!ctx) return VWGPU_ERR_ARGUMENT;
+  ctx->err.clear();
   if (!l2r || !r2l || lw < 0 || lh < 0 || rw < 0 || rh < 0)
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "cross_corr_consistency_check: bad image");
   if (ls == 0) ls = lw;
@@ -703,24 +714,14 @@ int vwgpu_cross_corr_consistency_check_diff(vwgpu_ctx* ctx, int32_t* l2r, int lw
   if (dstride == 0) dstride = dcols;
   if (lw == 0 || lh == 0) return VWGPU_OK;
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t lb = vwgpu_align_up((size_t)lw * lh * 12, 256), rb = vwgpu_align_up((size_t)rw * rh * 12, 256);
-  const size_t db = diff ? vwgpu_align_up((size_t)dcols * drows * 8, 256) : 0;
-  int rc = vwgpu_arena_reserve(ctx, &ctx->staging, lb + rb + db);
+  vwgpu_stage st(ctx);
+  const int pl = st.add(l2r, lw, lh, 12, ls, VWGPU_STAGE_INOUT), pr = st.add(r2l, rw, rh, 12, rs, VWGPU_STAGE_IN);
+  const int pd = st.add(diff, dcols, drows, 8, dstride, VWGPU_STAGE_INOUT);
+  int rc = st.commit();
   if (rc) return rc;
-  char* base = static_cast<char*>(ctx->staging.base);
-  int32_t* d_l = reinterpret_cast<int32_t*>(base);
-  int32_t* d_r = reinterpret_cast<int32_t*>(base + lb);
-  float* d_d = reinterpret_cast<float*>(base + lb + rb);
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(d_l, (size_t)lw * 12, l2r, (size_t)ls * 12, (size_t)lw * 12, lh, hipMemcpyHostToDevice, ctx->stream));
-  if (rw > 0 && rh > 0)
-    VWGPU_HIP(ctx, hipMemcpy2DAsync(d_r, (size_t)rw * 12, r2l, (size_t)rs * 12, (size_t)rw * 12, rh, hipMemcpyHostToDevice, ctx->stream));
-  if (diff) VWGPU_HIP(ctx, hipMemcpy2DAsync(d_d, (size_t)dcols * 8, diff, (size_t)dstride * 8, (size_t)dcols * 8, drows, hipMemcpyHostToDevice, ctx->stream));
-  rc = vwgpu_cross_corr_consistency_check_diff_dev(ctx, d_l, lw, lh, lw, d_r, rw, rh, rw, thr, diff ? d_d : nullptr, dcols, drows, dcols, ulx, uly);
+  rc = vwgpu_cross_corr_consistency_check_diff_dev(ctx, st.dev<int32_t>(pl), lw, lh, lw, st.dev<int32_t>(pr), rw, rh, rw, thr, st.dev<float>(pd), dcols, drows, dcols, ulx, uly);
   if (rc) return rc;
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(l2r, (size_t)ls * 12, d_l, (size_t)lw * 12, (size_t)lw * 12, lh, hipMemcpyDeviceToHost, ctx->stream));
-  if (diff) VWGPU_HIP(ctx, hipMemcpy2DAsync(diff, (size_t)dstride * 8, d_d, (size_t)dcols * 8, (size_t)dcols * 8, drows, hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VWGPU_OK;
+  return st.finish();
 }
 
 }  // extern "C"

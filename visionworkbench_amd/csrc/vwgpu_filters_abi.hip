@@ -18,25 +18,6 @@ int check_image(vwgpu_ctx* ctx, const char* what, const void* src, int w, int h,
   return VWGPU_OK;
 }
 
-// Host-pointer variants: stage src, run `body(d_src, d_dst)`, copy back.
-template <class T, class Body>
-int staged(vwgpu_ctx* ctx, const T* src, int w, int h, ptrdiff_t stride, T* dst, int ow, int oh, ptrdiff_t dstride, Body body) {
-  VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t sb = vwgpu_align_up((size_t)w * h * sizeof(T), 256), db = vwgpu_align_up((size_t)ow * oh * sizeof(T), 256);
-  int rc = vwgpu_arena_reserve(ctx, &ctx->staging, sb + db);
-  if (rc) return rc;
-  T* d_s = reinterpret_cast<T*>(ctx->staging.base);
-  T* d_d = reinterpret_cast<T*>(static_cast<char*>(ctx->staging.base) + sb);
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(d_s, (size_t)w * sizeof(T), src, (size_t)stride * sizeof(T), (size_t)w * sizeof(T), h,
-                                  hipMemcpyHostToDevice, ctx->stream));
-  rc = body(d_s, d_d);
-  if (rc) return rc;
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(dst, (size_t)dstride * sizeof(T), d_d, (size_t)ow * sizeof(T), (size_t)ow * sizeof(T), oh,
-                                  hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VWGPU_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -100,9 +81,13 @@ int vwgpu_separable_convolution(vwgpu_ctx* ctx, const float* src, int w, int h, 
   if (subsample < 1) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "separable_convolution_filter: subsample < 1");
   const int ow = 1 + (w - 1) / subsample, oh = 1 + (h - 1) / subsample;
   if (dstride == 0) dstride = ow;
-  return staged<float>(ctx, src, w, h, stride, dst, ow, oh, dstride, [&](float* ds, float* dd) {
-    return vwgpu_separable_convolution_dev(ctx, ds, w, h, w, xk, nx, cx, yk, ny, cy, edge, subsample, dd, ow);
-  });
+  VWGPU_HIP(ctx, hipSetDevice(ctx->device));
+  vwgpu_stage st(ctx);
+  const int ps = st.add(src, w, h, sizeof(float), stride, VWGPU_STAGE_IN), pd = st.add(dst, ow, oh, sizeof(float), dstride, VWGPU_STAGE_OUT);
+  if ((rc = st.commit())) return rc;
+  rc = vwgpu_separable_convolution_dev(ctx, st.dev<float>(ps), w, h, w, xk, nx, cx, yk, ny, cy, edge, subsample, st.dev<float>(pd), ow);
+  if (rc) return rc;
+  return st.finish();
 }
 
 int vwgpu_convolution_2d_dev(vwgpu_ctx* ctx, const float* d_src, int w, int h, ptrdiff_t stride,
@@ -123,9 +108,13 @@ int vwgpu_convolution_2d(vwgpu_ctx* ctx, const float* src, int w, int h, ptrdiff
   int rc = check_image(ctx, "convolution_filter", src, w, h, stride, dst);
   if (rc) return rc;
   if (dstride == 0) dstride = w;
-  return staged<float>(ctx, src, w, h, stride, dst, w, h, dstride, [&](float* ds, float* dd) {
-    return vwgpu_convolution_2d_dev(ctx, ds, w, h, w, kernel, kw, kh, ci, cj, edge, dd, w);
-  });
+  VWGPU_HIP(ctx, hipSetDevice(ctx->device));
+  vwgpu_stage st(ctx);
+  const int ps = st.add(src, w, h, sizeof(float), stride, VWGPU_STAGE_IN), pd = st.add(dst, w, h, sizeof(float), dstride, VWGPU_STAGE_OUT);
+  if ((rc = st.commit())) return rc;
+  rc = vwgpu_convolution_2d_dev(ctx, st.dev<float>(ps), w, h, w, kernel, kw, kh, ci, cj, edge, st.dev<float>(pd), w);
+  if (rc) return rc;
+  return st.finish();
 }
 
 int vwgpu_subsample_mask_by_two_dev(vwgpu_ctx* ctx, const uint8_t* d_src, int w, int h, ptrdiff_t stride,
@@ -145,9 +134,13 @@ int vwgpu_subsample_mask_by_two(vwgpu_ctx* ctx, const uint8_t* src, int w, int h
   if (rc) return rc;
   const int ow = 1 + (w - 1) / 2, oh = 1 + (h - 1) / 2;
   if (dstride == 0) dstride = ow;
-  return staged<uint8_t>(ctx, src, w, h, stride, dst, ow, oh, dstride, [&](uint8_t* ds, uint8_t* dd) {
-    return vwgpu_subsample_mask_by_two_dev(ctx, ds, w, h, w, dd, ow);
-  });
+  VWGPU_HIP(ctx, hipSetDevice(ctx->device));
+  vwgpu_stage st(ctx);
+  const int ps = st.add(src, w, h, sizeof(uint8_t), stride, VWGPU_STAGE_IN), pd = st.add(dst, ow, oh, sizeof(uint8_t), dstride, VWGPU_STAGE_OUT);
+  if ((rc = st.commit())) return rc;
+  rc = vwgpu_subsample_mask_by_two_dev(ctx, st.dev<uint8_t>(ps), w, h, w, st.dev<uint8_t>(pd), ow);
+  if (rc) return rc;
+  return st.finish();
 }
 
 int vwgpu_prefilter_image_dev(vwgpu_ctx* ctx, const float* d_src, int w, int h, ptrdiff_t stride,
@@ -230,9 +223,13 @@ int vwgpu_prefilter_image(vwgpu_ctx* ctx, const float* src, int w, int h, ptrdif
   int rc = check_image(ctx, "prefilter_image", src, w, h, stride, dst);
   if (rc) return rc;
   if (dstride == 0) dstride = w;
-  return staged<float>(ctx, src, w, h, stride, dst, w, h, dstride, [&](float* ds, float* dd) {
-    return vwgpu_prefilter_image_dev(ctx, ds, w, h, w, mode, width, dd, w);
-  });
+  VWGPU_HIP(ctx, hipSetDevice(ctx->device));
+  vwgpu_stage st(ctx);
+  const int ps = st.add(src, w, h, sizeof(float), stride, VWGPU_STAGE_IN), pd = st.add(dst, w, h, sizeof(float), dstride, VWGPU_STAGE_OUT);
+  if ((rc = st.commit())) return rc;
+  rc = vwgpu_prefilter_image_dev(ctx, st.dev<float>(ps), w, h, w, mode, width, st.dev<float>(pd), w);
+  if (rc) return rc;
+  return st.finish();
 }
 
 
@@ -317,6 +314,7 @@ int vwgpu_parabola_subpixel(vwgpu_ctx* ctx, const float* disp, int w, int h, ptr
                             const float* left, ptrdiff_t lstride, const float* right, int rw, int rh, ptrdiff_t rstride,
                             int mode, float width, int kx, int ky, float* out, ptrdiff_t ostride) {
   if (!ctx) return VWGPU_ERR_ARGUMENT;
+  ctx->err.clear();
   if (!disp || !left || !right || !out || w <= 0 || h <= 0 || rw <= 0 || rh <= 0)
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "parabola_subpixel: empty image or null pointer");
   if (dstride == 0) dstride = w;
@@ -324,23 +322,14 @@ int vwgpu_parabola_subpixel(vwgpu_ctx* ctx, const float* disp, int w, int h, ptr
   if (lstride == 0) lstride = w;
   if (rstride == 0) rstride = rw;
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t db = vwgpu_align_up((size_t)w * h * 12, 256), lb = vwgpu_align_up((size_t)w * h * 4, 256),
-               rb = vwgpu_align_up((size_t)rw * rh * 4, 256);
-  int rc = vwgpu_arena_reserve(ctx, &ctx->staging, 2 * db + lb + rb);
+  vwgpu_stage st(ctx);
+  const int pd = st.add(disp, w, h, 12, dstride, VWGPU_STAGE_IN), po = st.add(out, w, h, 12, ostride, VWGPU_STAGE_OUT);
+  const int pl = st.add(left, w, h, 4, lstride, VWGPU_STAGE_IN), pr = st.add(right, rw, rh, 4, rstride, VWGPU_STAGE_IN);
+  int rc = st.commit();
   if (rc) return rc;
-  char* base = static_cast<char*>(ctx->staging.base);
-  float* d_d = reinterpret_cast<float*>(base);
-  float* d_o = reinterpret_cast<float*>(base + db);
-  float* d_l = reinterpret_cast<float*>(base + 2 * db);
-  float* d_r = reinterpret_cast<float*>(base + 2 * db + lb);
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(d_d, (size_t)w * 12, disp, (size_t)dstride * 12, (size_t)w * 12, h, hipMemcpyHostToDevice, ctx->stream));
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(d_l, (size_t)w * 4, left, (size_t)lstride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(d_r, (size_t)rw * 4, right, (size_t)rstride * 4, (size_t)rw * 4, rh, hipMemcpyHostToDevice, ctx->stream));
-  rc = vwgpu_parabola_subpixel_dev(ctx, d_d, w, h, w, d_l, w, d_r, rw, rh, rw, mode, width, kx, ky, d_o, w);
+  rc = vwgpu_parabola_subpixel_dev(ctx, st.dev<float>(pd), w, h, w, st.dev<float>(pl), w, st.dev<float>(pr), rw, rh, rw, mode, width, kx, ky, st.dev<float>(po), w);
   if (rc) return rc;
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(out, (size_t)ostride * 12, d_o, (size_t)w * 12, (size_t)w * 12, h, hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VWGPU_OK;
+  return st.finish();
 }
 
 }  // extern "C"

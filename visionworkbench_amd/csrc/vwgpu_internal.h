@@ -113,6 +113,30 @@ struct vwgpu_prof_scope {
 
 static inline size_t vwgpu_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Host-pointer entry points (vwgpu_abi.hip): a plan of dense 2-D pieces in ctx->staging.  An entry registers its operands, commits (ONE
+// reservation, then the uploads), runs the device path on dev<T>() pointers with dense strides, and finishes (the downloads, one
+// synchronise).  Every copy is a hipMemcpy2DAsync on ctx->stream.
+enum { VWGPU_STAGE_NONE = 0, VWGPU_STAGE_IN = 1, VWGPU_STAGE_OUT = 2, VWGPU_STAGE_INOUT = 3 };
+struct vwgpu_stage {
+  static constexpr int MAX_PIECES = 24;
+  explicit vwgpu_stage(vwgpu_ctx* c) : ctx(c) {}
+  // A piece of w x h elements of `elem` bytes, vwgpu_align_up(w * h * elem, 256) bytes of the arena, in registration order; host_stride in
+  // elements.  dir: IN = uploaded by commit, OUT = downloaded by finish, INOUT = both (outputs the kernels write only in part), NONE = device
+  // scratch that is never copied.  host == nullptr with another dir than NONE: an absent optional operand, no bytes, dev() == nullptr.
+  int add(const void* host, int w, int h, size_t elem, ptrdiff_t host_stride, int dir);
+  int commit();
+  template <class T> T* dev(int piece) const { return reinterpret_cast<T*>(p[piece].dev); }
+  // Queue the download of the first h rows of w elements of a piece whose rows are w elements apart (extents known only after the call).
+  int download(int piece, void* host, int w, int h, ptrdiff_t host_stride);
+  int finish();
+ private:
+  struct piece { void* host; char* dev; size_t off, elem; ptrdiff_t stride; int w, h, dir; bool present; };
+  vwgpu_ctx* ctx;
+  piece p[MAX_PIECES];
+  int n = 0;
+  size_t total = 0;
+};
+
 // ---- kernel-family launchers (each in its own .hip) ------------------------------------------------
 // All pointers are device pointers; every launcher enqueues on ctx->stream and returns a vwgpu_status.
 

@@ -72,35 +72,22 @@ int vwgpu_calc_disparity_sgm(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const fl
   if (ls == 0) ls = lw;
   if (rs == 0) rs = rw;
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t lb = vwgpu_align_up((size_t)lw * lh * 4, 256), rb = vwgpu_align_up((size_t)rw * rh * 4, 256);
-  const size_t lmb = lmask ? vwgpu_align_up((size_t)lmw * lmh, 256) : 0, rmb = rmask ? vwgpu_align_up((size_t)rmw * rmh, 256) : 0;
-  const size_t pb = prev ? vwgpu_align_up((size_t)pw * ph * 12, 256) : 0;
-  const size_t ob = vwgpu_align_up((size_t)lw * lh * 12, 256);
-  rc = vwgpu_arena_reserve(ctx, &ctx->staging, lb + rb + lmb + rmb + pb + 2 * ob);
-  if (rc) return rc;
-  char* q = static_cast<char*>(ctx->staging.base);
-  float* d_l = reinterpret_cast<float*>(q); q += lb;
-  float* d_r = reinterpret_cast<float*>(q); q += rb;
-  uint8_t* d_lm = reinterpret_cast<uint8_t*>(q); q += lmb;
-  uint8_t* d_rm = reinterpret_cast<uint8_t*>(q); q += rmb;
-  int32_t* d_p = reinterpret_cast<int32_t*>(q); q += pb;
-  int32_t* d_o = reinterpret_cast<int32_t*>(q); q += ob;
-  float* d_s = reinterpret_cast<float*>(q);
-  hipStream_t st = ctx->stream;
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(d_l, (size_t)lw * 4, left, (size_t)ls * 4, (size_t)lw * 4, lh, hipMemcpyHostToDevice, st));
-  VWGPU_HIP(ctx, hipMemcpy2DAsync(d_r, (size_t)rw * 4, right, (size_t)rs * 4, (size_t)rw * 4, rh, hipMemcpyHostToDevice, st));
-  if (lmask) VWGPU_HIP(ctx, hipMemcpyAsync(d_lm, lmask, (size_t)lmw * lmh, hipMemcpyHostToDevice, st));
-  if (rmask) VWGPU_HIP(ctx, hipMemcpyAsync(d_rm, rmask, (size_t)rmw * rmh, hipMemcpyHostToDevice, st));
-  if (prev) VWGPU_HIP(ctx, hipMemcpyAsync(d_p, prev, (size_t)pw * ph * 12, hipMemcpyHostToDevice, st));
-  rc = vwgpu_sgm_impl(ctx, P, d_l, lw, lh, lw, d_r, rw, rh, rw, sx, sy, lmask ? d_lm : nullptr, lmw, lmh, rmask ? d_rm : nullptr, rmw, rmh,
-                      prev ? d_p : nullptr, pw, ph, d_o, sub ? d_s : nullptr, (size_t)lw * lh, ow, oh);
+  vwgpu_stage st(ctx);
+  const int pl = st.add(left, lw, lh, 4, ls, VWGPU_STAGE_IN), pr = st.add(right, rw, rh, 4, rs, VWGPU_STAGE_IN);
+  const int plm = st.add(lmask, lmw, lmh, 1, lmw, VWGPU_STAGE_IN), prm = st.add(rmask, rmw, rmh, 1, rmw, VWGPU_STAGE_IN);
+  const int pp = st.add(prev, pw, ph, 12, pw, VWGPU_STAGE_IN);
+  // the output size is known only after the call: room for lw x lh pixels of both outputs, downloaded below with their extents
+  const int po = st.add(nullptr, lw, lh, 12, lw, VWGPU_STAGE_NONE), ps = st.add(nullptr, lw, lh, 12, lw, VWGPU_STAGE_NONE);
+  if ((rc = st.commit())) return rc;
+  rc = vwgpu_sgm_impl(ctx, P, st.dev<float>(pl), lw, lh, lw, st.dev<float>(pr), rw, rh, rw, sx, sy, st.dev<uint8_t>(plm), lmw, lmh,
+                      st.dev<uint8_t>(prm), rmw, rmh, st.dev<int32_t>(pp), pw, ph, st.dev<int32_t>(po), sub ? st.dev<float>(ps) : nullptr,
+                      (size_t)lw * lh, ow, oh);
   if (rc) return rc;
   const size_t n = (size_t)(*ow) * (*oh);
   if (n > cap) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "calc_disparity_sgm: output buffer too small (%d x %d needed)", *ow, *oh);
-  VWGPU_HIP(ctx, hipMemcpyAsync(out, d_o, n * 12, hipMemcpyDeviceToHost, st));
-  if (sub) VWGPU_HIP(ctx, hipMemcpyAsync(sub, d_s, n * 12, hipMemcpyDeviceToHost, st));
-  VWGPU_HIP(ctx, hipStreamSynchronize(st));
-  return VWGPU_OK;
+  if ((rc = st.download(po, out, *ow, *oh, *ow))) return rc;
+  if (sub && (rc = st.download(ps, sub, *ow, *oh, *ow))) return rc;
+  return st.finish();
 }
 
 }  // extern "C"

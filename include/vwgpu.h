@@ -544,6 +544,73 @@ int vwgpu_texture_preserving_disparity_filter(vwgpu_ctx* ctx, const float* in, i
                                               int max_kernel_size, int semantics, const int* boxes, int nboxes,
                                               float* out, ptrdiff_t ostride, long long* stats);
 
+/* ---- local outlier filters of Stereo/DisparityMap.h and std_dev_image ---------------------------------- */
+
+/* The window filters of DisparityMap.h besides rm_outliers_using_thresh (vwgpu_disparity_filter below). */
+typedef enum vwgpu_outlier_method { VWGPU_OUTLIER_MEAN = 0, VWGPU_OUTLIER_STDDEV = 1, VWGPU_OUTLIER_PLANE = 2 } vwgpu_outlier_method;
+/* RmOutliersUsingMeanFunc skips a pixel whose magnitude exceeds the cutoff with a `continue` that also skips
+ * col_acc.next_col() (src/vw/Stereo/DisparityMap.h:525): the accessor stops advancing and the rest of that window row is
+ * never read.
+ *   VWGPU_OUTLIER_REFERENCE  that behaviour: a window row ends at its first valid pixel above the cutoff.
+ *   VWGPU_OUTLIER_SKIP       only the offending pixel is skipped (what the comment at :492-496 describes).
+ * The other two methods ignore the value (it must still be one of the two). */
+typedef enum vwgpu_outlier_semantics { VWGPU_OUTLIER_REFERENCE = 0, VWGPU_OUTLIER_SKIP = 1 } vwgpu_outlier_semantics;
+/* PixelMask<Vector2i> as int32 {dx, dy, valid != 0}; PixelMask<Vector2f> as float {dx, dy, valid != 0}. */
+typedef enum vwgpu_disparity_type { VWGPU_DISPARITY_I32 = 0, VWGPU_DISPARITY_F32 = 1 } vwgpu_disparity_type;
+
+/* Replaces rasterising, over a whole image of either disparity pixel type (DESIGN.md section 4.16;
+ * tests/refimpl/outlier_filters_ref.cc),
+ *   VWGPU_OUTLIER_MEAN    vw::stereo::rm_outliers_using_mean(d, half_h, half_v, p0 = max_mean_diff)
+ *                         (src/vw/Stereo/DisparityMap.h:444-578; p1 is ignored),
+ *   VWGPU_OUTLIER_STDDEV  vw::stereo::rm_outliers_using_stddev(d, half_h, half_v, p0 = pixel_threshold,
+ *                         p1 = rejection_threshold) (DisparityMap.h:600-748),
+ *   VWGPU_OUTLIER_PLANE   vw::stereo::rm_outliers_using_plane(d, half_h, half_v, p0 = pixel_threshold,
+ *                         p1 = rejection_threshold) (DisparityMap.h:769-927, DisparityMap.cc:37-118),
+ * and with cleanup != 0 disparity_cleanup_using_mean (:580-598), disparity_cleanup_using_stddev (:750-767),
+ * disparity_clean_using_plane (:929-947): the filter followed by RmOutliersUsingThreshFunc(1, 1, 3.0, 0.2) (:357-385)
+ * on the inner VIEW, which is also read one pixel outside the image, where the inner functor runs on clamped reads.
+ * Every window is (2 half_h + 1) x (2 half_v + 1) pixels of edge_extend(d, ConstantEdgeExtension()), rows outer and
+ * columns inner, read from the unmodified input; arithmetic is double in the reference's order without contraction.
+ * An invalid centre is copied (stored values included); a rejected pixel becomes {0, 0, 0}.
+ *   mean    cutoff = 2.0 * sorted(|dx| + |dy| of the valid pixels)[(int)(0.75 n)] (a float add for float pixels, an int
+ *           add for int pixels); the mean of the valid pixels with magnitude <= cutoff (see vwgpu_outlier_semantics);
+ *           rejected when (x-mx)*(x-mx) + (y-my)*(y-my) > p0*p0, or with no pixel matched (max_mean_diff^2 + 1.0 >
+ *           max_mean_diff^2, as :536 has it).  A window with a NaN among its valid disparities (std::sort is undefined
+ *           there) leaves its pixel unchanged.
+ *   stddev  mean, then sigma = sqrt(sum((v - mean)^2) / n) per channel, raised to p1 when below it; rejected when
+ *           |x - mx| > p0 * sigma_x or |y - my| > p0 * sigma_y.  The reference sizes its value buffer (2 half_v + 1)^2
+ *           (:656): half_h > half_v is outside what it defines; the evident result is computed.
+ *   plane   per channel z = a xk + b yk + c fitted to the valid pixels at window offsets (xk, yk) by the normal
+ *           equations of fitPlaneToPoints; sigma = sqrt(sum(dist^2) / n) with dist = |a xk + b yk - z + c| /
+ *           sqrt(a^2 + b^2 + 1), raised to p1 when below it; rejected when the distance of (0, 0, z_centre) exceeds
+ *           p0 * sigma in either channel.  The reference solves with LAPACK gesv and keeps the pixel when that reports
+ *           an exactly zero pivot (:866-875).  LAPACK's bits are not pinned; the specification is the restatement's
+ *           elimination: unblocked LU with partial pivoting (column-wise search, the first largest |a| wins),
+ *           multipliers by the reciprocal of the pivot, rank-1 update, two triangular solves; an exactly zero pivot
+ *           keeps the pixel.
+ * in / out  w x h pixels of `type`, strides in PIXELS, 0 = packed; they must be different images.
+ * half_h, half_v  1 .. 15; <= 0: VWGPU_ERR_ARGUMENT ("half kernel sizes must be non-zero."); above 15: VWGPU_ERR_NOIMPL.
+ * A NaN threshold: VWGPU_ERR_ARGUMENT.
+ * stats  optional HOST long long[2]: pixels rejected by the filter and by the clean-up pass, both counted inside the
+ *        image (asking for it synchronises the stream). */
+int vwgpu_rm_outliers_dev(vwgpu_ctx* ctx, int method, int type, const void* d_in, int w, int h, ptrdiff_t istride, int half_h,
+                          int half_v, double p0, double p1, int cleanup, int semantics, void* d_out, ptrdiff_t ostride,
+                          long long* stats);
+int vwgpu_rm_outliers(vwgpu_ctx* ctx, int method, int type, const void* in, int w, int h, ptrdiff_t istride, int half_h,
+                      int half_v, double p0, double p1, int cleanup, int semantics, void* out, ptrdiff_t ostride,
+                      long long* stats);
+
+/* Replaces rasterising vw::stereo::std_dev_image(image, kernel_width, kernel_height[, edge]) on a plain float image
+ * (src/vw/Stereo/DisparityMap.h:949-1014, DisparityMap.cc:24-34): float accumulators in the reference's order over the
+ * offsets -k/2 .. k/2 in each direction (an even size reads k + 1 samples), mean = sum / (kw kh), result = sum of
+ * squared differences / (kw kh - 1): the variance, despite the name; at 1 x 1 that is 0.0f / 0, NaN.  edge:
+ * VWGPU_EDGE_ZERO (the reference's default overload) or VWGPU_EDGE_CONSTANT.  Strides in elements, 0 = packed.  A size
+ * <= 0: VWGPU_ERR_ARGUMENT ("kernel sizes must be non-zero."); above 31: VWGPU_ERR_NOIMPL. */
+int vwgpu_std_dev_image_dev(vwgpu_ctx* ctx, const float* d_image, int w, int h, ptrdiff_t stride, int kernel_width,
+                            int kernel_height, int edge, float* d_out, ptrdiff_t ostride);
+int vwgpu_std_dev_image(vwgpu_ctx* ctx, const float* image, int w, int h, ptrdiff_t stride, int kernel_width, int kernel_height,
+                        int edge, float* out, ptrdiff_t ostride);
+
 /* ---- disparity clean-up filters and the zone scheduler ------------------------------------------------- */
 
 /* Replaces rasterising vw::stereo::rm_outliers_using_thresh (cleanup == 0) or

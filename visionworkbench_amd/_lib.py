@@ -27,6 +27,7 @@ SYMBOLS = [
     "vwgpu_disparity_neighbor_filter_dev", "vwgpu_disparity_neighbor_filter",
     "vwgpu_texture_measure_dev", "vwgpu_texture_measure",
     "vwgpu_texture_preserving_disparity_filter_dev", "vwgpu_texture_preserving_disparity_filter",
+    "vwgpu_rm_outliers_dev", "vwgpu_rm_outliers", "vwgpu_std_dev_image_dev", "vwgpu_std_dev_image",
     "vwgpu_disparity_filter_dev", "vwgpu_disparity_filter",
     "vwgpu_disparity_mask_dev", "vwgpu_disparity_mask",
     "vwgpu_subdivide_regions",
@@ -169,6 +170,12 @@ def load():
     tpf = [P, P, I, I, PD, P, PD, F, I, I, P, I, P, PD, P]
     lib.vwgpu_texture_preserving_disparity_filter_dev.argtypes = tpf
     lib.vwgpu_texture_preserving_disparity_filter.argtypes = tpf
+    rmo = [P, I, I, P, I, I, PD, I, I, D, D, I, I, P, PD, P]
+    lib.vwgpu_rm_outliers_dev.argtypes = rmo
+    lib.vwgpu_rm_outliers.argtypes = rmo
+    sdi = [P, P, I, I, PD, I, I, I, P, PD]
+    lib.vwgpu_std_dev_image_dev.argtypes = sdi
+    lib.vwgpu_std_dev_image.argtypes = sdi
     df = [P, P, I, I, I, I, D, D, I, P]
     lib.vwgpu_disparity_filter_dev.argtypes = df
     lib.vwgpu_disparity_filter.argtypes = df

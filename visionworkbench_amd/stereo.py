@@ -828,7 +828,146 @@ def texture_measure(image, kernel_size=9, gradient_weight=0.5, stddev_weight=0.5
     return out
 
 
+OUTLIER_METHODS = {"mean": 0, "stddev": 1, "plane": 2}   # vwgpu_outlier_method
+OUTLIER_SEMANTICS = {"reference": 0, "skip": 1}          # vwgpu_outlier_semantics
+OUTLIER_MAX_HALF_KERNEL = 15
+STD_DEV_IMAGE_MAX_KERNEL = 31
+EDGE_EXTENSIONS = {"constant": 0, "zero": 1}             # vwgpu_edge
+
+
+def _rm_outliers(name, method, disparity, hh, hv, p0, p1, cleanup, semantics, ctx, stats):
+    """One of the window filters of DisparityMap.h through vwgpu_rm_outliers[_dev], on either disparity pixel type."""
+    if semantics not in OUTLIER_SEMANTICS:
+        raise ArgumentErr("%s: semantics must be 'reference' or 'skip', not %r" % (name, semantics))
+    if disparity.ndim != 3 or disparity.shape[2] != 3:
+        raise ArgumentErr("%s: disparity must be (rows, cols, 3) {dx, dy, valid}" % name)
+    h, w = int(disparity.shape[0]), int(disparity.shape[1])
+    if int(hh) <= 0 or int(hv) <= 0:
+        raise ArgumentErr("%s: half kernel sizes must be non-zero."
+                          % ("RmOutliersUsingMeanFunc" if method == "mean" else "RmOutliersFunc"))
+    if int(hh) > OUTLIER_MAX_HALF_KERNEL or int(hv) > OUTLIER_MAX_HALF_KERNEL:
+        raise core.NoImplErr("%s: half kernel sizes %d, %d are larger than %d" % (name, int(hh), int(hv), OUTLIER_MAX_HALF_KERNEL))
+    st = (ctypes.c_longlong * 2)()
+    want_stats = st if stats is not None else None
+    ctx = _ctx_for(disparity, ctx)
+    lib = ctx._lib
+    head = (OUTLIER_METHODS[method],)
+    tail = (int(hh), int(hv), float(p0), float(p1), int(bool(cleanup)), OUTLIER_SEMANTICS[semantics])
+    if _is_tensor(disparity):
+        if not disparity.is_cuda or disparity.dtype not in (torch.int32, torch.float32):
+            raise ArgumentErr("%s: the disparity must be an int32 or float32 CUDA tensor" % name)
+        d = disparity.contiguous()
+        out = torch.empty_like(d)
+        ctx.set_stream(torch.cuda.current_stream(d.device).cuda_stream)
+        ctx.check(lib.vwgpu_rm_outliers_dev(ctx._h, *head, 0 if d.dtype == torch.int32 else 1, d.data_ptr(), w, h, 0, *tail,
+                                            out.data_ptr(), 0, want_stats))
+    else:
+        if disparity.dtype not in (np.int32, np.float32):
+            raise ArgumentErr("%s: the disparity must be int32 (PixelMask<Vector2i>) or float32 (PixelMask<Vector2f>)" % name)
+        d = np.ascontiguousarray(disparity)
+        out = np.empty_like(d)
+        ctx.check(lib.vwgpu_rm_outliers(ctx._h, *head, 0 if d.dtype == np.int32 else 1, d.ctypes.data, w, h, 0, *tail,
+                                        out.ctypes.data, 0, want_stats))
+    if stats is not None:
+        stats[:] = list(st)
+    return out
+
+
+def rm_outliers_using_mean(disparity, half_h_kernel, half_v_kernel, max_mean_diff, semantics="reference", ctx=None,
+                           stats=None):
+    """vw::stereo::rm_outliers_using_mean (src/vw/Stereo/DisparityMap.h:444-578), rasterised over the whole image with
+    the reference's ConstantEdgeExtension: a valid pixel farther than max_mean_diff from the mean of its window's valid
+    pixels, gross outliers (magnitude above twice the 75th percentile) left out, becomes {0, 0, 0}.
+
+    disparity: (rows, cols, 3) int32 (PixelMask<Vector2i>) or float32 (PixelMask<Vector2f>) {dx, dy, valid}; numpy in ->
+    numpy out (host entry), CUDA tensor in -> CUDA tensor out on the current stream.  semantics="reference" (default)
+    reproduces the reference's loop, in which a window row ends at its first pixel above the cutoff (the `continue` at
+    :525 skips next_col()); "skip" leaves out only that pixel, as the comment at :492-496 describes.  Half kernel sizes
+    1 .. 15 (NoImplErr above).  stats (optional list) receives [pixels rejected, 0]."""
+    return _rm_outliers("rm_outliers_using_mean", "mean", disparity, half_h_kernel, half_v_kernel, max_mean_diff, 0.0, 0,
+                        semantics, ctx, stats)
+
+
+def disparity_cleanup_using_mean(disparity, h_half_kernel, v_half_kernel, max_mean_diff, semantics="reference", ctx=None,
+                                 stats=None):
+    """vw::stereo::disparity_cleanup_using_mean (src/vw/Stereo/DisparityMap.h:580-598): rm_outliers_using_mean followed by
+    RmOutliersUsingThreshFunc(1, 1, 3.0, 0.2) on the inner view.  stats receives [rejected by the filter, rejected by
+    the second pass]."""
+    return _rm_outliers("disparity_cleanup_using_mean", "mean", disparity, h_half_kernel, v_half_kernel, max_mean_diff, 0.0, 1,
+                        semantics, ctx, stats)
+
+
+def rm_outliers_using_stddev(disparity, half_h_kernel, half_v_kernel, pixel_threshold, rejection_threshold, ctx=None,
+                             stats=None):
+    """vw::stereo::rm_outliers_using_stddev (src/vw/Stereo/DisparityMap.h:600-748): a valid pixel more than
+    pixel_threshold standard deviations (at least rejection_threshold each) from its window's mean in dx or dy becomes
+    {0, 0, 0}.  Pixel types, devices, limits and stats as rm_outliers_using_mean."""
+    return _rm_outliers("rm_outliers_using_stddev", "stddev", disparity, half_h_kernel, half_v_kernel, pixel_threshold,
+                        rejection_threshold, 0, "reference", ctx, stats)
+
+
+def disparity_cleanup_using_stddev(disparity, h_half_kernel, v_half_kernel, pixel_threshold, rejection_threshold, ctx=None,
+                                   stats=None):
+    """vw::stereo::disparity_cleanup_using_stddev (src/vw/Stereo/DisparityMap.h:750-767): rm_outliers_using_stddev followed
+    by RmOutliersUsingThreshFunc(1, 1, 3.0, 0.2) on the inner view."""
+    return _rm_outliers("disparity_cleanup_using_stddev", "stddev", disparity, h_half_kernel, v_half_kernel, pixel_threshold,
+                        rejection_threshold, 1, "reference", ctx, stats)
+
+
+def rm_outliers_using_plane(disparity, half_h_kernel, half_v_kernel, pixel_threshold, rejection_threshold, ctx=None,
+                            stats=None):
+    """vw::stereo::rm_outliers_using_plane (src/vw/Stereo/DisparityMap.h:769-927, DisparityMap.cc:37-118): per channel a
+    plane is fitted to the window's valid pixels; a pixel farther from it than pixel_threshold times the RMS distance of
+    the window's pixels (at least rejection_threshold) becomes {0, 0, 0}; a window whose fit has an exactly zero pivot
+    (points on a line) keeps its pixel.  The 3 x 3 solve is the elimination include/vwgpu.h specifies.  Pixel types,
+    devices, limits and stats as rm_outliers_using_mean."""
+    return _rm_outliers("rm_outliers_using_plane", "plane", disparity, half_h_kernel, half_v_kernel, pixel_threshold,
+                        rejection_threshold, 0, "reference", ctx, stats)
+
+
+def disparity_clean_using_plane(disparity, h_half_kernel, v_half_kernel, pixel_threshold, rejection_threshold, ctx=None,
+                                stats=None):
+    """vw::stereo::disparity_clean_using_plane (src/vw/Stereo/DisparityMap.h:929-947, the reference's spelling):
+    rm_outliers_using_plane followed by RmOutliersUsingThreshFunc(1, 1, 3.0, 0.2) on the inner view."""
+    return _rm_outliers("disparity_clean_using_plane", "plane", disparity, h_half_kernel, v_half_kernel, pixel_threshold,
+                        rejection_threshold, 1, "reference", ctx, stats)
+
+
+def std_dev_image(image, kernel_width, kernel_height, edge="zero", ctx=None):
+    """vw::stereo::std_dev_image (src/vw/Stereo/DisparityMap.h:949-1014) of a plain (rows, cols) float32 image: per pixel
+    the sum of squared differences from the window mean divided by kernel_width * kernel_height - 1 (the variance,
+    despite the name), float accumulators, offsets -k/2 .. k/2 (an even size reads k + 1 samples; 1 x 1 gives NaN).
+    edge: "zero" (the reference's default overload) or "constant".  numpy or CUDA tensor as the input.  Kernel sizes up
+    to 31 (NoImplErr above)."""
+    if image.ndim != 2:
+        raise ArgumentErr("std_dev_image: the image must be (rows, cols)")
+    if edge not in EDGE_EXTENSIONS:
+        raise ArgumentErr("std_dev_image: edge must be 'zero' or 'constant', not %r" % (edge,))
+    kw, kh = int(kernel_width), int(kernel_height)
+    if kw <= 0 or kh <= 0:
+        raise ArgumentErr("StdDevImageFunc: kernel sizes must be non-zero.")
+    if kw > STD_DEV_IMAGE_MAX_KERNEL or kh > STD_DEV_IMAGE_MAX_KERNEL:
+        raise core.NoImplErr("std_dev_image: kernel size %d x %d is larger than %d" % (kw, kh, STD_DEV_IMAGE_MAX_KERNEL))
+    h, w = int(image.shape[0]), int(image.shape[1])
+    ctx = _ctx_for(image, ctx)
+    lib = ctx._lib
+    if _is_tensor(image):
+        if not image.is_cuda or image.dtype != torch.float32:
+            raise ArgumentErr("std_dev_image: the image must be a float32 CUDA tensor")
+        img = image.contiguous()
+        out = torch.empty_like(img)
+        ctx.set_stream(torch.cuda.current_stream(img.device).cuda_stream)
+        ctx.check(lib.vwgpu_std_dev_image_dev(ctx._h, img.data_ptr(), w, h, 0, kw, kh, EDGE_EXTENSIONS[edge], out.data_ptr(), 0))
+    else:
+        img = np.ascontiguousarray(image, np.float32)
+        out = np.empty_like(img)
+        ctx.check(lib.vwgpu_std_dev_image(ctx._h, img.ctypes.data, w, h, 0, kw, kh, EDGE_EXTENSIONS[edge], out.ctypes.data, 0))
+    return out
+
+
 __all__ = ["affine_subpixel", "bayes_em_subpixel", "corr_eval", "disparity_median_filter", "disparity_neighbor_filter",
            "texture_measure", "texture_preserving_disparity_filter","lk_subpixel", "phase_subpixel", "pyramid_subpixel", "calc_disparity", "calc_disparity_sgm", "cross_corr_consistency_check", "parabola_subpixel", "rm_outliers_using_thresh",
            "disparity_cleanup_using_thresh", "disparity_mask", "disparity_blob_filter", "subdivide_regions", "pyramid_correlate", "pyramid_correlate_batch",
+           "rm_outliers_using_mean", "rm_outliers_using_stddev", "rm_outliers_using_plane", "disparity_cleanup_using_mean",
+           "disparity_cleanup_using_stddev", "disparity_clean_using_plane", "std_dev_image",
            "BBox2i", "CostFunctionType"]

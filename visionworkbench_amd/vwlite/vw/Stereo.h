@@ -17,6 +17,9 @@
 //   prefilter_image              src/vw/Stereo/PreFilter.h:76-95
 //   rm_outliers_using_thresh / disparity_cleanup_using_thresh / disparity_mask
 //                                src/vw/Stereo/DisparityMap.h:387-441, 236-253
+//   rm_outliers_using_mean / _stddev / _plane, disparity_cleanup_using_mean / _stddev, disparity_clean_using_plane,
+//   std_dev_image                src/vw/Stereo/DisparityMap.h:444-1014, DisparityMap.cc:24-118 (vwgpu_rm_outliers,
+//                                vwgpu_std_dev_image)
 //   SearchParam, subdivide_regions, calc_seconds_per_op   src/vw/Stereo/Correlation.h:66-122
 //   SemiGlobalMatcher, calc_disparity_sgm                 src/vw/Stereo/SGM.h:75-157,360-375
 // Errors: the C ABI's status codes become the reference's exception types (src/vw/Core/Exception.h:225-253).
@@ -872,6 +875,85 @@ inline void texture_preserving_disparity_filter(ImageView<PixelMask<Vector2f>> c
                                                                  texture_image.data(), 0, texture_max, max_kernel_size,
                                                                  semantics, box, 1, reinterpret_cast<float*>(out), 0, NULL));
   });
+}
+
+// ---- the local outlier filters of Stereo/DisparityMap.h and std_dev_image ------------------------------------------
+// Rasterised over the whole image, on PixelMask<Vector2i> and PixelMask<Vector2f> disparities (include/vwgpu.h,
+// vwgpu_rm_outliers).  Half kernel sizes up to 15 (NoImplErr above).  reference_loop = false selects
+// VWGPU_OUTLIER_SKIP for the mean method.
+namespace detail {
+inline int disparity_type_code(PixelMask<Vector2i> const*) { return VWGPU_DISPARITY_I32; }
+inline int disparity_type_code(PixelMask<Vector2f> const*) { return VWGPU_DISPARITY_F32; }
+template <class PixelT>
+ImageView<PixelT> rm_outliers(ImageView<PixelT> const& d, int method, int32 hh, int32 hv, double p0, double p1, int cleanup,
+                              int semantics) {
+  VW_ASSERT(hh > 0 && hv > 0, ArgumentErr() << (method == VWGPU_OUTLIER_MEAN ? "RmOutliersUsingMeanFunc" : "RmOutliersFunc")
+                                            << ": half kernel sizes must be non-zero.");
+  ImageView<PixelT> out(d.cols(), d.rows());
+  if (d.cols() == 0 || d.rows() == 0) return out;
+  vwgpu_ctx* ctx = thread_context();
+  check(ctx, vwgpu_rm_outliers(ctx, method, disparity_type_code(d.data()), d.data(), d.cols(), d.rows(), 0, hh, hv, p0, p1, cleanup,
+                               semantics, out.data(), 0, NULL));
+  return out;
+}
+}  // namespace detail
+
+/// rm_outliers_using_mean (DisparityMap.h:567-578).
+template <class PixelT>
+ImageView<PixelT> rm_outliers_using_mean(ImageView<PixelT> const& disparity_map, int32 half_h_kernel, int32 half_v_kernel,
+                                         double max_mean_diff, bool reference_loop = true) {
+  return detail::rm_outliers(disparity_map, VWGPU_OUTLIER_MEAN, half_h_kernel, half_v_kernel, max_mean_diff, 0.0, 0,
+                             reference_loop ? VWGPU_OUTLIER_REFERENCE : VWGPU_OUTLIER_SKIP);
+}
+/// disparity_cleanup_using_mean (DisparityMap.h:580-598).
+template <class PixelT>
+ImageView<PixelT> disparity_cleanup_using_mean(ImageView<PixelT> const& disparity_map, int32 h_half_kernel, int32 v_half_kernel,
+                                               double max_mean_diff, bool reference_loop = true) {
+  return detail::rm_outliers(disparity_map, VWGPU_OUTLIER_MEAN, h_half_kernel, v_half_kernel, max_mean_diff, 0.0, 1,
+                             reference_loop ? VWGPU_OUTLIER_REFERENCE : VWGPU_OUTLIER_SKIP);
+}
+/// rm_outliers_using_stddev (DisparityMap.h:737-748).
+template <class PixelT>
+ImageView<PixelT> rm_outliers_using_stddev(ImageView<PixelT> const& disparity_map, int32 half_h_kernel, int32 half_v_kernel,
+                                           double pixel_threshold, double rejection_threshold) {
+  return detail::rm_outliers(disparity_map, VWGPU_OUTLIER_STDDEV, half_h_kernel, half_v_kernel, pixel_threshold,
+                             rejection_threshold, 0, VWGPU_OUTLIER_REFERENCE);
+}
+/// disparity_cleanup_using_stddev (DisparityMap.h:750-767).
+template <class PixelT>
+ImageView<PixelT> disparity_cleanup_using_stddev(ImageView<PixelT> const& disparity_map, int32 h_half_kernel, int32 v_half_kernel,
+                                                 double pixel_threshold, double rejection_threshold) {
+  return detail::rm_outliers(disparity_map, VWGPU_OUTLIER_STDDEV, h_half_kernel, v_half_kernel, pixel_threshold,
+                             rejection_threshold, 1, VWGPU_OUTLIER_REFERENCE);
+}
+/// rm_outliers_using_plane (DisparityMap.h:916-927).
+template <class PixelT>
+ImageView<PixelT> rm_outliers_using_plane(ImageView<PixelT> const& disparity_map, int32 half_h_kernel, int32 half_v_kernel,
+                                          double pixel_threshold, double rejection_threshold) {
+  return detail::rm_outliers(disparity_map, VWGPU_OUTLIER_PLANE, half_h_kernel, half_v_kernel, pixel_threshold,
+                             rejection_threshold, 0, VWGPU_OUTLIER_REFERENCE);
+}
+/// disparity_clean_using_plane (DisparityMap.h:929-947; the reference's spelling).
+template <class PixelT>
+ImageView<PixelT> disparity_clean_using_plane(ImageView<PixelT> const& disparity_map, int32 h_half_kernel, int32 v_half_kernel,
+                                              double pixel_threshold, double rejection_threshold) {
+  return detail::rm_outliers(disparity_map, VWGPU_OUTLIER_PLANE, h_half_kernel, v_half_kernel, pixel_threshold,
+                             rejection_threshold, 1, VWGPU_OUTLIER_REFERENCE);
+}
+
+/// std_dev_image (DisparityMap.h:998-1014) of a plain float image; kernel sizes up to 31 (NoImplErr above).
+template <class EdgeT>
+ImageView<float> std_dev_image(ImageView<float> const& image, int32 kernel_width, int32 kernel_height, EdgeT edge) {
+  VW_ASSERT(kernel_width > 0 && kernel_height > 0, ArgumentErr() << "StdDevImageFunc: kernel sizes must be non-zero.");
+  ImageView<float> out(image.cols(), image.rows());
+  if (image.cols() == 0 || image.rows() == 0) return out;
+  vwgpu_ctx* ctx = detail::thread_context();
+  detail::check(ctx, vwgpu_std_dev_image(ctx, image.data(), image.cols(), image.rows(), 0, kernel_width, kernel_height,
+                                         vw::detail::edge_code(edge), out.data(), 0));
+  return out;
+}
+inline ImageView<float> std_dev_image(ImageView<float> const& image, int32 kernel_width, int32 kernel_height) {
+  return std_dev_image(image, kernel_width, kernel_height, ZeroEdgeExtension());
 }
 
 }  // namespace stereo

@@ -611,6 +611,122 @@ int vwgpu_std_dev_image_dev(vwgpu_ctx* ctx, const float* d_image, int w, int h, 
 int vwgpu_std_dev_image(vwgpu_ctx* ctx, const float* image, int w, int h, ptrdiff_t stride, int kernel_width, int kernel_height,
                         int edge, float* out, ptrdiff_t ostride);
 
+/* ---- the rest of Stereo/DisparityMap.h: range, masks, transforms, resampling ---------------------------- */
+
+/* Common to the entries of this block (tests/refimpl/disparity_map_ref.cc): `type` is a
+ * vwgpu_disparity_type, pixels are {dx, dy, valid != 0} of int32 or float; strides are in PIXELS, 0 = packed; the _dev
+ * form takes device pointers and works on the context's stream, the other form host pointers.  Arithmetic is the
+ * reference's types in its order, without contraction.  Operators that use a pixel's location take x0, y0: the image
+ * coordinates of pixel (0, 0) of the buffer handed in, so a tile or a row strip of a larger map gives the same pixels as
+ * the whole map.  Null pointers, sizes <= 0, an unknown type / semantics / mode, a NaN in min / max / matrix, a stride
+ * below the width and in == out where it is not allowed give VWGPU_ERR_ARGUMENT before any device work; nothing here
+ * returns VWGPU_ERR_NOIMPL. */
+
+/* Replaces vw::stereo::get_disparity_range (src/vw/Stereo/DisparityMap.h:48-66) with its accumulator
+ * PixelAccumulator<EWMinMaxAccumulator> (src/vw/Image/Statistics.h:193-224, :283-290): range = {min.x, min.y, max.x,
+ * max.y} over the VALID pixels (PixelAccumulator skips the others, Statistics.h:287, whatever the TODO at
+ * DisparityMap.h:56 supposes), {0, 0, 0, 0} when there is none.  For int32 pixels the extrema are taken in int32 and
+ * converted to float at the end.  The accumulator's `if (arg < min) .. else if (arg > max)` never admits a NaN after the
+ * first sample: a NaN component makes both extrema of that component NaN when it sits in the first valid pixel in raster
+ * order, and is ignored anywhere else.  The sign of a zero extremum depends on the reference's visiting order and is not
+ * pinned (compare with ==).
+ * _dev: d_range (device float[4]) and host_range (host float[4]) are both optional, one of them must be given; only
+ * host_range synchronises the stream. */
+int vwgpu_get_disparity_range_dev(vwgpu_ctx* ctx, int type, const void* d_in, int w, int h, ptrdiff_t istride, float* d_range,
+                                  float* host_range);
+int vwgpu_get_disparity_range(vwgpu_ctx* ctx, int type, const void* in, int w, int h, ptrdiff_t istride, float* range);
+
+/* DisparityRangeMaskFunc compares the lower bound of y with m_min[0] (src/vw/Stereo/DisparityMap.h:279).
+ *   VWGPU_RANGE_MASK_REFERENCE  that comparison as written.
+ *   VWGPU_RANGE_MASK_FIXED      the lower bound of y is min[1]. */
+typedef enum vwgpu_range_mask_semantics { VWGPU_RANGE_MASK_REFERENCE = 0, VWGPU_RANGE_MASK_FIXED = 1 } vwgpu_range_mask_semantics;
+
+/* Replaces rasterising vw::stereo::disparity_range_mask(d, min, max) (src/vw/Stereo/DisparityMap.h:255-300): a valid
+ * pixel at location loc = (x0 + x, y0 + y) becomes {0, 0, 0} when loc + d leaves [min, max - 1) in x or y; loc + d is a
+ * double sum of the double location and the channel, the bounds are values of the pixel's channel type and max - 1 is
+ * computed in that type (min, max arrive as double[2] and are converted to it first: for int32 pixels they are truncated
+ * and must fit int32, max above INT32_MIN).  Invalid pixels are copied, stored values included.  in == out is allowed.
+ * stats  optional HOST long long[1]: the number of pixels masked (asking for it synchronises the stream). */
+int vwgpu_disparity_range_mask_dev(vwgpu_ctx* ctx, int type, const void* d_in, int w, int h, ptrdiff_t istride, int x0, int y0,
+                                   const double* min, const double* max, int semantics, void* d_out, ptrdiff_t ostride,
+                                   long long* stats);
+int vwgpu_disparity_range_mask(vwgpu_ctx* ctx, int type, const void* in, int w, int h, ptrdiff_t istride, int x0, int y0,
+                               const double* min, const double* max, int semantics, void* out, ptrdiff_t ostride, long long* stats);
+
+/*   VWGPU_TRANSFORM_FUNCTOR          transform_disparities(d, transform) (src/vw/Stereo/DisparityMap.h:1016-1057)
+ *   VWGPU_TRANSFORM_SUBREGION        transform_disparities(false, subregion, T, d) (:1190-1224)
+ *   VWGPU_TRANSFORM_SUBREGION_ROUND  transform_disparities(true, subregion, T, d) */
+typedef enum vwgpu_transform_mode {
+  VWGPU_TRANSFORM_FUNCTOR = 0, VWGPU_TRANSFORM_SUBREGION = 1, VWGPU_TRANSFORM_SUBREGION_ROUND = 2
+} vwgpu_transform_mode;
+
+/* Replaces both overloads of vw::stereo::transform_disparities.  matrix is a row-major double[9] applied to a point
+ * exactly as HomographyTransform::forward does (src/vw/Math/Transform.h:383-387): w = m20 px + m21 py + m22 first, then
+ * ((m00 px + m01 py + m02) / w, (m10 px + m11 py + m12) / w).  A translation or an affine transform is a matrix with last
+ * row (0, 0, 1).  With loc = (x0 + x, y0 + y) as doubles:
+ *   FUNCTOR    q = M(loc + d); the pixel becomes (q.x - loc.x, q.y - loc.y) converted to the channel type (for int32
+ *              the C++ conversion, toward zero); the mask word is copied, and an invalid pixel gets the transformed
+ *              stored values too (:1037-1042).  The functor calls transform.reverse(): the ABI is pinned on the APPLIED
+ *              matrix, which for HomographyTransform(H) is inverse(H).  The C++ and Python layers compute that inverse
+ *              with a plain 3 x 3 adjugate; the bits of the reference's inverse() are not pinned.
+ *   SUBREGION  (x0, y0) = subregion.min(), M = T: diff = M(loc + d) - loc, rounded with C round() in the _ROUND mode,
+ *              converted as above; an invalid pixel gives {0, 0, 0}.
+ * When the conversion of a result to int32 would leave int32 the pixel is unspecified.  in == out is allowed. */
+int vwgpu_transform_disparities_dev(vwgpu_ctx* ctx, int type, const void* d_in, int w, int h, ptrdiff_t istride, int x0, int y0,
+                                    const double* matrix, int mode, void* d_out, ptrdiff_t ostride);
+int vwgpu_transform_disparities(vwgpu_ctx* ctx, int type, const void* in, int w, int h, ptrdiff_t istride, int x0, int y0,
+                                const double* matrix, int mode, void* out, ptrdiff_t ostride);
+
+/* Replaces rasterising vw::stereo::disparity_subsample(d) (src/vw/Stereo/DisparityMap.h:1251-1322): out is
+ * (1 + (w - 1) / 2) x (1 + (h - 1) / 2); pixel (i, j) sums the valid ones of nine taps of edge_extend(d,
+ * ConstantEdgeExtension()) around (2i, 2j) in the order (0,0) (+1,0) (0,+1) (-1,0) (0,-1) (+1,+1) (-1,-1) (-1,+1)
+ * (+1,-1) with weights 10, 5, 5, 5, 5, 2, 2, 2, 2.  The accumulator is AccumulatorType<channel>
+ * (src/vw/Core/FundamentalTypes.h:118, :121): int64 for int32 pixels, double for float pixels.  The first three taps
+ * are cast to it before the product, the other six are multiplied in the pixel's own type (:1273-1299; an int32 product
+ * that overflows wraps).  The result is buffer / (count * 2) in the accumulator type (an integer division toward zero
+ * for int32 pixels), converted to the channel type, with the mask word validate() writes (INT32_MAX or 1.0f); with no
+ * valid tap {0, 0, 0}.  in and out must differ. */
+int vwgpu_disparity_subsample_dev(vwgpu_ctx* ctx, int type, const void* d_in, int w, int h, ptrdiff_t istride, void* d_out,
+                                  ptrdiff_t ostride);
+int vwgpu_disparity_subsample(vwgpu_ctx* ctx, int type, const void* in, int w, int h, ptrdiff_t istride, void* out, ptrdiff_t ostride);
+
+/* Replaces rasterising vw::stereo::disparity_upsample(d) (src/vw/Stereo/DisparityMap.h:1324-1358): out is 2w x 2h and
+ * pixel (i, j) is d(i >> 1, j >> 1) * 2 in the pixel's type (stored values of invalid pixels too), the mask word copied.
+ * in and out must differ. */
+int vwgpu_disparity_upsample_dev(vwgpu_ctx* ctx, int type, const void* d_in, int w, int h, ptrdiff_t istride, void* d_out,
+                                 ptrdiff_t ostride);
+int vwgpu_disparity_upsample(vwgpu_ctx* ctx, int type, const void* in, int w, int h, ptrdiff_t istride, void* out, ptrdiff_t ostride);
+
+/* Replaces rasterising transform(right, DisparityTransform(disparity)) (src/vw/Stereo/DisparityMap.h:1164-1187): the
+ * right image seen from the left one.  right and out are float images of rw x rh, disparity a float {dx, dy, valid} map
+ * of dw x dh (strides in elements / pixels, 0 = packed).  Output pixel (x, y): the offset is disparity(x, y) inside
+ * dw x dh and invalid outside (nearest interpolation at an integer position over ZeroEdgeExtension); an invalid offset
+ * gives p = (-1, y), a valid one p = (x + (double)dx, y + (double)dy); the result is BilinearInterpolationImpl
+ * (src/vw/Image/Interpolation.h:76-110) at p on the zero-extended right image, in float: right(px, py) itself when both
+ * coordinates are integers, otherwise normx = float(p.x) - float(floor p.x) (normy alike) and
+ * ((r00 (1 - normx) + r10 normx) (1 - normy)) + (r01 (1 - normx) + r11 normx) normy, every product and sum rounded on
+ * its own.  The reference converts floor(p) to int32, which is undefined for a NaN or a huge p; THIS project defines the
+ * result as 0 when a coordinate of p is NaN or beyond +-2^30.  The output must differ from both inputs. */
+int vwgpu_disparity_warp_dev(vwgpu_ctx* ctx, const float* d_right, int rw, int rh, ptrdiff_t rstride, const float* d_disparity, int dw,
+                             int dh, ptrdiff_t dstride, float* d_out, ptrdiff_t ostride);
+int vwgpu_disparity_warp(vwgpu_ctx* ctx, const float* right, int rw, int rh, ptrdiff_t rstride, const float* disparity, int dw, int dh,
+                         ptrdiff_t dstride, float* out, ptrdiff_t ostride);
+
+/* Replaces rasterising vw::stereo::missing_pixel_image(d) (src/vw/Stereo/DisparityMap.h:68-87): out is w x h pixels of
+ * three uint8 (PixelRGB<uint8>; ostride in pixels), (200, 200, 200) for a valid pixel and (255, 0, 0) for an invalid one. */
+int vwgpu_missing_pixel_image_dev(vwgpu_ctx* ctx, int type, const void* d_in, int w, int h, ptrdiff_t istride, unsigned char* d_out,
+                                  ptrdiff_t ostride);
+int vwgpu_missing_pixel_image(vwgpu_ctx* ctx, int type, const void* in, int w, int h, ptrdiff_t istride, unsigned char* out,
+                              ptrdiff_t ostride);
+
+/* Replaces rasterising vw::stereo::intersect_mask_and_data(data, mask) (src/vw/Stereo/DisparityMap.h:1226-1249) on two
+ * maps of the same type and size: the data pixel if it is valid, else the mask pixel if that is valid, else the data
+ * pixel.  out may be either input. */
+int vwgpu_intersect_mask_and_data_dev(vwgpu_ctx* ctx, int type, const void* d_data, ptrdiff_t dstride, const void* d_mask,
+                                      ptrdiff_t mstride, int w, int h, void* d_out, ptrdiff_t ostride);
+int vwgpu_intersect_mask_and_data(vwgpu_ctx* ctx, int type, const void* data, ptrdiff_t dstride, const void* mask, ptrdiff_t mstride,
+                                  int w, int h, void* out, ptrdiff_t ostride);
+
 /* ---- disparity clean-up filters and the zone scheduler ------------------------------------------------- */
 
 /* Replaces rasterising vw::stereo::rm_outliers_using_thresh (cleanup == 0) or

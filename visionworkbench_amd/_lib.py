@@ -28,6 +28,11 @@ SYMBOLS = [
     "vwgpu_texture_measure_dev", "vwgpu_texture_measure",
     "vwgpu_texture_preserving_disparity_filter_dev", "vwgpu_texture_preserving_disparity_filter",
     "vwgpu_rm_outliers_dev", "vwgpu_rm_outliers", "vwgpu_std_dev_image_dev", "vwgpu_std_dev_image",
+    "vwgpu_get_disparity_range_dev", "vwgpu_get_disparity_range", "vwgpu_disparity_range_mask_dev", "vwgpu_disparity_range_mask",
+    "vwgpu_transform_disparities_dev", "vwgpu_transform_disparities",
+    "vwgpu_disparity_subsample_dev", "vwgpu_disparity_subsample", "vwgpu_disparity_upsample_dev", "vwgpu_disparity_upsample",
+    "vwgpu_disparity_warp_dev", "vwgpu_disparity_warp", "vwgpu_missing_pixel_image_dev", "vwgpu_missing_pixel_image",
+    "vwgpu_intersect_mask_and_data_dev", "vwgpu_intersect_mask_and_data",
     "vwgpu_disparity_filter_dev", "vwgpu_disparity_filter",
     "vwgpu_disparity_mask_dev", "vwgpu_disparity_mask",
     "vwgpu_subdivide_regions",
@@ -176,6 +181,24 @@ def load():
     sdi = [P, P, I, I, PD, I, I, I, P, PD]
     lib.vwgpu_std_dev_image_dev.argtypes = sdi
     lib.vwgpu_std_dev_image.argtypes = sdi
+    lib.vwgpu_get_disparity_range_dev.argtypes = [P, I, P, I, I, PD, P, P]
+    lib.vwgpu_get_disparity_range.argtypes = [P, I, P, I, I, PD, P]
+    drm = [P, I, P, I, I, PD, I, I, P, P, I, P, PD, P]
+    lib.vwgpu_disparity_range_mask_dev.argtypes = drm
+    lib.vwgpu_disparity_range_mask.argtypes = drm
+    trd = [P, I, P, I, I, PD, I, I, P, I, P, PD]
+    lib.vwgpu_transform_disparities_dev.argtypes = trd
+    lib.vwgpu_transform_disparities.argtypes = trd
+    rsm = [P, I, P, I, I, PD, P, PD]
+    for name in ("disparity_subsample", "disparity_upsample", "missing_pixel_image"):
+        getattr(lib, "vwgpu_%s_dev" % name).argtypes = rsm
+        getattr(lib, "vwgpu_%s" % name).argtypes = rsm
+    dwp = [P, P, I, I, PD, P, I, I, PD, P, PD]
+    lib.vwgpu_disparity_warp_dev.argtypes = dwp
+    lib.vwgpu_disparity_warp.argtypes = dwp
+    imd = [P, I, P, PD, P, PD, I, I, P, PD]
+    lib.vwgpu_intersect_mask_and_data_dev.argtypes = imd
+    lib.vwgpu_intersect_mask_and_data.argtypes = imd
     df = [P, P, I, I, I, I, D, D, I, P]
     lib.vwgpu_disparity_filter_dev.argtypes = df
     lib.vwgpu_disparity_filter.argtypes = df

@@ -965,9 +965,226 @@ def std_dev_image(image, kernel_width, kernel_height, edge="zero", ctx=None):
     return out
 
 
+RANGE_MASK_SEMANTICS = {"reference": 0, "fixed": 1}                     # vwgpu_range_mask_semantics
+TRANSFORM_MODES = {"functor": 0, "subregion": 1, "subregion_round": 2}  # vwgpu_transform_mode
+
+
+class HomographyTransform(object):
+    """vw::HomographyTransform(H) (src/vw/Math/Transform.h:369-389): forward applies H, reverse applies inverse(H), each
+    as w = m20 x + m21 y + m22 first, then the two quotients.  The inverse is a plain 3 x 3 adjugate divided by the
+    determinant (the bits of the reference's inverse() are not pinned); transform_disparities(d, HomographyTransform(H))
+    applies it, as TransformDisparitiesFunc calls reverse()."""
+
+    def __init__(self, H):
+        m = np.array(H, np.float64)
+        if m.shape != (3, 3):
+            raise ArgumentErr("HomographyTransform: the matrix must be 3 x 3")
+        self.matrix = m
+        a, b, c, d, e, f, g, h, i = [float(v) for v in m.reshape(9)]
+        adj = np.array([[e * i - f * h, c * h - b * i, b * f - c * e],
+                        [f * g - d * i, a * i - c * g, c * d - a * f],
+                        [d * h - e * g, b * g - a * h, a * e - b * d]], np.float64)
+        det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g)
+        self.inverse_matrix = adj / det
+
+    @staticmethod
+    def _apply(m, p):
+        x, y = float(p[0]), float(p[1])
+        w = m[2, 0] * x + m[2, 1] * y + m[2, 2]
+        return ((m[0, 0] * x + m[0, 1] * y + m[0, 2]) / w, (m[1, 0] * x + m[1, 1] * y + m[1, 2]) / w)
+
+    def forward(self, p):
+        return self._apply(self.matrix, p)
+
+    def reverse(self, p):
+        return self._apply(self.inverse_matrix, p)
+
+
+def _dm_disparity(name, disparity):
+    """Checks a {dx, dy, valid} map; returns (contiguous map, vwgpu_disparity_type, w, h, is a tensor)."""
+    if disparity.ndim != 3 or disparity.shape[2] != 3:
+        raise ArgumentErr("%s: disparity must be (rows, cols, 3) {dx, dy, valid}" % name)
+    if int(disparity.shape[0]) <= 0 or int(disparity.shape[1]) <= 0:
+        raise ArgumentErr("%s: empty image" % name)
+    if _is_tensor(disparity):
+        if not disparity.is_cuda or disparity.dtype not in (torch.int32, torch.float32):
+            raise ArgumentErr("%s: the disparity must be an int32 or float32 CUDA tensor" % name)
+        d = disparity.contiguous()
+        return d, (0 if d.dtype == torch.int32 else 1), int(d.shape[1]), int(d.shape[0]), True
+    if disparity.dtype not in (np.int32, np.float32):
+        raise ArgumentErr("%s: the disparity must be int32 (PixelMask<Vector2i>) or float32 (PixelMask<Vector2f>)" % name)
+    d = np.ascontiguousarray(disparity)
+    return d, (0 if d.dtype == np.int32 else 1), int(d.shape[1]), int(d.shape[0]), False
+
+
+def _dm_ptr(a):
+    return a.data_ptr() if _is_tensor(a) else a.ctypes.data
+
+
+def _dm_empty(like, shape, dtype=None):
+    if _is_tensor(like):
+        return torch.empty(shape, dtype=like.dtype if dtype is None else dtype, device=like.device)
+    return np.empty(shape, like.dtype if dtype is None else dtype)
+
+
+def _dm_entry(ctx, name, d, tensor):
+    """The _dev entry on the current torch stream for tensors, the host entry for numpy arrays."""
+    if tensor:
+        ctx.set_stream(torch.cuda.current_stream(d.device).cuda_stream)
+        return getattr(ctx._lib, "vwgpu_%s_dev" % name)
+    return getattr(ctx._lib, "vwgpu_%s" % name)
+
+
+def get_disparity_range(disparity, ctx=None, device_result=False):
+    """vw::stereo::get_disparity_range (src/vw/Stereo/DisparityMap.h:48-66): the box of the VALID disparities, returned
+    as float32[4] {min.x, min.y, max.x, max.y} (BBox2f(min, max)); zeros when no pixel is valid.  A NaN component counts
+    only in the first valid pixel in raster order (then both extrema of that component are NaN), as the reference's
+    accumulator has it.  numpy in -> numpy out; CUDA tensor in -> numpy out after one synchronisation, or with
+    device_result=True a CUDA float32[4] tensor without any host round trip."""
+    d, t, w, h, tensor = _dm_disparity("get_disparity_range", disparity)
+    ctx = _ctx_for(d, ctx)
+    host = np.zeros(4, np.float32)
+    if tensor:
+        ctx.set_stream(torch.cuda.current_stream(d.device).cuda_stream)
+        if device_result:
+            out = torch.empty(4, dtype=torch.float32, device=d.device)
+            ctx.check(ctx._lib.vwgpu_get_disparity_range_dev(ctx._h, t, d.data_ptr(), w, h, 0, out.data_ptr(), None))
+            return out
+        ctx.check(ctx._lib.vwgpu_get_disparity_range_dev(ctx._h, t, d.data_ptr(), w, h, 0, None, host.ctypes.data))
+        return host
+    if device_result:
+        raise ArgumentErr("get_disparity_range: device_result needs a CUDA tensor")
+    ctx.check(ctx._lib.vwgpu_get_disparity_range(ctx._h, t, d.ctypes.data, w, h, 0, host.ctypes.data))
+    return host
+
+
+def disparity_range_mask(disparity, min, max, semantics="reference", x0=0, y0=0, ctx=None, stats=None):
+    """vw::stereo::disparity_range_mask(d, min, max) (src/vw/Stereo/DisparityMap.h:255-300): a valid pixel whose target
+    location (x0 + x + dx, y0 + y + dy) leaves [min, max - 1) becomes {0, 0, 0}; min, max are (x, y) pairs in the
+    pixel's channel type.  semantics="reference" (default) keeps the reference's comparison of the lower bound of y with
+    min[0] (:279), "fixed" uses min[1].  x0, y0: the image coordinates of pixel (0, 0) of `disparity` (a tile of a
+    larger map).  stats (optional list) receives [pixels masked]."""
+    if semantics not in RANGE_MASK_SEMANTICS:
+        raise ArgumentErr("disparity_range_mask: semantics must be 'reference' or 'fixed', not %r" % (semantics,))
+    d, t, w, h, tensor = _dm_disparity("disparity_range_mask", disparity)
+    lo, hi = np.array(min, np.float64).reshape(-1), np.array(max, np.float64).reshape(-1)
+    if lo.size != 2 or hi.size != 2:
+        raise ArgumentErr("disparity_range_mask: min and max must be (x, y) pairs")
+    ctx = _ctx_for(d, ctx)
+    out = _dm_empty(d, d.shape)
+    st = (ctypes.c_longlong * 1)()
+    ctx.check(_dm_entry(ctx, "disparity_range_mask", d, tensor)(
+        ctx._h, t, _dm_ptr(d), w, h, 0, int(x0), int(y0), lo.ctypes.data, hi.ctypes.data, RANGE_MASK_SEMANTICS[semantics],
+        _dm_ptr(out), 0, st if stats is not None else None))
+    if stats is not None:
+        stats[:] = list(st)
+    return out
+
+
+def _transform(name, disparity, matrix, mode, x0, y0, ctx):
+    d, t, w, h, tensor = _dm_disparity(name, disparity)
+    m = np.ascontiguousarray(np.array(matrix, np.float64))
+    if m.shape != (3, 3):
+        raise ArgumentErr("%s: the matrix must be 3 x 3" % name)
+    ctx = _ctx_for(d, ctx)
+    out = _dm_empty(d, d.shape)
+    ctx.check(_dm_entry(ctx, "transform_disparities", d, tensor)(
+        ctx._h, t, _dm_ptr(d), w, h, 0, int(x0), int(y0), m.ctypes.data, TRANSFORM_MODES[mode], _dm_ptr(out), 0))
+    return out
+
+
+def transform_disparities(disparity, matrix, x0=0, y0=0, ctx=None):
+    """vw::stereo::transform_disparities(d, transform) (src/vw/Stereo/DisparityMap.h:1016-1057): every pixel's target
+    point loc + d is mapped by the transform and the disparity becomes the mapped point minus loc, converted to the
+    pixel's channel type (int32: toward zero).  Validity is copied; invalid pixels carry the transformed stored values.
+    matrix: a HomographyTransform (its INVERSE is applied, as the reference's functor calls reverse()), or the 3 x 3
+    matrix to apply as it is (row-major; last row (0, 0, 1) for a translation or an affine transform).  x0, y0: the
+    image coordinates of pixel (0, 0) of `disparity`."""
+    m = matrix.inverse_matrix if isinstance(matrix, HomographyTransform) else matrix
+    return _transform("transform_disparities", disparity, m, "functor", x0, y0, ctx)
+
+
+def transform_disparities_subregion(do_round, subregion, T, disparity, ctx=None):
+    """vw::stereo::transform_disparities(do_round, subregion, T, disparity) (src/vw/Stereo/DisparityMap.h:1190-1224):
+    with beg = subregion.min + (x, y), the disparity becomes HomographyTransform(T).forward(beg + d) - beg, rounded with
+    round() when do_round; invalid pixels become {0, 0, 0}.  subregion: a BBox2i of the disparity's size."""
+    x0, y0 = subregion.min
+    x1, y1 = subregion.max
+    if x1 - x0 != int(disparity.shape[1]) or y1 - y0 != int(disparity.shape[0]):
+        raise ArgumentErr("transform_disparities: The sizes of subregion and disparity don't match.")
+    return _transform("transform_disparities", disparity, T, "subregion_round" if do_round else "subregion", x0, y0, ctx)
+
+
+def _resample(name, disparity, shape_of, dtype, ctx):
+    d, t, w, h, tensor = _dm_disparity(name, disparity)
+    ctx = _ctx_for(d, ctx)
+    out = _dm_empty(d, shape_of(h, w), dtype)
+    ctx.check(_dm_entry(ctx, name, d, tensor)(ctx._h, t, _dm_ptr(d), w, h, 0, _dm_ptr(out), 0))
+    return out
+
+
+def disparity_subsample(disparity, ctx=None):
+    """vw::stereo::disparity_subsample (src/vw/Stereo/DisparityMap.h:1251-1322): (1 + (rows-1)//2, 1 + (cols-1)//2, 3);
+    each pixel is the weighted mean (10 / 5 / 2) of the valid ones of nine taps around (2i, 2j) of the constant-extended
+    map, divided by two; accumulated in double (float pixels) or int64 with an integer division (int32 pixels)."""
+    return _resample("disparity_subsample", disparity, lambda h, w: (1 + (h - 1) // 2, 1 + (w - 1) // 2, 3), None, ctx)
+
+
+def disparity_upsample(disparity, ctx=None):
+    """vw::stereo::disparity_upsample (src/vw/Stereo/DisparityMap.h:1324-1358): (2 rows, 2 cols, 3), pixel (i, j) is
+    pixel (i >> 1, j >> 1) times 2 with its validity."""
+    return _resample("disparity_upsample", disparity, lambda h, w: (2 * h, 2 * w, 3), None, ctx)
+
+
+def missing_pixel_image(disparity, ctx=None):
+    """vw::stereo::missing_pixel_image (src/vw/Stereo/DisparityMap.h:68-87): (rows, cols, 3) uint8, (200, 200, 200)
+    where the disparity is valid and (255, 0, 0) where it is not."""
+    return _resample("missing_pixel_image", disparity, lambda h, w: (h, w, 3), torch.uint8 if _is_tensor(disparity) else np.uint8, ctx)
+
+
+def intersect_mask_and_data(data, mask, ctx=None):
+    """vw::stereo::intersect_mask_and_data (src/vw/Stereo/DisparityMap.h:1226-1249): the data pixel where it is valid,
+    else the mask pixel where that is valid, else the data pixel.  Both maps have one type and size."""
+    d, t, w, h, tensor = _dm_disparity("intersect_mask_and_data", data)
+    m, tm, wm, hm, mtensor = _dm_disparity("intersect_mask_and_data", mask)
+    if (t, w, h, tensor) != (tm, wm, hm, mtensor):
+        raise ArgumentErr("intersect_mask_and_data: data and mask must have the same type and size")
+    ctx = _ctx_for(d, ctx)
+    out = _dm_empty(d, d.shape)
+    ctx.check(_dm_entry(ctx, "intersect_mask_and_data", d, tensor)(ctx._h, t, _dm_ptr(d), 0, _dm_ptr(m), 0, w, h, _dm_ptr(out), 0))
+    return out
+
+
+def disparity_transform_image(right, disparity, ctx=None):
+    """transform(right, DisparityTransform(disparity)) (src/vw/Stereo/DisparityMap.h:1164-1187): the (rows, cols)
+    float32 right image seen from the left one, bilinear over zero edge extension; a pixel without a valid disparity
+    (or outside the float32 disparity map, which may have another size) samples (-1, y) and becomes 0."""
+    d, t, dw, dh, tensor = _dm_disparity("disparity_transform_image", disparity)
+    if t != 1:
+        raise ArgumentErr("disparity_transform_image: the disparity must be float32 (PixelMask<Vector2f>)")
+    if right.ndim != 2 or _is_tensor(right) != tensor:
+        raise ArgumentErr("disparity_transform_image: the image must be (rows, cols), on the same side as the disparity")
+    if tensor:
+        if not right.is_cuda or right.dtype != torch.float32:
+            raise ArgumentErr("disparity_transform_image: the image must be a float32 CUDA tensor")
+        r = right.contiguous()
+    else:
+        r = np.ascontiguousarray(right, np.float32)
+    rh, rw = int(r.shape[0]), int(r.shape[1])
+    if rw <= 0 or rh <= 0:
+        raise ArgumentErr("disparity_transform_image: empty image")
+    ctx = _ctx_for(d, ctx)
+    out = _dm_empty(r, r.shape)
+    ctx.check(_dm_entry(ctx, "disparity_warp", d, tensor)(ctx._h, _dm_ptr(r), rw, rh, 0, _dm_ptr(d), dw, dh, 0, _dm_ptr(out), 0))
+    return out
+
+
 __all__ = ["affine_subpixel", "bayes_em_subpixel", "corr_eval", "disparity_median_filter", "disparity_neighbor_filter",
            "texture_measure", "texture_preserving_disparity_filter","lk_subpixel", "phase_subpixel", "pyramid_subpixel", "calc_disparity", "calc_disparity_sgm", "cross_corr_consistency_check", "parabola_subpixel", "rm_outliers_using_thresh",
            "disparity_cleanup_using_thresh", "disparity_mask", "disparity_blob_filter", "subdivide_regions", "pyramid_correlate", "pyramid_correlate_batch",
            "rm_outliers_using_mean", "rm_outliers_using_stddev", "rm_outliers_using_plane", "disparity_cleanup_using_mean",
            "disparity_cleanup_using_stddev", "disparity_clean_using_plane", "std_dev_image",
+           "get_disparity_range", "disparity_range_mask", "transform_disparities", "transform_disparities_subregion",
+           "HomographyTransform", "disparity_subsample", "disparity_upsample", "disparity_transform_image",
+           "missing_pixel_image", "intersect_mask_and_data",
            "BBox2i", "CostFunctionType"]

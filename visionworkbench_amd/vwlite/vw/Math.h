@@ -1,5 +1,6 @@
 // vw/Math.h — Vector2i/Vector2f and the half-open integer box BBox2i with the semantics of
-// src/vw/Math/BBox.tcc:82-197,268-290.
+// src/vw/Math/BBox.tcc:82-197,268-290; Matrix3x3 and HomographyTransform
+// (src/vw/Math/Transform.h:365-389).
 #ifndef VWLITE_MATH_H
 #define VWLITE_MATH_H
 
@@ -81,6 +82,43 @@ inline BBox2i operator/(BBox2i b, int32 s) { return b /= s; }
 inline std::ostream& operator<<(std::ostream& o, BBox2i const& b) {
   return o << "(" << b.min() << "-" << b.max() << ")";
 }
+
+// A row-major 3 x 3 double matrix, as much of vw::Matrix3x3 as a homography needs.
+class Matrix3x3 {
+  double m[9];
+public:
+  Matrix3x3() { for (int i = 0; i < 9; ++i) m[i] = 0.0; }
+  void set_identity() { for (int i = 0; i < 9; ++i) m[i] = (i % 4 == 0) ? 1.0 : 0.0; }
+  double& operator()(int r, int c) { return m[r * 3 + c]; }
+  double const& operator()(int r, int c) const { return m[r * 3 + c]; }
+  const double* data() const { return m; }
+};
+// The adjugate over the determinant.  The bits of the reference's inverse() (an LU solve) are not pinned.
+inline Matrix3x3 inverse(Matrix3x3 const& h) {
+  const double a = h(0, 0), b = h(0, 1), c = h(0, 2), d = h(1, 0), e = h(1, 1), f = h(1, 2), g = h(2, 0), i = h(2, 1), j = h(2, 2);
+  const double det = a * (e * j - f * i) - b * (d * j - f * g) + c * (d * i - e * g);
+  Matrix3x3 r;
+  r(0, 0) = (e * j - f * i) / det; r(0, 1) = (c * i - b * j) / det; r(0, 2) = (b * f - c * e) / det;
+  r(1, 0) = (f * g - d * j) / det; r(1, 1) = (a * j - c * g) / det; r(1, 2) = (c * d - a * f) / det;
+  r(2, 0) = (d * i - e * g) / det; r(2, 1) = (b * g - a * i) / det; r(2, 2) = (a * e - b * d) / det;
+  return r;
+}
+
+// HomographyTransform (src/vw/Math/Transform.h:369-389): forward applies H, reverse its inverse; w first, then the
+// two quotients.
+class HomographyTransform {
+  Matrix3x3 m_H, m_H_inverse;
+  static Vector2 apply(Matrix3x3 const& m, Vector2 const& p) {
+    const double w = m(2, 0) * p[0] + m(2, 1) * p[1] + m(2, 2);
+    return Vector2((m(0, 0) * p[0] + m(0, 1) * p[1] + m(0, 2)) / w, (m(1, 0) * p[0] + m(1, 1) * p[1] + m(1, 2)) / w);
+  }
+public:
+  HomographyTransform(Matrix3x3 const& H) : m_H(H), m_H_inverse(inverse(H)) {}
+  Vector2 forward(Vector2 const& p) const { return apply(m_H, p); }
+  Vector2 reverse(Vector2 const& p) const { return apply(m_H_inverse, p); }
+  Matrix3x3 const& matrix() const { return m_H; }
+  Matrix3x3 const& inverse_matrix() const { return m_H_inverse; }
+};
 
 }  // namespace vw
 #endif

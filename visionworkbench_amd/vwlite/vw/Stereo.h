@@ -20,6 +20,9 @@
 //   rm_outliers_using_mean / _stddev / _plane, disparity_cleanup_using_mean / _stddev, disparity_clean_using_plane,
 //   std_dev_image                src/vw/Stereo/DisparityMap.h:444-1014, DisparityMap.cc:24-118 (vwgpu_rm_outliers,
 //                                vwgpu_std_dev_image)
+//   get_disparity_range, missing_pixel_image, disparity_range_mask, transform_disparities (both overloads),
+//   DisparityTransform, intersect_mask_and_data, disparity_subsample, disparity_upsample
+//                                src/vw/Stereo/DisparityMap.h:48-87, 255-300, 1016-1057, 1164-1358
 //   SearchParam, subdivide_regions, calc_seconds_per_op   src/vw/Stereo/Correlation.h:66-122
 //   SemiGlobalMatcher, calc_disparity_sgm                 src/vw/Stereo/SGM.h:75-157,360-375
 // Errors: the C ABI's status codes become the reference's exception types (src/vw/Core/Exception.h:225-253).
@@ -956,6 +959,160 @@ inline ImageView<float> std_dev_image(ImageView<float> const& image, int32 kerne
   return std_dev_image(image, kernel_width, kernel_height, ZeroEdgeExtension());
 }
 
+// ---- the rest of Stereo/DisparityMap.h: range, masks, transforms, resampling ---------------------------------------
+// Each function rasterises its argument, calls the engine on the whole image (include/vwgpu.h) and returns the result
+// as an ImageView, which takes part in the block protocol like the other filter results.  Both disparity pixel types.
+
+/// The (min, max) corners of get_disparity_range's BBox2f.
+struct BBox2f {
+  Vector2f m_min, m_max;
+  BBox2f() {}
+  BBox2f(Vector2f const& mn, Vector2f const& mx) : m_min(mn), m_max(mx) {}
+  Vector2f const& min() const { return m_min; }
+  Vector2f const& max() const { return m_max; }
+};
+
+/// get_disparity_range (DisparityMap.h:48-66): over the valid pixels, BBox2f(0, 0, 0, 0) when there is none.
+template <class ViewT>
+BBox2f get_disparity_range(ImageViewBase<ViewT> const& disparity_map) {
+  ImageView<typename ViewT::pixel_type> d = disparity_map.impl();
+  if (d.cols() == 0 || d.rows() == 0) return BBox2f();
+  float r[4] = {0, 0, 0, 0};
+  vwgpu_ctx* ctx = detail::thread_context();
+  detail::check(ctx, vwgpu_get_disparity_range(ctx, detail::disparity_type_code(d.data()), d.data(), d.cols(), d.rows(), 0, r));
+  return BBox2f(Vector2f(r[0], r[1]), Vector2f(r[2], r[3]));
+}
+
+/// PixelRGB<uint8> of missing_pixel_image.
+struct PixelRGB8 {
+  uint8 r, g, b;
+  bool operator==(PixelRGB8 const& o) const { return r == o.r && g == o.g && b == o.b; }
+};
+/// missing_pixel_image (DisparityMap.h:68-87).
+template <class ViewT>
+ImageView<PixelRGB8> missing_pixel_image(ImageViewBase<ViewT> const& image) {
+  ImageView<typename ViewT::pixel_type> d = image.impl();
+  ImageView<PixelRGB8> out(d.cols(), d.rows());
+  if (d.cols() == 0 || d.rows() == 0) return out;
+  vwgpu_ctx* ctx = detail::thread_context();
+  detail::check(ctx, vwgpu_missing_pixel_image(ctx, detail::disparity_type_code(d.data()), d.data(), d.cols(), d.rows(), 0,
+                                               reinterpret_cast<unsigned char*>(out.data()), 0));
+  return out;
+}
+
+/// disparity_range_mask (DisparityMap.h:255-300); reference_bounds = false compares the lower bound of y with min[1]
+/// instead of the reference's min[0] (:279).
+template <class ViewT>
+ImageView<typename ViewT::pixel_type> disparity_range_mask(ImageViewBase<ViewT> const& disparity_map,
+                                                           typename ViewT::pixel_type const& min,
+                                                           typename ViewT::pixel_type const& max, bool reference_bounds = true) {
+  ImageView<typename ViewT::pixel_type> d = disparity_map.impl(), out(d.cols(), d.rows());
+  if (d.cols() == 0 || d.rows() == 0) return out;
+  const double mn[2] = {(double)min[0], (double)min[1]}, mx[2] = {(double)max[0], (double)max[1]};
+  vwgpu_ctx* ctx = detail::thread_context();
+  detail::check(ctx, vwgpu_disparity_range_mask(ctx, detail::disparity_type_code(d.data()), d.data(), d.cols(), d.rows(), 0, 0, 0, mn, mx,
+                                                reference_bounds ? VWGPU_RANGE_MASK_REFERENCE : VWGPU_RANGE_MASK_FIXED, out.data(), 0,
+                                                NULL));
+  return out;
+}
+
+namespace detail {
+template <class PixelT>
+ImageView<PixelT> transform_disparities(ImageView<PixelT> const& d, Matrix3x3 const& applied, int mode, int32 x0, int32 y0) {
+  ImageView<PixelT> out(d.cols(), d.rows());
+  if (d.cols() == 0 || d.rows() == 0) return out;
+  vwgpu_ctx* ctx = thread_context();
+  check(ctx, vwgpu_transform_disparities(ctx, disparity_type_code(d.data()), d.data(), d.cols(), d.rows(), 0, x0, y0, applied.data(), mode,
+                                         out.data(), 0));
+  return out;
+}
+}  // namespace detail
+
+/// transform_disparities(disparity_map, HomographyTransform(H)) (DisparityMap.h:1046-1057): the functor calls
+/// transform.reverse(), so inverse(H) is applied.
+template <class ViewT>
+ImageView<typename ViewT::pixel_type> transform_disparities(ImageViewBase<ViewT> const& disparity_map,
+                                                            HomographyTransform const& transform) {
+  ImageView<typename ViewT::pixel_type> d = disparity_map.impl();
+  return detail::transform_disparities(d, transform.inverse_matrix(), VWGPU_TRANSFORM_FUNCTOR, 0, 0);
+}
+/// transform_disparities(do_round, subregion, T, disparity) (DisparityMap.h:1190-1224).
+template <class DispT>
+ImageView<typename DispT::pixel_type> transform_disparities(bool do_round, BBox2i subregion, Matrix3x3 const& T,
+                                                            DispT const& disparity) {
+  VW_ASSERT(subregion.width() == disparity.cols() && subregion.height() == disparity.rows(),
+            ArgumentErr() << "transform_disparities: The sizes of subregion and disparity don't match.\n");
+  ImageView<typename DispT::pixel_type> d = disparity;
+  return detail::transform_disparities(d, T, do_round ? VWGPU_TRANSFORM_SUBREGION_ROUND : VWGPU_TRANSFORM_SUBREGION,
+                                       subregion.min().x(), subregion.min().y());
+}
+
+/// intersect_mask_and_data (DisparityMap.h:1226-1249).
+template <class ViewT, class MaskViewT>
+ImageView<typename ViewT::pixel_type> intersect_mask_and_data(ImageViewBase<ViewT> const& view, ImageViewBase<MaskViewT> const& mask_view) {
+  ImageView<typename ViewT::pixel_type> d = view.impl(), m = mask_view.impl(), out(d.cols(), d.rows());
+  VW_ASSERT(d.cols() == m.cols() && d.rows() == m.rows(), ArgumentErr() << "intersect_mask_and_data: the images differ in size.");
+  if (d.cols() == 0 || d.rows() == 0) return out;
+  vwgpu_ctx* ctx = detail::thread_context();
+  detail::check(ctx, vwgpu_intersect_mask_and_data(ctx, detail::disparity_type_code(d.data()), d.data(), 0, m.data(), 0, d.cols(), d.rows(),
+                                                   out.data(), 0));
+  return out;
+}
+
+/// disparity_subsample (DisparityMap.h:1318-1322).
+template <class ViewT>
+ImageView<typename ViewT::pixel_type> disparity_subsample(ImageViewBase<ViewT> const& view) {
+  ImageView<typename ViewT::pixel_type> d = view.impl();
+  if (d.cols() == 0 || d.rows() == 0) return ImageView<typename ViewT::pixel_type>();
+  ImageView<typename ViewT::pixel_type> out(1 + (d.cols() - 1) / 2, 1 + (d.rows() - 1) / 2);
+  vwgpu_ctx* ctx = detail::thread_context();
+  detail::check(ctx, vwgpu_disparity_subsample(ctx, detail::disparity_type_code(d.data()), d.data(), d.cols(), d.rows(), 0, out.data(), 0));
+  return out;
+}
+/// disparity_upsample (DisparityMap.h:1354-1358).
+template <class ViewT>
+ImageView<typename ViewT::pixel_type> disparity_upsample(ImageViewBase<ViewT> const& view) {
+  ImageView<typename ViewT::pixel_type> d = view.impl(), out(d.cols() * 2, d.rows() * 2);
+  if (d.cols() == 0 || d.rows() == 0) return out;
+  vwgpu_ctx* ctx = detail::thread_context();
+  detail::check(ctx, vwgpu_disparity_upsample(ctx, detail::disparity_type_code(d.data()), d.data(), d.cols(), d.rows(), 0, out.data(), 0));
+  return out;
+}
+
+/// DisparityTransform (DisparityMap.h:1164-1187): transform(right_image, DisparityTransform(disparity)) projects the
+/// right image into the perspective of the left.
+class DisparityTransform {
+  ImageView<PixelMask<Vector2f>> m_offset_image;
+public:
+  template <class DisparityT>
+  DisparityTransform(ImageViewBase<DisparityT> const& offset_image) : m_offset_image(offset_image.impl()) {}
+  ImageView<PixelMask<Vector2f>> const& offset_image() const { return m_offset_image; }
+  /// nearest pixel of the zero-extended offset image (Image/Interpolation.h:221-224, Math/Functions.h:48-51)
+  Vector2 reverse(Vector2 const& p) const {
+    const int32 x = p.x() < 0 ? int32(p.x() - 0.5) : int32(p.x() + 0.5), y = p.y() < 0 ? int32(p.y() - 0.5) : int32(p.y() + 0.5);
+    if (x < 0 || y < 0 || x >= m_offset_image.cols() || y >= m_offset_image.rows() || !is_valid(m_offset_image(x, y)))
+      return Vector2(-1, p.y());
+    return Vector2(p.x() + m_offset_image(x, y).child()[0], p.y() + m_offset_image(x, y).child()[1]);
+  }
+};
+
 }  // namespace stereo
+
+/// transform(image, DisparityTransform) (src/vw/Image/Transform.h: ZeroEdgeExtension, BilinearInterpolation) on a float
+/// or PixelGray<float> image, rasterised over the image's own size.
+template <class ViewT>
+ImageView<typename ViewT::pixel_type> transform(ImageViewBase<ViewT> const& image, stereo::DisparityTransform const& tx) {
+  static_assert(sizeof(typename ViewT::pixel_type) == sizeof(float), "transform(image, DisparityTransform): one float per pixel");
+  ImageView<typename ViewT::pixel_type> r = image.impl(), out(r.cols(), r.rows());
+  ImageView<PixelMask<Vector2f>> const& d = tx.offset_image();
+  if (r.cols() == 0 || r.rows() == 0) return out;
+  VW_ASSERT(d.cols() > 0 && d.rows() > 0, ArgumentErr() << "DisparityTransform: empty disparity image.");
+  vwgpu_ctx* ctx = stereo::detail::thread_context();
+  stereo::detail::check(ctx, vwgpu_disparity_warp(ctx, reinterpret_cast<const float*>(r.data()), r.cols(), r.rows(), 0,
+                                                  reinterpret_cast<const float*>(d.data()), d.cols(), d.rows(), 0,
+                                                  reinterpret_cast<float*>(out.data()), 0));
+  return out;
+}
+
 }  // namespace vw
 #endif

@@ -349,11 +349,13 @@ typedef enum vwgpu_subpixel_algorithm {
  * subpixel_optimized_affine_2d and subpixel_optimized_affine_2d_EM, src/vw/Stereo/Correlate.cc:1203-1391, 848-1200,
  * 500-845).
  * The result of a pixel depends on its tile, as in the reference.
- *   disp   w x h x {dx, dy, valid (!= 0)} float, the left image's size; the stored values of invalid pixels count in the
- *          tile's disparity range, as in the reference (DisparityMap.h:52-64).  Strides of disp / out in PIXELS.
+ *   disp   w x h x {dx, dy, valid (!= 0)} float, the left image's size; a tile's disparity range is taken over its valid
+ *          pixels (zeros without any), as in the reference (DisparityMap.h:48-66, Image/Statistics.h:283-290): what an
+ *          invalid pixel stores is never read.  Strides of disp / out in PIXELS.
  *   left   w x h float, right rw x rh float (any size); prefiltered internally (mode / width as prefilter_image) with the
  *          constant edge extension of the source wherever a crop leaves an image (as vwgpu_parabola_subpixel).
- *          A non-finite disparity (valid or not) inside a tile: VWGPU_ERR_ARGUMENT.
+ *          A non-finite disparity in a valid pixel of a tile: VWGPU_ERR_ARGUMENT; every tile is checked before the
+ *          first one is written.
  *   kx, ky odd (even sizes: VWGPU_ERR_ARGUMENT); max_pyramid_levels < 0 counts as 0.
  *   algorithm  VWGPU_SUBPIXEL_LUCAS_KANADE, VWGPU_SUBPIXEL_FAST_AFFINE or VWGPU_SUBPIXEL_BAYES_EM; VWGPU_SUBPIXEL_PHASE
  *          returns VWGPU_ERR_NOIMPL (use vwgpu_phase_subpixel[_dev]).

@@ -21,7 +21,7 @@ __all__ = ["build", "lib", "fast_box_sum", "cost_image", "calc_disparity", "calc
            "CROSS_CORRELATION", "VALID", "generate_gaussian_kernel", "separable_convolution", "convolution_2d",
            "subsample_mask_by_two", "prefilter_image", "pyramid_smoothing_kernel",
            "EDGE_CONSTANT", "EDGE_ZERO", "PREFILTER_NONE", "PREFILTER_MEANSUB", "PREFILTER_LOG",
-           "subdivide_regions", "prefilter_region", "parabola_subpixel", "pyramid_correlate", "disparity_filter",
+           "subdivide_regions", "prefilter_region", "parabola_subpixel", "parabola_range", "pyramid_correlate", "disparity_filter",
            "disparity_mask", "u8_convert", "census_transform", "hamming_distance", "SemiGlobalMatcher", "calc_disparity_sgm",
            "pyramid_correlate_sgm", "set_sgm_host_threads", "blob_sizes", "disparity_blob_filter", "set_blob_filter_area", "cross_corr_consistency_check_diff", "set_lr_disp_diff", "CENSUS_TRANSFORM", "TERNARY_CENSUS_TRANSFORM", "SUBPIXEL_NONE", "SUBPIXEL_PARABOLA", "SUBPIXEL_LINEAR",
            "SUBPIXEL_POLY4", "SUBPIXEL_COSINE", "SUBPIXEL_LC_BLEND"]
@@ -69,6 +69,8 @@ def _load():
     so.vwo_subdivide_regions.argtypes = [P, I, I, I, I, P, I]
     so.vwo_prefilter_region.argtypes = [P, I, I, I, F, I, I, I, I, P]
     so.vwo_parabola_subpixel.argtypes = [P, I, I, P, P, I, I, I, F, I, I, P]
+    so.vwo_parabola_range.argtypes = [P, I, I, P]
+    so.vwo_parabola_range.restype = None
     so.vwo_pyramid_correlate.argtypes = [P, I, I, P, I, I, P, P, I, F, I, I, I, I, I, I, I, I, D, F, I, I, I, I, I, I, P]
     so.vwo_disparity_filter.argtypes = [P, I, I, I, I, D, D, I]
     so.vwo_disparity_mask.argtypes = [P, I, I, P, P, I, I]
@@ -268,6 +270,15 @@ def parabola_subpixel(disparity, left, right, prefilter_mode, prefilter_width, k
     rc = lib().vwo_parabola_subpixel(_p(d), w, h, _p(l), _p(r), r.shape[1], r.shape[0], int(prefilter_mode),
                                      float(prefilter_width), kernel[0], kernel[1], _p(out))
     assert rc == 0
+    return out
+
+
+def parabola_range(disparity):
+    """int32 [min x, min y, max x, max y] of the truncated disparity over its valid pixels (zeros without any): the range
+    parabola_subpixel sizes its rasters with."""
+    d = np.ascontiguousarray(disparity, np.float32)
+    out = np.zeros(4, np.int32)
+    lib().vwo_parabola_range(_p(d), d.shape[1], d.shape[0], _p(out))
     return out
 
 

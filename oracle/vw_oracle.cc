@@ -632,22 +632,29 @@ int vwo_prefilter_region(const float* src, int w, int h, int mode, float width, 
   return prefilter_region(src, w, h, mode, width, x0, y0, bw, bh, dst);
 }
 
+// get_disparity_range of the truncated disparity (ParabolaSubpixelView.cc:283-287): PixelAccumulator takes the VALID pixels
+// only (Image/Statistics.h:283-290), and without any the box is (0, 0, 0, 0).  range4 = {min x, min y, max x, max y}.
+void vwo_parabola_range(const float* disp3f, int w, int h, int32_t* range4) {
+  MinMax a;
+  for (size_t i = 0; i < (size_t)w * h; ++i)
+    if (disp3f[3*i+2] != 0.0f) a.add((int32_t)disp3f[3*i], (int32_t)disp3f[3*i+1]);
+  range4[0] = a.mnx; range4[1] = a.mny; range4[2] = a.mxx; range4[3] = a.mxy;
+}
+
 int vwo_parabola_subpixel(const float* disp3f, int w, int h, const float* left, const float* right, int rw, int rh,
                           int prefilter_mode, float prefilter_width, int kx, int ky, float* out3f) {
   if (kx % 2 != 1 || ky % 2 != 1 || w <= 0 || h <= 0) return -1;
   const size_t n = (size_t)w * h;
   // prerasterize(bbox = whole image), ParabolaSubpixelView.cc:277-298
   std::vector<int32_t> idisp(n * 3);                                       // crop(m_disparity, bbox) as PixelMask<Vector2i>
-  for (size_t i = 0; i < n; ++i) {
-    idisp[3*i] = (int32_t)disp3f[3*i]; idisp[3*i+1] = (int32_t)disp3f[3*i+1];  // float -> int32 conversion truncates
-    idisp[3*i+2] = disp3f[3*i+2] != 0.0f ? std::numeric_limits<int32_t>::max() : 0;
+  for (size_t i = 0; i < n; ++i) {                                         // float -> int32 conversion truncates
+    const bool v = disp3f[3*i+2] != 0.0f;                                   // (what an invalid pixel stores is never read: zeros here)
+    idisp[3*i] = v ? (int32_t)disp3f[3*i] : 0; idisp[3*i+1] = v ? (int32_t)disp3f[3*i+1] : 0;
+    idisp[3*i+2] = v ? std::numeric_limits<int32_t>::max() : 0;
   }
-  // get_disparity_range does NOT skip invalid pixels (src/vw/Stereo/DisparityMap.h:52-66)
-  int mnx = idisp[0], mxx = idisp[0], mny = idisp[1], mxy = idisp[1];
-  for (size_t i = 0; i < n; ++i) {
-    mnx = std::min(mnx, idisp[3*i]); mxx = std::max(mxx, idisp[3*i]);
-    mny = std::min(mny, idisp[3*i+1]); mxy = std::max(mxy, idisp[3*i+1]);
-  }
+  int r4[4];
+  vwo_parabola_range(disp3f, w, h, r4);
+  const int mnx = r4[0], mny = r4[1], mxx = r4[2], mxy = r4[3];
   Box range(mnx, mny, mxx + 1, mxy + 1);                                  // entire_search_range, max += (1,1)
   range.expand(1);
   const int hx = kx / 2, hy = ky / 2;

@@ -112,6 +112,11 @@ int vwo_prefilter_region(const float* src, int w, int h, int mode, float width,
 int vwo_parabola_subpixel(const float* disp3f, int w, int h, const float* left, const float* right, int rw, int rh,
                           int prefilter_mode, float prefilter_width, int kx, int ky, float* out3f);
 
+/* The range vwo_parabola_subpixel sizes its rasters with: get_disparity_range of the truncated disparity
+ * (ParabolaSubpixelView.cc:283-287) over the VALID pixels (Image/Statistics.h:283-290), zeros without any.
+ * range4 = {min x, min y, max x, max y}. */
+void vwo_parabola_range(const float* disp3f, int w, int h, int32_t* range4);
+
 /* ---- pyramid block matching ------------------------------------------------------------------------------------ */
 
 /* One tile of pyramid_correlate(...) with VW_CORRELATION_BM: PyramidCorrelationView::prerasterize(bbox),

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../oracle/vw_oracle.h"
+#include "tile_range.h"
 
 namespace {
 
@@ -334,6 +335,14 @@ void affine_2d(DImg& D, const FImg& L, const FImg& R, int kw, int kh, int rx0, i
 
 extern "C" {
 
+// The range of one tile {x, y, w, h} (tile_range.h) as {min x, min y, max x, max y}.  Returns 0, -1 on bad arguments.
+int afr_tile_range(const float* disp3, int w, int h, const int* tile, int* out4) {
+  if (!disp3 || !tile || !out4 || w <= 0 || h <= 0) return -1;
+  if (tile[2] <= 0 || tile[3] <= 0 || tile[0] < 0 || tile[1] < 0 || tile[0] + tile[2] > w || tile[1] + tile[3] > h) return -1;
+  tile_disparity_range(disp3, w, tile, out4);
+  return 0;
+}
+
 // One call = PyramidSubpixelView::prerasterize(bbox) for each of the ntiles boxes {x, y, w, h} (inside the left image),
 // written into out3 (w x h x 3).  Returns 0, -1 on bad arguments, -2 for an algorithm other than FAST_AFFINE (1).
 // stats (may be NULL): [0] += window-loop iterations run.
@@ -350,23 +359,11 @@ int afr_pyramid_subpixel(const float* disp3, int w, int h, const float* left, co
   }
   for (int t = 0; t < ntiles; ++t) {
     const int bx = tiles[4 * t], by = tiles[4 * t + 1], bw = tiles[4 * t + 2], bh = tiles[4 * t + 3];
-    // get_disparity_range over crop(disparity, bbox): element-wise min / max of every stored value, invalid pixels
-    // included (DisparityMap.h:52-64); BBox2f -> BBox2i converts each corner with a C cast (BBox.tcc:49-50).
-    float mnx = 0, mny = 0, mxx = 0, mxy = 0;
-    for (int y = by; y < by + bh; ++y)
-      for (int x = bx; x < bx + bw; ++x) {
-        const float* q = disp3 + ((size_t)y * w + x) * 3;
-        if (y == by && x == bx) {
-          mnx = mxx = q[0];
-          mny = mxy = q[1];
-        } else {
-          mnx = q[0] < mnx ? q[0] : mnx;
-          mny = q[1] < mny ? q[1] : mny;
-          mxx = q[0] > mxx ? q[0] : mxx;
-          mxy = q[1] > mxy ? q[1] : mxy;
-        }
-      }
-    const int sminx = (int)mnx, sminy = (int)mny, smaxx = (int)mxx, smaxy = (int)mxy;
+    // get_disparity_range over crop(disparity, bbox) (SubpixelView.cc:42): over the tile's valid pixels, zeros without any;
+    // BBox2f -> BBox2i converts each corner with a C cast (tile_range.h).
+    int rng[4];
+    tile_disparity_range(disp3, w, tiles + 4 * t, rng);
+    const int sminx = rng[0], sminy = rng[1], smaxx = rng[2], smaxy = rng[3];
     // crop boxes (SubpixelView.cc:46-63): both of the right box's size, grown by the full kernel size
     const int pw = bw + (smaxx - sminx) + 2 * kx, ph = bh + (smaxy - sminy) + 2 * ky;
     const int lx0 = bx - kx, ly0 = by - ky, rx0 = bx + sminx - kx, ry0 = by + sminy - ky;

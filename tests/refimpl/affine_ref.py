@@ -21,7 +21,21 @@ def lib():
         p, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
         _LIB.afr_pyramid_subpixel.argtypes = [p, i, i, p, p, i, i, i, f, i, i, i, i, p, i, p, i, p]
         _LIB.afr_pyramid_subpixel.restype = i
+        _LIB.afr_tile_range.argtypes = [p, i, i, p, p]
+        _LIB.afr_tile_range.restype = i
     return _LIB
+
+
+def tile_range(disparity, tile=None):
+    """The search range of one tile {x, y, w, h} (default: the whole map), as the three restatements take it
+    (tile_range.h): int32 [min x, min y, max x, max y] over the tile's valid pixels, zeros without any."""
+    d = np.ascontiguousarray(disparity, np.float32)
+    h, w = d.shape[:2]
+    t = np.ascontiguousarray(tile if tile is not None else (0, 0, w, h), np.int32)
+    out = np.zeros(4, np.int32)
+    if lib().afr_tile_range(d.ctypes.data, w, h, t.ctypes.data, out.ctypes.data):
+        raise ValueError("afr_tile_range: bad arguments")
+    return out
 
 
 def tiles_for(w, h, block_size=None):
@@ -86,7 +100,7 @@ def cascade_scene(w, h, seed=5):
     band[: h // 3] = False
     band[2 * h // 3:] = False
     d[band, 2] = 0
-    d[band, 0] = rng.uniform(-30, 30, size=band.sum())   # stored values of invalid pixels count in the range
+    d[band, 0] = rng.uniform(-30, 30, size=band.sum())   # stored values of invalid pixels lie outside the valid range
     return left, right, d, true
 
 

@@ -3,7 +3,8 @@
 The specified arithmetic of visionworkbench_amd/csrc/subpixel.hip (its header comment) and of the reference's
 ParabolaSubpixelView.cc:187-257, stated once more without zones and without running sums:
 
-  * the disparity is truncated toward zero; its range is taken over ALL pixels, invalid ones included;
+  * the disparity is truncated toward zero; its range is taken over the VALID pixels (get_disparity_range,
+    Image/Statistics.h:283-290), zeros without any: what an invalid pixel stores is never read;
   * left raster = prefilter over [-hx, w + hx) x [-hy, h + hy); right raster = the left region moved by (range.min - 1) and
     grown by (range size + 2) — the reference's `left_region`, `right_region` (:293-298), rasterised by oracle.prefilter_region;
   * per valid pixel nine costs: float64 sums, accumulated term by term (rows outer, columns inner), of the float32 |l - r|,
@@ -29,10 +30,19 @@ _PINV = np.array([[1 / 6, -1 / 3, 1 / 6, 1 / 6, -1 / 3, 1 / 6, 1 / 6, -1 / 3, 1 
 
 
 def disparity_range(disp):
-    """(min x, min y, max x, max y) of the truncated disparity over all pixels, and the truncated fields."""
-    idx = np.trunc(disp[..., 0]).astype(np.int64)
-    idy = np.trunc(disp[..., 1]).astype(np.int64)
-    return (int(idx.min()), int(idy.min()), int(idx.max()), int(idy.max())), idx, idy
+    """(min x, min y, max x, max y) of the truncated disparity over the valid pixels ((0, 0, 0, 0) without any), and the
+    truncated fields; an invalid pixel takes the range minimum there, so that its (unused) windows stay inside the rasters."""
+    disp = np.asarray(disp, np.float32)
+    valid = disp[..., 2] != 0
+    idx = np.zeros(disp.shape[:2], np.int64)
+    idy = np.zeros(disp.shape[:2], np.int64)
+    idx[valid] = np.trunc(disp[..., 0][valid]).astype(np.int64)
+    idy[valid] = np.trunc(disp[..., 1][valid]).astype(np.int64)
+    if not valid.any():
+        return (0, 0, 0, 0), idx, idy
+    rng = (int(idx[valid].min()), int(idy[valid].min()), int(idx[valid].max()), int(idy[valid].max()))
+    idx[~valid], idy[~valid] = rng[0], rng[1]
+    return rng, idx, idy
 
 
 def rasters(oracle, disp, left, right, mode, width, kernel):

@@ -431,21 +431,10 @@ int phr_phase_subpixel(const float* disp3, int w, int h, const float* left, cons
   }
   for (int t = 0; t < ntiles; ++t) {
     const int bx = tiles[4 * t], by = tiles[4 * t + 1], bw = tiles[4 * t + 2], bh = tiles[4 * t + 3];
-    float mnx = 0, mny = 0, mxx = 0, mxy = 0;  // get_disparity_range (DisparityMap.h:52-64), invalid pixels included
-    for (int y = by; y < by + bh; ++y)
-      for (int x = bx; x < bx + bw; ++x) {
-        const float* q = disp3 + ((size_t)y * w + x) * 3;
-        if (y == by && x == bx) {
-          mnx = mxx = q[0];
-          mny = mxy = q[1];
-        } else {
-          mnx = q[0] < mnx ? q[0] : mnx;
-          mny = q[1] < mny ? q[1] : mny;
-          mxx = q[0] > mxx ? q[0] : mxx;
-          mxy = q[1] > mxy ? q[1] : mxy;
-        }
-      }
-    const int sminx = (int)mnx, sminy = (int)mny, smaxx = (int)mxx, smaxy = (int)mxy;
+    // get_disparity_range (SubpixelView.cc:42) over the tile's valid pixels (tile_range.h)
+    int rng[4];
+    tile_disparity_range(disp3, w, tiles + 4 * t, rng);
+    const int sminx = rng[0], sminy = rng[1], smaxx = rng[2], smaxy = rng[3];
     const int pw = bw + (smaxx - sminx) + 2 * kx, ph = bh + (smaxy - sminy) + 2 * ky;
     const int lx0 = bx - kx, ly0 = by - ky, rx0 = bx + sminx - kx, ry0 = by + sminy - ky;
     FImg L, R;

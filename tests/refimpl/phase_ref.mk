@@ -9,7 +9,7 @@ all: libphase_ref.so
 $(ORACLE)/libvw_oracle.so:
 	$(MAKE) -s -C $(ORACLE)
 
-libphase_ref.so: phase_ref.cc affine_ref.cc $(ORACLE)/vw_oracle.h $(ORACLE)/libvw_oracle.so
+libphase_ref.so: phase_ref.cc affine_ref.cc tile_range.h $(ORACLE)/vw_oracle.h $(ORACLE)/libvw_oracle.so
 	$(CXX) $(CXXFLAGS) -shared -o $@ phase_ref.cc -L$(ORACLE) -lvw_oracle -Wl,-rpath,'$$ORIGIN/../../oracle' -pthread
 
 clean:

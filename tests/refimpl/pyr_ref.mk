@@ -9,7 +9,7 @@ all: libpyr_ref.so
 $(ORACLE)/libvw_oracle.so:
 	$(MAKE) -s -C $(ORACLE)
 
-libpyr_ref.so: pyr_ref.cc affine_ref.cc $(ORACLE)/vw_oracle.h $(ORACLE)/libvw_oracle.so
+libpyr_ref.so: pyr_ref.cc affine_ref.cc tile_range.h $(ORACLE)/vw_oracle.h $(ORACLE)/libvw_oracle.so
 	$(CXX) $(CXXFLAGS) -shared -o $@ pyr_ref.cc -L$(ORACLE) -lvw_oracle -Wl,-rpath,'$$ORIGIN/../../oracle'
 
 clean:

@@ -243,7 +243,7 @@ def parabola_disparity_scene(sid):
     elif kind == "outside":                                 # the right raster leaves the right image on all four sides
         d[..., 0] = np.where(xx < 40, -30, 40)
         d[..., 1] = np.where(yy < 24, -20, 25)
-    elif kind == "invalid_extreme":                         # invalid pixels hold the extremes of the range: they widen the rasters only
+    elif kind == "invalid_extreme":                         # invalid pixels store values far outside the valid range: never read
         d = parabola_disparity(h, w, rng, 0.0)
         d[5, 7] = (40.6, -25.3, 0)
         d[30, 60] = (-33.2, 19.9, 0)

@@ -491,6 +491,16 @@ def test_parabola_recovers_fractional_shift(oracle):
     assert err.mean() < 0.4                                          # the integer start has error 0.35 + 0.4 = 0.75
 
 
+def test_parabola_range_known_answer(oracle):
+    """src/vw/Stereo/tests/TestDisparity.cxx (GetDisparityRange) on the range the parabola sizes its rasters with: (2, 2), (3, 5) and
+    an invalidated (-4, -1) give min (2, 2), max (3, 5); all pixels invalid gives zeros."""
+    d = _pm2f(0, 0, 1, 3)
+    d[0, 0, :2], d[0, 1, :2], d[0, 2] = (2, 2), (3, 5), (-4, -1, 0)
+    assert oracle.parabola_range(d).tolist() == [2, 2, 3, 5]
+    d[..., 2] = 0
+    assert oracle.parabola_range(d).tolist() == [0, 0, 0, 0]
+
+
 def test_subdivide_regions_basic(oracle):
     """subdivide_regions (Correlation.cc:139-328): zones tile the image, each zone's range contains its pixels'
     disparities, a uniform image stays one zone, a two-valued image splits."""

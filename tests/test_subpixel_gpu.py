@@ -140,8 +140,8 @@ def test_order_free_scene_is_identical_to_oracle(ctx, oracle, sid):
 
 
 def test_invalid_pixels_widen_the_rasters_and_change_no_valid_pixel(ctx, oracle):
-    """Invalid pixels that store the extremes of the disparity range move the right raster's origin and size (the range is over ALL pixels)
-    and must not change a single valid pixel."""
+    """Invalid pixels that store values far outside the valid disparity range (the range is over the valid pixels: they are never read)
+    must not change a single valid pixel.  (The name dates from a range taken over all pixels.)"""
     for variant in ("u8", "f01"):
         c = scenes.parabola_scene("disparity:invalid_extreme-" + variant)
         tame = c["disp"].copy()

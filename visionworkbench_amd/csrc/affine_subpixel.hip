@@ -28,7 +28,9 @@ namespace {
 
 constexpr int AFF_BX = 16, AFF_BY = 16;
 
-// ---- per-tile disparity range (get_disparity_range, DisparityMap.h:52-64: invalid pixels count) ----------------------
+// ---- per-tile disparity range (get_disparity_range, DisparityMap.h:48-66) ---------------------------------------------
+// PixelAccumulator<EWMinMaxAccumulator> takes the VALID pixels only (Image/Statistics.h:283-290): what an invalid pixel
+// stores never reaches the range.  A tile without a valid pixel leaves its keys at the initial values (range 0, 0, 0, 0).
 
 __device__ inline int aff_float_key(float f) {   // order-preserving float -> int map for atomicMin / atomicMax
   const int b = __float_as_int(f);
@@ -44,6 +46,7 @@ affine_range_kernel(const float* __restrict__ d, ptrdiff_t stride_px, const int*
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const int y = by + (int)(i / bw), x = bx + (int)(i % bw);
     const float* q = d + ((ptrdiff_t)y * stride_px + x) * 3;
+    if (q[2] == 0.0f) continue;
     const int kx = aff_float_key(q[0]), ky = aff_float_key(q[1]);
     mnx = min(mnx, kx); mxx = max(mxx, kx);
     mny = min(mny, ky); mxy = max(mxy, ky);
@@ -776,20 +779,29 @@ int vwgpu_pyramid_subpixel_tiles(vwgpu_ctx* ctx, const float* d_disp, int w, int
   const float var2_plane = 1e-3f, var2_noise = 1e-2f;
   const float plane_nf = 1.0 / std::sqrt(2 * M_PI * var2_plane), noise_nf = 1.0 / std::sqrt(2 * M_PI * var2_noise);
 
+  // BBox2f -> BBox2i: a C cast of each corner (BBox.tcc:49-50).  Every tile is checked before the first one is written.
+  std::vector<int> rng((size_t)4 * ntiles, 0);
   for (int t = 0; t < ntiles; ++t) {
-    const int bx = tiles[4 * t], by = tiles[4 * t + 1], bw = tiles[4 * t + 2], bh = tiles[4 * t + 3];
-    // BBox2f -> BBox2i: a C cast of each corner (BBox.tcc:49-50)
-    const float fmnx = key_float(keys[4 * t]), fmny = key_float(keys[4 * t + 1]);
-    const float fmxx = key_float(keys[4 * t + 2]), fmxy = key_float(keys[4 * t + 3]);
-    if (!(std::isfinite(fmnx) && std::isfinite(fmny) && std::isfinite(fmxx) && std::isfinite(fmxy)))
-      return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "pyramid_subpixel: tile %d holds a non-finite disparity", t);
-    // the patch spans the range: a range this wide cannot be held (and would overflow the int conversion below)
-    if (!(std::fabs(fmnx) < 1e9f && std::fabs(fmny) < 1e9f && std::fabs(fmxx) < 1e9f && std::fabs(fmxy) < 1e9f))
-      return vwgpu_fail(ctx, VWGPU_ERR_NOMEM, "pyramid_subpixel: the disparity range of tile %d needs a patch that cannot be held", t);
-    const int sminx = (int)fmnx, sminy = (int)fmny, smaxx = (int)fmxx, smaxy = (int)fmxy;
-    const long long pwl = (long long)bw + (smaxx - sminx) + 2LL * kx, phl = (long long)bh + (smaxy - sminy) + 2LL * ky;
+    const int bw = tiles[4 * t + 2], bh = tiles[4 * t + 3];
+    if (!(keys[4 * t] == INT_MAX && keys[4 * t + 2] == INT_MIN)) {     // min > max: the initial keys, no valid pixel
+      const float fmnx = key_float(keys[4 * t]), fmny = key_float(keys[4 * t + 1]);
+      const float fmxx = key_float(keys[4 * t + 2]), fmxy = key_float(keys[4 * t + 3]);
+      if (!(std::isfinite(fmnx) && std::isfinite(fmny) && std::isfinite(fmxx) && std::isfinite(fmxy)))
+        return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "pyramid_subpixel: tile %d holds a non-finite disparity in a valid pixel", t);
+      // the patch spans the range: a range this wide cannot be held (and would overflow the int conversion below)
+      if (!(std::fabs(fmnx) < 1e9f && std::fabs(fmny) < 1e9f && std::fabs(fmxx) < 1e9f && std::fabs(fmxy) < 1e9f))
+        return vwgpu_fail(ctx, VWGPU_ERR_NOMEM, "pyramid_subpixel: the disparity range of tile %d needs a patch that cannot be held", t);
+      rng[4 * t] = (int)fmnx; rng[4 * t + 1] = (int)fmny; rng[4 * t + 2] = (int)fmxx; rng[4 * t + 3] = (int)fmxy;
+    }
+    const long long pwl = (long long)bw + (rng[4 * t + 2] - rng[4 * t]) + 2LL * kx, phl = (long long)bh + (rng[4 * t + 3] - rng[4 * t + 1]) + 2LL * ky;
     if (pwl > 32768 || phl > 32768 || pwl * phl > (1LL << 28))
       return vwgpu_fail(ctx, VWGPU_ERR_NOMEM, "pyramid_subpixel: tile %d needs a %lld x %lld patch", t, pwl, phl);
+  }
+
+  for (int t = 0; t < ntiles; ++t) {
+    const int bx = tiles[4 * t], by = tiles[4 * t + 1], bw = tiles[4 * t + 2], bh = tiles[4 * t + 3];
+    const int sminx = rng[4 * t], sminy = rng[4 * t + 1], smaxx = rng[4 * t + 2], smaxy = rng[4 * t + 3];
+    const long long pwl = (long long)bw + (smaxx - sminx) + 2LL * kx, phl = (long long)bh + (smaxy - sminy) + 2LL * ky;
     const int pw = (int)pwl, ph = (int)phl;
     const int lx0 = bx - kx, ly0 = by - ky, rx0 = bx + sminx - kx, ry0 = by + sminy - ky;
 

@@ -25,8 +25,10 @@
 
 namespace {
 
-// get_disparity_range over ALL pixels (invalid ones included, src/vw/Stereo/DisparityMap.h:52-66) of the disparity truncated to int
-// (the PixelMask<Vector2f> -> PixelMask<Vector2i> conversion of ParabolaSubpixelView.cc:283): parabola_prepass_kernel, blockIdx.z = 0.
+// get_disparity_range over the VALID pixels (src/vw/Stereo/DisparityMap.h:48-66: PixelAccumulator, Image/Statistics.h:283-290) of the
+// disparity truncated to int (the PixelMask<Vector2f> -> PixelMask<Vector2i> conversion of ParabolaSubpixelView.cc:283):
+// parabola_prepass_kernel, blockIdx.z = 0.  What an invalid pixel stores is never read; without a valid pixel the four words keep their
+// initial values and the caller takes the range (0, 0, 0, 0).
 
 // The class of the imagery in the SAME launch as the disparity range (blockIdx.z = 1, 2: the left / the right image): lowest set mantissa
 // bit, largest exponent, "non-finite" (bit 0) and "negative" (bit 1) over all pixels, as float_grain_kernel (bm_exact.hip) measures them —
@@ -53,12 +55,15 @@ parabola_prepass_kernel(const float* __restrict__ d, int w, int h, ptrdiff_t str
   const int xs = gridDim.x * blockDim.x, xf = blockIdx.x * blockDim.x + threadIdx.x;
   if (blockIdx.z == 0) {
     // A row of the disparity is 3 w floats {dx, dy, valid, dx, ...}: four pixels = three float4 (dx at elements 0, 3, 6, 9, dy at 1, 4, 7,
-    // 10), two such groups in flight per thread where the rows are 16-byte aligned; pixel by pixel otherwise.
+    // 10, valid at 2, 5, 8, 11), two such groups in flight per thread where the rows are 16-byte aligned; pixel by pixel otherwise.
     int mnx = INT_MAX, mny = INT_MAX, mxx = INT_MIN, mxy = INT_MIN;
     const bool vec = ((reinterpret_cast<uintptr_t>(d) & 15) == 0) && (stride_px % 4 == 0);
     const int n12 = vec ? w / 4 : 0;                            // whole groups of four pixels
-    auto tx = [&](float v) __attribute__((always_inline)) { const int iv = (int)v; mnx = min(mnx, iv); mxx = max(mxx, iv); };
-    auto ty = [&](float v) __attribute__((always_inline)) { const int iv = (int)v; mny = min(mny, iv); mxy = max(mxy, iv); };
+    auto take = [&](float vx, float vy, float valid) __attribute__((always_inline)) {
+      if (valid == 0.0f) return;
+      const int ix = (int)vx, iy = (int)vy;
+      mnx = min(mnx, ix); mxx = max(mxx, ix); mny = min(mny, iy); mxy = max(mxy, iy);
+    };
     // (the loads in flight are two ROWS of the thread's column group — a 4096-wide row is one group per thread of the 1024-wide grid row)
     const int ys = gridDim.y * blockDim.y;
     for (int y = blockIdx.y * blockDim.y + threadIdx.y; y < h; y += 2 * ys) {
@@ -70,11 +75,12 @@ parabola_prepass_kernel(const float* __restrict__ d, int w, int h, ptrdiff_t str
       for (int j = xf; j < n12; j += xs) {
         const float4 a0 = row4[3 * j], a1 = row4[3 * j + 1], a2 = row4[3 * j + 2];
         const float4 b0 = rowb4[3 * j], b1 = rowb4[3 * j + 1], b2 = rowb4[3 * j + 2];
-        tx(a0.x); ty(a0.y); tx(a0.w); ty(a1.x); tx(a1.z); ty(a1.w); tx(a2.y); ty(a2.z);
-        tx(b0.x); ty(b0.y); tx(b0.w); ty(b1.x); tx(b1.z); ty(b1.w); tx(b2.y); ty(b2.z);
+        take(a0.x, a0.y, a0.z); take(a0.w, a1.x, a1.y); take(a1.z, a1.w, a2.x); take(a2.y, a2.z, a2.w);
+        take(b0.x, b0.y, b0.z); take(b0.w, b1.x, b1.y); take(b1.z, b1.w, b2.x); take(b2.y, b2.z, b2.w);
       }
       for (int x = 4 * n12 + xf; x < w; x += xs) {
-        tx(row[(ptrdiff_t)x * 3]); ty(row[(ptrdiff_t)x * 3 + 1]); tx(rowb[(ptrdiff_t)x * 3]); ty(rowb[(ptrdiff_t)x * 3 + 1]);
+        take(row[(ptrdiff_t)x * 3], row[(ptrdiff_t)x * 3 + 1], row[(ptrdiff_t)x * 3 + 2]);
+        take(rowb[(ptrdiff_t)x * 3], rowb[(ptrdiff_t)x * 3 + 1], rowb[(ptrdiff_t)x * 3 + 2]);
       }
     }
     for (int o = 32; o > 0; o >>= 1) {

@@ -267,6 +267,7 @@ int vwgpu_parabola_subpixel_dev(vwgpu_ctx* ctx, const float* d_disp, int w, int 
   int r4[4];
   VWGPU_HIP(ctx, hipMemcpyAsync(r4, d_range, sizeof r4, hipMemcpyDeviceToHost, ctx->stream));
   VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));              // the ROI sizes depend on the data
+  if (r4[0] > r4[2]) r4[0] = r4[1] = r4[2] = r4[3] = 0;           // no valid pixel: get_disparity_range gives BBox2f(0, 0, 0, 0)
   // 0: any float (float64 sums); 1: integers of magnitude below 2^21; 2: integers in [0,255]
   int integer_class = 0;
   if (mode == VWGPU_PREFILTER_NONE && !(grain[2] & 1) && (grain[0] == INT_MAX || (grain[0] >= 0 && grain[1] <= 20)))

@@ -250,8 +250,8 @@ def pyramid_subpixel(disparity, left, right, prefilter_mode, prefilter_width, ke
     phase_subpixel, which takes its accuracy argument), rasterised one
     prerasterize(bbox) per tile (SubpixelView.cc:33-224).
 
-    disparity: (rows, cols, 3) float32 PixelMask<Vector2f> {dx, dy, valid}, the left image's size; stored values of invalid
-    pixels count in each tile's disparity range, as in the reference.  left / right: 2-D float32 (any sizes), numpy arrays
+    disparity: (rows, cols, 3) float32 PixelMask<Vector2f> {dx, dy, valid}, the left image's size; each tile's disparity range
+    is taken over its valid pixels, as in the reference (what an invalid pixel stores is never read).  left / right: 2-D float32 (any sizes), numpy arrays
     (host entry) or CUDA tensors (device entry, result on the device).  block_size None = one tile, the whole image
     (ImageView out = view); (bw, bh) = the blocks of block_write_image.  Returns refined {dx, dy, 1}, invalid {0, 0, 0}.
     stats (optional list) receives [fixpoint rounds summed over tiles and levels, most rounds of one tile level, window

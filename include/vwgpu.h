@@ -729,6 +729,115 @@ int vwgpu_intersect_mask_and_data_dev(vwgpu_ctx* ctx, int type, const void* d_da
 int vwgpu_intersect_mask_and_data(vwgpu_ctx* ctx, int type, const void* data, ptrdiff_t dstride, const void* mask, ptrdiff_t mstride,
                                   int w, int h, void* out, ptrdiff_t ostride);
 
+/* ---- Stereo/StereoModel.{h,cc} and Stereo/StereoView.h: triangulation and the universe radius ---------- */
+
+/* The part of vw::camera that triangulation needs (tests/refimpl/triangulate_ref.cc): a flat
+ * descriptor, passed to the kernels by value.
+ *   VWGPU_CAMERA_PINHOLE  PinholeModel::pixel_to_vector / camera_center (src/vw/Camera/PinholeModel.cc:422-434):
+ *                         normalize(inv_camera_transform * (undistort(pix * pixel_pitch), 1)) from `center`.
+ *                         inv_camera_transform is the reference's m_inv_camera_transform, row-major.
+ *     VWGPU_DISTORTION_NULL  the identity.
+ *     VWGPU_DISTORTION_TSAI  TsaiLensDistortion::undistorted_coordinates (src/vw/Camera/LensDistortion.cc:371-400) with
+ *                            distortion = {k1, k2, p1, p2, k3}: TsaiDistortionNorm (:260-276), the analytic Jacobian
+ *                            (:286-324) and NewtonRaphson::solve (src/vw/Math/NewtonRaphson.cc:58-119) with its start
+ *                            point, its 19 passes, its best-so-far fallbacks and its 1e-9 stop on the step; fu or fv
+ *                            below 1e-300 gives HUGE_VAL.
+ *   VWGPU_CAMERA_CAHV     CAHVModel::pixel_to_vector / camera_center (src/vw/Camera/CAHVModel.cc:173-189):
+ *                         normalize(cross(V - y A, H - x A)), times -1.0 when dot(cross(V, H), A) < 0, from C = `center`. */
+typedef enum vwgpu_camera_kind { VWGPU_CAMERA_PINHOLE = 0, VWGPU_CAMERA_CAHV = 1 } vwgpu_camera_kind;
+typedef enum vwgpu_distortion_kind { VWGPU_DISTORTION_NULL = 0, VWGPU_DISTORTION_TSAI = 1 } vwgpu_distortion_kind;
+typedef struct vwgpu_camera {
+  int kind;                          /* vwgpu_camera_kind */
+  int distortion_kind;               /* vwgpu_distortion_kind (pinhole) */
+  double center[3];                  /* camera centre (pinhole), C (CAHV) */
+  double inv_camera_transform[9];    /* pinhole */
+  double pixel_pitch, fu, fv, cu, cv;
+  double distortion[5];
+  double A[3], H[3], V[3];           /* CAHV */
+} vwgpu_camera;
+
+/* Fills a pinhole descriptor the way PinholeModel::rebuild_camera_matrix does (src/vw/Camera/PinholeModel.cc:553-605):
+ * inv_camera_transform = inverse(uvwRotation * transpose(rotation)) * inverse(K), with the rows of uvwRotation u_dir,
+ * v_dir, w_dir and K = [fu 0 cu; 0 fv cv; 0 0 1]; both inverses are plain 3 x 3 adjugates, the bits of the reference's
+ * inverse() are not pinned.  center, u_dir, v_dir, w_dir: double[3]; rotation: row-major double[9]; distortion:
+ * double[5] {k1, k2, p1, p2, k3} or NULL with VWGPU_DISTORTION_NULL.  u, v, w that are not orthonormal under the
+ * reference's own asserts (:586-591: the three dot products == 0, every norm within 0.001 of 1), a null pointer or an
+ * unknown distortion kind: VWGPU_ERR_ARGUMENT.  Pure host arithmetic, no context. */
+int vwgpu_pinhole_camera(const double* center, const double* rotation, double fu, double fv, double cu, double cv,
+                         const double* u_dir, const double* v_dir, const double* w_dir, double pixel_pitch, int distortion_kind,
+                         const double* distortion, vwgpu_camera* out);
+
+/* How the right pixel of a pair is formed (the two entry points of the reference differ, and the difference is kept):
+ *   VWGPU_TRIANGULATE_VIEW   StereoView::operator() (src/vw/Stereo/StereoView.h:91-99): Vector2(i, j) + Vector2((double)dx,
+ *                            (double)dy), a double add.
+ *   VWGPU_TRIANGULATE_MODEL  StereoModel::operator()(disparity_map, error) (src/vw/Stereo/StereoModel.cc:276-281): x + dx
+ *                            with x an int32 and dx a float, added in float and then widened (int32 pixels: added in
+ *                            int32).  In this overload a point whose error is not >= 0 (a NaN) becomes zero (:283-293).
+ * OR one vwgpu_disparity_layout into `semantics` for the other pixel forms DispHelper accepts (StereoView.h:37-53); the
+ * channel type stays `type` and the disparity stride stays in pixels of that layout:
+ *   VWGPU_DISPARITY_LAYOUT_DXDYV  {dx, dy, valid}, PixelMask<Vector2> (default)
+ *   VWGPU_DISPARITY_LAYOUT_DXDY   {dx, dy}, every pixel valid
+ *   VWGPU_DISPARITY_LAYOUT_DV     {dx, valid}, dy = 0 (a masked scalar)
+ *   VWGPU_DISPARITY_LAYOUT_D      {dx}, dy = 0, every pixel valid */
+typedef enum vwgpu_triangulate_semantics { VWGPU_TRIANGULATE_VIEW = 0, VWGPU_TRIANGULATE_MODEL = 1 } vwgpu_triangulate_semantics;
+typedef enum vwgpu_disparity_layout {
+  VWGPU_DISPARITY_LAYOUT_DXDYV = 0, VWGPU_DISPARITY_LAYOUT_DXDY = 0x100, VWGPU_DISPARITY_LAYOUT_DV = 0x200,
+  VWGPU_DISPARITY_LAYOUT_D = 0x300
+} vwgpu_disparity_layout;
+
+/* The quantities StereoModel::operator()(disparity_map, error) reports (StereoModel.cc:258-307) over the valid pixels whose
+ * error is >= 0 (every pixel but a NaN error; nearly parallel rays count with error 0).  max_error is exact; sum_error is
+ * summed lane by lane, wavefront by wavefront and workgroup by workgroup in a fixed order without floating-point atomics:
+ * two calls return the same bits, the reference's raster-order sum may differ in the last places. */
+typedef struct vwgpu_triangulate_stats {
+  long long point_count;
+  double max_error, sum_error;
+} vwgpu_triangulate_stats;
+
+/* Replaces rasterising vw::stereo::stereo_triangulate(d, cam1, cam2) (StereoView, src/vw/Stereo/StereoView.h:56-130) and
+ * StereoModel::operator()(disparity_map, error) (src/vw/Stereo/StereoModel.cc:254-309) for two cameras.  disp is w x h
+ * pixels of `type` (a vwgpu_disparity_type) in the layout named in `semantics`; x0, y0 are the image coordinates of pixel
+ * (0, 0) of the buffer, so a tile or row strip equals that region of the whole-map call.  Per valid pixel, with pix1 =
+ * (x0 + x, y0 + y) and pix2 by `semantics`, StereoModel::operator()(pixVec, errorVec) (:97-147): a pixel that is NaN or
+ * equals CameraModel::invalid_pixel() = (-1e8, -1e8) gives no ray, and with fewer than two rays the point and the error
+ * vector are zero; rays with !(1 - dot(d0, d1) >= tol) (tol = 1e-4, or angle_tol when angle_tol > 0) give a zero point;
+ * otherwise triangulate_pair (:35-48) in its expression order, reflected (-p + 2 ctr0) when the point lies behind either
+ * camera.  error = norm_2(errvec).  An invalid disparity pixel gives a zero point, error and error vector.
+ *   xyz     w x h x 3 double (stride in pixels); error (optional) w x h double; errvec (optional) w x h x 3 double.
+ *   stats   optional vwgpu_triangulate_stats: a DEVICE pointer for _dev (no synchronisation), a host pointer otherwise.
+ * Null disp / xyz / cameras, w or h <= 0, a stride below the width, type, camera kind, distortion kind, semantics or layout
+ * out of range, NaN angle_tol: VWGPU_ERR_ARGUMENT before any device work.  Outputs must not alias each other. */
+int vwgpu_stereo_triangulate_dev(vwgpu_ctx* ctx, int type, const void* d_disp, int w, int h, ptrdiff_t dstride, int x0, int y0,
+                                 const vwgpu_camera* cam1, const vwgpu_camera* cam2, double angle_tol, int semantics, double* d_xyz,
+                                 ptrdiff_t xstride, double* d_error, ptrdiff_t estride, double* d_errvec, ptrdiff_t vstride,
+                                 vwgpu_triangulate_stats* d_stats);
+int vwgpu_stereo_triangulate(vwgpu_ctx* ctx, int type, const void* disp, int w, int h, ptrdiff_t dstride, int x0, int y0,
+                             const vwgpu_camera* cam1, const vwgpu_camera* cam2, double angle_tol, int semantics, double* xyz,
+                             ptrdiff_t xstride, double* error, ptrdiff_t estride, double* errvec, ptrdiff_t vstride,
+                             vwgpu_triangulate_stats* stats);
+
+/* Replaces StereoModel::convergence_angle (src/vw/Stereo/StereoModel.cc:174-177) over a disparity map: out is w x h double,
+ * acos(dot(cam1.pixel_to_vector(pix1), cam2.pixel_to_vector(pix2))) with the pixel pair formed as above (no pixel is
+ * skipped: a NaN pixel gives a NaN angle); invalid disparity pixels give 0.  The dot product is the reference's bits, acos
+ * is the device library's. */
+int vwgpu_convergence_angle_dev(vwgpu_ctx* ctx, int type, const void* d_disp, int w, int h, ptrdiff_t dstride, int x0, int y0,
+                                const vwgpu_camera* cam1, const vwgpu_camera* cam2, int semantics, double* d_out, ptrdiff_t ostride);
+int vwgpu_convergence_angle(vwgpu_ctx* ctx, int type, const void* disp, int w, int h, ptrdiff_t dstride, int x0, int y0,
+                            const vwgpu_camera* cam1, const vwgpu_camera* cam2, int semantics, double* out, ptrdiff_t ostride);
+
+/* Replaces per_pixel_filter(points, UniverseRadiusFunc(origin, near, far)) (src/vw/Stereo/StereoView.h:139-222) on a point
+ * image of `channels` = 3, 4 or 6 doubles per pixel (xyz; xyz + error; xyz + error vector; strides in pixels): a pixel
+ * whose first three channels are all zero becomes all zero; otherwise, with dist = norm_2(xyz - origin), the whole pixel
+ * becomes zero when (near_radius != 0 && dist < near_radius) || (far_radius != 0 && dist > far_radius), else it is
+ * copied.  counts (optional HOST long long[2], asking for it synchronises the stream) = {total_points (every pixel),
+ * rejected_points}.  Negative or NaN radii, near_radius > far_radius (the constructor's asserts), other channel counts:
+ * VWGPU_ERR_ARGUMENT.  out == points is allowed. */
+int vwgpu_universe_radius_dev(vwgpu_ctx* ctx, const double* d_points, int channels, int w, int h, ptrdiff_t stride,
+                              const double* origin, double near_radius, double far_radius, double* d_out, ptrdiff_t ostride,
+                              long long* counts);
+int vwgpu_universe_radius(vwgpu_ctx* ctx, const double* points, int channels, int w, int h, ptrdiff_t stride, const double* origin,
+                          double near_radius, double far_radius, double* out, ptrdiff_t ostride, long long* counts);
+
 /* ---- disparity clean-up filters and the zone scheduler ------------------------------------------------- */
 
 /* Replaces rasterising vw::stereo::rm_outliers_using_thresh (cleanup == 0) or

@@ -8,11 +8,11 @@ from . import core, synth  # noqa: F401
 from .core import (ABSOLUTE_DIFFERENCE, CROSS_CORRELATION, SQUARED_DIFFERENCE, ArgumentErr, BBox2i, Context,  # noqa: F401
                    CostFunctionType, LogicErr, NoImplErr, bounding_box)
 
-__all__ = ["core", "synth", "stereo", "Context", "BBox2i", "CostFunctionType", "bounding_box"]
+__all__ = ["core", "synth", "stereo", "camera", "Context", "BBox2i", "CostFunctionType", "bounding_box"]
 
 
 def __getattr__(name):
-    if name == "stereo":
+    if name in ("stereo", "camera"):
         import importlib
-        return importlib.import_module(".stereo", __name__)
+        return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -33,6 +33,8 @@ SYMBOLS = [
     "vwgpu_disparity_subsample_dev", "vwgpu_disparity_subsample", "vwgpu_disparity_upsample_dev", "vwgpu_disparity_upsample",
     "vwgpu_disparity_warp_dev", "vwgpu_disparity_warp", "vwgpu_missing_pixel_image_dev", "vwgpu_missing_pixel_image",
     "vwgpu_intersect_mask_and_data_dev", "vwgpu_intersect_mask_and_data",
+    "vwgpu_pinhole_camera", "vwgpu_stereo_triangulate_dev", "vwgpu_stereo_triangulate",
+    "vwgpu_convergence_angle_dev", "vwgpu_convergence_angle", "vwgpu_universe_radius_dev", "vwgpu_universe_radius",
     "vwgpu_disparity_filter_dev", "vwgpu_disparity_filter",
     "vwgpu_disparity_mask_dev", "vwgpu_disparity_mask",
     "vwgpu_subdivide_regions",
@@ -51,6 +53,21 @@ class SgmParams(ctypes.Structure):
         ("p1", ctypes.c_int), ("p2", ctypes.c_int), ("ternary_census_threshold", ctypes.c_int), ("num_threads", ctypes.c_int),
         ("allow_block_cost", ctypes.c_int),
     ]
+
+
+class Camera(ctypes.Structure):
+    """struct vwgpu_camera (include/vwgpu.h)."""
+    _fields_ = [
+        ("kind", ctypes.c_int), ("distortion_kind", ctypes.c_int), ("center", ctypes.c_double * 3),
+        ("inv_camera_transform", ctypes.c_double * 9), ("pixel_pitch", ctypes.c_double),
+        ("fu", ctypes.c_double), ("fv", ctypes.c_double), ("cu", ctypes.c_double), ("cv", ctypes.c_double),
+        ("distortion", ctypes.c_double * 5), ("A", ctypes.c_double * 3), ("H", ctypes.c_double * 3), ("V", ctypes.c_double * 3),
+    ]
+
+
+class TriangulateStats(ctypes.Structure):
+    """struct vwgpu_triangulate_stats (include/vwgpu.h)."""
+    _fields_ = [("point_count", ctypes.c_longlong), ("max_error", ctypes.c_double), ("sum_error", ctypes.c_double)]
 
 
 class PyramidParams(ctypes.Structure):
@@ -199,6 +216,17 @@ def load():
     imd = [P, I, P, PD, P, PD, I, I, P, PD]
     lib.vwgpu_intersect_mask_and_data_dev.argtypes = imd
     lib.vwgpu_intersect_mask_and_data.argtypes = imd
+    CP = ctypes.POINTER(Camera)
+    lib.vwgpu_pinhole_camera.argtypes = [P, P, D, D, D, D, P, P, P, D, I, P, CP]
+    tri = [P, I, P, I, I, PD, I, I, CP, CP, D, I, P, PD, P, PD, P, PD, P]
+    lib.vwgpu_stereo_triangulate_dev.argtypes = tri
+    lib.vwgpu_stereo_triangulate.argtypes = tri
+    cva = [P, I, P, I, I, PD, I, I, CP, CP, I, P, PD]
+    lib.vwgpu_convergence_angle_dev.argtypes = cva
+    lib.vwgpu_convergence_angle.argtypes = cva
+    unr = [P, P, I, I, I, PD, P, D, D, P, PD, P]
+    lib.vwgpu_universe_radius_dev.argtypes = unr
+    lib.vwgpu_universe_radius.argtypes = unr
     df = [P, P, I, I, I, I, D, D, I, P]
     lib.vwgpu_disparity_filter_dev.argtypes = df
     lib.vwgpu_disparity_filter.argtypes = df

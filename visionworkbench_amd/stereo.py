@@ -1179,6 +1179,175 @@ def disparity_transform_image(right, disparity, ctx=None):
     return out
 
 
+TRIANGULATE_SEMANTICS = {"view": 0, "model": 1}
+DISPARITY_LAYOUTS = {"dxdyv": 0x000, "dxdy": 0x100, "dv": 0x200, "d": 0x300}
+_LAYOUT_WORDS = {"dxdyv": 3, "dxdy": 2, "dv": 2, "d": 1}
+
+
+def _tri_disparity(name, disparity, layout):
+    """A disparity image in one of the pixel forms DispHelper accepts (src/vw/Stereo/StereoView.h:37-53); returns
+    (contiguous image, vwgpu_disparity_type, layout flag, w, h, is a tensor).  Never copies a tensor to the host."""
+    if layout is None:
+        if disparity.ndim == 2:
+            layout = "d"
+        elif disparity.ndim == 3 and int(disparity.shape[2]) in (2, 3):
+            layout = "dxdyv" if int(disparity.shape[2]) == 3 else "dxdy"
+    if layout not in DISPARITY_LAYOUTS:
+        raise ArgumentErr("%s: disparity must be (rows, cols, 3) {dx, dy, valid}, (rows, cols, 2) {dx, dy} or, with layout='dv', "
+                          "{d, valid}, or (rows, cols) {d}" % name)
+    words = _LAYOUT_WORDS[layout]
+    if (disparity.ndim != 2 if words == 1 else (disparity.ndim != 3 or int(disparity.shape[2]) != words)):
+        raise ArgumentErr("%s: layout %r needs %d word(s) per pixel" % (name, layout, words))
+    if int(disparity.shape[0]) <= 0 or int(disparity.shape[1]) <= 0:
+        raise ArgumentErr("%s: empty image" % name)
+    tensor = _is_tensor(disparity)
+    if tensor:
+        if not disparity.is_cuda or disparity.dtype not in (torch.int32, torch.float32):
+            raise ArgumentErr("%s: the disparity must be an int32 or float32 CUDA tensor" % name)
+        d = disparity.contiguous()
+        t = 0 if d.dtype == torch.int32 else 1
+    else:
+        if disparity.dtype not in (np.int32, np.float32):
+            raise ArgumentErr("%s: the disparity must be int32 or float32" % name)
+        d = np.ascontiguousarray(disparity)
+        t = 0 if d.dtype == np.int32 else 1
+    return d, t, DISPARITY_LAYOUTS[layout], int(d.shape[1]), int(d.shape[0]), tensor
+
+
+def _f64(like):
+    return torch.float64 if _is_tensor(like) else np.float64
+
+
+def _triangulate(name, disparity, cam1, cam2, x0, y0, angle_tol, semantics, layout, want_error, want_errvec, stats, ctx):
+    from . import _lib, camera
+    if semantics not in TRIANGULATE_SEMANTICS:
+        raise ArgumentErr("%s: semantics must be 'view' or 'model', not %r" % (name, semantics))
+    d, t, lay, w, h, tensor = _tri_disparity(name, disparity, layout)
+    c1, c2 = camera.descriptor_of(cam1), camera.descriptor_of(cam2)
+    ctx = _ctx_for(d, ctx)
+    xyz = _dm_empty(d, (h, w, 3), _f64(d))
+    err = _dm_empty(d, (h, w), _f64(d)) if want_error else None
+    vec = _dm_empty(d, (h, w, 3), _f64(d)) if want_errvec else None
+    st, st_dev = None, None
+    if stats is not None:
+        if _is_tensor(stats):
+            if not tensor or not stats.is_cuda or stats.dtype != torch.int64 or stats.numel() != 3 or not stats.is_contiguous():
+                raise ArgumentErr("%s: a device stats must be a contiguous int64[3] CUDA tensor, with a CUDA disparity" % name)
+            st = stats.data_ptr()
+        elif tensor:
+            st_dev = torch.empty(3, dtype=torch.int64, device=d.device)
+            st = st_dev.data_ptr()
+        else:
+            st_host = _lib.TriangulateStats()
+            st = ctypes.addressof(st_host)
+    ctx.check(_dm_entry(ctx, "stereo_triangulate", d, tensor)(
+        ctx._h, t, _dm_ptr(d), w, h, 0, int(x0), int(y0), ctypes.byref(c1), ctypes.byref(c2), float(angle_tol),
+        TRIANGULATE_SEMANTICS[semantics] | lay, _dm_ptr(xyz), 0, _dm_ptr(err) if want_error else None, 0,
+        _dm_ptr(vec) if want_errvec else None, 0, st))
+    if stats is not None and not _is_tensor(stats):
+        if tensor:
+            words = st_dev.cpu().numpy()
+            stats[:] = [int(words[0]), float(words[1:2].view(np.float64)[0]), float(words[2:3].view(np.float64)[0])]
+        else:
+            stats[:] = [int(st_host.point_count), float(st_host.max_error), float(st_host.sum_error)]
+    return xyz, err, vec
+
+
+def stereo_triangulate(disparity, cam1, cam2, x0=0, y0=0, error=False, error_vector=False, stats=None, ctx=None, layout=None,
+                       angle_tol=0.0):
+    """vw::stereo::stereo_triangulate(disparity, cam1, cam2) rasterised (StereoView, src/vw/Stereo/StereoView.h:56-130): the
+    (rows, cols, 3) float64 point image; the right pixel of a pair is Vector2(i, j) + Vector2((double)dx, (double)dy).
+    Invalid disparities, pixel pairs with fewer than two rays and nearly parallel rays give (0, 0, 0); points behind a
+    camera are reflected (StereoModel::operator(), src/vw/Stereo/StereoModel.cc:97-147).  cam1, cam2: camera.PinholeModel /
+    camera.CAHVModel.  x0, y0: the image coordinates of pixel (0, 0) of `disparity` (a tile of a larger map).
+    error=True adds the (rows, cols) ray-intersection error norm_2(error vector), error_vector=True the (rows, cols, 3)
+    vector between the closest points; the result is then a tuple (xyz[, error][, error_vector]).  StereoView::error() has
+    no definition behind it in the reference; the error here is StereoModel's.
+    disparity: (rows, cols, 3) {dx, dy, valid}, (rows, cols, 2) {dx, dy}, (rows, cols) {d}, or with layout="dv" a masked
+    scalar (rows, cols, 2) {d, valid}; int32 or float32; numpy in -> numpy out, CUDA tensor in -> CUDA tensors out on the
+    current torch stream.  stats: a list that receives [point_count, max_error, sum_error] (for tensors after one
+    synchronisation), or an int64[3] CUDA tensor that receives the three 8-byte words without any (the last two are
+    float64 bits: stats[1:].view(torch.float64))."""
+    xyz, err, vec = _triangulate("stereo_triangulate", disparity, cam1, cam2, x0, y0, angle_tol, "view", layout, error, error_vector,
+                                 stats, ctx)
+    out = (xyz,) + ((err,) if error else ()) + ((vec,) if error_vector else ())
+    return out[0] if len(out) == 1 else out
+
+
+class StereoModel(object):
+    """vw::stereo::StereoModel(cam1, cam2, angle_tol) for two cameras (src/vw/Stereo/StereoModel.h)."""
+
+    def __init__(self, cam1, cam2, angle_tol=0.0):
+        self.cam1, self.cam2, self.angle_tol = cam1, cam2, float(angle_tol)
+
+    def __call__(self, disparity, x0=0, y0=0, stats=None, ctx=None, layout=None):
+        """StereoModel::operator()(disparity_map, error) (src/vw/Stereo/StereoModel.cc:254-309): (xyz, error).  The right pixel is
+        x + dx with x an int32 and dx a float (a float add, widened afterwards), and a point whose error is not >= 0
+        becomes zero.  stats as in stereo_triangulate: the quantities this overload prints."""
+        xyz, err, _ = _triangulate("StereoModel", disparity, self.cam1, self.cam2, x0, y0, self.angle_tol, "model", layout, True,
+                                   False, stats, ctx)
+        return xyz, err
+
+    def convergence_angle(self, disparity, x0=0, y0=0, semantics="model", ctx=None, layout=None):
+        """StereoModel::convergence_angle (src/vw/Stereo/StereoModel.cc:174-177) for every pixel pair of a disparity map:
+        (rows, cols) float64 acos(dot(ray1, ray2)); 0 at invalid pixels."""
+        from . import camera
+        if semantics not in TRIANGULATE_SEMANTICS:
+            raise ArgumentErr("convergence_angle: semantics must be 'view' or 'model', not %r" % (semantics,))
+        d, t, lay, w, h, tensor = _tri_disparity("convergence_angle", disparity, layout)
+        c1, c2 = camera.descriptor_of(self.cam1), camera.descriptor_of(self.cam2)
+        ctx = _ctx_for(d, ctx)
+        out = _dm_empty(d, (h, w), _f64(d))
+        ctx.check(_dm_entry(ctx, "convergence_angle", d, tensor)(
+            ctx._h, t, _dm_ptr(d), w, h, 0, int(x0), int(y0), ctypes.byref(c1), ctypes.byref(c2),
+            TRIANGULATE_SEMANTICS[semantics] | lay, _dm_ptr(out), 0))
+        return out
+
+
+DBL_MAX = float(np.finfo(np.float64).max)
+
+
+def universe_radius(points, origin, near_radius=0.0, far_radius=DBL_MAX, stats=None, ctx=None, out=None):
+    """per_pixel_filter(points, UniverseRadiusFunc(origin, near_radius, far_radius)) (src/vw/Stereo/StereoView.h:139-222) on a
+    (rows, cols, 3 | 4 | 6) float64 point image (xyz; xyz + error; xyz + error vector): a pixel whose xyz is zero becomes
+    all zero, one whose distance from origin is below a non-zero near_radius or above a non-zero far_radius too.  Negative
+    radii or near_radius > far_radius raise ArgumentErr, as the reference's constructor asserts.  stats (optional list)
+    receives [total_points, rejected_points] (one synchronisation).  out=points filters in place."""
+    tensor = _is_tensor(points)
+    if points.ndim != 3 or int(points.shape[2]) not in (3, 4, 6):
+        raise ArgumentErr("universe_radius: points must be (rows, cols, 3 | 4 | 6)")
+    if tensor:
+        if not points.is_cuda or points.dtype != torch.float64:
+            raise ArgumentErr("universe_radius: the points must be a float64 CUDA tensor")
+        p = points if out is points else points.contiguous()
+    else:
+        if points.dtype != np.float64:
+            raise ArgumentErr("universe_radius: the points must be float64")
+        p = points if out is points else np.ascontiguousarray(points)
+    if out is points:
+        if not (p.is_contiguous() if tensor else p.flags["C_CONTIGUOUS"]):
+            raise ArgumentErr("universe_radius: an image filtered in place must be contiguous")
+        res = p
+    elif out is not None:
+        raise ArgumentErr("universe_radius: out must be None or the points themselves")
+    else:
+        res = _dm_empty(p, tuple(p.shape))
+    h, w, ch = int(p.shape[0]), int(p.shape[1]), int(p.shape[2])
+    if w <= 0 or h <= 0:
+        raise ArgumentErr("universe_radius: empty image")
+    o = np.array(origin, np.float64).reshape(-1)
+    if o.size != 3:
+        raise ArgumentErr("universe_radius: the origin must have three elements")
+    ctx = _ctx_for(p, ctx)
+    st = (ctypes.c_longlong * 2)()
+    ctx.check(_dm_entry(ctx, "universe_radius", p, tensor)(
+        ctx._h, _dm_ptr(p), ch, w, h, 0, o.ctypes.data, float(near_radius), float(far_radius), _dm_ptr(res), 0,
+        st if stats is not None else None))
+    if stats is not None:
+        stats[:] = list(st)
+    return res
+
+
 __all__ = ["affine_subpixel", "bayes_em_subpixel", "corr_eval", "disparity_median_filter", "disparity_neighbor_filter",
            "texture_measure", "texture_preserving_disparity_filter","lk_subpixel", "phase_subpixel", "pyramid_subpixel", "calc_disparity", "calc_disparity_sgm", "cross_corr_consistency_check", "parabola_subpixel", "rm_outliers_using_thresh",
            "disparity_cleanup_using_thresh", "disparity_mask", "disparity_blob_filter", "subdivide_regions", "pyramid_correlate", "pyramid_correlate_batch",
@@ -1187,4 +1356,5 @@ __all__ = ["affine_subpixel", "bayes_em_subpixel", "corr_eval", "disparity_media
            "get_disparity_range", "disparity_range_mask", "transform_disparities", "transform_disparities_subregion",
            "HomographyTransform", "disparity_subsample", "disparity_upsample", "disparity_transform_image",
            "missing_pixel_image", "intersect_mask_and_data",
+           "StereoModel", "stereo_triangulate", "universe_radius",
            "BBox2i", "CostFunctionType"]

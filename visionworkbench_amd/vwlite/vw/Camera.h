@@ -1,0 +1,145 @@
+// vw/Camera.h — the part of vw::camera that triangulation needs: PinholeModel with the null or the Tsai lens distortion
+// (src/vw/Camera/PinholeModel.{h,cc}, LensDistortion.{h,cc}) and CAHVModel (src/vw/Camera/CAHVModel.{h,cc}).  Each model
+// carries the flat camera descriptor of the C ABI (struct vwgpu_camera, include/vwgpu.h), which is what the engine's
+// triangulation kernels read; pixel_to_vector, camera_center and point_to_pixel are host code for single pixels, with the
+// reference's expressions (the rays of whole images are computed on the device, vw/Stereo.h).
+#ifndef VWLITE_CAMERA_H
+#define VWLITE_CAMERA_H
+
+#include <cmath>
+#include <limits>
+#include <memory>
+
+#include "Core.h"
+#include "Math.h"
+#include "vwgpu.h"
+
+namespace vw {
+namespace camera {
+
+namespace detail {
+inline double dot3(const double* a, Vector3 const& b) { return 0.0 + a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+inline double dot3(Vector3 const& a, Vector3 const& b) { return 0.0 + a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+inline Vector3 cross3(Vector3 const& a, Vector3 const& b) {
+  return Vector3(a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]);
+}
+inline Vector3 normalize3(Vector3 const& v) {
+  const double n = std::sqrt(dot3(v, v));
+  return Vector3(v[0] / n, v[1] / n, v[2] / n);
+}
+}  // namespace detail
+
+/// What StereoModel needs of a camera (src/vw/Camera/CameraModel.h).
+class CameraModel {
+public:
+  virtual ~CameraModel() {}
+  virtual Vector2 point_to_pixel(Vector3 const& point) const = 0;
+  virtual Vector3 pixel_to_vector(Vector2 const& pix) const = 0;
+  virtual Vector3 camera_center(Vector2 const& pix = Vector2()) const = 0;
+  /// the descriptor the engine reads
+  vwgpu_camera const& descriptor() const { return m_desc; }
+  static Vector2 invalid_pixel() { return Vector2(-1e8, -1e8); }
+protected:
+  vwgpu_camera m_desc;
+};
+
+/// TsaiLensDistortion (LensDistortion.cc:225-400): parameters k1, k2, p1, p2, k3.
+class TsaiLensDistortion {
+  double m_p[5];
+public:
+  TsaiLensDistortion(double k1, double k2, double p1, double p2, double k3 = 0) { m_p[0] = k1; m_p[1] = k2; m_p[2] = p1; m_p[3] = p2; m_p[4] = k3; }
+  const double* distortion_parameters() const { return m_p; }
+  /// TsaiDistortionNorm (:260-276)
+  Vector2 distort_norm(Vector2 const& P) const {
+    const double x = P[0], y = P[1], k1 = m_p[0], k2 = m_p[1], p1 = m_p[2], p2 = m_p[3], k3 = m_p[4];
+    const double r2 = x * x + y * y;
+    const double rdist = 1.0 + k1 * r2 + k2 * r2 * r2 + k3 * r2 * r2 * r2;
+    return Vector2(x * rdist + (2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)), y * rdist + (p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y));
+  }
+};
+
+/// PinholeModel(center, rotation, fu, fv, cu, cv[, u, v, w][, distortion][, pixel_pitch]) (PinholeModel.h).
+class PinholeModel : public CameraModel {
+  Vector3 m_center;
+  Matrix3x3 m_rotation;
+  Vector3 m_u, m_v, m_w;
+  std::shared_ptr<TsaiLensDistortion> m_distortion;   // null: NullLensDistortion
+  void rebuild() {
+    const double c[3] = {m_center[0], m_center[1], m_center[2]}, u[3] = {m_u[0], m_u[1], m_u[2]}, v[3] = {m_v[0], m_v[1], m_v[2]},
+                 w[3] = {m_w[0], m_w[1], m_w[2]};
+    const double fu = m_desc.fu, fv = m_desc.fv, cu = m_desc.cu, cv = m_desc.cv, pitch = m_desc.pixel_pitch;
+    const int rc = vwgpu_pinhole_camera(c, m_rotation.data(), fu, fv, cu, cv, u, v, w, pitch,
+                                        m_distortion ? VWGPU_DISTORTION_TSAI : VWGPU_DISTORTION_NULL,
+                                        m_distortion ? m_distortion->distortion_parameters() : NULL, &m_desc);
+    VW_ASSERT(rc == VWGPU_OK, ArgumentErr() << "PinholeModel: the coordinate frame u, v, w must be orthonormal.");
+  }
+public:
+  PinholeModel(Vector3 const& center, Matrix3x3 const& rotation, double fu, double fv, double cu, double cv,
+               Vector3 const& u = Vector3(1, 0, 0), Vector3 const& v = Vector3(0, 1, 0), Vector3 const& w = Vector3(0, 0, 1),
+               TsaiLensDistortion const* distortion = NULL, double pixel_pitch = 1.0)
+      : m_center(center), m_rotation(rotation), m_u(u), m_v(v), m_w(w) {
+    if (distortion) m_distortion.reset(new TsaiLensDistortion(*distortion));
+    m_desc.fu = fu; m_desc.fv = fv; m_desc.cu = cu; m_desc.cv = cv; m_desc.pixel_pitch = pixel_pitch;
+    rebuild();
+  }
+  PinholeModel(Vector3 const& center, Matrix3x3 const& rotation, double fu, double fv, double cu, double cv,
+               TsaiLensDistortion const* distortion, double pixel_pitch = 1.0)
+      : PinholeModel(center, rotation, fu, fv, cu, cv, Vector3(1, 0, 0), Vector3(0, 1, 0), Vector3(0, 0, 1), distortion, pixel_pitch) {}
+
+  Vector3 camera_center(Vector2 const& = Vector2()) const { return m_center; }
+
+  /// PinholeModel::pixel_to_vector (PinholeModel.cc:422-430); a Tsai lens is undone by the engine's restated solver on the
+  /// device only, so this host method serves undistorted pinholes (NoImplErr otherwise)
+  Vector3 pixel_to_vector(Vector2 const& pix) const {
+    VW_ASSERT(!m_distortion, NoImplErr() << "PinholeModel::pixel_to_vector: lens distortion is undone on the device only.");
+    const Vector3 p(pix[0] * m_desc.pixel_pitch, pix[1] * m_desc.pixel_pitch, 1);
+    const double* m = m_desc.inv_camera_transform;
+    return detail::normalize3(Vector3(detail::dot3(m, p), detail::dot3(m + 3, p), detail::dot3(m + 6, p)));
+  }
+
+  /// PinholeModel::point_to_pixel without its round-trip check (PinholeModel.cc:370-413): K [uvw R^T | -uvw R^T C]
+  Vector2 point_to_pixel(Vector3 const& point) const {
+    double q[3];
+    const Vector3 uvw[3] = {m_u, m_v, m_w};
+    for (int i = 0; i < 3; ++i) {
+      q[i] = 0;
+      for (int j = 0; j < 3; ++j) {
+        double e = 0;   // (uvw R^T)(i, j)
+        for (int k = 0; k < 3; ++k) e += uvw[i][k] * m_rotation(j, k);
+        q[i] += e * (point[j] - m_center[j]);
+      }
+    }
+    Vector2 pix(q[0] / q[2], q[1] / q[2]);   // normalised; the intrinsics follow
+    if (m_distortion) pix = m_distortion->distort_norm(pix);
+    return Vector2((pix[0] * m_desc.fu + m_desc.cu) / m_desc.pixel_pitch, (pix[1] * m_desc.fv + m_desc.cv) / m_desc.pixel_pitch);
+  }
+};
+
+/// CAHVModel(C, A, H, V) (CAHVModel.h).
+class CAHVModel : public CameraModel {
+public:
+  Vector3 C, A, H, V;
+  CAHVModel(Vector3 const& c, Vector3 const& a, Vector3 const& h, Vector3 const& v) : C(c), A(a), H(h), V(v) {
+    m_desc = vwgpu_camera();
+    m_desc.kind = VWGPU_CAMERA_CAHV;
+    for (int i = 0; i < 3; ++i) { m_desc.center[i] = C[i]; m_desc.A[i] = A[i]; m_desc.H[i] = H[i]; m_desc.V[i] = V[i]; }
+  }
+  /// CAHVModel::point_to_pixel (CAHVModel.cc:167-171)
+  Vector2 point_to_pixel(Vector3 const& point) const {
+    const Vector3 p = point - C;
+    const double dDot = detail::dot3(p, A);
+    return Vector2(detail::dot3(p, H) / dDot, detail::dot3(p, V) / dDot);
+  }
+  /// CAHVModel::pixel_to_vector (CAHVModel.cc:173-185)
+  Vector3 pixel_to_vector(Vector2 const& pix) const {
+    Vector3 vec = detail::normalize3(detail::cross3(Vector3(V[0] - pix[1] * A[0], V[1] - pix[1] * A[1], V[2] - pix[1] * A[2]),
+                                                    Vector3(H[0] - pix[0] * A[0], H[1] - pix[0] * A[1], H[2] - pix[0] * A[2])));
+    if (detail::dot3(detail::cross3(V, H), A) < 0.0) vec = Vector3(vec[0] * -1.0, vec[1] * -1.0, vec[2] * -1.0);
+    return vec;
+  }
+  Vector3 camera_center(Vector2 const& = Vector2()) const { return C; }
+};
+
+}  // namespace camera
+}  // namespace vw
+#endif

@@ -17,6 +17,7 @@ class Vector {
 public:
   Vector() { for (int i = 0; i < N; ++i) m[i] = T(); }
   Vector(T a, T b) { static_assert(N == 2, "2-vector ctor"); m[0] = a; m[1] = b; }
+  Vector(T a, T b, T c) { static_assert(N == 3, "3-vector ctor"); m[0] = a; m[1] = b; m[2] = c; }
   template <class U> Vector(Vector<U, N> const& o) { for (int i = 0; i < N; ++i) m[i] = T(o[i]); }
   T& operator[](int i) { return m[i]; }
   T const& operator[](int i) const { return m[i]; }
@@ -40,6 +41,7 @@ template <class T, int N> std::ostream& operator<<(std::ostream& o, Vector<T, N>
 typedef Vector<int32, 2> Vector2i;
 typedef Vector<float, 2> Vector2f;
 typedef Vector<double, 2> Vector2;
+typedef Vector<double, 3> Vector3;
 
 // Half-open box [min, max).  An empty box reports zero width/height/area (BBox.tcc:156-174).
 class BBox2i {

@@ -23,6 +23,8 @@
 //   get_disparity_range, missing_pixel_image, disparity_range_mask, transform_disparities (both overloads),
 //   DisparityTransform, intersect_mask_and_data, disparity_subsample, disparity_upsample
 //                                src/vw/Stereo/DisparityMap.h:48-87, 255-300, 1016-1057, 1164-1358
+//   StereoModel, StereoView / stereo_triangulate, UniverseRadiusFunc (with the cameras of vw/Camera.h)
+//                                src/vw/Stereo/StereoModel.{h,cc}, StereoView.h
 //   SearchParam, subdivide_regions, calc_seconds_per_op   src/vw/Stereo/Correlation.h:66-122
 //   SemiGlobalMatcher, calc_disparity_sgm                 src/vw/Stereo/SGM.h:75-157,360-375
 // Errors: the C ABI's status codes become the reference's exception types (src/vw/Core/Exception.h:225-253).
@@ -40,6 +42,7 @@
 #include <utility>
 #include <vector>
 
+#include "Camera.h"
 #include "Engine.h"
 #include "Filter.h"
 #include "Image.h"
@@ -1093,6 +1096,155 @@ public:
     if (x < 0 || y < 0 || x >= m_offset_image.cols() || y >= m_offset_image.rows() || !is_valid(m_offset_image(x, y)))
       return Vector2(-1, p.y());
     return Vector2(p.x() + m_offset_image(x, y).child()[0], p.y() + m_offset_image(x, y).child()[1]);
+  }
+};
+
+// ---- Stereo/StereoModel.{h,cc} and Stereo/StereoView.h: triangulation and the universe radius -----------------------
+
+namespace detail {
+// the pixel forms DispHelper accepts (StereoView.h:37-53): channel type and layout of a disparity pixel type
+template <class PixelT> struct disparity_form;
+template <> struct disparity_form<PixelMask<Vector2f>> { enum { type = VWGPU_DISPARITY_F32, layout = VWGPU_DISPARITY_LAYOUT_DXDYV }; };
+template <> struct disparity_form<PixelMask<Vector2i>> { enum { type = VWGPU_DISPARITY_I32, layout = VWGPU_DISPARITY_LAYOUT_DXDYV }; };
+template <> struct disparity_form<Vector2f> { enum { type = VWGPU_DISPARITY_F32, layout = VWGPU_DISPARITY_LAYOUT_DXDY }; };
+template <> struct disparity_form<Vector2i> { enum { type = VWGPU_DISPARITY_I32, layout = VWGPU_DISPARITY_LAYOUT_DXDY }; };
+template <> struct disparity_form<PixelMask<float>> { enum { type = VWGPU_DISPARITY_F32, layout = VWGPU_DISPARITY_LAYOUT_DV }; };
+template <> struct disparity_form<PixelMask<int32>> { enum { type = VWGPU_DISPARITY_I32, layout = VWGPU_DISPARITY_LAYOUT_DV }; };
+template <> struct disparity_form<float> { enum { type = VWGPU_DISPARITY_F32, layout = VWGPU_DISPARITY_LAYOUT_D }; };
+template <> struct disparity_form<int32> { enum { type = VWGPU_DISPARITY_I32, layout = VWGPU_DISPARITY_LAYOUT_D }; };
+static_assert(sizeof(Vector3) == 24 && sizeof(PixelMask<float>) == 8 && sizeof(Vector2f) == 8, "pixel layouts of the triangulation entries");
+}  // namespace detail
+
+/// StereoModel(camera1, camera2, angle_tol) for two cameras (StereoModel.h).  The cameras are vw::camera models of
+/// vw/Camera.h; like the reference, the model keeps pointers to them.
+class StereoModel {
+  camera::CameraModel const* m_cam1;
+  camera::CameraModel const* m_cam2;
+  double m_angle_tol;
+public:
+  StereoModel(camera::CameraModel const* camera_model1, camera::CameraModel const* camera_model2, double angle_tol = 0.0)
+      : m_cam1(camera_model1), m_cam2(camera_model2), m_angle_tol(angle_tol) {}
+  camera::CameraModel const* camera1() const { return m_cam1; }
+  camera::CameraModel const* camera2() const { return m_cam2; }
+  double angle_tol() const { return m_angle_tol; }
+
+  /// One box of a disparity image on the engine: w x h pixels at `disp` whose pixel (0, 0) is image pixel (x0, y0).
+  template <class PixelT>
+  void triangulate(PixelT const* disp, int32 w, int32 h, ptrdiff_t dstride, int32 x0, int32 y0, int semantics, Vector3* xyz, double* error,
+                   vwgpu_triangulate_stats* stats = NULL) const {
+    vwgpu_ctx* ctx = detail::thread_context();
+    detail::check(ctx, vwgpu_stereo_triangulate(ctx, detail::disparity_form<PixelT>::type, disp, w, h, dstride, x0, y0, &m_cam1->descriptor(),
+                                                &m_cam2->descriptor(), m_angle_tol, semantics | detail::disparity_form<PixelT>::layout,
+                                                reinterpret_cast<double*>(xyz), 0, error, 0, NULL, 0, stats));
+  }
+
+  /// operator()(disparity_map, error) (StereoModel.cc:254-309): the point image and the ray-intersection error; the right
+  /// pixel is x + dx with x an int32 and dx a float.  The statistics the reference prints are returned through stats.
+  template <class PixelT>
+  ImageView<Vector3> operator()(ImageView<PixelT> const& disparity_map, ImageView<double>& error,
+                                vwgpu_triangulate_stats* stats = NULL) const {
+    ImageView<Vector3> xyz(disparity_map.cols(), disparity_map.rows());
+    error.set_size(disparity_map.cols(), disparity_map.rows());
+    if (disparity_map.cols() == 0 || disparity_map.rows() == 0) return xyz;
+    triangulate(disparity_map.data(), disparity_map.cols(), disparity_map.rows(), 0, 0, 0, VWGPU_TRIANGULATE_MODEL, xyz.data(), error.data(),
+                stats);
+    return xyz;
+  }
+
+  /// convergence_angle (StereoModel.cc:174-177) for every pixel pair of a disparity image; 0 at invalid pixels.
+  template <class PixelT>
+  ImageView<double> convergence_angle(ImageView<PixelT> const& disparity_map, int semantics = VWGPU_TRIANGULATE_MODEL) const {
+    ImageView<double> out(disparity_map.cols(), disparity_map.rows());
+    if (disparity_map.cols() == 0 || disparity_map.rows() == 0) return out;
+    vwgpu_ctx* ctx = detail::thread_context();
+    detail::check(ctx, vwgpu_convergence_angle(ctx, detail::disparity_form<PixelT>::type, disparity_map.data(), disparity_map.cols(),
+                                               disparity_map.rows(), 0, 0, 0, &m_cam1->descriptor(), &m_cam2->descriptor(),
+                                               semantics | detail::disparity_form<PixelT>::layout, out.data(), 0));
+    return out;
+  }
+};
+
+/// StereoView (StereoView.h:56-123): a lazy ImageView<Vector3>-style view of a disparity image.  rasterize() hands each
+/// box to the engine with the box's origin as x0, y0, so any tiling gives the pixels of the whole image.  error() of the
+/// reference has no definition behind it (StereoModelHelper is declared nowhere); the error of this project is
+/// StereoModel's scalar error, through error_image().
+template <class DisparityImageT>
+class StereoView : public ImageViewBase<StereoView<DisparityImageT>> {
+  typedef typename DisparityImageT::pixel_type dpixel_type;
+  ImageView<dpixel_type> m_disparity_map;
+  StereoModel m_stereo_model;
+public:
+  typedef Vector3 pixel_type;
+  typedef ImageView<Vector3> prerasterize_type;
+  StereoView(DisparityImageT const& disparity_map, camera::CameraModel const* camera_model1, camera::CameraModel const* camera_model2)
+      : m_disparity_map(disparity_map), m_stereo_model(camera_model1, camera_model2) {}
+  StereoView(DisparityImageT const& disparity_map, StereoModel const& stereo_model)
+      : m_disparity_map(disparity_map), m_stereo_model(stereo_model) {}
+  int32 cols() const { return m_disparity_map.cols(); }
+  int32 rows() const { return m_disparity_map.rows(); }
+  int32 planes() const { return 1; }
+  ImageView<dpixel_type> const& disparity_map() const { return m_disparity_map; }
+
+  /// the box as an image of its own
+  ImageView<Vector3> box(BBox2i const& bbox, ImageView<double>* error = NULL) const {
+    ImageView<Vector3> out(bbox.width(), bbox.height());
+    if (error) error->set_size(bbox.width(), bbox.height());
+    if (bbox.empty()) return out;
+    VW_ASSERT(bounding_box(m_disparity_map).contains(bbox), ArgumentErr() << "StereoView: the box leaves the disparity image.");
+    m_stereo_model.triangulate(&m_disparity_map(bbox.min().x(), bbox.min().y()), bbox.width(), bbox.height(), m_disparity_map.cols(),
+                               bbox.min().x(), bbox.min().y(), VWGPU_TRIANGULATE_VIEW, out.data(), error ? error->data() : NULL);
+    return out;
+  }
+  Vector3 operator()(int32 i, int32 j) const { return box(BBox2i(i, j, 1, 1))(0, 0); }
+  ImageView<double> error_image() const {
+    ImageView<double> e;
+    box(bounding_box(m_disparity_map), &e);
+    return e;
+  }
+  prerasterize_type prerasterize(BBox2i const& bbox) const { return box(bbox); }
+  template <class DestT> void rasterize(DestT const& dest, BBox2i const& bbox) const {
+    vw::rasterize(box(bbox), dest, BBox2i(0, 0, bbox.width(), bbox.height()));
+  }
+};
+
+/// stereo_triangulate(disparity, camera1, camera2) (StereoView.h:125-130).
+template <class ImageT>
+StereoView<ImageT> stereo_triangulate(ImageViewBase<ImageT> const& v, camera::CameraModel const* camera1, camera::CameraModel const* camera2) {
+  return StereoView<ImageT>(v.impl(), camera1, camera2);
+}
+
+/// UniverseRadiusFunc (StereoView.h:139-222) applied to a whole point image of Vector<double, 3 | 4 | 6> pixels: the
+/// functor keeps the reference's shared counters, operator() filters an image on the engine.
+class UniverseRadiusFunc {
+  struct UniverseRadiusState { int64 rejected_points, total_points; };
+  Vector3 m_origin;
+  double m_near_radius, m_far_radius;
+  std::shared_ptr<UniverseRadiusState> m_state;
+public:
+  UniverseRadiusFunc(Vector3 universe_origin, double near_radius = 0, double far_radius = std::numeric_limits<double>::max())
+      : m_origin(universe_origin), m_near_radius(near_radius), m_far_radius(far_radius), m_state(new UniverseRadiusState()) {
+    VW_ASSERT(m_near_radius >= 0 && m_far_radius >= 0, ArgumentErr() << "UniverseRadius: radii must be >= 0.");
+    VW_ASSERT(m_near_radius <= m_far_radius, ArgumentErr() << "UniverseRadius: near radius must be <= far radius.");
+    m_state->rejected_points = m_state->total_points = 0;
+  }
+  double near_radius() const { return m_near_radius; }
+  double far_radius() const { return m_far_radius; }
+  int64 rejected_points() const { return m_state->rejected_points; }
+  int64 total_points() const { return m_state->total_points; }
+
+  template <int N>
+  ImageView<Vector<double, N>> operator()(ImageView<Vector<double, N>> const& points) const {
+    static_assert(N == 3 || N == 4 || N == 6, "UniverseRadiusFunc: points, points with error, points with the error vector");
+    ImageView<Vector<double, N>> out(points.cols(), points.rows());
+    if (points.cols() == 0 || points.rows() == 0) return out;
+    const double origin[3] = {m_origin[0], m_origin[1], m_origin[2]};
+    long long counts[2] = {0, 0};
+    vwgpu_ctx* ctx = detail::thread_context();
+    detail::check(ctx, vwgpu_universe_radius(ctx, reinterpret_cast<const double*>(points.data()), N, points.cols(), points.rows(), 0, origin,
+                                             m_near_radius, m_far_radius, reinterpret_cast<double*>(out.data()), 0, counts));
+    m_state->total_points += counts[0];
+    m_state->rejected_points += counts[1];
+    return out;
   }
 };
 

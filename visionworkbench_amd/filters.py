@@ -13,13 +13,8 @@ numpy arrays go through the host entry points, torch CUDA tensors through the de
 import numpy as np
 
 from . import _lib
+from ._operands import Operands
 from .core import ArgumentErr
-from .stereo import _ctx_for, _is_tensor
-
-try:
-    import torch
-except Exception:  # pragma: no cover
-    torch = None
 
 ConstantEdgeExtension, ZeroEdgeExtension = 0, 1
 PREFILTER_NONE, PREFILTER_MEANSUB, PREFILTER_LOG = 0, 1, 2
@@ -37,39 +32,18 @@ def generate_pyramid_smoothing_kernel():
     return np.array([1.0 / 16.0, 4.0 / 16.0, 6.0 / 16.0, 4.0 / 16.0, 1.0 / 16.0], np.float32)
 
 
-def _prep(img, dtype):
-    if _is_tensor(img):
-        if not img.is_cuda:
-            raise ArgumentErr("torch inputs must be CUDA tensors (no CPU path)")
-        if img.stride(-1) != 1:
-            img = img.contiguous()
-        return img
-    return np.ascontiguousarray(img, dtype)
-
-
-def _stream(ctx, img):
-    ctx.set_stream(torch.cuda.current_stream(img.device).cuda_stream)
-
-
 def separable_convolution_filter(src, x_kernel, y_kernel, cx=None, cy=None, edge=ConstantEdgeExtension, subsample=1, ctx=None):
-    src = _prep(src, np.float32)
+    ops = Operands("separable_convolution_filter", src, ctx)
+    src = ops.image(src, np.float32, rows=True)
     xk = np.ascontiguousarray(x_kernel, np.float32)
     yk = np.ascontiguousarray(y_kernel, np.float32)
     cx = ((len(xk) - 1) // 2 if len(xk) else 0) if cx is None else cx
     cy = ((len(yk) - 1) // 2 if len(yk) else 0) if cy is None else cy
     h, w = src.shape
     oh, ow = 1 + (h - 1) // subsample, 1 + (w - 1) // subsample
-    ctx = _ctx_for(src, ctx)
-    lib = ctx._lib
-    if _is_tensor(src):
-        out = torch.empty((oh, ow), dtype=torch.float32, device=src.device)
-        _stream(ctx, src)
-        ctx.check(lib.vwgpu_separable_convolution_dev(ctx._h, src.data_ptr(), w, h, src.stride(0), xk.ctypes.data, len(xk), cx,
-                                                      yk.ctypes.data, len(yk), cy, edge, subsample, out.data_ptr(), 0))
-        return out
-    out = np.empty((oh, ow), np.float32)
-    ctx.check(lib.vwgpu_separable_convolution(ctx._h, src.ctypes.data, w, h, w, xk.ctypes.data, len(xk), cx,
-                                              yk.ctypes.data, len(yk), cy, edge, subsample, out.ctypes.data, 0))
+    out = ops.empty((oh, ow), np.float32)
+    ops.call("separable_convolution", ops.ptr(src), w, h, ops.row_stride(src), xk.ctypes.data, len(xk), cx,
+             yk.ctypes.data, len(yk), cy, edge, subsample, ops.ptr(out), 0)
     return out
 
 
@@ -80,22 +54,15 @@ def gaussian_filter(src, x_sigma, y_sigma=None, x_dim=0, y_dim=0, edge=ConstantE
 
 
 def convolution_filter(src, kernel, ci=None, cj=None, edge=ConstantEdgeExtension, ctx=None):
-    src = _prep(src, np.float32)
+    ops = Operands("convolution_filter", src, ctx)
+    src = ops.image(src, np.float32, rows=True)
     k = np.ascontiguousarray(kernel, np.float32)
     kh, kw = k.shape
     ci = (kw - 1) // 2 if ci is None else ci
     cj = (kh - 1) // 2 if cj is None else cj
     h, w = src.shape
-    ctx = _ctx_for(src, ctx)
-    lib = ctx._lib
-    if _is_tensor(src):
-        out = torch.empty((h, w), dtype=torch.float32, device=src.device)
-        _stream(ctx, src)
-        ctx.check(lib.vwgpu_convolution_2d_dev(ctx._h, src.data_ptr(), w, h, src.stride(0), k.ctypes.data, kw, kh, ci, cj, edge,
-                                               out.data_ptr(), 0))
-        return out
-    out = np.empty((h, w), np.float32)
-    ctx.check(lib.vwgpu_convolution_2d(ctx._h, src.ctypes.data, w, h, w, k.ctypes.data, kw, kh, ci, cj, edge, out.ctypes.data, 0))
+    out = ops.empty((h, w), np.float32)
+    ops.call("convolution_2d", ops.ptr(src), w, h, ops.row_stride(src), k.ctypes.data, kw, kh, ci, cj, edge, ops.ptr(out), 0)
     return out
 
 
@@ -104,37 +71,21 @@ def laplacian_filter(src, edge=ConstantEdgeExtension, ctx=None):
 
 
 def subsample_mask_by_two(mask, ctx=None):
-    mask = _prep(mask, np.uint8)
+    ops = Operands("subsample_mask_by_two", mask, ctx)
+    mask = ops.image(mask, np.uint8, rows=True)
     h, w = mask.shape
-    oh, ow = 1 + (h - 1) // 2, 1 + (w - 1) // 2
-    ctx = _ctx_for(mask, ctx)
-    lib = ctx._lib
-    if _is_tensor(mask):
-        if mask.dtype != torch.uint8:
-            raise ArgumentErr("subsample_mask_by_two: uint8 mask expected")
-        out = torch.empty((oh, ow), dtype=torch.uint8, device=mask.device)
-        _stream(ctx, mask)
-        ctx.check(lib.vwgpu_subsample_mask_by_two_dev(ctx._h, mask.data_ptr(), w, h, mask.stride(0), out.data_ptr(), 0))
-        return out
-    out = np.empty((oh, ow), np.uint8)
-    ctx.check(lib.vwgpu_subsample_mask_by_two(ctx._h, mask.ctypes.data, w, h, w, out.ctypes.data, 0))
+    out = ops.empty((1 + (h - 1) // 2, 1 + (w - 1) // 2), np.uint8)
+    ops.call("subsample_mask_by_two", ops.ptr(mask), w, h, ops.row_stride(mask), ops.ptr(out), 0)
     return out
 
 
 def prefilter_image(image, prefilter_mode, prefilter_width, ctx=None):
-    image = _prep(image, np.float32)
+    ops = Operands("prefilter_image", image, ctx)
+    image = ops.image(image, np.float32, rows=True)
     h, w = image.shape
-    ctx = _ctx_for(image, ctx)
-    lib = ctx._lib
-    if _is_tensor(image):
-        out = torch.empty((h, w), dtype=torch.float32, device=image.device)
-        _stream(ctx, image)
-        ctx.check(lib.vwgpu_prefilter_image_dev(ctx._h, image.data_ptr(), w, h, image.stride(0), int(prefilter_mode),
-                                                float(prefilter_width), out.data_ptr(), 0))
-        return out
-    out = np.empty((h, w), np.float32)
-    ctx.check(lib.vwgpu_prefilter_image(ctx._h, image.ctypes.data, w, h, w, int(prefilter_mode), float(prefilter_width),
-                                        out.ctypes.data, 0))
+    out = ops.empty((h, w), np.float32)
+    ops.call("prefilter_image", ops.ptr(image), w, h, ops.row_stride(image), int(prefilter_mode), float(prefilter_width),
+             ops.ptr(out), 0)
     return out
 
 

@@ -10,24 +10,9 @@ import ctypes
 
 import numpy as np
 
-from . import core
+from . import _lib, camera, core
+from ._operands import Operands, is_tensor as _is_tensor, new_stats, put_stats
 from .core import ArgumentErr, BBox2i, CostFunctionType
-
-try:  # torch is plumbing (device memory, streams); the host-pointer path works without it
-    import torch
-except Exception:  # pragma: no cover
-    torch = None
-
-
-def _is_tensor(x):
-    return torch is not None and isinstance(x, torch.Tensor)
-
-
-def _ctx_for(x, ctx):
-    if ctx is not None:
-        return ctx
-    dev = x.device.index if _is_tensor(x) and x.is_cuda else 0
-    return core.default_context(dev or 0)
 
 
 def calc_disparity(cost_type, left_in, right_in, left_region, search_volume, kernel_size, ctx=None):
@@ -55,32 +40,14 @@ def calc_disparity(cost_type, left_in, right_in, left_region, search_volume, ker
     if rx1 > right_in.shape[1] or ry1 > right_in.shape[0]:
         raise ArgumentErr("calc_disparity: right image does not cover the search region")
     lw, lh = x1 - x0, y1 - y0
-    ctx = _ctx_for(left_in, ctx)
-    lib = ctx._lib
     ow, oh = lw - kx + 1, lh - ky + 1
-    if _is_tensor(left_in):
-        if not (left_in.is_cuda and right_in.is_cuda):
-            raise ArgumentErr("calc_disparity: torch inputs must be CUDA tensors (no CPU path)")
-        if left_in.dtype != torch.float32 or right_in.dtype != torch.float32:
-            raise ArgumentErr("calc_disparity: images must be float32")
-        if left_in.stride(1) != 1 or right_in.stride(1) != 1:
-            left_in, right_in = left_in.contiguous(), right_in.contiguous()
-        l = left_in[y0:y1, x0:x1]
-        r = right_in[y0:ry1, x0:rx1]
-        out = torch.empty((max(oh, 0), max(ow, 0), 3), dtype=torch.int32, device=left_in.device)
-        ctx.set_stream(torch.cuda.current_stream(left_in.device).cuda_stream)
-        rc = lib.vwgpu_calc_disparity_dev(ctx._h, int(cost_type), l.data_ptr(), lw, lh, l.stride(0),
-                                          r.data_ptr(), rx1 - x0, ry1 - y0, r.stride(0),
-                                          kx, ky, sx, sy, out.data_ptr(), 0)
-        ctx.check(rc)
-        return out
-    l = np.ascontiguousarray(left_in[y0:y1, x0:x1], np.float32)
-    r = np.ascontiguousarray(right_in[y0:ry1, x0:rx1], np.float32)
-    out = np.empty((max(oh, 0), max(ow, 0), 3), np.int32)
-    rc = lib.vwgpu_calc_disparity(ctx._h, int(cost_type), l.ctypes.data, lw, lh, lw,
-                                  r.ctypes.data, r.shape[1], r.shape[0], r.shape[1],
-                                  kx, ky, sx, sy, out.ctypes.data, 0)
-    ctx.check(rc)
+    ops = Operands("calc_disparity", left_in, ctx)
+    # the crops stay views of a tensor (row stride = the whole image's); a numpy crop is copied for the host entry
+    l = ops.image(left_in[y0:y1, x0:x1], np.float32, rows=True)
+    r = ops.image(right_in[y0:ry1, x0:rx1], np.float32, rows=True)
+    out = ops.empty((max(oh, 0), max(ow, 0), 3), np.int32)
+    ops.call("calc_disparity", int(cost_type), ops.ptr(l), lw, lh, ops.row_stride(l),
+             ops.ptr(r), rx1 - x0, ry1 - y0, ops.row_stride(r), kx, ky, sx, sy, ops.ptr(out), 0)
     return out
 
 
@@ -91,20 +58,10 @@ def fast_box_sum(image, kernel, ctx=None):
     if image.ndim != 2:
         raise ArgumentErr("fast_box_sum: the image must be 2-D (rows, cols)")
     h, w = image.shape
-    ctx = _ctx_for(image, ctx)
-    lib = ctx._lib
-    if _is_tensor(image):
-        if not image.is_cuda or image.dtype != torch.float32:
-            raise ArgumentErr("fast_box_sum: torch input must be a float32 CUDA tensor (no CPU path)")
-        if image.stride(1) != 1:
-            image = image.contiguous()
-        out = torch.empty((max(h - ky + 1, 0), max(w - kx + 1, 0)), dtype=torch.float64, device=image.device)
-        ctx.set_stream(torch.cuda.current_stream(image.device).cuda_stream)
-        ctx.check(lib.vwgpu_fast_box_sum_dev(ctx._h, image.data_ptr(), w, h, image.stride(0), kx, ky, out.data_ptr(), 0))
-        return out
-    img = np.ascontiguousarray(image, np.float32)
-    out = np.empty((max(h - ky + 1, 0), max(w - kx + 1, 0)), np.float64)
-    ctx.check(lib.vwgpu_fast_box_sum(ctx._h, img.ctypes.data, w, h, w, kx, ky, out.ctypes.data, 0))
+    ops = Operands("fast_box_sum", image, ctx)
+    img = ops.image(image, np.float32, rows=True)
+    out = ops.empty((max(h - ky + 1, 0), max(w - kx + 1, 0)), np.float64)
+    ops.call("fast_box_sum", ops.ptr(img), w, h, ops.row_stride(img), kx, ky, ops.ptr(out), 0)
     return out
 
 
@@ -113,45 +70,18 @@ def cross_corr_consistency_check(l2r, r2l, cross_corr_threshold, lr_disp_diff=No
 
     l2r, r2l: (rows, cols, 3) int32 PixelMask<Vector2i> images.  lr_disp_diff (optional, modified in place): (rows, cols, 2)
     float32 PixelMask<float> {value, valid}; every kept pixel stores its discrepancy at (c, r) + ul_corner_offset."""
-    ctx = _ctx_for(l2r, ctx)
-    lib = ctx._lib
-    if lr_disp_diff is not None:
-        ux, uy = int(ul_corner_offset[0]), int(ul_corner_offset[1])
-        if lr_disp_diff.ndim != 3 or lr_disp_diff.shape[2] != 2:
-            raise ArgumentErr("cross_corr_consistency_check: lr_disp_diff must be (rows, cols, 2) float32")
-        dr, dc = lr_disp_diff.shape[:2]
-        if _is_tensor(l2r):
-            if not (l2r.is_cuda and r2l.is_cuda and lr_disp_diff.is_cuda and l2r.is_contiguous() and r2l.is_contiguous()
-                    and lr_disp_diff.is_contiguous() and lr_disp_diff.dtype == torch.float32):
-                raise ArgumentErr("cross_corr_consistency_check: contiguous CUDA tensors required")
-            ctx.set_stream(torch.cuda.current_stream(l2r.device).cuda_stream)
-            ctx.check(lib.vwgpu_cross_corr_consistency_check_diff_dev(ctx._h, l2r.data_ptr(), l2r.shape[1], l2r.shape[0], 0, r2l.data_ptr(),
-                                                                      r2l.shape[1], r2l.shape[0], 0, float(cross_corr_threshold),
-                                                                      lr_disp_diff.data_ptr(), dc, dr, 0, ux, uy))
-            return l2r
-        if not (l2r.flags.c_contiguous and l2r.dtype == np.int32 and lr_disp_diff.flags.c_contiguous and lr_disp_diff.dtype == np.float32):
-            raise ArgumentErr("cross_corr_consistency_check: contiguous int32 / float32 arrays required (modified in place)")
-        r2l = np.ascontiguousarray(r2l, np.int32)
-        ctx.check(lib.vwgpu_cross_corr_consistency_check_diff(ctx._h, l2r.ctypes.data, l2r.shape[1], l2r.shape[0], 0, r2l.ctypes.data,
-                                                              r2l.shape[1], r2l.shape[0], 0, float(cross_corr_threshold),
-                                                              lr_disp_diff.ctypes.data, dc, dr, 0, ux, uy))
-        return l2r
-    if _is_tensor(l2r):
-        if not (l2r.is_cuda and r2l.is_cuda and l2r.is_contiguous() and r2l.is_contiguous()):
-            raise ArgumentErr("cross_corr_consistency_check: contiguous CUDA tensors required")
-        ctx.set_stream(torch.cuda.current_stream(l2r.device).cuda_stream)
-        rc = lib.vwgpu_cross_corr_consistency_check_dev(ctx._h, l2r.data_ptr(), l2r.shape[1], l2r.shape[0], 0,
-                                                        r2l.data_ptr(), r2l.shape[1], r2l.shape[0], 0,
-                                                        float(cross_corr_threshold))
-        ctx.check(rc)
-        return l2r
-    if not (l2r.flags.c_contiguous and l2r.dtype == np.int32):
-        raise ArgumentErr("cross_corr_consistency_check: l2r must be a contiguous int32 array (modified in place)")
-    r2l = np.ascontiguousarray(r2l, np.int32)
-    rc = lib.vwgpu_cross_corr_consistency_check(ctx._h, l2r.ctypes.data, l2r.shape[1], l2r.shape[0], 0,
-                                                r2l.ctypes.data, r2l.shape[1], r2l.shape[0], 0,
-                                                float(cross_corr_threshold))
-    ctx.check(rc)
+    ops = Operands("cross_corr_consistency_check", l2r, ctx)
+    if lr_disp_diff is not None and (lr_disp_diff.ndim != 3 or lr_disp_diff.shape[2] != 2):
+        raise ArgumentErr("cross_corr_consistency_check: lr_disp_diff must be (rows, cols, 2) float32")
+    ops.image(l2r, np.int32, in_place=True)
+    diff = ops.image(lr_disp_diff, np.float32, in_place=True)
+    r2l = ops.image(r2l, np.int32)
+    args = (ops.ptr(l2r), l2r.shape[1], l2r.shape[0], 0, ops.ptr(r2l), r2l.shape[1], r2l.shape[0], 0, float(cross_corr_threshold))
+    if diff is None:
+        ops.call("cross_corr_consistency_check", *args)
+    else:
+        ops.call("cross_corr_consistency_check_diff", *args, ops.ptr(diff), diff.shape[1], diff.shape[0], 0,
+                 int(ul_corner_offset[0]), int(ul_corner_offset[1]))
     return l2r
 
 
@@ -165,23 +95,11 @@ def parabola_subpixel(disparity, left_image, right_image, prefilter_mode, prefil
         raise ArgumentErr("SubpixelView: Disparity image must match left image.")
     h, w = left_image.shape
     rh, rw = right_image.shape
-    ctx = _ctx_for(left_image, ctx)
-    lib = ctx._lib
-    if _is_tensor(left_image):
-        d, l, r = disparity.contiguous(), left_image.contiguous(), right_image.contiguous()
-        if not (d.is_cuda and l.is_cuda and r.is_cuda) or d.dtype != torch.float32:
-            raise ArgumentErr("parabola_subpixel: float32 CUDA tensors required")
-        out = torch.empty_like(d)
-        ctx.set_stream(torch.cuda.current_stream(l.device).cuda_stream)
-        ctx.check(lib.vwgpu_parabola_subpixel_dev(ctx._h, d.data_ptr(), w, h, 0, l.data_ptr(), 0, r.data_ptr(), rw, rh, 0,
-                                                  int(prefilter_mode), float(prefilter_width), kx, ky, out.data_ptr(), 0))
-        return out
-    d = np.ascontiguousarray(disparity, np.float32)
-    l = np.ascontiguousarray(left_image, np.float32)
-    r = np.ascontiguousarray(right_image, np.float32)
-    out = np.empty_like(d)
-    ctx.check(lib.vwgpu_parabola_subpixel(ctx._h, d.ctypes.data, w, h, 0, l.ctypes.data, 0, r.ctypes.data, rw, rh, 0,
-                                          int(prefilter_mode), float(prefilter_width), kx, ky, out.ctypes.data, 0))
+    ops = Operands("parabola_subpixel", left_image, ctx)
+    d, l, r = (ops.image(x, np.float32) for x in (disparity, left_image, right_image))
+    out = ops.empty(d.shape, np.float32)
+    ops.call("parabola_subpixel", ops.ptr(d), w, h, 0, ops.ptr(l), 0, ops.ptr(r), rw, rh, 0,
+             int(prefilter_mode), float(prefilter_width), kx, ky, ops.ptr(out), 0)
     return out
 
 
@@ -217,29 +135,13 @@ def _pyramid_subpixel(name, disparity, left, right, prefilter_mode, prefilter_wi
     h, w = left.shape
     rh, rw = right.shape
     tiles = subpixel_tiles(w, h, block_size)
-    st = (ctypes.c_longlong * 3)()
-    ctx = _ctx_for(left, ctx)
-    lib = ctx._lib
-    if _is_tensor(left):
-        d, l, r = disparity.contiguous(), left.contiguous(), right.contiguous()
-        if not (d.is_cuda and l.is_cuda and r.is_cuda) or d.dtype != torch.float32 or l.dtype != torch.float32 \
-                or r.dtype != torch.float32:
-            raise ArgumentErr("%s: float32 CUDA tensors required" % name)
-        out = torch.zeros_like(d)
-        ctx.set_stream(torch.cuda.current_stream(l.device).cuda_stream)
-        ctx.check(getattr(lib, "vwgpu_%s_dev" % entry)(ctx._h, d.data_ptr(), w, h, 0, l.data_ptr(), 0, r.data_ptr(), rw, rh, 0,
-                                                 int(prefilter_mode), float(prefilter_width), kx, ky, int(max_pyramid_levels),
-                                                 selector, tiles.ctypes.data, len(tiles), out.data_ptr(), 0, st))
-    else:
-        d = np.ascontiguousarray(disparity, np.float32)
-        l = np.ascontiguousarray(left, np.float32)
-        r = np.ascontiguousarray(right, np.float32)
-        out = np.zeros_like(d)
-        ctx.check(getattr(lib, "vwgpu_" + entry)(ctx._h, d.ctypes.data, w, h, 0, l.ctypes.data, 0, r.ctypes.data, rw, rh, 0,
-                                             int(prefilter_mode), float(prefilter_width), kx, ky, int(max_pyramid_levels),
-                                             selector, tiles.ctypes.data, len(tiles), out.ctypes.data, 0, st))
-    if stats is not None:
-        stats[:] = list(st)
+    st = new_stats(3)
+    ops = Operands(name, left, ctx)
+    d, l, r = (ops.image(x, np.float32) for x in (disparity, left, right))
+    out = ops.zeros(d.shape, np.float32)     # pixels outside every tile stay 0
+    ops.call(entry, ops.ptr(d), w, h, 0, ops.ptr(l), 0, ops.ptr(r), rw, rh, 0, int(prefilter_mode), float(prefilter_width),
+             kx, ky, int(max_pyramid_levels), selector, tiles.ctypes.data, len(tiles), ops.ptr(out), 0, st)
+    put_stats(stats, st)
     return out
 
 
@@ -343,41 +245,16 @@ def corr_eval(left, right, disparity, kernel_size, metric, sample_rate=1, round_
     h, w = left.shape
     rh, rw = right.shape
     tiles = subpixel_tiles(w, h, block_size)
-    st = (ctypes.c_longlong * 4)()
-    if _is_tensor(left):
-        # every operand, the masks included, must live on the left image's device: the kernels read them all
-        operands = [(disparity, True), (left, True), (right, True), (left_valid, False), (right_valid, False)]
-        for x, is_float in operands:
-            if x is not None and (not _is_tensor(x) or not x.is_cuda or x.device != left.device
-                                  or (is_float and x.dtype != torch.float32)):
-                raise ArgumentErr("corr_eval: float32 images and disparity, and masks, as CUDA tensors on %s" % left.device)
-    elif any(_is_tensor(x) for x in (disparity, right, left_valid, right_valid)):
-        raise ArgumentErr("corr_eval: with a numpy left image every operand must be a numpy array")
-    ctx = _ctx_for(left, ctx)
-    lib = ctx._lib
-    args = (CORR_EVAL_METRICS[metric], int(sample_rate), 1 if round_to_int else 0, int(prefilter_mode),
-            float(prefilter_kernel_width), tiles.ctypes.data, len(tiles))
-    if _is_tensor(left):
-        d, l, r = disparity.contiguous(), left.contiguous(), right.contiguous()
-        lv = None if left_valid is None else (left_valid != 0).to(torch.uint8).contiguous()
-        rv = None if right_valid is None else (right_valid != 0).to(torch.uint8).contiguous()
-        out = torch.zeros((h, w, 2), dtype=torch.float32, device=l.device)
-        ctx.set_stream(torch.cuda.current_stream(l.device).cuda_stream)
-        ctx.check(lib.vwgpu_corr_eval_dev(ctx._h, d.data_ptr(), w, h, 0, l.data_ptr(), None if lv is None else lv.data_ptr(), 0,
-                                          r.data_ptr(), None if rv is None else rv.data_ptr(), rw, rh, 0, kx, ky, *args,
-                                          out.data_ptr(), 0, st))
-    else:
-        d = np.ascontiguousarray(disparity, np.float32)
-        l = np.ascontiguousarray(left, np.float32)
-        r = np.ascontiguousarray(right, np.float32)
-        lv = None if left_valid is None else np.ascontiguousarray(np.asarray(left_valid) != 0, np.uint8)
-        rv = None if right_valid is None else np.ascontiguousarray(np.asarray(right_valid) != 0, np.uint8)
-        out = np.zeros((h, w, 2), np.float32)
-        ctx.check(lib.vwgpu_corr_eval(ctx._h, d.ctypes.data, w, h, 0, l.ctypes.data, None if lv is None else lv.ctypes.data, 0,
-                                      r.ctypes.data, None if rv is None else rv.ctypes.data, rw, rh, 0, kx, ky, *args,
-                                      out.ctypes.data, 0, st))
-    if stats is not None:
-        stats[:] = list(st)
+    st = new_stats(4)
+    ops = Operands("corr_eval", left, ctx)
+    # every operand, the masks included, must live on the left image's device: the kernels read them all
+    d, l, r = (ops.image(x, np.float32, same_device=True) for x in (disparity, left, right))
+    lv, rv = (ops.nonzero_u8(x, same_device=True) for x in (left_valid, right_valid))
+    out = ops.zeros((h, w, 2), np.float32)     # pixels outside every tile stay 0
+    ops.call("corr_eval", ops.ptr(d), w, h, 0, ops.ptr(l), ops.ptr(lv), 0, ops.ptr(r), ops.ptr(rv), rw, rh, 0, kx, ky,
+             CORR_EVAL_METRICS[metric], int(sample_rate), 1 if round_to_int else 0, int(prefilter_mode),
+             float(prefilter_kernel_width), tiles.ctypes.data, len(tiles), ops.ptr(out), 0, st)
+    put_stats(stats, st)
     return out
 
 
@@ -387,21 +264,10 @@ def _filter_call(name, disparity, hh, hv, pthr, rthr, cleanup, ctx):
     h, w = disparity.shape[:2]
     if hh <= 0 or hv <= 0:
         raise ArgumentErr("RmOutliersFunc: half kernel sizes must be non-zero.")
-    ctx = _ctx_for(disparity, ctx)
-    lib = ctx._lib
-    if _is_tensor(disparity):
-        if not disparity.is_cuda or disparity.dtype != torch.int32:
-            raise ArgumentErr("%s: int32 CUDA tensor required" % name)
-        d = disparity.contiguous()
-        out = torch.empty_like(d)
-        ctx.set_stream(torch.cuda.current_stream(d.device).cuda_stream)
-        ctx.check(lib.vwgpu_disparity_filter_dev(ctx._h, d.data_ptr(), w, h, int(hh), int(hv), float(pthr), float(rthr),
-                                                 int(cleanup), out.data_ptr()))
-        return out
-    d = np.ascontiguousarray(disparity, np.int32)
-    out = np.empty_like(d)
-    ctx.check(lib.vwgpu_disparity_filter(ctx._h, d.ctypes.data, w, h, int(hh), int(hv), float(pthr), float(rthr),
-                                         int(cleanup), out.ctypes.data))
+    ops = Operands(name, disparity, ctx)
+    d = ops.image(disparity, np.int32)
+    out = ops.empty(d.shape, np.int32)
+    ops.call("disparity_filter", ops.ptr(d), w, h, int(hh), int(hv), float(pthr), float(rthr), int(cleanup), ops.ptr(out))
     return out
 
 
@@ -426,20 +292,10 @@ def disparity_mask(disparity, left_mask, right_mask, ctx=None):
         raise ArgumentErr("disparity_mask: left mask must match the disparity image")
     h, w = left_mask.shape
     rmh, rmw = right_mask.shape
-    ctx = _ctx_for(disparity, ctx)
-    lib = ctx._lib
-    if _is_tensor(disparity):
-        if not (disparity.is_cuda and left_mask.is_cuda and right_mask.is_cuda) or disparity.dtype != torch.int32:
-            raise ArgumentErr("disparity_mask: int32 / uint8 CUDA tensors required")
-        out = disparity.contiguous().clone()
-        m1, m2 = left_mask.contiguous(), right_mask.contiguous()
-        ctx.set_stream(torch.cuda.current_stream(out.device).cuda_stream)
-        ctx.check(lib.vwgpu_disparity_mask_dev(ctx._h, out.data_ptr(), w, h, m1.data_ptr(), m2.data_ptr(), rmw, rmh))
-        return out
-    out = np.array(disparity, np.int32, order="C", copy=True)
-    m1 = np.ascontiguousarray(left_mask, np.uint8)
-    m2 = np.ascontiguousarray(right_mask, np.uint8)
-    ctx.check(lib.vwgpu_disparity_mask(ctx._h, out.ctypes.data, w, h, m1.ctypes.data, m2.ctypes.data, rmw, rmh))
+    ops = Operands("disparity_mask", disparity, ctx)
+    m1, m2 = ops.image(left_mask, np.uint8), ops.image(right_mask, np.uint8)
+    out = ops.copy_of(disparity, np.int32)
+    ops.call("disparity_mask", ops.ptr(out), w, h, ops.ptr(m1), ops.ptr(m2), rmw, rmh)
     return out
 
 
@@ -449,17 +305,9 @@ def disparity_blob_filter(disparity, max_blob_area, ctx=None):
     if disparity.ndim != 3 or disparity.shape[2] != 3:
         raise ArgumentErr("disparity_blob_filter: disparity must be (rows, cols, 3) int32")
     h, w = disparity.shape[:2]
-    ctx = _ctx_for(disparity, ctx)
-    lib = ctx._lib
-    if _is_tensor(disparity):
-        if not disparity.is_cuda or disparity.dtype != torch.int32:
-            raise ArgumentErr("disparity_blob_filter: int32 CUDA tensor required")
-        out = disparity.contiguous().clone()
-        ctx.set_stream(torch.cuda.current_stream(out.device).cuda_stream)
-        ctx.check(lib.vwgpu_disparity_blob_filter_dev(ctx._h, out.data_ptr(), w, h, int(max_blob_area)))
-        return out
-    out = np.array(disparity, np.int32, order="C", copy=True)
-    ctx.check(lib.vwgpu_disparity_blob_filter(ctx._h, out.ctypes.data, w, h, int(max_blob_area)))
+    ops = Operands("disparity_blob_filter", disparity, ctx)
+    out = ops.copy_of(disparity, np.int32)
+    ops.call("disparity_blob_filter", ops.ptr(out), w, h, int(max_blob_area))
     return out
 
 
@@ -467,7 +315,6 @@ def subdivide_regions(disparity, kernel_size):
     """vw::stereo::subdivide_regions(disparity, bounding_box(disparity), list, kernel_size)
     (src/vw/Stereo/Correlation.cc:139-328).  Host logic (the zone scheduler of pyramid_correlate) on a numpy
     PixelMask<Vector2i> image; returns [(region BBox2i, disparity_range BBox2i), ...] in the reference's order."""
-    from . import _lib
     lib = _lib.load()
     d = np.ascontiguousarray(disparity, np.int32)
     if d.ndim != 3 or d.shape[2] != 3:
@@ -483,6 +330,34 @@ def subdivide_regions(disparity, kernel_size):
             break
         cap = n
     return [(BBox2i.from_corners(z[0:2], z[2:4]), BBox2i.from_corners(z[4:6], z[6:8])) for z in buf[:n].tolist()]
+
+
+def _pyramid_params(prefilter_mode, prefilter_width, search_region, kernel_size, cost_type, corr_timeout, seconds_per_op,
+                    consistency_threshold, min_consistency_level, filter_half_kernel, max_pyramid_levels, algorithm,
+                    blob_filter_area, sgm_subpixel_mode, sgm_search_buffer, memory_limit_mb, sgm_num_threads, region_ul=(0, 0)):
+    """struct vwgpu_pyramid_params, without an lr_disp_diff image."""
+    return _lib.PyramidParams(
+        int(prefilter_mode), float(prefilter_width),
+        int(search_region.min[0]), int(search_region.min[1]), int(search_region.max[0]), int(search_region.max[1]),
+        int(kernel_size[0]), int(kernel_size[1]), int(cost_type), int(corr_timeout), float(seconds_per_op),
+        float(consistency_threshold), int(min_consistency_level), int(filter_half_kernel),
+        int(max_pyramid_levels), int(algorithm), int(blob_filter_area), int(sgm_subpixel_mode),
+        int(sgm_search_buffer[0]), int(sgm_search_buffer[1]), int(memory_limit_mb), int(sgm_num_threads),
+        None, 0, 0, 0, int(region_ul[0]), int(region_ul[1]))
+
+
+def _masks(ops, left_mask, right_mask):
+    """The optional uint8 masks of an image pair (None = every pixel valid)."""
+    return ops.image(left_mask, np.uint8), ops.image(right_mask, np.uint8)
+
+
+def _pyramid_images(ops, left, right, left_mask, right_mask):
+    l, r = ops.image(left, np.float32), ops.image(right, np.float32)
+    lm, rm = _masks(ops, left_mask, right_mask)
+    for m, shp in ((lm, l.shape), (rm, r.shape)):
+        if m is not None and tuple(m.shape) != tuple(shp):
+            raise ArgumentErr("pyramid_correlate: masks must have the image size")
+    return l, r, lm, rm
 
 
 def pyramid_correlate(left, right, left_mask, right_mask, prefilter_mode, prefilter_width, search_region, kernel_size,
@@ -503,7 +378,6 @@ def pyramid_correlate(left, right, left_mask, right_mask, prefilter_mode, prefil
     lr_disp_diff (optional, modified in place): (rows, cols, 2) float32 PixelMask<float> image covering the image pixels from
     region_ul on; the level-0 consistency check stores the L-R / R-L discrepancy of the pixels it keeps there and pixels
     the filters remove are invalidated again (CorrelationView.h:84, .cc:277-283, 683-693, 846-855)."""
-    from ._lib import PyramidParams
     if left.ndim != 2 or right.ndim != 2:
         raise ArgumentErr("pyramid_correlate: images must be 2-D (rows, cols)")
     lh, lw = left.shape
@@ -511,55 +385,20 @@ def pyramid_correlate(left, right, left_mask, right_mask, prefilter_mode, prefil
     if bbox is None:
         bbox = BBox2i(0, 0, lw, lh)
     (bx, by), (bx1, by1) = bbox.min, bbox.max
-    P = PyramidParams(int(prefilter_mode), float(prefilter_width),
-                      int(search_region.min[0]), int(search_region.min[1]), int(search_region.max[0]), int(search_region.max[1]),
-                      int(kernel_size[0]), int(kernel_size[1]), int(cost_type), int(corr_timeout), float(seconds_per_op),
-                      float(consistency_threshold), int(min_consistency_level), int(filter_half_kernel),
-                      int(max_pyramid_levels), int(algorithm), int(blob_filter_area), int(sgm_subpixel_mode),
-                      int(sgm_search_buffer[0]), int(sgm_search_buffer[1]), int(memory_limit_mb), int(sgm_num_threads),
-                      None, 0, 0, 0, int(region_ul[0]), int(region_ul[1]))
+    P = _pyramid_params(prefilter_mode, prefilter_width, search_region, kernel_size, cost_type, corr_timeout, seconds_per_op,
+                        consistency_threshold, min_consistency_level, filter_half_kernel, max_pyramid_levels, algorithm,
+                        blob_filter_area, sgm_subpixel_mode, sgm_search_buffer, memory_limit_mb, sgm_num_threads, region_ul)
+    ops = Operands("pyramid_correlate", left, ctx)
     if lr_disp_diff is not None:
         if lr_disp_diff.ndim != 3 or lr_disp_diff.shape[2] != 2:
             raise ArgumentErr("pyramid_correlate: lr_disp_diff must be (rows, cols, 2) float32")
-        if _is_tensor(lr_disp_diff) != _is_tensor(left):
-            raise ArgumentErr("pyramid_correlate: lr_disp_diff must live where the images live")
-        ok = (lr_disp_diff.is_cuda and lr_disp_diff.is_contiguous() and lr_disp_diff.dtype == torch.float32) if _is_tensor(lr_disp_diff) \
-            else (lr_disp_diff.flags.c_contiguous and lr_disp_diff.dtype == np.float32)
-        if not ok:
-            raise ArgumentErr("pyramid_correlate: lr_disp_diff must be contiguous float32")
-        P.lr_disp_diff = lr_disp_diff.data_ptr() if _is_tensor(lr_disp_diff) else lr_disp_diff.ctypes.data
+        P.lr_disp_diff = ops.ptr(ops.image(lr_disp_diff, np.float32, in_place=True))
         P.lr_disp_diff_rows, P.lr_disp_diff_cols = int(lr_disp_diff.shape[0]), int(lr_disp_diff.shape[1])
-    ctx = _ctx_for(left, ctx)
-    lib = ctx._lib
     bw, bh = bx1 - bx, by1 - by
-    if _is_tensor(left):
-        if not (left.is_cuda and right.is_cuda) or left.dtype != torch.float32 or right.dtype != torch.float32:
-            raise ArgumentErr("pyramid_correlate: float32 CUDA tensors required (no CPU path)")
-        l, r = left.contiguous(), right.contiguous()
-        lm = left_mask.contiguous() if left_mask is not None else None
-        rm = right_mask.contiguous() if right_mask is not None else None
-        for m, shp in ((lm, l.shape), (rm, r.shape)):
-            if m is not None and (m.dtype != torch.uint8 or tuple(m.shape) != tuple(shp) or not m.is_cuda):
-                raise ArgumentErr("pyramid_correlate: masks must be uint8 CUDA tensors of the image size")
-        out = torch.empty((max(bh, 0), max(bw, 0), 3), dtype=torch.float32, device=l.device)
-        ctx.set_stream(torch.cuda.current_stream(l.device).cuda_stream)
-        ctx.check(lib.vwgpu_pyramid_correlate_dev(ctx._h, l.data_ptr(), lw, lh, 0, r.data_ptr(), rw, rh, 0,
-                                                  lm.data_ptr() if lm is not None else None, 0,
-                                                  rm.data_ptr() if rm is not None else None, 0,
-                                                  ctypes.byref(P), bx, by, bw, bh, out.data_ptr(), 0))
-        return out
-    l = np.ascontiguousarray(left, np.float32)
-    r = np.ascontiguousarray(right, np.float32)
-    lm = np.ascontiguousarray(left_mask, np.uint8) if left_mask is not None else None
-    rm = np.ascontiguousarray(right_mask, np.uint8) if right_mask is not None else None
-    for m, shp in ((lm, l.shape), (rm, r.shape)):
-        if m is not None and tuple(m.shape) != tuple(shp):
-            raise ArgumentErr("pyramid_correlate: masks must have the image size")
-    out = np.empty((max(bh, 0), max(bw, 0), 3), np.float32)
-    ctx.check(lib.vwgpu_pyramid_correlate(ctx._h, l.ctypes.data, lw, lh, 0, r.ctypes.data, rw, rh, 0,
-                                          lm.ctypes.data if lm is not None else None, 0,
-                                          rm.ctypes.data if rm is not None else None, 0,
-                                          ctypes.byref(P), bx, by, bw, bh, out.ctypes.data, 0))
+    l, r, lm, rm = _pyramid_images(ops, left, right, left_mask, right_mask)
+    out = ops.empty((max(bh, 0), max(bw, 0), 3), np.float32)
+    ops.call("pyramid_correlate", ops.ptr(l), lw, lh, 0, ops.ptr(r), rw, rh, 0, ops.ptr(lm), 0, ops.ptr(rm), 0,
+             ctypes.byref(P), bx, by, bw, bh, ops.ptr(out), 0)
     return out
 
 
@@ -571,53 +410,23 @@ def pyramid_correlate_batch(left, right, left_mask, right_mask, prefilter_mode, 
     to its tile threads one at a time (src/vw/Image/ImageIO.h:228-251).  Runs of consecutive tiles of equal size go through the pyramid
     level loop together (vwgpu_pyramid_correlate_batch[_dev], include/vwgpu.h); every tile's result is identical to pyramid_correlate on
     that tile.  Returns a list of (rows, cols, 3) float32 PixelMask<Vector2f> images: CUDA tensors for CUDA inputs, numpy arrays otherwise."""
-    from ._lib import PyramidParams
     if left.ndim != 2 or right.ndim != 2:
         raise ArgumentErr("pyramid_correlate: images must be 2-D (rows, cols)")
     lh, lw = left.shape
     rh, rw = right.shape
-    P = PyramidParams(int(prefilter_mode), float(prefilter_width),
-                      int(search_region.min[0]), int(search_region.min[1]), int(search_region.max[0]), int(search_region.max[1]),
-                      int(kernel_size[0]), int(kernel_size[1]), int(cost_type), int(corr_timeout), float(seconds_per_op),
-                      float(consistency_threshold), int(min_consistency_level), int(filter_half_kernel),
-                      int(max_pyramid_levels), int(algorithm), int(blob_filter_area), int(sgm_subpixel_mode),
-                      int(sgm_search_buffer[0]), int(sgm_search_buffer[1]), int(memory_limit_mb), int(sgm_num_threads),
-                      None, 0, 0, 0, 0, 0)
+    P = _pyramid_params(prefilter_mode, prefilter_width, search_region, kernel_size, cost_type, corr_timeout, seconds_per_op,
+                        consistency_threshold, min_consistency_level, filter_half_kernel, max_pyramid_levels, algorithm,
+                        blob_filter_area, sgm_subpixel_mode, sgm_search_buffer, memory_limit_mb, sgm_num_threads)
     n = len(bboxes)
     IA = ctypes.c_int * max(n, 1)
     bx = IA(*[int(b.min[0]) for b in bboxes]); by = IA(*[int(b.min[1]) for b in bboxes])
     bw = IA(*[int(b.max[0] - b.min[0]) for b in bboxes]); bh = IA(*[int(b.max[1] - b.min[1]) for b in bboxes])
-    ctx = _ctx_for(left, ctx)
-    lib = ctx._lib
-    PA = ctypes.c_void_p * max(n, 1)
-    if _is_tensor(left):
-        if not (left.is_cuda and right.is_cuda) or left.dtype != torch.float32 or right.dtype != torch.float32:
-            raise ArgumentErr("pyramid_correlate: float32 CUDA tensors required (no CPU path)")
-        l, r = left.contiguous(), right.contiguous()
-        lm = left_mask.contiguous() if left_mask is not None else None
-        rm = right_mask.contiguous() if right_mask is not None else None
-        for m, shp in ((lm, l.shape), (rm, r.shape)):
-            if m is not None and (m.dtype != torch.uint8 or tuple(m.shape) != tuple(shp) or not m.is_cuda):
-                raise ArgumentErr("pyramid_correlate: masks must be uint8 CUDA tensors of the image size")
-        outs = [torch.empty((max(bh[t], 0), max(bw[t], 0), 3), dtype=torch.float32, device=l.device) for t in range(n)]
-        ptrs = PA(*[o.data_ptr() for o in outs])
-        ctx.set_stream(torch.cuda.current_stream(l.device).cuda_stream)
-        ctx.check(lib.vwgpu_pyramid_correlate_batch_dev(ctx._h, l.data_ptr(), lw, lh, 0, r.data_ptr(), rw, rh, 0,
-                                                        lm.data_ptr() if lm is not None else None, 0, rm.data_ptr() if rm is not None else None, 0,
-                                                        ctypes.byref(P), n, bx, by, bw, bh, ptrs, None))
-        return outs
-    l = np.ascontiguousarray(left, np.float32)
-    r = np.ascontiguousarray(right, np.float32)
-    lm = np.ascontiguousarray(left_mask, np.uint8) if left_mask is not None else None
-    rm = np.ascontiguousarray(right_mask, np.uint8) if right_mask is not None else None
-    for m, shp in ((lm, l.shape), (rm, r.shape)):
-        if m is not None and tuple(m.shape) != tuple(shp):
-            raise ArgumentErr("pyramid_correlate: masks must have the image size")
-    outs = [np.empty((max(bh[t], 0), max(bw[t], 0), 3), np.float32) for t in range(n)]
-    ptrs = PA(*[o.ctypes.data for o in outs])
-    ctx.check(lib.vwgpu_pyramid_correlate_batch(ctx._h, l.ctypes.data, lw, lh, 0, r.ctypes.data, rw, rh, 0,
-                                                lm.ctypes.data if lm is not None else None, 0, rm.ctypes.data if rm is not None else None, 0,
-                                                ctypes.byref(P), n, bx, by, bw, bh, ptrs, None))
+    ops = Operands("pyramid_correlate", left, ctx)
+    l, r, lm, rm = _pyramid_images(ops, left, right, left_mask, right_mask)
+    outs = [ops.empty((max(bh[t], 0), max(bw[t], 0), 3), np.float32) for t in range(n)]
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[ops.ptr(o) for o in outs])
+    ops.call("pyramid_correlate_batch", ops.ptr(l), lw, lh, 0, ops.ptr(r), rw, rh, 0, ops.ptr(lm), 0, ops.ptr(rm), 0,
+             ctypes.byref(P), n, bx, by, bw, bh, ptrs, None)
     return outs
 
 
@@ -640,7 +449,6 @@ def calc_disparity_sgm(cost_type, left_in, right_in, left_region, search_volume,
     Masks / prev_disparity as in SemiGlobalMatcher::semi_global_matching_func (SGM.h:149-157).
     Returns the integer disparity (rows-k+1, cols-k+1, 3) int32; with_subpixel=True also returns the matcher's
     create_disparity_view_subpixel result (the reference hands the matcher back through matcher_ptr for that)."""
-    from ._lib import SgmParams
     kx, ky = int(kernel_size[0]), int(kernel_size[1])
     sx, sy = int(search_volume[0]), int(search_volume[1])
     if left_in.ndim != 2 or right_in.ndim != 2:
@@ -655,47 +463,29 @@ def calc_disparity_sgm(cost_type, left_in, right_in, left_region, search_volume,
     if kx > lw or ky > lh:
         raise ArgumentErr("calc_disparity_sgm: Kernel size too large of active region.")
     rx1, ry1 = min(x1 + sx, right_in.shape[1]), min(y1 + sy, right_in.shape[0])
-    P = SgmParams(int(cost_type), int(bool(use_mgm)), kx, int(subpixel_mode), int(search_buffer[0]), int(search_buffer[1]),
-                  int(memory_limit_mb), int(p1), int(p2), int(ternary_census_threshold), int(num_threads), int(bool(allow_block_cost)))
-    ctx = _ctx_for(left_in, ctx)
-    lib = ctx._lib
+    P = _lib.SgmParams(int(cost_type), int(bool(use_mgm)), kx, int(subpixel_mode), int(search_buffer[0]), int(search_buffer[1]),
+                       int(memory_limit_mb), int(p1), int(p2), int(ternary_census_threshold), int(num_threads),
+                       int(bool(allow_block_cost)))
     ow, oh = ctypes.c_int(), ctypes.c_int()
     cap = lw * lh
+    ops = Operands("calc_disparity_sgm", left_in, ctx)
+    l = ops.image(left_in[y0:y1, x0:x1], np.float32)
+    r = ops.image(right_in[y0:ry1, x0:rx1], np.float32)
+    lm, rm = _masks(ops, left_mask, right_mask)
+    pd = ops.image(prev_disparity, np.int32)
+    out = ops.empty((cap, 3), np.int32)
+    sub = ops.empty((cap, 3), np.float32) if with_subpixel else None
 
-    def shape2(a):
-        return (0, 0) if a is None else (a.shape[1], a.shape[0])
-    if _is_tensor(left_in):
-        if not (left_in.is_cuda and right_in.is_cuda) or left_in.dtype != torch.float32 or right_in.dtype != torch.float32:
-            raise ArgumentErr("calc_disparity_sgm: float32 CUDA tensors required (no CPU path)")
-        l = left_in[y0:y1, x0:x1].contiguous()
-        r = right_in[y0:ry1, x0:rx1].contiguous()
-        lm = left_mask.contiguous() if left_mask is not None else None
-        rm = right_mask.contiguous() if right_mask is not None else None
-        pd = prev_disparity.contiguous() if prev_disparity is not None else None
-        out = torch.empty((cap, 3), dtype=torch.int32, device=l.device)
-        sub = torch.empty((cap, 3), dtype=torch.float32, device=l.device) if with_subpixel else None
-        ctx.set_stream(torch.cuda.current_stream(l.device).cuda_stream)
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        ctx.check(lib.vwgpu_calc_disparity_sgm_dev(ctx._h, ctypes.byref(P), l.data_ptr(), lw, lh, 0, r.data_ptr(), r.shape[1], r.shape[0], 0,
-                                                   sx, sy, ptr(lm), *shape2(lm), ptr(rm), *shape2(rm), ptr(pd), *shape2(pd),
-                                                   out.data_ptr(), ptr(sub), cap, ctypes.byref(ow), ctypes.byref(oh)))
-        n = ow.value * oh.value
-        res = out[:n].reshape(oh.value, ow.value, 3)
-        return (res, sub[:n].reshape(oh.value, ow.value, 3)) if with_subpixel else res
-    l = np.ascontiguousarray(left_in[y0:y1, x0:x1], np.float32)
-    r = np.ascontiguousarray(right_in[y0:ry1, x0:rx1], np.float32)
-    lm = np.ascontiguousarray(left_mask, np.uint8) if left_mask is not None else None
-    rm = np.ascontiguousarray(right_mask, np.uint8) if right_mask is not None else None
-    pd = np.ascontiguousarray(prev_disparity, np.int32) if prev_disparity is not None else None
-    out = np.empty((cap, 3), np.int32)
-    sub = np.empty((cap, 3), np.float32) if with_subpixel else None
-    ptr = lambda a: a.ctypes.data if a is not None else None
-    ctx.check(lib.vwgpu_calc_disparity_sgm(ctx._h, ctypes.byref(P), l.ctypes.data, lw, lh, 0, r.ctypes.data, r.shape[1], r.shape[0], 0,
-                                           sx, sy, ptr(lm), *shape2(lm), ptr(rm), *shape2(rm), ptr(pd), *shape2(pd),
-                                           out.ctypes.data, ptr(sub), cap, ctypes.byref(ow), ctypes.byref(oh)))
+    def sized(a):
+        return (ops.ptr(a), 0, 0) if a is None else (ops.ptr(a), a.shape[1], a.shape[0])
+    ops.call("calc_disparity_sgm", ctypes.byref(P), ops.ptr(l), lw, lh, 0, ops.ptr(r), r.shape[1], r.shape[0], 0, sx, sy,
+             *sized(lm), *sized(rm), *sized(pd), ops.ptr(out), ops.ptr(sub), cap, ctypes.byref(ow), ctypes.byref(oh))
     n = ow.value * oh.value
-    res = out[:n].reshape(oh.value, ow.value, 3).copy()
-    return (res, sub[:n].reshape(oh.value, ow.value, 3).copy()) if with_subpixel else res
+
+    def result(a):     # a tensor stays a view of its cap-sized buffer, a numpy result lets go of it
+        a = a[:n].reshape(oh.value, ow.value, 3)
+        return a if ops.tensor else a.copy()
+    return (result(out), result(sub)) if with_subpixel else result(out)
 
 
 FILTER_SEMANTICS = {"reference": 0, "snapshot": 1}   # vwgpu_filter_semantics
@@ -721,38 +511,15 @@ def _post_filter(name, disparity, dtype, semantics, block_size, tiles, ctx, stat
     if texture is not None and (texture.ndim != 2 or tuple(texture.shape) != (h, w)):
         raise ArgumentErr("%s: the texture image and the disparity differ in size" % name)
     boxes = _filter_boxes(name, w, h, block_size, tiles)
-    st = (ctypes.c_longlong * 1)()
-    ctx = _ctx_for(disparity, ctx)
-    lib = ctx._lib
-    sem = FILTER_SEMANTICS[semantics]
-    want_stats = st if stats is not None else None
-    if _is_tensor(disparity):
-        tdt = torch.float32 if dtype == np.float32 else torch.int32
-        if not disparity.is_cuda or disparity.dtype != tdt:
-            raise ArgumentErr("%s: the disparity must be a %s CUDA tensor" % (name, tdt))
-        if texture is not None and (not _is_tensor(texture) or texture.device != disparity.device
-                                    or texture.dtype != torch.float32):
-            raise ArgumentErr("%s: the texture image must be a float32 CUDA tensor on %s" % (name, disparity.device))
-        d = disparity.contiguous()
-        out = torch.empty_like(d)
-        tex = () if texture is None else (texture.contiguous(),)
-        ctx.set_stream(torch.cuda.current_stream(d.device).cuda_stream)
-        fn = getattr(lib, "vwgpu_%s_dev" % name)
-        targs = () if texture is None else (tex[0].data_ptr(), 0)
-        ctx.check(fn(ctx._h, d.data_ptr(), w, h, 0, *targs, *head, sem, boxes.ctypes.data, len(boxes), out.data_ptr(), 0,
-                     want_stats))
-    else:
-        if _is_tensor(texture):
-            raise ArgumentErr("%s: with a numpy disparity the texture image must be a numpy array" % name)
-        d = np.ascontiguousarray(disparity, dtype)
-        out = np.empty_like(d)
-        tex = None if texture is None else np.ascontiguousarray(texture, np.float32)
-        targs = () if tex is None else (tex.ctypes.data, 0)
-        fn = getattr(lib, "vwgpu_%s" % name)
-        ctx.check(fn(ctx._h, d.ctypes.data, w, h, 0, *targs, *head, sem, boxes.ctypes.data, len(boxes), out.ctypes.data, 0,
-                     want_stats))
-    if stats is not None:
-        stats[:] = list(st)
+    st = new_stats(1)
+    ops = Operands(name, disparity, ctx)
+    d = ops.image(disparity, dtype)
+    tex = ops.image(texture, np.float32, same_device=True)
+    out = ops.empty(d.shape, dtype)
+    targs = () if tex is None else (ops.ptr(tex), 0)
+    ops.call(name, ops.ptr(d), w, h, 0, *targs, *head, FILTER_SEMANTICS[semantics], boxes.ctypes.data, len(boxes), ops.ptr(out), 0,
+             st if stats is not None else None)
+    put_stats(stats, st)
     return out
 
 
@@ -809,20 +576,11 @@ def texture_measure(image, kernel_size=9, gradient_weight=0.5, stddev_weight=0.5
     boxes = _filter_boxes("texture_measure", w, h, block_size, tiles)
     mx = ctypes.c_float(0)
     want = ctypes.addressof(mx) if stats is not None else None
-    ctx = _ctx_for(image, ctx)
-    lib = ctx._lib
-    args = (int(kernel_size), float(gradient_weight), float(stddev_weight), boxes.ctypes.data, len(boxes))
-    if _is_tensor(image):
-        if not image.is_cuda or image.dtype != torch.float32:
-            raise ArgumentErr("texture_measure: the image must be a float32 CUDA tensor")
-        img = image.contiguous()
-        out = torch.zeros((h, w), dtype=torch.float32, device=img.device)
-        ctx.set_stream(torch.cuda.current_stream(img.device).cuda_stream)
-        ctx.check(lib.vwgpu_texture_measure_dev(ctx._h, img.data_ptr(), w, h, 0, *args, out.data_ptr(), 0, want))
-    else:
-        img = np.ascontiguousarray(image, np.float32)
-        out = np.zeros((h, w), np.float32)
-        ctx.check(lib.vwgpu_texture_measure(ctx._h, img.ctypes.data, w, h, 0, *args, out.ctypes.data, 0, want))
+    ops = Operands("texture_measure", image, ctx)
+    img = ops.image(image, np.float32)
+    out = ops.zeros((h, w), np.float32)     # zero outside the boxes
+    ops.call("texture_measure", ops.ptr(img), w, h, 0, int(kernel_size), float(gradient_weight), float(stddev_weight),
+             boxes.ctypes.data, len(boxes), ops.ptr(out), 0, want)
     if stats is not None:
         stats[:] = [mx.value]
     return out
@@ -833,6 +591,12 @@ OUTLIER_SEMANTICS = {"reference": 0, "skip": 1}          # vwgpu_outlier_semanti
 OUTLIER_MAX_HALF_KERNEL = 15
 STD_DEV_IMAGE_MAX_KERNEL = 31
 EDGE_EXTENSIONS = {"constant": 0, "zero": 1}             # vwgpu_edge
+
+
+def _typed_disparity(ops, disparity):
+    """An int32 (PixelMask<Vector2i>) or float32 (PixelMask<Vector2f>) image and its vwgpu_disparity_type."""
+    d = ops.image(disparity, (np.int32, np.float32))
+    return d, 0 if ops.dtype_of(d) == np.int32 else 1
 
 
 def _rm_outliers(name, method, disparity, hh, hv, p0, p1, cleanup, semantics, ctx, stats):
@@ -847,29 +611,13 @@ def _rm_outliers(name, method, disparity, hh, hv, p0, p1, cleanup, semantics, ct
                           % ("RmOutliersUsingMeanFunc" if method == "mean" else "RmOutliersFunc"))
     if int(hh) > OUTLIER_MAX_HALF_KERNEL or int(hv) > OUTLIER_MAX_HALF_KERNEL:
         raise core.NoImplErr("%s: half kernel sizes %d, %d are larger than %d" % (name, int(hh), int(hv), OUTLIER_MAX_HALF_KERNEL))
-    st = (ctypes.c_longlong * 2)()
-    want_stats = st if stats is not None else None
-    ctx = _ctx_for(disparity, ctx)
-    lib = ctx._lib
-    head = (OUTLIER_METHODS[method],)
-    tail = (int(hh), int(hv), float(p0), float(p1), int(bool(cleanup)), OUTLIER_SEMANTICS[semantics])
-    if _is_tensor(disparity):
-        if not disparity.is_cuda or disparity.dtype not in (torch.int32, torch.float32):
-            raise ArgumentErr("%s: the disparity must be an int32 or float32 CUDA tensor" % name)
-        d = disparity.contiguous()
-        out = torch.empty_like(d)
-        ctx.set_stream(torch.cuda.current_stream(d.device).cuda_stream)
-        ctx.check(lib.vwgpu_rm_outliers_dev(ctx._h, *head, 0 if d.dtype == torch.int32 else 1, d.data_ptr(), w, h, 0, *tail,
-                                            out.data_ptr(), 0, want_stats))
-    else:
-        if disparity.dtype not in (np.int32, np.float32):
-            raise ArgumentErr("%s: the disparity must be int32 (PixelMask<Vector2i>) or float32 (PixelMask<Vector2f>)" % name)
-        d = np.ascontiguousarray(disparity)
-        out = np.empty_like(d)
-        ctx.check(lib.vwgpu_rm_outliers(ctx._h, *head, 0 if d.dtype == np.int32 else 1, d.ctypes.data, w, h, 0, *tail,
-                                        out.ctypes.data, 0, want_stats))
-    if stats is not None:
-        stats[:] = list(st)
+    st = new_stats(2)
+    ops = Operands(name, disparity, ctx)
+    d, t = _typed_disparity(ops, disparity)
+    out = ops.empty(d.shape, ops.dtype_of(d))
+    ops.call("rm_outliers", OUTLIER_METHODS[method], t, ops.ptr(d), w, h, 0, int(hh), int(hv), float(p0), float(p1),
+             int(bool(cleanup)), OUTLIER_SEMANTICS[semantics], ops.ptr(out), 0, st if stats is not None else None)
+    put_stats(stats, st)
     return out
 
 
@@ -949,19 +697,10 @@ def std_dev_image(image, kernel_width, kernel_height, edge="zero", ctx=None):
     if kw > STD_DEV_IMAGE_MAX_KERNEL or kh > STD_DEV_IMAGE_MAX_KERNEL:
         raise core.NoImplErr("std_dev_image: kernel size %d x %d is larger than %d" % (kw, kh, STD_DEV_IMAGE_MAX_KERNEL))
     h, w = int(image.shape[0]), int(image.shape[1])
-    ctx = _ctx_for(image, ctx)
-    lib = ctx._lib
-    if _is_tensor(image):
-        if not image.is_cuda or image.dtype != torch.float32:
-            raise ArgumentErr("std_dev_image: the image must be a float32 CUDA tensor")
-        img = image.contiguous()
-        out = torch.empty_like(img)
-        ctx.set_stream(torch.cuda.current_stream(img.device).cuda_stream)
-        ctx.check(lib.vwgpu_std_dev_image_dev(ctx._h, img.data_ptr(), w, h, 0, kw, kh, EDGE_EXTENSIONS[edge], out.data_ptr(), 0))
-    else:
-        img = np.ascontiguousarray(image, np.float32)
-        out = np.empty_like(img)
-        ctx.check(lib.vwgpu_std_dev_image(ctx._h, img.ctypes.data, w, h, 0, kw, kh, EDGE_EXTENSIONS[edge], out.ctypes.data, 0))
+    ops = Operands("std_dev_image", image, ctx)
+    img = ops.image(image, np.float32)
+    out = ops.empty(img.shape, np.float32)
+    ops.call("std_dev_image", ops.ptr(img), w, h, 0, kw, kh, EDGE_EXTENSIONS[edge], ops.ptr(out), 0)
     return out
 
 
@@ -1000,39 +739,14 @@ class HomographyTransform(object):
         return self._apply(self.inverse_matrix, p)
 
 
-def _dm_disparity(name, disparity):
-    """Checks a {dx, dy, valid} map; returns (contiguous map, vwgpu_disparity_type, w, h, is a tensor)."""
+def _disparity_map(ops, disparity):
+    """Checks a {dx, dy, valid} map; returns (contiguous map, vwgpu_disparity_type, w, h)."""
     if disparity.ndim != 3 or disparity.shape[2] != 3:
-        raise ArgumentErr("%s: disparity must be (rows, cols, 3) {dx, dy, valid}" % name)
+        raise ArgumentErr("%s: disparity must be (rows, cols, 3) {dx, dy, valid}" % ops.name)
     if int(disparity.shape[0]) <= 0 or int(disparity.shape[1]) <= 0:
-        raise ArgumentErr("%s: empty image" % name)
-    if _is_tensor(disparity):
-        if not disparity.is_cuda or disparity.dtype not in (torch.int32, torch.float32):
-            raise ArgumentErr("%s: the disparity must be an int32 or float32 CUDA tensor" % name)
-        d = disparity.contiguous()
-        return d, (0 if d.dtype == torch.int32 else 1), int(d.shape[1]), int(d.shape[0]), True
-    if disparity.dtype not in (np.int32, np.float32):
-        raise ArgumentErr("%s: the disparity must be int32 (PixelMask<Vector2i>) or float32 (PixelMask<Vector2f>)" % name)
-    d = np.ascontiguousarray(disparity)
-    return d, (0 if d.dtype == np.int32 else 1), int(d.shape[1]), int(d.shape[0]), False
-
-
-def _dm_ptr(a):
-    return a.data_ptr() if _is_tensor(a) else a.ctypes.data
-
-
-def _dm_empty(like, shape, dtype=None):
-    if _is_tensor(like):
-        return torch.empty(shape, dtype=like.dtype if dtype is None else dtype, device=like.device)
-    return np.empty(shape, like.dtype if dtype is None else dtype)
-
-
-def _dm_entry(ctx, name, d, tensor):
-    """The _dev entry on the current torch stream for tensors, the host entry for numpy arrays."""
-    if tensor:
-        ctx.set_stream(torch.cuda.current_stream(d.device).cuda_stream)
-        return getattr(ctx._lib, "vwgpu_%s_dev" % name)
-    return getattr(ctx._lib, "vwgpu_%s" % name)
+        raise ArgumentErr("%s: empty image" % ops.name)
+    d, t = _typed_disparity(ops, disparity)
+    return d, t, int(d.shape[1]), int(d.shape[0])
 
 
 def get_disparity_range(disparity, ctx=None, device_result=False):
@@ -1041,20 +755,20 @@ def get_disparity_range(disparity, ctx=None, device_result=False):
     only in the first valid pixel in raster order (then both extrema of that component are NaN), as the reference's
     accumulator has it.  numpy in -> numpy out; CUDA tensor in -> numpy out after one synchronisation, or with
     device_result=True a CUDA float32[4] tensor without any host round trip."""
-    d, t, w, h, tensor = _dm_disparity("get_disparity_range", disparity)
-    ctx = _ctx_for(d, ctx)
+    ops = Operands("get_disparity_range", disparity, ctx)
+    d, t, w, h = _disparity_map(ops, disparity)
     host = np.zeros(4, np.float32)
-    if tensor:
-        ctx.set_stream(torch.cuda.current_stream(d.device).cuda_stream)
-        if device_result:
-            out = torch.empty(4, dtype=torch.float32, device=d.device)
-            ctx.check(ctx._lib.vwgpu_get_disparity_range_dev(ctx._h, t, d.data_ptr(), w, h, 0, out.data_ptr(), None))
-            return out
-        ctx.check(ctx._lib.vwgpu_get_disparity_range_dev(ctx._h, t, d.data_ptr(), w, h, 0, None, host.ctypes.data))
-        return host
+    # the two entries differ: the device one takes (range on the device, range on the host), the host one a single pointer
     if device_result:
-        raise ArgumentErr("get_disparity_range: device_result needs a CUDA tensor")
-    ctx.check(ctx._lib.vwgpu_get_disparity_range(ctx._h, t, d.ctypes.data, w, h, 0, host.ctypes.data))
+        if not ops.tensor:
+            raise ArgumentErr("get_disparity_range: device_result needs a CUDA tensor")
+        out = ops.empty(4, np.float32)
+        ops.call("get_disparity_range", t, ops.ptr(d), w, h, 0, ops.ptr(out), None)
+        return out
+    if ops.tensor:
+        ops.call("get_disparity_range", t, ops.ptr(d), w, h, 0, None, host.ctypes.data)
+    else:
+        ops.call("get_disparity_range", t, ops.ptr(d), w, h, 0, host.ctypes.data)
     return host
 
 
@@ -1066,30 +780,28 @@ def disparity_range_mask(disparity, min, max, semantics="reference", x0=0, y0=0,
     larger map).  stats (optional list) receives [pixels masked]."""
     if semantics not in RANGE_MASK_SEMANTICS:
         raise ArgumentErr("disparity_range_mask: semantics must be 'reference' or 'fixed', not %r" % (semantics,))
-    d, t, w, h, tensor = _dm_disparity("disparity_range_mask", disparity)
+    ops = Operands("disparity_range_mask", disparity, ctx)
+    d, t, w, h = _disparity_map(ops, disparity)
     lo, hi = np.array(min, np.float64).reshape(-1), np.array(max, np.float64).reshape(-1)
     if lo.size != 2 or hi.size != 2:
         raise ArgumentErr("disparity_range_mask: min and max must be (x, y) pairs")
-    ctx = _ctx_for(d, ctx)
-    out = _dm_empty(d, d.shape)
-    st = (ctypes.c_longlong * 1)()
-    ctx.check(_dm_entry(ctx, "disparity_range_mask", d, tensor)(
-        ctx._h, t, _dm_ptr(d), w, h, 0, int(x0), int(y0), lo.ctypes.data, hi.ctypes.data, RANGE_MASK_SEMANTICS[semantics],
-        _dm_ptr(out), 0, st if stats is not None else None))
-    if stats is not None:
-        stats[:] = list(st)
+    out = ops.empty(d.shape, ops.dtype_of(d))
+    st = new_stats(1)
+    ops.call("disparity_range_mask", t, ops.ptr(d), w, h, 0, int(x0), int(y0), lo.ctypes.data, hi.ctypes.data,
+             RANGE_MASK_SEMANTICS[semantics], ops.ptr(out), 0, st if stats is not None else None)
+    put_stats(stats, st)
     return out
 
 
 def _transform(name, disparity, matrix, mode, x0, y0, ctx):
-    d, t, w, h, tensor = _dm_disparity(name, disparity)
+    ops = Operands(name, disparity, ctx)
+    d, t, w, h = _disparity_map(ops, disparity)
     m = np.ascontiguousarray(np.array(matrix, np.float64))
     if m.shape != (3, 3):
         raise ArgumentErr("%s: the matrix must be 3 x 3" % name)
-    ctx = _ctx_for(d, ctx)
-    out = _dm_empty(d, d.shape)
-    ctx.check(_dm_entry(ctx, "transform_disparities", d, tensor)(
-        ctx._h, t, _dm_ptr(d), w, h, 0, int(x0), int(y0), m.ctypes.data, TRANSFORM_MODES[mode], _dm_ptr(out), 0))
+    out = ops.empty(d.shape, ops.dtype_of(d))
+    ops.call("transform_disparities", t, ops.ptr(d), w, h, 0, int(x0), int(y0), m.ctypes.data, TRANSFORM_MODES[mode],
+             ops.ptr(out), 0)
     return out
 
 
@@ -1116,10 +828,10 @@ def transform_disparities_subregion(do_round, subregion, T, disparity, ctx=None)
 
 
 def _resample(name, disparity, shape_of, dtype, ctx):
-    d, t, w, h, tensor = _dm_disparity(name, disparity)
-    ctx = _ctx_for(d, ctx)
-    out = _dm_empty(d, shape_of(h, w), dtype)
-    ctx.check(_dm_entry(ctx, name, d, tensor)(ctx._h, t, _dm_ptr(d), w, h, 0, _dm_ptr(out), 0))
+    ops = Operands(name, disparity, ctx)
+    d, t, w, h = _disparity_map(ops, disparity)
+    out = ops.empty(shape_of(h, w), ops.dtype_of(d) if dtype is None else dtype)
+    ops.call(name, t, ops.ptr(d), w, h, 0, ops.ptr(out), 0)
     return out
 
 
@@ -1139,19 +851,19 @@ def disparity_upsample(disparity, ctx=None):
 def missing_pixel_image(disparity, ctx=None):
     """vw::stereo::missing_pixel_image (src/vw/Stereo/DisparityMap.h:68-87): (rows, cols, 3) uint8, (200, 200, 200)
     where the disparity is valid and (255, 0, 0) where it is not."""
-    return _resample("missing_pixel_image", disparity, lambda h, w: (h, w, 3), torch.uint8 if _is_tensor(disparity) else np.uint8, ctx)
+    return _resample("missing_pixel_image", disparity, lambda h, w: (h, w, 3), np.uint8, ctx)
 
 
 def intersect_mask_and_data(data, mask, ctx=None):
     """vw::stereo::intersect_mask_and_data (src/vw/Stereo/DisparityMap.h:1226-1249): the data pixel where it is valid,
     else the mask pixel where that is valid, else the data pixel.  Both maps have one type and size."""
-    d, t, w, h, tensor = _dm_disparity("intersect_mask_and_data", data)
-    m, tm, wm, hm, mtensor = _dm_disparity("intersect_mask_and_data", mask)
-    if (t, w, h, tensor) != (tm, wm, hm, mtensor):
+    ops = Operands("intersect_mask_and_data", data, ctx)
+    d, t, w, h = _disparity_map(ops, data)
+    m, tm, wm, hm = _disparity_map(ops, mask)
+    if (t, w, h) != (tm, wm, hm):
         raise ArgumentErr("intersect_mask_and_data: data and mask must have the same type and size")
-    ctx = _ctx_for(d, ctx)
-    out = _dm_empty(d, d.shape)
-    ctx.check(_dm_entry(ctx, "intersect_mask_and_data", d, tensor)(ctx._h, t, _dm_ptr(d), 0, _dm_ptr(m), 0, w, h, _dm_ptr(out), 0))
+    out = ops.empty(d.shape, ops.dtype_of(d))
+    ops.call("intersect_mask_and_data", t, ops.ptr(d), 0, ops.ptr(m), 0, w, h, ops.ptr(out), 0)
     return out
 
 
@@ -1159,23 +871,18 @@ def disparity_transform_image(right, disparity, ctx=None):
     """transform(right, DisparityTransform(disparity)) (src/vw/Stereo/DisparityMap.h:1164-1187): the (rows, cols)
     float32 right image seen from the left one, bilinear over zero edge extension; a pixel without a valid disparity
     (or outside the float32 disparity map, which may have another size) samples (-1, y) and becomes 0."""
-    d, t, dw, dh, tensor = _dm_disparity("disparity_transform_image", disparity)
+    ops = Operands("disparity_transform_image", disparity, ctx)
+    d, t, dw, dh = _disparity_map(ops, disparity)
     if t != 1:
         raise ArgumentErr("disparity_transform_image: the disparity must be float32 (PixelMask<Vector2f>)")
-    if right.ndim != 2 or _is_tensor(right) != tensor:
+    if right.ndim != 2:
         raise ArgumentErr("disparity_transform_image: the image must be (rows, cols), on the same side as the disparity")
-    if tensor:
-        if not right.is_cuda or right.dtype != torch.float32:
-            raise ArgumentErr("disparity_transform_image: the image must be a float32 CUDA tensor")
-        r = right.contiguous()
-    else:
-        r = np.ascontiguousarray(right, np.float32)
+    r = ops.image(right, np.float32)
     rh, rw = int(r.shape[0]), int(r.shape[1])
     if rw <= 0 or rh <= 0:
         raise ArgumentErr("disparity_transform_image: empty image")
-    ctx = _ctx_for(d, ctx)
-    out = _dm_empty(r, r.shape)
-    ctx.check(_dm_entry(ctx, "disparity_warp", d, tensor)(ctx._h, _dm_ptr(r), rw, rh, 0, _dm_ptr(d), dw, dh, 0, _dm_ptr(out), 0))
+    out = ops.empty(r.shape, np.float32)
+    ops.call("disparity_warp", ops.ptr(r), rw, rh, 0, ops.ptr(d), dw, dh, 0, ops.ptr(out), 0)
     return out
 
 
@@ -1184,9 +891,10 @@ DISPARITY_LAYOUTS = {"dxdyv": 0x000, "dxdy": 0x100, "dv": 0x200, "d": 0x300}
 _LAYOUT_WORDS = {"dxdyv": 3, "dxdy": 2, "dv": 2, "d": 1}
 
 
-def _tri_disparity(name, disparity, layout):
+def _tri_disparity(ops, disparity, layout):
     """A disparity image in one of the pixel forms DispHelper accepts (src/vw/Stereo/StereoView.h:37-53); returns
-    (contiguous image, vwgpu_disparity_type, layout flag, w, h, is a tensor).  Never copies a tensor to the host."""
+    (contiguous image, vwgpu_disparity_type, layout flag, w, h).  Never copies a tensor to the host."""
+    name = ops.name
     if layout is None:
         if disparity.ndim == 2:
             layout = "d"
@@ -1200,52 +908,35 @@ def _tri_disparity(name, disparity, layout):
         raise ArgumentErr("%s: layout %r needs %d word(s) per pixel" % (name, layout, words))
     if int(disparity.shape[0]) <= 0 or int(disparity.shape[1]) <= 0:
         raise ArgumentErr("%s: empty image" % name)
-    tensor = _is_tensor(disparity)
-    if tensor:
-        if not disparity.is_cuda or disparity.dtype not in (torch.int32, torch.float32):
-            raise ArgumentErr("%s: the disparity must be an int32 or float32 CUDA tensor" % name)
-        d = disparity.contiguous()
-        t = 0 if d.dtype == torch.int32 else 1
-    else:
-        if disparity.dtype not in (np.int32, np.float32):
-            raise ArgumentErr("%s: the disparity must be int32 or float32" % name)
-        d = np.ascontiguousarray(disparity)
-        t = 0 if d.dtype == np.int32 else 1
-    return d, t, DISPARITY_LAYOUTS[layout], int(d.shape[1]), int(d.shape[0]), tensor
-
-
-def _f64(like):
-    return torch.float64 if _is_tensor(like) else np.float64
+    d, t = _typed_disparity(ops, disparity)
+    return d, t, DISPARITY_LAYOUTS[layout], int(d.shape[1]), int(d.shape[0])
 
 
 def _triangulate(name, disparity, cam1, cam2, x0, y0, angle_tol, semantics, layout, want_error, want_errvec, stats, ctx):
-    from . import _lib, camera
     if semantics not in TRIANGULATE_SEMANTICS:
         raise ArgumentErr("%s: semantics must be 'view' or 'model', not %r" % (name, semantics))
-    d, t, lay, w, h, tensor = _tri_disparity(name, disparity, layout)
+    ops = Operands(name, disparity, ctx)
+    d, t, lay, w, h = _tri_disparity(ops, disparity, layout)
     c1, c2 = camera.descriptor_of(cam1), camera.descriptor_of(cam2)
-    ctx = _ctx_for(d, ctx)
-    xyz = _dm_empty(d, (h, w, 3), _f64(d))
-    err = _dm_empty(d, (h, w), _f64(d)) if want_error else None
-    vec = _dm_empty(d, (h, w, 3), _f64(d)) if want_errvec else None
+    xyz = ops.empty((h, w, 3), np.float64)
+    err = ops.empty((h, w), np.float64) if want_error else None
+    vec = ops.empty((h, w, 3), np.float64) if want_errvec else None
     st, st_dev = None, None
     if stats is not None:
         if _is_tensor(stats):
-            if not tensor or not stats.is_cuda or stats.dtype != torch.int64 or stats.numel() != 3 or not stats.is_contiguous():
+            if not ops.tensor or stats.numel() != 3:
                 raise ArgumentErr("%s: a device stats must be a contiguous int64[3] CUDA tensor, with a CUDA disparity" % name)
-            st = stats.data_ptr()
-        elif tensor:
-            st_dev = torch.empty(3, dtype=torch.int64, device=d.device)
-            st = st_dev.data_ptr()
+            st = ops.ptr(ops.image(stats, np.int64, in_place=True))     # contiguous, int64, CUDA: or ArgumentErr
+        elif ops.tensor:
+            st_dev = ops.empty(3, np.int64)
+            st = ops.ptr(st_dev)
         else:
             st_host = _lib.TriangulateStats()
             st = ctypes.addressof(st_host)
-    ctx.check(_dm_entry(ctx, "stereo_triangulate", d, tensor)(
-        ctx._h, t, _dm_ptr(d), w, h, 0, int(x0), int(y0), ctypes.byref(c1), ctypes.byref(c2), float(angle_tol),
-        TRIANGULATE_SEMANTICS[semantics] | lay, _dm_ptr(xyz), 0, _dm_ptr(err) if want_error else None, 0,
-        _dm_ptr(vec) if want_errvec else None, 0, st))
+    ops.call("stereo_triangulate", t, ops.ptr(d), w, h, 0, int(x0), int(y0), ctypes.byref(c1), ctypes.byref(c2), float(angle_tol),
+             TRIANGULATE_SEMANTICS[semantics] | lay, ops.ptr(xyz), 0, ops.ptr(err), 0, ops.ptr(vec), 0, st)
     if stats is not None and not _is_tensor(stats):
-        if tensor:
+        if ops.tensor:
             words = st_dev.cpu().numpy()
             stats[:] = [int(words[0]), float(words[1:2].view(np.float64)[0]), float(words[2:3].view(np.float64)[0])]
         else:
@@ -1291,16 +982,14 @@ class StereoModel(object):
     def convergence_angle(self, disparity, x0=0, y0=0, semantics="model", ctx=None, layout=None):
         """StereoModel::convergence_angle (src/vw/Stereo/StereoModel.cc:174-177) for every pixel pair of a disparity map:
         (rows, cols) float64 acos(dot(ray1, ray2)); 0 at invalid pixels."""
-        from . import camera
         if semantics not in TRIANGULATE_SEMANTICS:
             raise ArgumentErr("convergence_angle: semantics must be 'view' or 'model', not %r" % (semantics,))
-        d, t, lay, w, h, tensor = _tri_disparity("convergence_angle", disparity, layout)
+        ops = Operands("convergence_angle", disparity, ctx)
+        d, t, lay, w, h = _tri_disparity(ops, disparity, layout)
         c1, c2 = camera.descriptor_of(self.cam1), camera.descriptor_of(self.cam2)
-        ctx = _ctx_for(d, ctx)
-        out = _dm_empty(d, (h, w), _f64(d))
-        ctx.check(_dm_entry(ctx, "convergence_angle", d, tensor)(
-            ctx._h, t, _dm_ptr(d), w, h, 0, int(x0), int(y0), ctypes.byref(c1), ctypes.byref(c2),
-            TRIANGULATE_SEMANTICS[semantics] | lay, _dm_ptr(out), 0))
+        out = ops.empty((h, w), np.float64)
+        ops.call("convergence_angle", t, ops.ptr(d), w, h, 0, int(x0), int(y0), ctypes.byref(c1), ctypes.byref(c2),
+                 TRIANGULATE_SEMANTICS[semantics] | lay, ops.ptr(out), 0)
         return out
 
 
@@ -1313,48 +1002,73 @@ def universe_radius(points, origin, near_radius=0.0, far_radius=DBL_MAX, stats=N
     all zero, one whose distance from origin is below a non-zero near_radius or above a non-zero far_radius too.  Negative
     radii or near_radius > far_radius raise ArgumentErr, as the reference's constructor asserts.  stats (optional list)
     receives [total_points, rejected_points] (one synchronisation).  out=points filters in place."""
-    tensor = _is_tensor(points)
     if points.ndim != 3 or int(points.shape[2]) not in (3, 4, 6):
         raise ArgumentErr("universe_radius: points must be (rows, cols, 3 | 4 | 6)")
-    if tensor:
-        if not points.is_cuda or points.dtype != torch.float64:
-            raise ArgumentErr("universe_radius: the points must be a float64 CUDA tensor")
-        p = points if out is points else points.contiguous()
-    else:
-        if points.dtype != np.float64:
-            raise ArgumentErr("universe_radius: the points must be float64")
-        p = points if out is points else np.ascontiguousarray(points)
+    ops = Operands("universe_radius", points, ctx)
+    if ops.dtype_of(points) != np.float64:     # on either side: a numpy image of another type is not converted
+        raise ArgumentErr("universe_radius: the points must be float64")
+    p = ops.image(points, np.float64, in_place=out is points)
     if out is points:
-        if not (p.is_contiguous() if tensor else p.flags["C_CONTIGUOUS"]):
-            raise ArgumentErr("universe_radius: an image filtered in place must be contiguous")
         res = p
     elif out is not None:
         raise ArgumentErr("universe_radius: out must be None or the points themselves")
     else:
-        res = _dm_empty(p, tuple(p.shape))
+        res = ops.empty(tuple(p.shape), np.float64)
     h, w, ch = int(p.shape[0]), int(p.shape[1]), int(p.shape[2])
     if w <= 0 or h <= 0:
         raise ArgumentErr("universe_radius: empty image")
     o = np.array(origin, np.float64).reshape(-1)
     if o.size != 3:
         raise ArgumentErr("universe_radius: the origin must have three elements")
-    ctx = _ctx_for(p, ctx)
-    st = (ctypes.c_longlong * 2)()
-    ctx.check(_dm_entry(ctx, "universe_radius", p, tensor)(
-        ctx._h, _dm_ptr(p), ch, w, h, 0, o.ctypes.data, float(near_radius), float(far_radius), _dm_ptr(res), 0,
-        st if stats is not None else None))
-    if stats is not None:
-        stats[:] = list(st)
+    st = new_stats(2)
+    ops.call("universe_radius", ops.ptr(p), ch, w, h, 0, o.ctypes.data, float(near_radius), float(far_radius), ops.ptr(res), 0,
+             st if stats is not None else None)
+    put_stats(stats, st)
     return res
 
 
-__all__ = ["affine_subpixel", "bayes_em_subpixel", "corr_eval", "disparity_median_filter", "disparity_neighbor_filter",
-           "texture_measure", "texture_preserving_disparity_filter","lk_subpixel", "phase_subpixel", "pyramid_subpixel", "calc_disparity", "calc_disparity_sgm", "cross_corr_consistency_check", "parabola_subpixel", "rm_outliers_using_thresh",
-           "disparity_cleanup_using_thresh", "disparity_mask", "disparity_blob_filter", "subdivide_regions", "pyramid_correlate", "pyramid_correlate_batch",
-           "rm_outliers_using_mean", "rm_outliers_using_stddev", "rm_outliers_using_plane", "disparity_cleanup_using_mean",
-           "disparity_cleanup_using_stddev", "disparity_clean_using_plane", "std_dev_image",
-           "get_disparity_range", "disparity_range_mask", "transform_disparities", "transform_disparities_subregion",
-           "HomographyTransform", "disparity_subsample", "disparity_upsample", "disparity_transform_image",
-           "missing_pixel_image", "intersect_mask_and_data",
-           "StereoModel", "stereo_triangulate", "universe_radius",
-           "BBox2i", "CostFunctionType"]
+__all__ = [
+    "affine_subpixel",
+    "bayes_em_subpixel",
+    "corr_eval",
+    "disparity_median_filter",
+    "disparity_neighbor_filter",
+    "texture_measure",
+    "texture_preserving_disparity_filter",
+    "lk_subpixel",
+    "phase_subpixel",
+    "pyramid_subpixel",
+    "calc_disparity",
+    "calc_disparity_sgm",
+    "cross_corr_consistency_check",
+    "parabola_subpixel",
+    "rm_outliers_using_thresh",
+    "disparity_cleanup_using_thresh",
+    "disparity_mask",
+    "disparity_blob_filter",
+    "subdivide_regions",
+    "pyramid_correlate",
+    "pyramid_correlate_batch",
+    "rm_outliers_using_mean",
+    "rm_outliers_using_stddev",
+    "rm_outliers_using_plane",
+    "disparity_cleanup_using_mean",
+    "disparity_cleanup_using_stddev",
+    "disparity_clean_using_plane",
+    "std_dev_image",
+    "get_disparity_range",
+    "disparity_range_mask",
+    "transform_disparities",
+    "transform_disparities_subregion",
+    "HomographyTransform",
+    "disparity_subsample",
+    "disparity_upsample",
+    "disparity_transform_image",
+    "missing_pixel_image",
+    "intersect_mask_and_data",
+    "StereoModel",
+    "stereo_triangulate",
+    "universe_radius",
+    "BBox2i",
+    "CostFunctionType",
+]

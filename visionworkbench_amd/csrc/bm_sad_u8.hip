@@ -187,7 +187,7 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
   // XCD-aware tile order: workgroup i runs on XCD i % 8 (round-robin dispatch), so XCD x takes the contiguous band of
   // tiles [x * per, (x + 1) * per) — whole tile rows in raster order.  Tiles that share halo rows (ky-1 of TY+ky-1) or
   // output cache lines are then staged at the same time behind the same L2 instead of being fetched once per XCD
-  // (FETCH_SIZE 203 -> 148 MB per launch on the 4096^2 case; the kernel time does not move: staging is latency bound).
+  // (FETCH_SIZE 203 -> 148 MB per launch on the 4096^2 case; the kernel time did not move).
   const int per_xcd = gridDim.x >> 3;
   const int wg = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);   // tile index, raster order
   if (wg >= ntiles) return;                         // grid rounded up to a multiple of 8
@@ -209,7 +209,9 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
   // ---- LEFT: float tile -> u8 in LDS (borrowing the entry array) -> per-lane register windows ----
   // Both tiles are staged before anything else is live in registers (the LEFT tile borrows the entry array).
   // (both images' main loads in flight before the first conversion — one memory latency instead of two — was tried for the
-  // latency-bound 1/8 strips in round 4: nothing there, 2 us slower at 4096^2; the tiles are staged one after the other)
+  // 1/8 strips in round 4: nothing there, 2 us slower at 4096^2; measured again with one 16-byte load per row, 44 in flight:
+  // 0.5-1 us slower at 4096^2 in every run — staging moves its bytes at the rate of an all-CU burst (profiles/u8_staging_loads.md);
+  // the tiles are staged one after the other)
   stage_u8_rows<NR>(L, ls, lw, lh, x0, y0, C::LBW, C::LBW, ent, tid, NT, bad_acc);
   stage_u8_rows<NR>(R, rs, rcw, rch, x0, y0, bpitch, bpitch, base, tid, NT, bad_acc);
   __syncthreads();

@@ -1,6 +1,17 @@
 // u8_tile.h — staging of float image tiles as packed u8 dwords in LDS, shared by the packed-u8 matchers
 // (bm_sad_u8.hip, bm_corr_u8.hip).  Every pixel is checked on the way: the packed kernels are exact only for
 // integer-valued pixels in [0,255]; anything else ORs a non-zero value into `acc`.
+//
+// The loads: every group of four pixels is ONE 16-byte load (global_load_dwordx4) — one per row and lane in the main part of a tile, four
+// in flight per lane in the remainder columns — through a packed, 4-byte aligned struct (load_f4), for aligned images and for views cut
+// at any column or with any row stride alike.  Only the group that straddles the right edge of the image is read pixel by pixel
+// (patch_right_edge).  An earlier form chose per row between a float4 load and four scalar loads on a run-time alignment flag; the
+// compiler merged the arms into four single-dword loads with selected addresses in every row but the last, so each lane fetched its 16
+// bytes as four requests at a 16-byte lane stride.  tests/test_u8_tile_isa_cpu.py reads the instruction counts off the assembly.
+// What staging costs with them (profiles/u8_staging_loads.md): a 7x7 tile pair of 1024 x 16 pixels at 129 disparities (22 input rows,
+// 194 KB) takes 8.1-8.7 us when every CU stages one pair at the same moment and 15.4-15.6 us when it stages two — 10-11 bytes per clock
+// and CU either way, the rate of an all-CU burst of wide loads: the phase is bound by the bytes it moves (13.5 and 20.4 us with the
+// four-dword form, which was bound by its requests).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -8,19 +19,6 @@
 namespace vwgpu_u8 {
 
 typedef uint32_t u32;
-
-// float -> u8 with the exactness test of the fast path: integer-valued and inside [0,255].
-__device__ __forceinline__ u32 to_u8(float v, bool& bad) {
-  const float r = rintf(v);
-  bad |= !(r == v && v >= 0.0f && v <= 255.0f);
-  return (u32)(int)fminf(fmaxf(r, 0.0f), 255.0f);
-}
-
-// Loads a row-segment of a float image as packed u8 dwords into LDS: dst[g] = bytes (x0+4g .. x0+4g+3),
-// zero outside [0,w) x [0,h).  `vec4` (workgroup-uniform) = every in-range group of 4 floats is 16-byte aligned.
-__device__ __forceinline__ u32 pack4(float v0, float v1, float v2, float v3, bool& bad) {
-  return to_u8(v0, bad) | (to_u8(v1, bad) << 8) | (to_u8(v2, bad) << 16) | (to_u8(v3, bad) << 24);
-}
 
 // float4 -> 4 packed u8 (v_cvt_pk_u8_f32 saturates) and the exactness test of the fast path: a pixel is
 // representable iff converting the byte back gives the same float; the differences are OR-ed into `acc`
@@ -38,7 +36,7 @@ __device__ __forceinline__ u32 pack4_check(float4 v, u32& acc) {
   return p;
 }
 
-// Groups straddling the right image edge (x < w <= x+3, at most one per row): the vector paths wrote 0 there.
+// Groups straddling the right image edge (x < w <= x+3, at most one per row): the vector paths left them out.
 template <int NROWS>
 __device__ __forceinline__ void patch_right_edge(const float* __restrict__ img, ptrdiff_t stride, int w, int h,
                                                  int x0, int y0, int ndw, int dst_pitch_dw,
@@ -51,11 +49,9 @@ __device__ __forceinline__ void patch_right_edge(const float* __restrict__ img, 
       if (y < h) {
         const float* row = img + (ptrdiff_t)y * stride;
         const int x = x0 + 4 * ge;
-        bool bad = false;
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-          if (x + b < w) p |= to_u8(row[x + b], bad) << (8 * b);
-        if (bad) acc |= 1u;
+        // pixels behind the edge count as 0; the same conversion and exactness test as everywhere else
+        const float4 v = make_float4(row[x], x + 1 < w ? row[x + 1] : 0.0f, x + 2 < w ? row[x + 2] : 0.0f, 0.0f);
+        p = pack4_check(v, acc);
       }
       dst[r * dst_pitch_dw + ge] = p;
     }
@@ -65,26 +61,35 @@ __device__ __forceinline__ void patch_right_edge(const float* __restrict__ img, 
 // Loads NROWS rows of a float image as packed u8 dwords into LDS: dst[r][g] = bytes (x0+4g .. x0+4g+3), zero
 // outside [0,w) x [0,h).  Row base pointers are workgroup-uniform (scalar), the per-lane part of the address is one
 // offset shared by all rows, and all NROWS loads of a thread are unconditional (out-of-range groups read offset 0 of
-// a valid row and are zeroed afterwards), so they are in flight together: staging a tile costs about one memory
-// latency.  Columns beyond the first `nthreads` groups (the search margin) are spread evenly over the workgroup.
+// a valid row and are zeroed afterwards), so they are in flight together, one 16-byte request each.
+// Columns beyond the first `nthreads` groups (the search margin) are spread evenly over the workgroup.
 // Groups straddling the right image edge (at most one per row) are patched by a scalar tail loop.
+// (The dummy load reads four floats from the start of a row: inside the image for w >= 4, and from row 0 — whose successor exists, the
+// matchers' windows have three rows or more — for narrower images.)
 template <int NROWS>
 struct U8MainLoads { float4 v[NROWS]; };
+
+// Four consecutive floats of a row whose base is only known to be 4-byte aligned (an image view cut at any column, any row stride): the
+// packed, 4-byte aligned struct makes the access one global_load_dwordx4 for every image, so there is no second, scalar form of the loads
+// (the idiom of the SAD epilogue's stores, whose rows are 4-byte aligned as well).
+struct __attribute__((packed, aligned(4))) F4U { float x, y, z, w; };
+__device__ __forceinline__ float4 load_f4(const float* p) {
+  const F4U u = *reinterpret_cast<const F4U*>(p);
+  return make_float4(u.x, u.y, u.z, u.w);
+}
 
 // main part of a tile: group g = tid of every row.  `issue` requests the NROWS loads, `finish` converts and stores them.
 template <int NROWS>
 __device__ __forceinline__ void stage_u8_main_issue(const float* __restrict__ img, ptrdiff_t stride, int w, int h, int x0, int y0, int ndw,
                                                     int tid, U8MainLoads<NROWS>& ld) {
-  const bool vec4 = ((reinterpret_cast<uintptr_t>(img) & 15) == 0) && ((stride & 3) == 0);
   if (tid < ndw) {
     const int x = x0 + 4 * tid;
-    const bool colin = x + 3 < w;
-    const int off = colin ? x : 0;
+    const int off = (x + 3 < w) ? x : 0;
+    const int hv = w >= 4 ? h : 0;             // (an image narrower than a group has no full group: every load is the dummy one of row 0)
 #pragma unroll
     for (int r = 0; r < NROWS; ++r) {
-      const float* rowp = (y0 + r < h) ? img + (ptrdiff_t)(y0 + r) * stride : img;   // uniform
-      if (vec4) ld.v[r] = *reinterpret_cast<const float4*>(rowp + off);
-      else ld.v[r] = make_float4(rowp[off], rowp[off + (colin ? 1 : 0)], rowp[off + (colin ? 2 : 0)], rowp[off + (colin ? 3 : 0)]);
+      const float* rowp = (y0 + r < hv) ? img + (ptrdiff_t)(y0 + r) * stride : img;   // uniform
+      ld.v[r] = load_f4(rowp + off);
     }
   }
 }
@@ -110,11 +115,6 @@ template <int NROWS>
 __device__ __forceinline__ void stage_u8_rest(const float* __restrict__ img, ptrdiff_t stride, int w, int h,
                                               int x0, int y0, int ndw, int dst_pitch_dw,
                                               u32* __restrict__ dst, int tid, int nthreads, u32& acc) {
-  const bool vec4 = ((reinterpret_cast<uintptr_t>(img) & 15) == 0) && ((stride & 3) == 0);
-  auto load4 = [&](const float* rowp, int off, bool full) __attribute__((always_inline)) -> float4 {
-    if (vec4) return *reinterpret_cast<const float4*>(rowp + off);
-    return make_float4(rowp[off], rowp[off + (full ? 1 : 0)], rowp[off + (full ? 2 : 0)], rowp[off + (full ? 3 : 0)]);
-  };
   const int rem = ndw - nthreads;
   if (rem > 0) {
     const int total = NROWS * rem;
@@ -132,7 +132,7 @@ __device__ __forceinline__ void stage_u8_rest(const float* __restrict__ img, ptr
         inb[k] = (idx < total) && (x + 3 < w) && (y0 + r < h);
         di[k] = (idx < total && (x + 3 < w || x >= w)) ? r * dst_pitch_dw + g : -1;   // not the straddling group
         const float* src = inb[k] ? img + (ptrdiff_t)(y0 + r) * stride + x : img;
-        v[k] = load4(src, 0, inb[k]);
+        v[k] = load_f4(src);
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {

@@ -838,6 +838,79 @@ int vwgpu_universe_radius_dev(vwgpu_ctx* ctx, const double* d_points, int channe
 int vwgpu_universe_radius(vwgpu_ctx* ctx, const double* points, int channels, int w, int h, ptrdiff_t stride, const double* origin,
                           double near_radius, double far_radius, double* out, ptrdiff_t ostride, long long* counts);
 
+/* ---- epipolar rectification (tests/refimpl/epipolar_ref.cc) ---------------------- */
+
+/* The 3 x 4 row-major m_camera_matrix of PinholeModel::rebuild_camera_matrix (src/vw/Camera/PinholeModel.cc:593-603):
+ * K * [uvw * R^T | (uvw * (-R^T)) * C], every product a dot_prod whose accumulator starts from zero.  Same arguments and
+ * the same checks as vwgpu_pinhole_camera (pixel_pitch and distortion are not used); out receives 12 doubles.  The forward
+ * projection needs exactly these bits, and inv_camera_transform of the descriptor cannot give them back, so the matrix
+ * travels beside the descriptor.  Pure host arithmetic, no context. */
+int vwgpu_pinhole_camera_matrix(const double* center, const double* rotation, double fu, double fv, double cu, double cv,
+                                const double* u_dir, const double* v_dir, const double* w_dir, double pixel_pitch, int distortion_kind,
+                                const double* distortion, double* out);
+
+/* epipolar(PinholeModel, PinholeModel, ...) (src/vw/Camera/PinholeModel.cc:679-732): from the centres, the camera-to-world
+ * rotations (3 x 3 row-major), focal lengths (fu, fv), point offsets (cu, cv) and pixel pitches of two pinholes, the common
+ * rotation, focal length, point offset and pitch of the two rectified cameras.  The rotations go through
+ * camera_pose().rotation_matrix(), a round trip through a quaternion (src/vw/Math/Quaternion.h:211-340), as in the
+ * reference.  The caller builds the output cameras with the null lens, the default u, v, w and the input centres.
+ * Null pointers or equal centres (no baseline): VWGPU_ERR_ARGUMENT.  Pure host arithmetic, no context. */
+int vwgpu_epipolar_pinhole(const double* center0, const double* rotation0, const double* focal0, const double* offset0, double pitch0,
+                           const double* center1, const double* rotation1, const double* focal1, const double* offset1, double pitch1,
+                           double* rotation, double* focal, double* offset, double* pitch);
+
+/* epipolar(CAHVModel, CAHVModel, ...) (src/vw/Camera/CAHVModel.cc:297-337).  Anything but two CAHV descriptors, null
+ * pointers or equal centres: VWGPU_ERR_ARGUMENT.  Pure host arithmetic, no context. */
+int vwgpu_epipolar_cahv(const vwgpu_camera* src0, const vwgpu_camera* src1, vwgpu_camera* dst0, vwgpu_camera* dst1);
+
+/* Replaces rasterising camera_transform(image, src_camera, dst_camera, size, edge, BilinearInterpolation())
+ * (src/vw/Camera/CameraTransform.h:43-183) for a float image with an optional validity mask (PixelMask<float>).
+ *   src          sw x sh floats; src_mask optional uint8 of the same size (0 = invalid); strides in elements, 0 = packed
+ *   src_matrix, dst_matrix   vwgpu_pinhole_camera_matrix of a pinhole camera; NULL for a CAHV camera
+ *   w, h         output size; x0, y0 the image coordinates of output pixel (0, 0): a tile equals that region of the whole call
+ *   edge_value, edge_valid   the ValueEdgeExtension pixel; 0, 0 is ZeroEdgeExtension
+ *   check        PinholeModel::set_do_point_to_pixel_check of the source camera (the reference's default is on)
+ *   out          w x h floats; out_mask optional uint8 (255 valid, 0 invalid)
+ *   failed       optional count of pixels whose projection failed the check: a DEVICE long long for _dev (no
+ *                synchronisation), a host long long otherwise
+ * Output pixel p = (x0 + x, y0 + y): CameraTransform::reverse, q = src.point_to_pixel(dst.pixel_to_vector(p) + centre) in
+ * double in the reference's expression order (the rays of vwgpu_stereo_triangulate; CAHVModel.cc:167-171 or
+ * PinholeModel.cc:351-368 with TsaiLensDistortion::distorted_coordinates), then BilinearInterpolationImpl
+ * (src/vw/Image/Interpolation.h:76-110) exactly as vwgpu_disparity_warp computes it: the pixel itself at an integer
+ * position, otherwise four taps weighted in float, every product and sum rounded on its own; taps outside the source are
+ * the edge pixel.  A coordinate that is NaN or beyond +-2^30 gives 0, and in the masked form {0, invalid}.  The masked
+ * value is formed from the values whatever their validity, and is valid only if every tap used is valid
+ * (src/vw/Image/PixelMask.h:321-345, :424-433).  Where the reference throws PointToPixelErr (the round trip of
+ * PinholeModel.cc:378-394, ERROR_THRESHOLD 0.01) the pixel is written as the edge pixel and counted; the host-pointer
+ * entry then returns VWGPU_ERR_LOGIC with the reference's message and the count in vwgpu_last_error (the images are
+ * complete), the _dev entry only writes the count.
+ * Cameras whose centres differ: VWGPU_ERR_LOGIC (the reference's assert) before any device work.  Null src / out /
+ * cameras, sizes <= 0, a stride below the width, a camera or lens kind out of range, a pinhole without its matrix, out or
+ * out_mask aliasing an input or each other, a NaN edge_value with edge_valid: VWGPU_ERR_ARGUMENT before any device work. */
+int vwgpu_camera_transform_dev(vwgpu_ctx* ctx, const float* d_src, int sw, int sh, ptrdiff_t sstride, const uint8_t* d_src_mask,
+                               ptrdiff_t mstride, const vwgpu_camera* src_camera, const double* src_matrix,
+                               const vwgpu_camera* dst_camera, const double* dst_matrix, int w, int h, int x0, int y0, float edge_value,
+                               int edge_valid, int check, float* d_out, ptrdiff_t ostride, uint8_t* d_out_mask, ptrdiff_t omstride,
+                               long long* d_failed);
+int vwgpu_camera_transform(vwgpu_ctx* ctx, const float* src, int sw, int sh, ptrdiff_t sstride, const uint8_t* src_mask, ptrdiff_t mstride,
+                           const vwgpu_camera* src_camera, const double* src_matrix, const vwgpu_camera* dst_camera,
+                           const double* dst_matrix, int w, int h, int x0, int y0, float edge_value, int edge_valid, int check, float* out,
+                           ptrdiff_t ostride, uint8_t* out_mask, ptrdiff_t omstride, long long* failed);
+
+/* CameraTransform::forward / reverse (CameraTransform.h:52-74) of n points (x, y double pairs): forward is
+ * dst.point_to_pixel(src.pixel_to_vector(p) + centre), reverse the other way round.  `check` is that of the camera
+ * projected into.  A point whose projection fails the check becomes a NaN pair and is counted (failed as above; the
+ * host-pointer entry returns VWGPU_ERR_LOGIC).  This is what compute_transformed_bbox_fast needs for
+ * resize_epipolar_cameras_to_fit: the Tsai Newton solver exists on the device only.  n <= 0, null pointers, a direction
+ * out of range and the camera errors above: VWGPU_ERR_ARGUMENT; unequal centres: VWGPU_ERR_LOGIC.  out == points is allowed. */
+typedef enum vwgpu_camera_transform_direction { VWGPU_CAMERA_TRANSFORM_FORWARD = 0, VWGPU_CAMERA_TRANSFORM_REVERSE = 1 } vwgpu_camera_transform_direction;
+int vwgpu_camera_transform_points_dev(vwgpu_ctx* ctx, const vwgpu_camera* src_camera, const double* src_matrix,
+                                      const vwgpu_camera* dst_camera, const double* dst_matrix, int direction, int check,
+                                      const double* d_points, long long n, double* d_out, long long* d_failed);
+int vwgpu_camera_transform_points(vwgpu_ctx* ctx, const vwgpu_camera* src_camera, const double* src_matrix,
+                                  const vwgpu_camera* dst_camera, const double* dst_matrix, int direction, int check, const double* points,
+                                  long long n, double* out, long long* failed);
+
 /* ---- disparity clean-up filters and the zone scheduler ------------------------------------------------- */
 
 /* Replaces rasterising vw::stereo::rm_outliers_using_thresh (cleanup == 0) or

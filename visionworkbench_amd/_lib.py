@@ -35,6 +35,8 @@ SYMBOLS = [
     "vwgpu_intersect_mask_and_data_dev", "vwgpu_intersect_mask_and_data",
     "vwgpu_pinhole_camera", "vwgpu_stereo_triangulate_dev", "vwgpu_stereo_triangulate",
     "vwgpu_convergence_angle_dev", "vwgpu_convergence_angle", "vwgpu_universe_radius_dev", "vwgpu_universe_radius",
+    "vwgpu_pinhole_camera_matrix", "vwgpu_epipolar_pinhole", "vwgpu_epipolar_cahv",
+    "vwgpu_camera_transform_dev", "vwgpu_camera_transform", "vwgpu_camera_transform_points_dev", "vwgpu_camera_transform_points",
     "vwgpu_disparity_filter_dev", "vwgpu_disparity_filter",
     "vwgpu_disparity_mask_dev", "vwgpu_disparity_mask",
     "vwgpu_subdivide_regions",
@@ -227,6 +229,15 @@ def load():
     unr = [P, P, I, I, I, PD, P, D, D, P, PD, P]
     lib.vwgpu_universe_radius_dev.argtypes = unr
     lib.vwgpu_universe_radius.argtypes = unr
+    lib.vwgpu_pinhole_camera_matrix.argtypes = [P, P, D, D, D, D, P, P, P, D, I, P, P]
+    lib.vwgpu_epipolar_pinhole.argtypes = [P, P, P, P, D, P, P, P, P, D, P, P, P, P]
+    lib.vwgpu_epipolar_cahv.argtypes = [CP, CP, CP, CP]
+    ctr = [P, P, I, I, PD, P, PD, CP, P, CP, P, I, I, I, I, F, I, I, P, PD, P, PD, P]
+    lib.vwgpu_camera_transform_dev.argtypes = ctr
+    lib.vwgpu_camera_transform.argtypes = ctr
+    ctp = [P, CP, P, CP, P, I, I, P, ctypes.c_longlong, P, P]
+    lib.vwgpu_camera_transform_points_dev.argtypes = ctp
+    lib.vwgpu_camera_transform_points.argtypes = ctp
     df = [P, P, I, I, I, I, D, D, I, P]
     lib.vwgpu_disparity_filter_dev.argtypes = df
     lib.vwgpu_disparity_filter.argtypes = df

@@ -1,15 +1,18 @@
-"""The part of vw::camera that triangulation needs: PinholeModel with the null or the Tsai lens distortion and CAHVModel.
+"""The part of vw::camera that triangulation and epipolar rectification need: PinholeModel with the null or the Tsai lens
+distortion and CAHVModel, epipolar(), resize_epipolar_cameras_to_fit, CameraTransform and camera_transform.
 
-Each model is a host object that produces the flat camera descriptor of the C ABI (struct vwgpu_camera, include/vwgpu.h);
-the rays themselves are computed on the device inside stereo.stereo_triangulate / stereo.StereoModel.  point_to_pixel and
-the camera matrix are host conveniences in numpy (scene building, tests); nothing here needs a GPU.
+Each model is a host object that produces the flat camera descriptor of the C ABI (struct vwgpu_camera, include/vwgpu.h)
+and, for a pinhole, the 3 x 4 camera matrix that travels beside it; the rays and projections themselves are computed on
+the device (stereo.stereo_triangulate, camera_transform, CameraTransform).  point_to_pixel is a host convenience in numpy
+(scene building, tests); the models and epipolar() need no GPU.
 """
 import ctypes
 
 import numpy as np
 
 from . import _lib
-from .core import ArgumentErr
+from ._operands import Operands
+from .core import ArgumentErr, BBox2i
 
 CAMERA_PINHOLE, CAMERA_CAHV = 0, 1
 DISTORTION_NULL, DISTORTION_TSAI = 0, 1
@@ -69,18 +72,32 @@ class PinholeModel(object):
             params.ctypes.data if params is not None else None, ctypes.byref(self.descriptor))
         if rc != 0:
             raise ArgumentErr("PinholeModel: u, v, w must be orthonormal")
+        self.matrix = np.empty((3, 4), np.float64)
+        rc = _lib.load().vwgpu_pinhole_camera_matrix(
+            self.center.ctypes.data, self.rotation.ctypes.data, self.fu, self.fv, self.cu, self.cv, self.u.ctypes.data,
+            self.v.ctypes.data, self.w.ctypes.data, self.pixel_pitch, DISTORTION_TSAI if distortion is not None else DISTORTION_NULL,
+            params.ctypes.data if params is not None else None, self.matrix.ctypes.data)
+        if rc != 0:
+            raise ArgumentErr("PinholeModel: u, v, w must be orthonormal")
 
     def camera_center(self, pix=None):
         return self.center.copy()
 
     def camera_matrix(self):
-        """The 3 x 4 matrix K [uvw R^T | -uvw R^T C] of rebuild_camera_matrix (src/vw/Camera/PinholeModel.cc:593-603)."""
-        uvw = np.stack([self.u, self.v, self.w])
-        ext = np.empty((3, 4))
-        ext[:, :3] = uvw @ self.rotation.T
-        ext[:, 3] = uvw @ (-self.rotation.T) @ self.center
-        k = np.array([[self.fu, 0, self.cu], [0, self.fv, self.cv], [0, 0, 1.0]])
-        return k @ ext
+        """The 3 x 4 matrix K [uvw R^T | -uvw R^T C] of rebuild_camera_matrix (src/vw/Camera/PinholeModel.cc:593-603), in the
+        bits the reference's products give (vwgpu_pinhole_camera_matrix): what the device projects with."""
+        return self.matrix.copy()
+
+    def focal_length(self):
+        return np.array([self.fu, self.fv])
+
+    def point_offset(self):
+        return np.array([self.cu, self.cv])
+
+    def set_point_offset(self, offset):
+        """PinholeModel::set_point_offset: the descriptor and the camera matrix are rebuilt."""
+        self.__init__(self.center, self.rotation, self.fu, self.fv, offset[0], offset[1], self.u, self.v, self.w, self.distortion,
+                      self.pixel_pitch)
 
     def point_to_pixel(self, point):
         """PinholeModel::point_to_pixel without its round-trip check (src/vw/Camera/PinholeModel.cc:370-413)."""
@@ -123,4 +140,151 @@ def descriptor_of(camera):
     return d
 
 
-__all__ = ["PinholeModel", "TsaiLensDistortion", "CAHVModel", "descriptor_of"]
+def matrix_of(camera):
+    """The camera matrix that goes beside a descriptor: a (3, 4) float64 array for a PinholeModel, None for a CAHVModel."""
+    return getattr(camera, "matrix", None)
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def epipolar(cam0, cam1):
+    """vw::camera::epipolar(src0, src1, dst0, dst1) for two PinholeModels (src/vw/Camera/PinholeModel.cc:679-732) or two
+    CAHVModels (src/vw/Camera/CAHVModel.cc:297-337): the two rectified cameras.  Cameras without a baseline raise
+    ArgumentErr.  Host arithmetic in the library, no GPU."""
+    lib = _lib.load()
+    if isinstance(cam0, PinholeModel) and isinstance(cam1, PinholeModel):
+        rot, focal, offset, pitch = np.empty((3, 3)), np.empty(2), np.empty(2), ctypes.c_double(0)
+        f0, o0, f1, o1 = cam0.focal_length(), cam0.point_offset(), cam1.focal_length(), cam1.point_offset()
+        rc = lib.vwgpu_epipolar_pinhole(cam0.center.ctypes.data, cam0.rotation.ctypes.data, f0.ctypes.data, o0.ctypes.data, cam0.pixel_pitch,
+                                        cam1.center.ctypes.data, cam1.rotation.ctypes.data, f1.ctypes.data, o1.ctypes.data, cam1.pixel_pitch,
+                                        rot.ctypes.data, focal.ctypes.data, offset.ctypes.data, ctypes.addressof(pitch))
+        if rc != 0:
+            raise ArgumentErr("epipolar: the two cameras have the same centre")
+        return tuple(PinholeModel(c.center, rot, focal[0], focal[1], offset[0], offset[1], pixel_pitch=pitch.value) for c in (cam0, cam1))
+    if isinstance(cam0, CAHVModel) and isinstance(cam1, CAHVModel):
+        d0, d1 = _lib.Camera(), _lib.Camera()
+        rc = lib.vwgpu_epipolar_cahv(ctypes.byref(cam0.descriptor), ctypes.byref(cam1.descriptor), ctypes.byref(d0), ctypes.byref(d1))
+        if rc != 0:
+            raise ArgumentErr("epipolar: the two cameras have the same centre")
+        return tuple(CAHVModel(list(d.center), list(d.A), list(d.H), list(d.V)) for d in (d0, d1))
+    raise ArgumentErr("epipolar: expected two PinholeModels or two CAHVModels")
+
+
+FORWARD, REVERSE = 0, 1
+
+
+class CameraTransform(object):
+    """vw::camera::CameraTransform<Src, Dst>(src, dst) (src/vw/Camera/CameraTransform.h:43-79) for arrays of points:
+    forward maps pixels of src to pixels of dst, reverse the other way; both on the device.  The two cameras must share
+    their centre (LogicErr otherwise).  check: PinholeModel::set_do_point_to_pixel_check of the camera projected into; a
+    point that fails it raises LogicErr for numpy points, and becomes a NaN pair for tensors."""
+
+    def __init__(self, src, dst, check=True, ctx=None):
+        self.src, self.dst, self.check, self.ctx = src, dst, bool(check), ctx
+
+    def _run(self, direction, points):
+        ops = Operands("CameraTransform", points, self.ctx)
+        p = ops.image(points, np.float64)
+        if p.ndim < 1 or int(p.shape[-1]) != 2:
+            raise ArgumentErr("CameraTransform: the points must be (..., 2) {x, y}")
+        n = 1
+        for k in p.shape[:-1]:
+            n *= int(k)
+        if n <= 0:
+            raise ArgumentErr("CameraTransform: no points")
+        out = ops.empty(tuple(p.shape), np.float64)
+        ops.call("camera_transform_points", ctypes.byref(descriptor_of(self.src)), _ptr(matrix_of(self.src)),
+                 ctypes.byref(descriptor_of(self.dst)), _ptr(matrix_of(self.dst)), direction, int(self.check), ops.ptr(p), n, ops.ptr(out),
+                 None)
+        return out
+
+    def forward(self, points):
+        return self._run(FORWARD, points)
+
+    def reverse(self, points):
+        return self._run(REVERSE, points)
+
+
+def camera_transform(image, src, dst, size=None, mask=None, edge=(0, False), x0=0, y0=0, check=True, ctx=None, failed=None):
+    """camera_transform(image, src_camera, dst_camera, size, edge, BilinearInterpolation()) rasterised
+    (src/vw/Camera/CameraTransform.h:123-183): the (rows, cols) float32 image as the camera dst sees it.  size: (cols, rows)
+    of the result, the image's own by default; x0, y0: the image coordinates of its pixel (0, 0).  mask: an optional
+    validity mask of the image (PixelMask<float>); the result is then (image, uint8 mask 255 / 0), valid where every tap
+    is.  edge = (value, valid): the ValueEdgeExtension pixel; (0, False) is ZeroEdgeExtension.  check: the source
+    PinholeModel's point-to-pixel check (on by default, as in the reference); a failing pixel becomes the edge pixel, and
+    a numpy call then raises LogicErr with the reference's message, where a tensor call goes on without synchronising.
+    failed: an int64[1] CUDA tensor that receives the count of such pixels.  numpy in -> numpy out, CUDA tensors in -> CUDA
+    tensors out on the current torch stream."""
+    ops = Operands("camera_transform", image, ctx)
+    if image.ndim != 2:
+        raise ArgumentErr("camera_transform: the image must be (rows, cols)")
+    img = ops.image(image, np.float32, rows=True)
+    sh, sw = int(img.shape[0]), int(img.shape[1])
+    m = ops.nonzero_u8(mask, same_device=True)
+    if m is not None and tuple(m.shape) != (sh, sw):
+        raise ArgumentErr("camera_transform: the mask must have the image's shape")
+    w, h = (sw, sh) if size is None else (int(size[0]), int(size[1]))
+    if sw <= 0 or sh <= 0 or w <= 0 or h <= 0:
+        raise ArgumentErr("camera_transform: empty image")
+    out = ops.empty((h, w), np.float32)
+    out_mask = ops.empty((h, w), np.uint8) if m is not None else None
+    cnt = None
+    if failed is not None:
+        if not ops.tensor:
+            raise ArgumentErr("camera_transform: failed is an int64[1] CUDA tensor, with a CUDA image")
+        cnt = ops.ptr(ops.image(failed, np.int64, in_place=True))
+    ops.call("camera_transform", ops.ptr(img), sw, sh, ops.row_stride(img), ops.ptr(m), 0, ctypes.byref(descriptor_of(src)),
+             _ptr(matrix_of(src)), ctypes.byref(descriptor_of(dst)), _ptr(matrix_of(dst)), w, h, int(x0), int(y0), float(edge[0]),
+             int(bool(edge[1])), int(bool(check)), ops.ptr(out), 0, ops.ptr(out_mask), 0, cnt)
+    return out if m is None else (out, out_mask)
+
+
+def _roi_perimeter(roi):
+    """The points compute_transformed_bbox_fast visits (src/vw/Image/Transform.h:279-301), in its order."""
+    x0, y0, x1, y1 = roi.min[0], roi.min[1], roi.max[0], roi.max[1]
+    xs, ys = np.arange(x0, x1, dtype=np.float64), np.arange(y0, y1, dtype=np.float64)
+    return np.concatenate([np.stack([xs, np.full_like(xs, y0)], 1), np.stack([xs, np.full_like(xs, y1 - 1)], 1),
+                           np.stack([np.full_like(ys, x0), ys], 1), np.stack([np.full_like(ys, x1 - 1), ys], 1)])
+
+
+def compute_transformed_bbox_fast(roi, transform):
+    """compute_transformed_bbox_fast(roi, transform) (src/vw/Image/Transform.h:272-315): (min, max) of the BBox2f grown by
+    the forward-transformed perimeter of the BBox2i roi; the box is float, a coordinate is compared in double and stored
+    rounded to float (src/vw/Math/BBox.tcc:82-97)."""
+    pts = np.asarray(transform.forward(_roi_perimeter(roi)))
+    fmax = np.finfo(np.float32).max
+    lo, hi = np.array([fmax, fmax], np.float32), np.array([-fmax, -fmax], np.float32)    # BBox(): empty
+    for p in pts:
+        for i in (0, 1):
+            if p[i] > float(hi[i]):
+                hi[i] = np.float32(p[i])
+            if p[i] < float(lo[i]):
+                lo[i] = np.float32(p[i])
+    return lo, hi
+
+
+def resize_epipolar_cameras_to_fit(cam1, cam2, epi1, epi2, roi1, roi2, ctx=None):
+    """vw::camera::resize_epipolar_cameras_to_fit (src/vw/Camera/EpipolarUtils.cc:37-76): shifts the point offset of the two
+    rectified pinholes so that the transformed ROIs (BBox2i) begin at column and row 0; returns (epi1, epi2, size1, size2)
+    with the new cameras and the (cols, rows) needed to hold each transformed image."""
+    boxes = [compute_transformed_bbox_fast(roi, CameraTransform(c, e, ctx=ctx)) for c, e, roi in ((cam1, epi1, roi1), (cam2, epi2, roi2))]
+    min_col = min(float(boxes[0][0][0]), float(boxes[1][0][0]))
+    min_row = min(float(boxes[0][0][1]), float(boxes[1][0][1]))
+    point_offset = epi1.point_offset()
+    center_adjust = np.array([min_col, min_row]) * epi1.pixel_pitch
+    new = []
+    for e in (epi1, epi2):
+        n = PinholeModel(e.center, e.rotation, e.fu, e.fv, e.cu, e.cv, e.u, e.v, e.w, e.distortion, e.pixel_pitch)
+        n.set_point_offset(point_offset - center_adjust)
+        new.append(n)
+    sizes = []
+    for c, e, roi in ((cam1, new[0], roi1), (cam2, new[1], roi2)):
+        _, hi = compute_transformed_bbox_fast(roi, CameraTransform(c, e, ctx=ctx))
+        sizes.append((int(hi[0]), int(hi[1])))       # Vector2i = a float vector: truncation
+    return new[0], new[1], sizes[0], sizes[1]
+
+
+__all__ = ["PinholeModel", "TsaiLensDistortion", "CAHVModel", "descriptor_of", "matrix_of", "epipolar", "CameraTransform",
+           "camera_transform", "compute_transformed_bbox_fast", "resize_epipolar_cameras_to_fit", "BBox2i"]

@@ -1,0 +1,633 @@
+// camera_transform.hip — epipolar rectification: the host arithmetic of epipolar() for two pinholes
+// (src/vw/Camera/PinholeModel.cc:679-732, with the quaternion round trip of camera_pose().rotation_matrix(),
+// src/vw/Math/Quaternion.h:211-340) and two CAHV models (src/vw/Camera/CAHVModel.cc:297-337), the 3 x 4 camera matrix of
+// rebuild_camera_matrix (PinholeModel.cc:593-603), and the resampling camera_transform(image, src, dst, size, edge,
+// BilinearInterpolation()) (src/vw/Camera/CameraTransform.h:43-183): per output pixel CameraTransform::reverse
+// (dst.pixel_to_vector, src.point_to_pixel) and the bilinear tap of src/vw/Image/Interpolation.h:76-110 over a
+// ValueEdgeExtension, for float images with an optional validity mask (PixelMask<float>, src/vw/Image/PixelMask.h:321-345,
+// :424-433).  tests/refimpl/epipolar_ref.cc restates all of it and DESIGN §4.19 lists what is reproduced.
+//
+// One lane per output pixel, blocks of CT_BX x CT_BY, every band of CT_BY rows a workgroup of its own, no LDS.  Both
+// cameras and the source's camera matrix arrive by value and are read through scalar loads.  A lane gathers up to four
+// taps of the source and writes one float (and one mask byte); a wavefront's stores are row-contiguous.  The rays are
+// those of triangulate.hip (camera_rays.h).  A kernel is instantiated per (dst code, src code, masked): only a dst with
+// a lens, or a src with a lens whose round-trip check is on, carries the Newton loop.
+//
+// Everything up to the source position is double in the reference's expression order (-ffp-contract=off); the tap is
+// float, every product and sum rounded on its own.
+#include <cmath>
+#include <cstring>
+
+#include "camera_rays.h"
+#include "vwgpu_internal.h"
+
+namespace {
+
+#ifndef CT_BX
+#define CT_BX 64
+#define CT_BY 4
+#endif
+constexpr int CT_THREADS = CT_BX * CT_BY;
+constexpr int CT_COUNTERS = 1024;
+
+// how a kernel projects into a camera (point_to_pixel): a pinhole without the round-trip check (the lens kind is read at
+// run time: distorted_coordinates is closed form), a pinhole without lens with the check, a pinhole whose lens kind is
+// read at run time with the check (the Newton loop), CAHV (has no check)
+enum { CT_TO_PINHOLE_NOCHECK = 0, CT_TO_PINHOLE_NULL_CHECK = 1, CT_TO_PINHOLE_CHECK = 2, CT_TO_CAHV = 3 };
+
+struct ct_mat { double m[12]; };   // m_camera_matrix, row-major 3 x 4
+
+// TsaiLensDistortion::distorted_coordinates (LensDistortion.cc:345-369)
+__device__ inline tr_v2 ct_tsai_distort(const vwgpu_camera& c, const tr_v2& p) {
+  if (c.fu < 1e-300 || c.fv < 1e-300) return tr_v2{HUGE_VAL, HUGE_VAL};
+  const tr_v2 p0{(p.x - c.cu) / c.fu, (p.y - c.cv) / c.fv};
+  const tr_v2 d = tr_tsai_norm(p0, c.distortion);
+  double dx = d.x, dy = d.y;
+  dx = dx * c.fu + c.cu;
+  dy = dy * c.fv + c.cv;
+  return tr_v2{dx, dy};
+}
+
+// point_to_pixel of the camera `c`; false where PinholeModel::point_to_pixel throws PointToPixelErr (PinholeModel.cc:378-394)
+template <int TO>
+__device__ inline bool ct_point_to_pixel(const vwgpu_camera& c, const ct_mat& M, bool flip, const tr_v3& point, tr_v2& pix) {
+  if (TO == CT_TO_CAHV) {
+    // CAHVModel::point_to_pixel (CAHVModel.cc:167-171)
+    const tr_v3 d = tr_sub(point, tr_load3(c.center));
+    const double dDot = tr_dot(d, tr_load3(c.A));
+    pix = tr_v2{tr_dot(d, tr_load3(c.H)) / dDot, tr_dot(d, tr_load3(c.V)) / dDot};
+    return true;
+  }
+  // point_to_pixel_no_check (PinholeModel.cc:351-368)
+  const double* m = M.m;
+  const double den = m[8] * point.x + m[9] * point.y + m[10] * point.z + m[11];
+  tr_v2 pixel{(m[0] * point.x + m[1] * point.y + m[2] * point.z + m[3]) / den,
+              (m[4] * point.x + m[5] * point.y + m[6] * point.z + m[7]) / den};
+  if (TO != CT_TO_PINHOLE_NULL_CHECK && c.distortion_kind == VWGPU_DISTORTION_TSAI) pixel = ct_tsai_distort(c, pixel);
+  pix = tr_v2{pixel.x / c.pixel_pitch, pixel.y / c.pixel_pitch};
+  if (TO == CT_TO_PINHOLE_NOCHECK) return true;
+  // the round trip (:378-394)
+  const double ERROR_THRESHOLD = 0.01;
+  const tr_v3 pixel_vector = TO == CT_TO_PINHOLE_NULL_CHECK ? tr_ray<TR_CAM_PINHOLE_NULL>(c, pix, false) : tr_ray<TR_CAM_PINHOLE>(c, pix, false);
+  const tr_v3 phys_vector = tr_normalize(tr_sub(point, tr_load3(c.center)));
+  double diff = tr_norm(tr_sub(pixel_vector, phys_vector));
+  if (diff >= ERROR_THRESHOLD)
+    diff = tr_norm(tr_v3{pixel_vector.x + phys_vector.x, pixel_vector.y + phys_vector.y, pixel_vector.z + phys_vector.z});
+  return !(diff >= ERROR_THRESHOLD || diff != diff);
+}
+
+// CameraTransform::reverse / forward (CameraTransform.h:52-74): a pixel of `from` to the pixel of `to` that sees the same ray
+template <int FROM, int TO>
+__device__ inline bool ct_transform(const vwgpu_camera& from, bool flip_from, const vwgpu_camera& to, const ct_mat& Mto, const tr_v2& p,
+                                    tr_v2& q) {
+  const tr_v3 vec = tr_ray<FROM>(from, p, flip_from);
+  const tr_v3 point{vec.x + from.center[0], vec.y + from.center[1], vec.z + from.center[2]};
+  return ct_point_to_pixel<TO>(to, Mto, false, point, q);
+}
+
+// ---- the image ---------------------------------------------------------------------------------------------------------
+struct ct_args {
+  const float* src;
+  long long sstride;
+  int sw, sh;
+  const uint8_t* smask;
+  long long mstride;
+  int w, h;
+  int x0, y0;
+  int flip_dst;        // a CAHV dst: dot(cross(V, H), A) < 0
+  float edge_value;
+  int edge_valid;
+  float* out;
+  long long ostride;
+  uint8_t* omask;
+  long long omstride;
+  unsigned long long* failed;   // CT_COUNTERS words, or nullptr
+};
+
+// a pixel of the edge-extended source: ValueEdgeExtension(PixelMask<float>(edge_value) [invalidated])
+template <bool MASKED>
+__device__ inline float ct_tap(const ct_args& a, int x, int y, bool& valid) {
+  if (x >= 0 && y >= 0 && x < a.sw && y < a.sh) {
+    if (MASKED && a.smask && a.smask[(long long)y * a.mstride + x] == 0) valid = false;
+    return a.src[(long long)y * a.sstride + x];
+  }
+  if (MASKED && !a.edge_valid) valid = false;
+  return a.edge_value;
+}
+
+// Every band of CT_BY rows has a workgroup of its own, numbered through grid y and then z (as triangulate.hip does).
+__device__ inline bool ct_position(int w, int h, int& x, int& y, long long& band) {
+  x = blockIdx.x * CT_BX + threadIdx.x;
+  band = (long long)blockIdx.z * gridDim.y + blockIdx.y;
+  const long long row = band * CT_BY + threadIdx.y;
+  y = (int)row;
+  return x < w && row < h;
+}
+
+template <int DST, int SRC, bool MASKED>
+__global__ __launch_bounds__(CT_THREADS) void ct_image_kernel(ct_args a, vwgpu_camera dst, vwgpu_camera src, ct_mat Msrc) {
+  int x, y;
+  long long band;
+  bool failed = false;
+  if (ct_position(a.w, a.h, x, y, band)) {
+    const tr_v2 p{(double)((long long)a.x0 + x), (double)((long long)a.y0 + y)};
+    tr_v2 q;
+    float res = a.edge_value;
+    bool valid = a.edge_valid != 0;
+    if (ct_transform<DST, SRC>(dst, a.flip_dst != 0, src, Msrc, p, q)) {
+      // BilinearInterpolationImpl (Image/Interpolation.h:83-105).  Beyond 2^30 (or NaN) _floor's conversion to int32 is
+      // undefined: the result is 0 by definition, and the masked pixel is {0, invalid}.
+      const double lim = 1073741824.0;
+      res = 0.0f;
+      valid = false;
+      if (q.x >= -lim && q.x <= lim && q.y >= -lim && q.y <= lim) {
+        const int xi = (int)floor(q.x), yi = (int)floor(q.y);
+        valid = true;
+        if ((double)xi == q.x && (double)yi == q.y) {
+          res = ct_tap<MASKED>(a, xi, yi, valid);
+        } else {
+          const float normx = (float)q.x - (float)xi, normy = (float)q.y - (float)yi;
+          const float norm1mx = 1.0f - normx, norm1my = 1.0f - normy;
+          res = ct_tap<MASKED>(a, xi, yi, valid) * norm1mx;
+          res += ct_tap<MASKED>(a, xi + 1, yi, valid) * normx;
+          res *= norm1my;
+          float row = ct_tap<MASKED>(a, xi, yi + 1, valid) * norm1mx;
+          row += ct_tap<MASKED>(a, xi + 1, yi + 1, valid) * normx;
+          res += row * normy;
+        }
+      }
+    } else {
+      failed = true;   // PointToPixelErr: the edge pixel, counted
+    }
+    a.out[(long long)y * a.ostride + x] = res;
+    if (MASKED && a.omask) a.omask[(long long)y * a.omstride + x] = valid ? 255 : 0;
+  }
+  if (SRC == CT_TO_PINHOLE_NULL_CHECK || SRC == CT_TO_PINHOLE_CHECK) {
+    const int n = __syncthreads_count(failed);
+    if (n != 0 && threadIdx.x == 0 && threadIdx.y == 0)
+      atomicAdd(a.failed + (unsigned)((band * gridDim.x + blockIdx.x) % CT_COUNTERS), (unsigned long long)n);
+  }
+}
+
+// ---- points ------------------------------------------------------------------------------------------------------------
+struct ct_points_args {
+  const double* in;
+  double* out;
+  long long n;
+  int flip_from;
+  unsigned long long* failed;
+};
+template <int FROM, int TO, bool UNUSED>
+__global__ __launch_bounds__(CT_THREADS) void ct_points_kernel(ct_points_args a, vwgpu_camera from, vwgpu_camera to, ct_mat Mto) {
+  const long long i = (long long)blockIdx.x * CT_THREADS + threadIdx.y * CT_BX + threadIdx.x;
+  bool failed = false;
+  if (i < a.n) {
+    const tr_v2 p{a.in[2 * i], a.in[2 * i + 1]};
+    tr_v2 q;
+    if (!ct_transform<FROM, TO>(from, a.flip_from != 0, to, Mto, p, q)) {
+      failed = true;   // PointToPixelErr: a NaN pair, counted
+      q = tr_v2{__longlong_as_double(0x7ff8000000000000LL), __longlong_as_double(0x7ff8000000000000LL)};
+    }
+    a.out[2 * i] = q.x;
+    a.out[2 * i + 1] = q.y;
+  }
+  if (TO == CT_TO_PINHOLE_NULL_CHECK || TO == CT_TO_PINHOLE_CHECK) {
+    const int n = __syncthreads_count(failed);
+    if (n != 0 && threadIdx.x == 0 && threadIdx.y == 0) atomicAdd(a.failed + (blockIdx.x % CT_COUNTERS), (unsigned long long)n);
+  }
+}
+
+// the sum of the CT_COUNTERS words into word 0 (integers: any order)
+__global__ __launch_bounds__(CT_THREADS) void ct_count_fold_kernel(unsigned long long* counters) {
+  __shared__ unsigned long long lds[CT_THREADS];
+  const int tid = threadIdx.x;
+  unsigned long long s = 0;
+  for (int k = tid; k < CT_COUNTERS; k += CT_THREADS) s += counters[k];
+  lds[tid] = s;
+  __syncthreads();
+  if (tid == 0) {
+    for (int k = 1; k < CT_THREADS; ++k) s += lds[k];
+    counters[0] = s;
+  }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------
+
+const dim3 ct_block(CT_BX, CT_BY);
+dim3 ct_grid(int w, int h) {
+  const long long bands = ((long long)h + CT_BY - 1) / CT_BY, gy = bands < 65535 ? bands : 65535;
+  return dim3((unsigned)((w + CT_BX - 1) / CT_BX), (unsigned)gy, (unsigned)((bands + gy - 1) / gy));
+}
+
+int ct_cahv_flip(const vwgpu_camera& c) {
+  return c.kind == VWGPU_CAMERA_CAHV && tr_dot(tr_cross(tr_load3(c.V), tr_load3(c.H)), tr_load3(c.A)) < 0.0;   // CAHVModel.cc:182
+}
+
+int ct_camera_check(vwgpu_ctx* ctx, const char* name, const char* which, const vwgpu_camera* c, const double* matrix) {
+  if (!c) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: null %s camera", name, which);
+  if (c->kind != VWGPU_CAMERA_PINHOLE && c->kind != VWGPU_CAMERA_CAHV)
+    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: unknown camera kind %d", name, c->kind);
+  if (c->kind == VWGPU_CAMERA_PINHOLE && c->distortion_kind != VWGPU_DISTORTION_NULL && c->distortion_kind != VWGPU_DISTORTION_TSAI)
+    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: unknown lens distortion kind %d", name, c->distortion_kind);
+  if (c->kind == VWGPU_CAMERA_PINHOLE && !matrix)
+    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: the %s camera is a pinhole and has no camera matrix", name, which);
+  return VWGPU_OK;
+}
+
+int ct_same_center(vwgpu_ctx* ctx, const vwgpu_camera* src, const vwgpu_camera* dst) {
+  if (src->center[0] == dst->center[0] && src->center[1] == dst->center[1] && src->center[2] == dst->center[2]) return VWGPU_OK;
+  return vwgpu_fail(ctx, VWGPU_ERR_LOGIC,
+                    "CameraTransformFunctor: Camera transformation require that the camera center is always the same for both cameras.");
+}
+
+// the code a kernel carries for the camera whose rays it forms / for the camera it projects into
+int ct_from_code(const vwgpu_camera& c) {
+  return c.kind == VWGPU_CAMERA_CAHV ? TR_CAM_CAHV : c.distortion_kind == VWGPU_DISTORTION_NULL ? TR_CAM_PINHOLE_NULL : TR_CAM_PINHOLE;
+}
+int ct_to_code(const vwgpu_camera& c, int check) {
+  if (c.kind == VWGPU_CAMERA_CAHV) return CT_TO_CAHV;
+  if (!check) return CT_TO_PINHOLE_NOCHECK;
+  return c.distortion_kind == VWGPU_DISTORTION_NULL ? CT_TO_PINHOLE_NULL_CHECK : CT_TO_PINHOLE_CHECK;
+}
+bool ct_counts(int to) { return to == CT_TO_PINHOLE_NULL_CHECK || to == CT_TO_PINHOLE_CHECK; }
+
+ct_mat ct_matrix(const double* m) {
+  ct_mat M{};
+  if (m) std::memcpy(M.m, m, sizeof(M.m));
+  return M;
+}
+
+#define CT_LAUNCH_TO(KERNEL, FROM, TO, FLAG, GRID, ...)                                                                             \
+  do {                                                                                                                              \
+    switch (TO) {                                                                                                                   \
+      case CT_TO_PINHOLE_NOCHECK: hipLaunchKernelGGL((KERNEL<FROM, CT_TO_PINHOLE_NOCHECK, FLAG>), (GRID), ct_block, 0, ctx->stream, __VA_ARGS__); break;       \
+      case CT_TO_PINHOLE_NULL_CHECK: hipLaunchKernelGGL((KERNEL<FROM, CT_TO_PINHOLE_NULL_CHECK, FLAG>), (GRID), ct_block, 0, ctx->stream, __VA_ARGS__); break; \
+      case CT_TO_PINHOLE_CHECK: hipLaunchKernelGGL((KERNEL<FROM, CT_TO_PINHOLE_CHECK, FLAG>), (GRID), ct_block, 0, ctx->stream, __VA_ARGS__); break;           \
+      default: hipLaunchKernelGGL((KERNEL<FROM, CT_TO_CAHV, FLAG>), (GRID), ct_block, 0, ctx->stream, __VA_ARGS__); break;           \
+    }                                                                                                                               \
+  } while (0)
+#define CT_LAUNCH_FROM(KERNEL, FROM, TO, FLAG, GRID, ...)                                                        \
+  do {                                                                                                           \
+    switch (FROM) {                                                                                              \
+      case TR_CAM_PINHOLE_NULL: CT_LAUNCH_TO(KERNEL, TR_CAM_PINHOLE_NULL, TO, FLAG, GRID, __VA_ARGS__); break;   \
+      case TR_CAM_PINHOLE: CT_LAUNCH_TO(KERNEL, TR_CAM_PINHOLE, TO, FLAG, GRID, __VA_ARGS__); break;             \
+      default: CT_LAUNCH_TO(KERNEL, TR_CAM_CAHV, TO, FLAG, GRID, __VA_ARGS__); break;                            \
+    }                                                                                                            \
+  } while (0)
+
+// the counters of a call, zeroed; nullptr in *d_counter when the kernel does not count
+int ct_counters(vwgpu_ctx* ctx, bool counts, unsigned long long** d_counter) {
+  *d_counter = nullptr;
+  const size_t bytes = CT_COUNTERS * sizeof(unsigned long long);
+  int rc = vwgpu_arena_reserve(ctx, &ctx->scratch, bytes);
+  if (rc) return rc;
+  *d_counter = static_cast<unsigned long long*>(ctx->scratch.base);
+  // without the check nothing is counted and word 0 stays 0
+  VWGPU_HIP(ctx, hipMemsetAsync(*d_counter, 0, counts ? bytes : sizeof(unsigned long long), ctx->stream));
+  return VWGPU_OK;
+}
+
+// after the kernel: fold the counters; d_failed (device, optional) receives the count, *h_failed (host, optional) too (synchronises)
+int ct_count_out(vwgpu_ctx* ctx, bool counts, unsigned long long* d_counter, long long* d_failed, long long* h_failed) {
+  if (counts) hipLaunchKernelGGL(ct_count_fold_kernel, dim3(1), dim3(CT_THREADS), 0, ctx->stream, d_counter);
+  VWGPU_HIP(ctx, hipGetLastError());
+  if (d_failed) VWGPU_HIP(ctx, hipMemcpyAsync(d_failed, d_counter, 8, hipMemcpyDeviceToDevice, ctx->stream));
+  if (h_failed) {
+    unsigned long long cnt = 0;
+    VWGPU_HIP(ctx, hipMemcpyAsync(&cnt, d_counter, 8, hipMemcpyDeviceToHost, ctx->stream));
+    VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *h_failed = (long long)cnt;
+  }
+  return VWGPU_OK;
+}
+
+int ct_inaccurate(vwgpu_ctx* ctx, long long failed) {
+  return vwgpu_fail(ctx, VWGPU_ERR_LOGIC, "PinholeModel: Projection into pinhole camera is inaccurate. (%lld pixels)", failed);
+}
+
+struct ct_image_call {
+  const float* src; int sw, sh; ptrdiff_t sstride;
+  const uint8_t* smask; ptrdiff_t mstride;
+  const vwgpu_camera* src_cam; const double* src_matrix;
+  const vwgpu_camera* dst_cam; const double* dst_matrix;
+  int w, h, x0, y0;
+  float edge_value; int edge_valid, check;
+  float* out; ptrdiff_t ostride;
+  uint8_t* omask; ptrdiff_t omstride;
+};
+
+int ct_image_check(vwgpu_ctx* ctx, ct_image_call& c) {
+  const char* name = "camera_transform";
+  if (!ctx) return VWGPU_ERR_ARGUMENT;
+  ctx->err.clear();
+  if (!c.src || !c.out || c.sw <= 0 || c.sh <= 0 || c.w <= 0 || c.h <= 0)
+    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: empty image or null pointer", name);
+  int rc = ct_camera_check(ctx, name, "source", c.src_cam, c.src_matrix);
+  if (rc) return rc;
+  if ((rc = ct_camera_check(ctx, name, "destination", c.dst_cam, c.dst_matrix))) return rc;
+  if (c.sstride == 0) c.sstride = c.sw;
+  if (c.mstride == 0) c.mstride = c.sw;
+  if (c.ostride == 0) c.ostride = c.w;
+  if (c.omstride == 0) c.omstride = c.w;
+  if (c.sstride < c.sw || (c.smask && c.mstride < c.sw) || c.ostride < c.w || (c.omask && c.omstride < c.w))
+    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: row stride smaller than row width", name);
+  if ((const void*)c.out == (const void*)c.src || (const void*)c.out == (const void*)c.smask ||
+      (c.omask && ((const void*)c.omask == (const void*)c.src || c.omask == c.smask || (const void*)c.omask == (const void*)c.out)))
+    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: an output must not be an input or the other output", name);
+  if (c.edge_valid && std::isnan(c.edge_value)) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: a valid edge pixel must not be NaN", name);
+  return ct_same_center(ctx, c.src_cam, c.dst_cam);
+}
+
+// all pointers of `c` are device pointers here
+int ct_image_run(vwgpu_ctx* ctx, const ct_image_call& c, long long* d_failed, long long* h_failed) {
+  const int from = ct_from_code(*c.dst_cam), to = ct_to_code(*c.src_cam, c.check);
+  unsigned long long* d_counter = nullptr;
+  const bool want = d_failed || h_failed;
+  if (ct_counts(to) || want) {
+    int rc = ct_counters(ctx, ct_counts(to), &d_counter);
+    if (rc) return rc;
+  }
+  ct_args a{c.src, (long long)c.sstride, c.sw, c.sh, c.smask, (long long)c.mstride, c.w, c.h, c.x0, c.y0, ct_cahv_flip(*c.dst_cam),
+            c.edge_value, c.edge_valid != 0, c.out, (long long)c.ostride, c.omask, (long long)c.omstride, d_counter};
+  const ct_mat M = ct_matrix(c.src_matrix);
+  const bool masked = c.smask || c.omask;
+  {
+    vwgpu_prof_scope ps(ctx, "camera_transform");
+    if (masked) CT_LAUNCH_FROM(ct_image_kernel, from, to, true, ct_grid(c.w, c.h), a, *c.dst_cam, *c.src_cam, M);
+    else CT_LAUNCH_FROM(ct_image_kernel, from, to, false, ct_grid(c.w, c.h), a, *c.dst_cam, *c.src_cam, M);
+    VWGPU_HIP(ctx, hipGetLastError());
+  }
+  if (!want) return VWGPU_OK;
+  return ct_count_out(ctx, ct_counts(to), d_counter, d_failed, h_failed);
+}
+
+int ct_points_check(vwgpu_ctx* ctx, const vwgpu_camera* src, const double* src_matrix, const vwgpu_camera* dst, const double* dst_matrix,
+                    int direction, const double* points, long long n, const double* out) {
+  const char* name = "camera_transform_points";
+  if (!ctx) return VWGPU_ERR_ARGUMENT;
+  ctx->err.clear();
+  if (!points || !out || n <= 0) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: no points or null pointer", name);
+  if (direction != VWGPU_CAMERA_TRANSFORM_FORWARD && direction != VWGPU_CAMERA_TRANSFORM_REVERSE)
+    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: direction %d is neither forward nor reverse", name, direction);
+  int rc = ct_camera_check(ctx, name, "source", src, src_matrix);
+  if (rc) return rc;
+  if ((rc = ct_camera_check(ctx, name, "destination", dst, dst_matrix))) return rc;
+  return ct_same_center(ctx, src, dst);
+}
+
+int ct_points_run(vwgpu_ctx* ctx, const vwgpu_camera* src, const double* src_matrix, const vwgpu_camera* dst, const double* dst_matrix,
+                  int direction, int check, const double* d_points, long long n, double* d_out, long long* d_failed, long long* h_failed) {
+  const bool fwd = direction == VWGPU_CAMERA_TRANSFORM_FORWARD;
+  const vwgpu_camera& cfrom = fwd ? *src : *dst;
+  const vwgpu_camera& cto = fwd ? *dst : *src;
+  const int from = ct_from_code(cfrom), to = ct_to_code(cto, check);
+  unsigned long long* d_counter = nullptr;
+  const bool want = d_failed || h_failed;
+  if (ct_counts(to) || want) {
+    int rc = ct_counters(ctx, ct_counts(to), &d_counter);
+    if (rc) return rc;
+  }
+  ct_points_args a{d_points, d_out, n, ct_cahv_flip(cfrom), d_counter};
+  const ct_mat M = ct_matrix(fwd ? dst_matrix : src_matrix);
+  const dim3 grid((unsigned)((n + CT_THREADS - 1) / CT_THREADS));
+  {
+    vwgpu_prof_scope ps(ctx, "camera_transform_points");
+    CT_LAUNCH_FROM(ct_points_kernel, from, to, false, grid, a, cfrom, cto, M);
+    VWGPU_HIP(ctx, hipGetLastError());
+  }
+  if (!want) return VWGPU_OK;
+  return ct_count_out(ctx, ct_counts(to), d_counter, d_failed, h_failed);
+}
+
+// ---- host arithmetic -----------------------------------------------------------------------------------------------------
+
+// MatrixMatrixProduct (src/vw/Math/Matrix.h:2081-2086): a dot_prod per element, the accumulator starting from zero
+void ct_mat_mul3(const double* a, const double* b, double* out) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      double s = 0.0;
+      for (int k = 0; k < 3; ++k) s += a[i * 3 + k] * b[k * 3 + j];
+      out[i * 3 + j] = s;
+    }
+}
+
+// Quaternion(rotation).rotation_matrix() (Math/Quaternion.h:211-252, :314-329): what camera_pose().rotation_matrix() returns
+void ct_pose_round_trip(const double* rot, double* out) {
+  const double d0 = rot[0], d1 = rot[4], d2 = rot[8];
+  const double ww = 1.0 + d0 + d1 + d2;
+  const double xx = 1.0 + d0 - d1 - d2;
+  const double yy = 1.0 - d0 + d1 - d2;
+  const double zz = 1.0 - d0 - d1 + d2;
+  double max = ww;
+  if (xx > max) max = xx;
+  if (yy > max) max = yy;
+  if (zz > max) max = zz;
+  double c[4];
+  if (ww == max) {
+    const double w4 = sqrt(ww * 4.0);
+    c[0] = w4 / 4;
+    c[1] = (rot[7] - rot[5]) / w4;
+    c[2] = (rot[2] - rot[6]) / w4;
+    c[3] = (rot[3] - rot[1]) / w4;
+  } else if (xx == max) {
+    const double x4 = sqrt(xx * 4.0);
+    c[0] = (rot[7] - rot[5]) / x4;
+    c[1] = x4 / 4;
+    c[2] = (rot[1] + rot[3]) / x4;
+    c[3] = (rot[2] + rot[6]) / x4;
+  } else if (yy == max) {
+    const double y4 = sqrt(yy * 4.0);
+    c[0] = (rot[2] - rot[6]) / y4;
+    c[1] = (rot[1] + rot[3]) / y4;
+    c[2] = y4 / 4;
+    c[3] = (rot[5] + rot[7]) / y4;
+  } else {
+    const double z4 = sqrt(zz * 4.0);
+    c[0] = (rot[3] - rot[1]) / z4;
+    c[1] = (rot[2] + rot[6]) / z4;
+    c[2] = (rot[5] + rot[7]) / z4;
+    c[3] = z4 / 4;
+  }
+  const double w = c[0], x = c[1], y = c[2], z = c[3];
+  const double w2 = w * w, x2 = x * x, y2 = y * y, z2 = z * z;
+  const double wx = w * x, wy = w * y, wz = w * z;
+  const double xy = x * y, yz = y * z, zx = z * x;
+  out[0] = w2 + x2 - y2 - z2;
+  out[4] = w2 - x2 + y2 - z2;
+  out[8] = w2 - x2 - y2 + z2;
+  out[1] = 2 * (xy - wz);
+  out[2] = 2 * (zx + wy);
+  out[5] = 2 * (yz - wx);
+  out[3] = 2 * (xy + wz);
+  out[6] = 2 * (zx - wy);
+  out[7] = 2 * (yz + wx);
+}
+
+tr_v3 ct_scale(const tr_v3& a, double s) { return tr_v3{a.x * s, a.y * s, a.z * s}; }
+tr_v3 ct_div(const tr_v3& a, double s) { return tr_v3{a.x / s, a.y / s, a.z / s}; }
+tr_v3 ct_add(const tr_v3& a, const tr_v3& b) { return tr_v3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+void ct_store3(const tr_v3& a, double* p) { p[0] = a.x; p[1] = a.y; p[2] = a.z; }
+
+}  // namespace
+
+// ---- extern "C" entry points (include/vwgpu.h) -------------------------------------------------------------------------
+
+extern "C" {
+
+int vwgpu_pinhole_camera_matrix(const double* center, const double* rotation, double fu, double fv, double cu, double cv,
+                                const double* u_dir, const double* v_dir, const double* w_dir, double pixel_pitch, int distortion_kind,
+                                const double* distortion, double* out) {
+  (void)pixel_pitch; (void)distortion;
+  if (!center || !rotation || !u_dir || !v_dir || !w_dir || !out) return VWGPU_ERR_ARGUMENT;
+  if (distortion_kind != VWGPU_DISTORTION_NULL && distortion_kind != VWGPU_DISTORTION_TSAI) return VWGPU_ERR_ARGUMENT;
+  // the asserts of rebuild_camera_matrix (PinholeModel.cc:586-591)
+  const tr_v3 u = tr_load3(u_dir), v = tr_load3(v_dir), w = tr_load3(w_dir);
+  if (!(tr_dot(u, v) == 0) || !(tr_dot(u, w) == 0) || !(tr_dot(v, w) == 0)) return VWGPU_ERR_ARGUMENT;
+  if (!(fabs(tr_norm(u) - 1) < 0.001) || !(fabs(tr_norm(v) - 1) < 0.001) || !(fabs(tr_norm(w) - 1) < 0.001)) return VWGPU_ERR_ARGUMENT;
+  const double uvw[9] = {u.x, u.y, u.z, v.x, v.y, v.z, w.x, w.y, w.z};
+  const double rt[9] = {rotation[0], rotation[3], rotation[6], rotation[1], rotation[4], rotation[7], rotation[2], rotation[5], rotation[8]};
+  double neg_rt[9], r33[9], t33[9], ext[12];
+  for (int k = 0; k < 9; ++k) neg_rt[k] = -rt[k];
+  ct_mat_mul3(uvw, rt, r33);       // :600
+  ct_mat_mul3(uvw, neg_rt, t33);   // :601, (uvwRotation * (-rotation_inverse)) * m_camera_center
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) ext[i * 4 + j] = r33[i * 3 + j];
+    ext[i * 4 + 3] = tr_dot(tr_load3(t33 + 3 * i), tr_load3(center));
+  }
+  const double k[9] = {fu, 0, cu, 0, fv, cv, 0, 0, 1};
+  for (int i = 0; i < 3; ++i)      // :603
+    for (int j = 0; j < 4; ++j) {
+      double s = 0.0;
+      for (int q = 0; q < 3; ++q) s += k[i * 3 + q] * ext[q * 4 + j];
+      out[i * 4 + j] = s;
+    }
+  return VWGPU_OK;
+}
+
+int vwgpu_epipolar_pinhole(const double* center0, const double* rotation0, const double* focal0, const double* offset0, double pitch0,
+                           const double* center1, const double* rotation1, const double* focal1, const double* offset1, double pitch1,
+                           double* rotation, double* focal, double* offset, double* pitch) {
+  if (!center0 || !rotation0 || !focal0 || !offset0 || !center1 || !rotation1 || !focal1 || !offset1 || !rotation || !focal || !offset ||
+      !pitch)
+    return VWGPU_ERR_ARGUMENT;
+  const tr_v3 c0 = tr_load3(center0), c1 = tr_load3(center1);
+  if (c0.x == c1.x && c0.y == c1.y && c0.z == c1.z) return VWGPU_ERR_ARGUMENT;   // no baseline
+  double rot0[9], rot1[9];
+  ct_pose_round_trip(rotation0, rot0);
+  ct_pose_round_trip(rotation1, rot1);
+  const tr_v3 look0{-1 * rot0[2], -1 * rot0[5], -1 * rot0[8]}, look1{-1 * rot1[2], -1 * rot1[5], -1 * rot1[8]};
+  const tr_v3 u = ct_div(tr_sub(c1, c0), tr_norm(tr_sub(c1, c0)));
+  const tr_v3 mean_look = ct_div(ct_add(look0, look1), 2.0);
+  const tr_v3 temp = tr_cross(u, tr_cross(mean_look, u));
+  const tr_v3 w = ct_div(temp, tr_norm(temp));
+  const tr_v3 v = tr_cross(w, u);
+  const double new_rot[9] = {u.x, -v.x, -w.x, u.y, -v.y, -w.y, u.z, -v.z, -w.z};
+  std::memcpy(rotation, new_rot, sizeof(new_rot));
+  focal[0] = (focal0[0] + focal1[0]) / 2.0;
+  focal[1] = (focal0[1] + focal1[1]) / 2.0;
+  offset[0] = (offset0[0] + offset1[0]) / 2.0;
+  offset[1] = (offset0[1] + offset1[1]) / 2.0;
+  *pitch = (pitch0 + pitch1) / 2.0;
+  return VWGPU_OK;
+}
+
+int vwgpu_epipolar_cahv(const vwgpu_camera* src0, const vwgpu_camera* src1, vwgpu_camera* dst0, vwgpu_camera* dst1) {
+  if (!src0 || !src1 || !dst0 || !dst1) return VWGPU_ERR_ARGUMENT;
+  if (src0->kind != VWGPU_CAMERA_CAHV || src1->kind != VWGPU_CAMERA_CAHV) return VWGPU_ERR_ARGUMENT;
+  const tr_v3 C0 = tr_load3(src0->center), C1 = tr_load3(src1->center);
+  if (C0.x == C1.x && C0.y == C1.y && C0.z == C1.z) return VWGPU_ERR_ARGUMENT;
+  const tr_v3 A0 = tr_load3(src0->A), H0 = tr_load3(src0->H), V0 = tr_load3(src0->V);
+  const tr_v3 A1 = tr_load3(src1->A), H1 = tr_load3(src1->H), V1 = tr_load3(src1->V);
+  const double hc = tr_dot(H0, A0) / 2.0 + tr_dot(H1, A1) / 2.0;
+  const double vc = tr_dot(V0, A0) / 2.0 + tr_dot(V1, A1) / 2.0;
+  const double hs = tr_norm(tr_cross(A0, H0)) / 2.0 + tr_norm(tr_cross(A1, H1)) / 2.0;
+  const double vs = tr_norm(tr_cross(A0, V0)) / 2.0 + tr_norm(tr_cross(A1, V1)) / 2.0;
+  tr_v3 app = ct_add(A0, A1);
+  const tr_v3 f = tr_cross(tr_cross(app, tr_sub(C1, C0)), app);
+  tr_v3 hp;
+  if (tr_dot(f, H0) > 0) hp = ct_div(ct_scale(f, hs), tr_norm(f));
+  else hp = ct_div(ct_scale(tr_v3{-f.x, -f.y, -f.z}, hs), tr_norm(f));
+  app = ct_scale(app, 0.5);
+  const tr_v3 g = ct_div(ct_scale(hp, tr_dot(app, hp)), hs * hs);
+  const tr_v3 a = tr_normalize(tr_sub(app, g));
+  const tr_v3 vp = ct_div(ct_scale(tr_cross(a, hp), vs), hs);
+  vwgpu_camera out{};
+  out.kind = VWGPU_CAMERA_CAHV;
+  ct_store3(a, out.A);
+  ct_store3(ct_add(hp, ct_scale(a, hc)), out.H);
+  ct_store3(ct_add(vp, ct_scale(a, vc)), out.V);
+  ct_store3(C1, out.center);
+  const vwgpu_camera second = out;
+  ct_store3(C0, out.center);
+  *dst0 = out;
+  *dst1 = second;
+  return VWGPU_OK;
+}
+
+int vwgpu_camera_transform_dev(vwgpu_ctx* ctx, const float* d_src, int sw, int sh, ptrdiff_t sstride, const uint8_t* d_src_mask,
+                               ptrdiff_t mstride, const vwgpu_camera* src_camera, const double* src_matrix,
+                               const vwgpu_camera* dst_camera, const double* dst_matrix, int w, int h, int x0, int y0, float edge_value,
+                               int edge_valid, int check, float* d_out, ptrdiff_t ostride, uint8_t* d_out_mask, ptrdiff_t omstride,
+                               long long* d_failed) {
+  ct_image_call c{d_src, sw, sh, sstride, d_src_mask, mstride, src_camera, src_matrix, dst_camera, dst_matrix, w, h, x0, y0,
+                  edge_value, edge_valid, check, d_out, ostride, d_out_mask, omstride};
+  int rc = ct_image_check(ctx, c);
+  if (rc) return rc;
+  VWGPU_HIP(ctx, hipSetDevice(ctx->device));
+  return ct_image_run(ctx, c, d_failed, nullptr);
+}
+
+int vwgpu_camera_transform(vwgpu_ctx* ctx, const float* src, int sw, int sh, ptrdiff_t sstride, const uint8_t* src_mask, ptrdiff_t mstride,
+                           const vwgpu_camera* src_camera, const double* src_matrix, const vwgpu_camera* dst_camera,
+                           const double* dst_matrix, int w, int h, int x0, int y0, float edge_value, int edge_valid, int check, float* out,
+                           ptrdiff_t ostride, uint8_t* out_mask, ptrdiff_t omstride, long long* failed) {
+  ct_image_call c{src, sw, sh, sstride, src_mask, mstride, src_camera, src_matrix, dst_camera, dst_matrix, w, h, x0, y0,
+                  edge_value, edge_valid, check, out, ostride, out_mask, omstride};
+  int rc = ct_image_check(ctx, c);
+  if (rc) return rc;
+  VWGPU_HIP(ctx, hipSetDevice(ctx->device));
+  vwgpu_stage st(ctx);
+  const int ps = st.add(src, sw, sh, 4, c.sstride, VWGPU_STAGE_IN), pm = st.add(src_mask, sw, sh, 1, c.mstride, VWGPU_STAGE_IN),
+            po = st.add(out, w, h, 4, c.ostride, VWGPU_STAGE_OUT), pk = st.add(out_mask, w, h, 1, c.omstride, VWGPU_STAGE_OUT);
+  if ((rc = st.commit())) return rc;
+  ct_image_call d = c;
+  d.src = st.dev<float>(ps); d.sstride = sw;
+  d.smask = st.dev<uint8_t>(pm); d.mstride = sw;
+  d.out = st.dev<float>(po); d.ostride = w;
+  d.omask = st.dev<uint8_t>(pk); d.omstride = w;
+  long long count = 0;
+  if ((rc = ct_image_run(ctx, d, nullptr, &count))) return rc;
+  if ((rc = st.finish())) return rc;
+  if (failed) *failed = count;
+  return count != 0 ? ct_inaccurate(ctx, count) : VWGPU_OK;
+}
+
+int vwgpu_camera_transform_points_dev(vwgpu_ctx* ctx, const vwgpu_camera* src_camera, const double* src_matrix,
+                                      const vwgpu_camera* dst_camera, const double* dst_matrix, int direction, int check,
+                                      const double* d_points, long long n, double* d_out, long long* d_failed) {
+  int rc = ct_points_check(ctx, src_camera, src_matrix, dst_camera, dst_matrix, direction, d_points, n, d_out);
+  if (rc) return rc;
+  VWGPU_HIP(ctx, hipSetDevice(ctx->device));
+  return ct_points_run(ctx, src_camera, src_matrix, dst_camera, dst_matrix, direction, check, d_points, n, d_out, d_failed, nullptr);
+}
+
+int vwgpu_camera_transform_points(vwgpu_ctx* ctx, const vwgpu_camera* src_camera, const double* src_matrix,
+                                  const vwgpu_camera* dst_camera, const double* dst_matrix, int direction, int check, const double* points,
+                                  long long n, double* out, long long* failed) {
+  int rc = ct_points_check(ctx, src_camera, src_matrix, dst_camera, dst_matrix, direction, points, n, out);
+  if (rc) return rc;
+  if (n > 0x3fffffff) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "camera_transform_points: too many points for one call");
+  VWGPU_HIP(ctx, hipSetDevice(ctx->device));
+  vwgpu_stage st(ctx);
+  const int pi = st.add(points, (int)n, 1, 16, n, VWGPU_STAGE_IN), po = st.add(out, (int)n, 1, 16, n, VWGPU_STAGE_OUT);
+  if ((rc = st.commit())) return rc;
+  long long count = 0;
+  if ((rc = ct_points_run(ctx, src_camera, src_matrix, dst_camera, dst_matrix, direction, check, st.dev<double>(pi), n, st.dev<double>(po),
+                          nullptr, &count)))
+    return rc;
+  if ((rc = st.finish())) return rc;
+  if (failed) *failed = count;
+  return count != 0 ? ct_inaccurate(ctx, count) : VWGPU_OK;
+}
+
+}  // extern "C"

@@ -1027,6 +1027,36 @@ def universe_radius(points, origin, near_radius=0.0, far_radius=DBL_MAX, stats=N
     return res
 
 
+def epipolar_transformed_images(left, right, cam_l, cam_r, left_mask=None, right_mask=None, edge=(0, False), sizes=None,
+                                check=True, ctx=None):
+    """From two raw frames and their cameras to the epipolar-aligned pair (vw::camera::epipolar_transformed_images and
+    epipolar_transformed_cahv_images, src/vw/Camera/EpipolarUtils.cc:79-200, with the cameras given as models): epipolar(),
+    for pinholes resize_epipolar_cameras_to_fit over the whole frames, and one camera_transform per image.  Returns
+    (left_out, right_out, epi_l, epi_r), or with masks (left_out, left_out_mask, right_out, right_out_mask, epi_l, epi_r);
+    epi_l, epi_r are the rectified cameras stereo_triangulate takes for a disparity map of the aligned pair.
+    cam_l, cam_r: two camera.PinholeModel (null or Tsai lens) or two camera.CAHVModel.  (A distorted source against a CAHV
+    pair, the epipolar_transformed_cahv_images case, is two camera.camera_transform calls.)  The frames start at (0, 0):
+    there is no AdjustedCameraModel for cropped inputs.
+    sizes: ((cols, rows), (cols, rows)) of the results; by default what resize_epipolar_cameras_to_fit returns for
+    pinholes, and the frames' own sizes for CAHV models.  edge, check: as in camera.camera_transform."""
+    if left.ndim != 2 or right.ndim != 2:
+        raise ArgumentErr("epipolar_transformed_images: the images must be (rows, cols)")
+    epi_l, epi_r = camera.epipolar(cam_l, cam_r)
+    if isinstance(cam_l, camera.PinholeModel):
+        roi_l = BBox2i(0, 0, int(left.shape[1]), int(left.shape[0]))
+        roi_r = BBox2i(0, 0, int(right.shape[1]), int(right.shape[0]))
+        epi_l, epi_r, size_l, size_r = camera.resize_epipolar_cameras_to_fit(cam_l, cam_r, epi_l, epi_r, roi_l, roi_r, ctx=ctx)
+    else:
+        size_l, size_r = (int(left.shape[1]), int(left.shape[0])), (int(right.shape[1]), int(right.shape[0]))
+    if sizes is not None:
+        size_l, size_r = sizes
+    out_l = camera.camera_transform(left, cam_l, epi_l, size=size_l, mask=left_mask, edge=edge, check=check, ctx=ctx)
+    out_r = camera.camera_transform(right, cam_r, epi_r, size=size_r, mask=right_mask, edge=edge, check=check, ctx=ctx)
+    flat = lambda o: o if isinstance(o, tuple) else (o,)      # noqa: E731
+    return flat(out_l) + flat(out_r) + (epi_l, epi_r)
+
+
+# epipolar_transformed_images is public like fast_box_sum, and like it not listed: it is a composition of camera.py's wrappers
 __all__ = [
     "affine_subpixel",
     "bayes_em_subpixel",

@@ -1,8 +1,9 @@
-// vw/Camera.h — the part of vw::camera that triangulation needs: PinholeModel with the null or the Tsai lens distortion
-// (src/vw/Camera/PinholeModel.{h,cc}, LensDistortion.{h,cc}) and CAHVModel (src/vw/Camera/CAHVModel.{h,cc}).  Each model
-// carries the flat camera descriptor of the C ABI (struct vwgpu_camera, include/vwgpu.h), which is what the engine's
-// triangulation kernels read; pixel_to_vector, camera_center and point_to_pixel are host code for single pixels, with the
-// reference's expressions (the rays of whole images are computed on the device, vw/Stereo.h).
+// vw/Camera.h — the part of vw::camera that triangulation and epipolar rectification need: PinholeModel with the null or
+// the Tsai lens distortion (src/vw/Camera/PinholeModel.{h,cc}, LensDistortion.{h,cc}), CAHVModel
+// (src/vw/Camera/CAHVModel.{h,cc}) and epipolar() for both.  Each model carries the flat camera descriptor of the C ABI
+// (struct vwgpu_camera, include/vwgpu.h) and, for a pinhole, the 3 x 4 camera matrix beside it, which is what the engine's
+// kernels read; pixel_to_vector, camera_center and point_to_pixel are host code for single pixels, with the reference's
+// expressions (whole images are computed on the device: vw/Stereo.h, vw/CameraTransform.h).
 #ifndef VWLITE_CAMERA_H
 #define VWLITE_CAMERA_H
 
@@ -38,6 +39,10 @@ public:
   virtual Vector3 camera_center(Vector2 const& pix = Vector2()) const = 0;
   /// the descriptor the engine reads
   vwgpu_camera const& descriptor() const { return m_desc; }
+  /// m_camera_matrix (row-major 3 x 4) of a pinhole, which travels beside the descriptor; NULL for other models
+  virtual const double* camera_matrix() const { return NULL; }
+  /// PinholeModel::set_do_point_to_pixel_check (on by default, as in the reference); other models have no check
+  virtual bool do_point_to_pixel_check() const { return true; }
   static Vector2 invalid_pixel() { return Vector2(-1e8, -1e8); }
 protected:
   vwgpu_camera m_desc;
@@ -64,6 +69,8 @@ class PinholeModel : public CameraModel {
   Matrix3x3 m_rotation;
   Vector3 m_u, m_v, m_w;
   std::shared_ptr<TsaiLensDistortion> m_distortion;   // null: NullLensDistortion
+  double m_matrix[12];
+  bool m_check = true;
   void rebuild() {
     const double c[3] = {m_center[0], m_center[1], m_center[2]}, u[3] = {m_u[0], m_u[1], m_u[2]}, v[3] = {m_v[0], m_v[1], m_v[2]},
                  w[3] = {m_w[0], m_w[1], m_w[2]};
@@ -72,8 +79,11 @@ class PinholeModel : public CameraModel {
                                         m_distortion ? VWGPU_DISTORTION_TSAI : VWGPU_DISTORTION_NULL,
                                         m_distortion ? m_distortion->distortion_parameters() : NULL, &m_desc);
     VW_ASSERT(rc == VWGPU_OK, ArgumentErr() << "PinholeModel: the coordinate frame u, v, w must be orthonormal.");
+    vwgpu_pinhole_camera_matrix(c, m_rotation.data(), fu, fv, cu, cv, u, v, w, pitch, VWGPU_DISTORTION_NULL, NULL, m_matrix);
   }
+  static Matrix3x3 identity() { Matrix3x3 r; r.set_identity(); return r; }
 public:
+  PinholeModel() : PinholeModel(Vector3(0, 0, 0), identity(), 1, 1, 0, 0) {}
   PinholeModel(Vector3 const& center, Matrix3x3 const& rotation, double fu, double fv, double cu, double cv,
                Vector3 const& u = Vector3(1, 0, 0), Vector3 const& v = Vector3(0, 1, 0), Vector3 const& w = Vector3(0, 0, 1),
                TsaiLensDistortion const* distortion = NULL, double pixel_pitch = 1.0)
@@ -87,6 +97,14 @@ public:
       : PinholeModel(center, rotation, fu, fv, cu, cv, Vector3(1, 0, 0), Vector3(0, 1, 0), Vector3(0, 0, 1), distortion, pixel_pitch) {}
 
   Vector3 camera_center(Vector2 const& = Vector2()) const { return m_center; }
+  const double* camera_matrix() const { return m_matrix; }
+  Matrix3x3 const& get_rotation_matrix() const { return m_rotation; }
+  Vector2 focal_length() const { return Vector2(m_desc.fu, m_desc.fv); }
+  Vector2 point_offset() const { return Vector2(m_desc.cu, m_desc.cv); }
+  double pixel_pitch() const { return m_desc.pixel_pitch; }
+  void set_point_offset(Vector2 const& offset) { m_desc.cu = offset[0]; m_desc.cv = offset[1]; rebuild(); }
+  void set_do_point_to_pixel_check(bool value) { m_check = value; }
+  bool do_point_to_pixel_check() const { return m_check; }
 
   /// PinholeModel::pixel_to_vector (PinholeModel.cc:422-430); a Tsai lens is undone by the engine's restated solver on the
   /// device only, so this host method serves undistorted pinholes (NoImplErr otherwise)
@@ -119,6 +137,10 @@ public:
 class CAHVModel : public CameraModel {
 public:
   Vector3 C, A, H, V;
+  CAHVModel() : CAHVModel(Vector3(0, 0, 0), Vector3(0, 0, 1), Vector3(1, 0, 0), Vector3(0, 1, 0)) {}
+  explicit CAHVModel(vwgpu_camera const& d)
+      : CAHVModel(Vector3(d.center[0], d.center[1], d.center[2]), Vector3(d.A[0], d.A[1], d.A[2]), Vector3(d.H[0], d.H[1], d.H[2]),
+                  Vector3(d.V[0], d.V[1], d.V[2])) {}
   CAHVModel(Vector3 const& c, Vector3 const& a, Vector3 const& h, Vector3 const& v) : C(c), A(a), H(h), V(v) {
     m_desc = vwgpu_camera();
     m_desc.kind = VWGPU_CAMERA_CAHV;
@@ -139,6 +161,34 @@ public:
   }
   Vector3 camera_center(Vector2 const& = Vector2()) const { return C; }
 };
+
+/// epipolar(src0, src1, dst0, dst1) for two pinholes (PinholeModel.cc:679-732): host arithmetic in the engine
+/// (vwgpu_epipolar_pinhole); cameras without a baseline throw ArgumentErr.
+inline void epipolar(PinholeModel const& src_camera0, PinholeModel const& src_camera1, PinholeModel& dst_camera0, PinholeModel& dst_camera1) {
+  const Vector3 c0 = src_camera0.camera_center(), c1 = src_camera1.camera_center();
+  const Vector2 f0 = src_camera0.focal_length(), f1 = src_camera1.focal_length(), o0 = src_camera0.point_offset(), o1 = src_camera1.point_offset();
+  const double center0[3] = {c0[0], c0[1], c0[2]}, center1[3] = {c1[0], c1[1], c1[2]};
+  const double focal0[2] = {f0[0], f0[1]}, focal1[2] = {f1[0], f1[1]}, offset0[2] = {o0[0], o0[1]}, offset1[2] = {o1[0], o1[1]};
+  double rot[9], focal[2], offset[2], pitch;
+  const int rc = vwgpu_epipolar_pinhole(center0, src_camera0.get_rotation_matrix().data(), focal0, offset0, src_camera0.pixel_pitch(), center1,
+                                        src_camera1.get_rotation_matrix().data(), focal1, offset1, src_camera1.pixel_pitch(), rot, focal,
+                                        offset, &pitch);
+  VW_ASSERT(rc == VWGPU_OK, ArgumentErr() << "epipolar: the two cameras have the same centre.");
+  Matrix3x3 new_rot;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) new_rot(i, j) = rot[i * 3 + j];
+  dst_camera0 = PinholeModel(c0, new_rot, focal[0], focal[1], offset[0], offset[1], NULL, pitch);
+  dst_camera1 = PinholeModel(c1, new_rot, focal[0], focal[1], offset[0], offset[1], NULL, pitch);
+}
+
+/// epipolar(src0, src1, dst0, dst1) for two CAHV models (CAHVModel.cc:297-337).
+inline void epipolar(CAHVModel const& src_camera0, CAHVModel const& src_camera1, CAHVModel& dst_camera0, CAHVModel& dst_camera1) {
+  vwgpu_camera d0, d1;
+  const int rc = vwgpu_epipolar_cahv(&src_camera0.descriptor(), &src_camera1.descriptor(), &d0, &d1);
+  VW_ASSERT(rc == VWGPU_OK, ArgumentErr() << "epipolar: the two cameras have the same centre.");
+  dst_camera0 = CAHVModel(d0);
+  dst_camera1 = CAHVModel(d1);
+}
 
 }  // namespace camera
 }  // namespace vw

@@ -280,7 +280,13 @@ int vwgpu_generate_gaussian_kernel(double sigma, int size, float* taps, int cap)
  * pyramid-level operation of build_image_pyramids (src/vw/Stereo/CorrelationView.cc:210-214).
  *   nx / ny may be 0 (axis not filtered); cx, cy = kernel origins ((n-1)/2 is the reference's default).
  *   dst is (1+(w-1)/subsample) x (1+(h-1)/subsample).  x_kernel / y_kernel are HOST pointers in both variants.
- * Accumulation order and float arithmetic are the reference's; results are bit-identical for any float input. */
+ * Accumulation order and float arithmetic are the reference's; results are bit-identical for any float input.
+ * Accepted kernels: at most 160 taps per axis, and the two tiles of a workgroup must fit 64 KB of LDS:
+ *     ((15 s + 1 + max(ny - 1, 0)) * ((63 s + 1 + max(nx - 1, 0)) + 64)) * 4 <= 65536      (s = subsample)
+ *   so 67 x 67 taps at s = 1 (also 160 x 0 and 0 x 113), 39 x 39 at s = 2, 15 x 15 at s = 3.  Larger: VWGPU_ERR_NOIMPL.
+ * In place: NOT allowed.  Every output reads source pixels that other workgroups would overwrite; the _dev entry returns
+ *   VWGPU_ERR_ARGUMENT before any device work when the byte ranges of d_src and d_dst (strides included) overlap.
+ *   The host entry stages both images and may be given dst == src. */
 int vwgpu_separable_convolution_dev(vwgpu_ctx* ctx, const float* d_src, int w, int h, ptrdiff_t stride,
                                     const float* x_kernel, int nx, int cx, const float* y_kernel, int ny, int cy,
                                     int edge, int subsample, float* d_dst, ptrdiff_t dstride);
@@ -290,7 +296,9 @@ int vwgpu_separable_convolution(vwgpu_ctx* ctx, const float* src, int w, int h, 
 
 /* Replaces rasterising vw::convolution_filter(src, kernel, ci, cj, edge) for small 2-D kernels (<= 49 taps)
  * (ConvolutionView, src/vw/Image/Convolution.h:105-170); kernel is row-major kw x kh, HOST pointer.
- * vw::laplacian_filter (src/vw/Image/Filter.h:320-335) is this call with {0,1,0,1,-4,1,0,1,0}, origin (1,1). */
+ * vw::laplacian_filter (src/vw/Image/Filter.h:320-335) is this call with {0,1,0,1,-4,1,0,1,0}, origin (1,1).
+ * More than 49 taps: VWGPU_ERR_NOIMPL.  In place: NOT allowed, as for vwgpu_separable_convolution(_dev): overlapping
+ * d_src / d_dst are VWGPU_ERR_ARGUMENT before any device work; the host entry stages and may be given dst == src. */
 int vwgpu_convolution_2d_dev(vwgpu_ctx* ctx, const float* d_src, int w, int h, ptrdiff_t stride,
                              const float* kernel, int kw, int kh, int ci, int cj, int edge,
                              float* d_dst, ptrdiff_t dstride);
@@ -299,14 +307,22 @@ int vwgpu_convolution_2d(vwgpu_ctx* ctx, const float* src, int w, int h, ptrdiff
                          float* dst, ptrdiff_t dstride);
 
 /* Replaces vw::stereo::subsample_mask_by_two (src/vw/Stereo/CorrelationView.cc:38-63): a 2x2 block with at least
- * two non-zero pixels gives 255, else 0; dst is (1+(w-1)/2) x (1+(h-1)/2). */
+ * two non-zero pixels gives 255, else 0; dst is (1+(w-1)/2) x (1+(h-1)/2).
+ * In place: NOT allowed (an output's 2 x 2 block lies where other outputs are written): overlapping d_src / d_dst are
+ * VWGPU_ERR_ARGUMENT before any device work; the host entry stages and may be given dst == src. */
 int vwgpu_subsample_mask_by_two_dev(vwgpu_ctx* ctx, const uint8_t* d_src, int w, int h, ptrdiff_t stride,
                                     uint8_t* d_dst, ptrdiff_t dstride);
 int vwgpu_subsample_mask_by_two(vwgpu_ctx* ctx, const uint8_t* src, int w, int h, ptrdiff_t stride,
                                 uint8_t* dst, ptrdiff_t dstride);
 
 /* Replaces vw::stereo::prefilter_image (src/vw/Stereo/PreFilter.h:76-95): NONE = copy, MEANSUB = image -
- * gaussian_filter(image, width), LOG = laplacian_filter(gaussian_filter(image, width)); constant edge extension. */
+ * gaussian_filter(image, width), LOG = laplacian_filter(gaussian_filter(image, width)); constant edge extension.
+ * The Gaussian has max(3, 7 * width rounded down to odd) taps on each axis and goes through vwgpu_separable_convolution's
+ * limit at s = 1: 67 taps, width < 9.86 (69 taps).  Wider: VWGPU_ERR_NOIMPL.
+ * In place (d_dst == d_src, same stride): allowed for NONE, MEANSUB at any width and LOG with a non-empty kernel: the
+ *   Gaussian goes to a scratch image first, and what follows reads only that, or only the pixel it writes.  LOG with
+ *   width 0 is the bare Laplacian of the source: overlapping d_src / d_dst are VWGPU_ERR_ARGUMENT before any device work.
+ *   Operands that overlap without being the same image are undefined in the allowed forms too.  The host entry stages. */
 int vwgpu_prefilter_image_dev(vwgpu_ctx* ctx, const float* d_src, int w, int h, ptrdiff_t stride,
                               int mode, float width, float* d_dst, ptrdiff_t dstride);
 int vwgpu_prefilter_image(vwgpu_ctx* ctx, const float* src, int w, int h, ptrdiff_t stride,

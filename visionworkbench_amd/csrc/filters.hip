@@ -21,7 +21,11 @@
 
 namespace {
 
-constexpr int MAXT = 160;          // taps per axis (sigma up to ~22)
+// Taps per axis.  What a launch accepts is set by the 64 KB of LDS its two tiles need (vwgpu_launch_sepconv_jobs):
+//   ((15 s + 1 + max(ny - 1, 0)) * ((63 s + 1 + max(nx - 1, 0)) + 64)) * 4 <= 65536   with s the decimation step,
+// i.e. 67 x 67 taps at step 1 (a Gaussian of sigma <= 9.7 by its default size), 39 x 39 at step 2, 15 x 15 at step 3; one axis alone
+// takes 160 x 0 or 0 x 113 taps.  Anything larger is VWGPU_ERR_NOIMPL.
+constexpr int MAXT = 160;
 constexpr int TW = 64, TH = 16;    // outputs per workgroup
 
 struct Taps {

@@ -18,6 +18,16 @@ int check_image(vwgpu_ctx* ctx, const char* what, const void* src, int w, int h,
   return VWGPU_OK;
 }
 
+// The entries whose outputs read pixels that other workgroups write (neighbours, or the 2 x 2 block of a decimated mask) cannot work
+// in place: true when the byte ranges of the two strided images share a byte.
+bool images_overlap(const void* a, int aw, int ah, ptrdiff_t as, const void* b, int bw, int bh, ptrdiff_t bs, size_t elem) {
+  const char* a0 = static_cast<const char*>(a);
+  const char* b0 = static_cast<const char*>(b);
+  const char* a1 = a0 + ((size_t)(ah - 1) * as + aw) * elem;
+  const char* b1 = b0 + ((size_t)(bh - 1) * bs + bw) * elem;
+  return a0 < b1 && b0 < a1;
+}
+
 }  // namespace
 
 extern "C" {
@@ -69,6 +79,8 @@ int vwgpu_separable_convolution_dev(vwgpu_ctx* ctx, const float* d_src, int w, i
   const int ow = 1 + (w - 1) / subsample;
   if (dstride == 0) dstride = ow;
   if (dstride < ow) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "separable_convolution_filter: destination stride too small");
+  if (images_overlap(d_src, w, h, stride, d_dst, ow, 1 + (h - 1) / subsample, dstride, sizeof(float)))
+    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "separable_convolution_filter: source and destination overlap");
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
   return vwgpu_launch_sepconv(ctx, d_src, w, h, stride, xk, nx, cx, yk, ny, cy, edge, subsample, d_dst, dstride);
 }
@@ -99,6 +111,8 @@ int vwgpu_convolution_2d_dev(vwgpu_ctx* ctx, const float* d_src, int w, int h, p
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "convolution_filter: bad kernel / origin / edge argument");
   if (dstride == 0) dstride = w;
   if (dstride < w) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "convolution_filter: destination stride too small");
+  if (images_overlap(d_src, w, h, stride, d_dst, w, h, dstride, sizeof(float)))
+    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "convolution_filter: source and destination overlap");
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
   return vwgpu_launch_conv2d(ctx, d_src, w, h, stride, kernel, kw, kh, ci, cj, edge, d_dst, dstride);
 }
@@ -124,6 +138,8 @@ int vwgpu_subsample_mask_by_two_dev(vwgpu_ctx* ctx, const uint8_t* d_src, int w,
   const int ow = 1 + (w - 1) / 2;
   if (dstride == 0) dstride = ow;
   if (dstride < ow) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "subsample_mask_by_two: destination stride too small");
+  if (images_overlap(d_src, w, h, stride, d_dst, ow, 1 + (h - 1) / 2, dstride, sizeof(uint8_t)))
+    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "subsample_mask_by_two: source and destination overlap");
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
   return vwgpu_launch_mask_by_two(ctx, d_src, w, h, stride, d_dst, dstride);
 }
@@ -162,6 +178,9 @@ int vwgpu_prefilter_image_dev(vwgpu_ctx* ctx, const float* d_src, int w, int h, 
   if (nt < 0) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "prefilter_image: prefilter width %g too large", (double)width);
   if (nt == 0) {   // sigma == 0: empty kernels, gaussian_filter is the identity
     if (mode == VWGPU_PREFILTER_MEANSUB) return vwgpu_launch_subtract(ctx, d_src, stride, d_src, stride, w, h, d_dst, dstride);
+    // the Laplacian would read the image it writes (every other form goes through the scratch image and may run in place)
+    if (images_overlap(d_src, w, h, stride, d_dst, w, h, dstride, sizeof(float)))
+      return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "prefilter_image: LOG with an empty kernel cannot run in place");
     const float lap0[9] = {0, 1, 0, 1, -4, 1, 0, 1, 0};
     return vwgpu_launch_conv2d(ctx, d_src, w, h, stride, lap0, 3, 3, 1, 1, 0, d_dst, dstride);
   }

@@ -37,7 +37,7 @@ extern "C" {
  *     of version 2 changed, but observable behaviour did (VWGPU_PATH_CERTIFIED where a version-2 host saw VWGPU_PATH_EXACT_ORDER), and hosts
  *     compare versions for EQUALITY: a host built against version 2 refuses this library and is rebuilt against this header.
  *     Round 6 added option values only (VWGPU_OPT_SGM_PATH_MODE, VWGPU_OPT_SAD_GROUPS = 3): same version.
- *     VWGPU_OPT_SAD_LAYOUT, VWGPU_OPT_SAD_LAST_LAUNCH (options 20, 21) likewise.
+ *     VWGPU_OPT_SAD_LAYOUT, VWGPU_OPT_SAD_LAST_LAUNCH, VWGPU_OPT_SAD_ROUND_SLOTS (options 20, 21, 22) likewise.
  * A host checks vwgpu_abi_version() == VWGPU_ABI_VERSION once after loading the library (vw::engine does, vw/Engine.h). */
 #define VWGPU_ABI_VERSION 3
 
@@ -131,6 +131,10 @@ const char* vwgpu_last_error(const vwgpu_ctx* ctx);
  *       (row offsets are immediates; its rows are padded, so the widest searches keep the row-major array), 1 = always row-major.  Same results.
  *   VWGPU_OPT_SAD_LAST_LAUNCH  (read only) what the launcher chose for the context's last packed-u8 SAD launch (0 = none yet): bits 0-7 = tile
  *       rows, bits 8-11 = tile columns / 256, bits 12-15 = wave groups per tile, bit 16 = entry-major word groups.  For tests and tools.
+ *   VWGPU_OPT_SAD_ROUND_SLOTS  workgroup slots the packed-u8 SAD launcher assumes when it marks the first and the last round of dispatch of a
+ *       one-group grid (the first-round hand-off and the end balance engage on grids of at least two rounds): 0 (default) = from the
+ *       device's CU count, n (1 .. 1048576) = n slots — the launcher then plans, tile choice included, for a device of n / 2 CUs, so that
+ *       small grids reach the round logic of the kernels a large image runs.  Timing only; same results.  For tests and tools.
  *   VWGPU_OPT_EXACT_SCRATCH_MB scratch budget of the exact-order path in MiB (16 .. 65536, default 4096): column-sum volumes
  *       beyond it are swept in row bands / zone groups / disparity groups.
  *   VWGPU_OPT_TRACE            bit 0: host-side timeline of a pyramid tile on stderr, bit 1: the zone shapes of a level, bit 2: certification
@@ -177,7 +181,7 @@ typedef enum vwgpu_option {
   VWGPU_OPT_TRACE = 5, VWGPU_OPT_SGM_SWEEP = 6, /* 7: removed in ABI 2 */ VWGPU_OPT_MGM_SWEEP = 8, VWGPU_OPT_EXACT_SPLIT = 9,
   /* 10: removed in ABI 2 */ VWGPU_OPT_HOST_RING_KB = 11, VWGPU_OPT_HOST_RING_WRAPS = 12, VWGPU_OPT_CERTIFY = 13,
   VWGPU_OPT_CERT_PERMILLE = 14, VWGPU_OPT_ZONE_SXC = 15, VWGPU_OPT_CERT_F32 = 16, VWGPU_OPT_CERT_F64_PERMILLE = 17, VWGPU_OPT_ZONE_TILE16 = 18,
-  VWGPU_OPT_SGM_PATH_MODE = 19, VWGPU_OPT_SAD_LAYOUT = 20, VWGPU_OPT_SAD_LAST_LAUNCH = 21
+  VWGPU_OPT_SGM_PATH_MODE = 19, VWGPU_OPT_SAD_LAYOUT = 20, VWGPU_OPT_SAD_LAST_LAUNCH = 21, VWGPU_OPT_SAD_ROUND_SLOTS = 22
 } vwgpu_option;
 int vwgpu_set_option(vwgpu_ctx* ctx, int option, int value);
 int vwgpu_get_option(const vwgpu_ctx* ctx, int option, int* value);

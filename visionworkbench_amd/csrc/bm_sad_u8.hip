@@ -50,6 +50,8 @@
 //             through LDS and writes three coalesced 1 KiB pieces instead.
 //   grids     1-D grid, tile = XCD-banded raster order; grids too small for two waves per SIMD run the two-wave-group
 //             variant (SPLIT); tile height and variant are picked by pick_launch's cost model.
+//             One-group grids of two rounds or more: the second first-round workgroup of every CU starts 14 us late (first-round hand-off),
+//             and last-round workgroups take priority by the byte phases they have left (end balance).
 //
 // Limits (else the generic path): SAD only; kernel sizes in kLaunch; 4*ceil(kx/4)*ky*255 < 65536;
 // sx*sy <= 65535; LDS footprint <= 80 KiB.
@@ -133,6 +135,14 @@ __device__ __forceinline__ void divmod_small(int idx, int d, float inv, int& quo
   quo = qq; rem = rr;
 }
 
+// Which of the two first-round workgroups of a CU waits (see the kernel).  Workgroup i goes to XCD i % 8, and an XCD gives its first
+// workgroups one to each of its CUs before any CU gets a second: with j = i / 8 counting within the XCD, j and j + CUs per XCD share a CU
+// (stamps build: on 256 of 256 CUs in every run, profiles/sad_first_round_handoff.md; consecutive j never do), and the one with the
+// larger j is also the younger wave on every SIMD, which oldest-first arbitration serves second anyway.  first_round = 2 x CUs = 16 x CUs per XCD.
+__device__ __forceinline__ bool sad_second_on_cu(unsigned block, int first_round) {
+  return (int)(block >> 3) >= (first_round >> 4);
+}
+
 // dwords of the entry array: the word groups of a byte phase, or what borrows the array after the sweep (see the kernel)
 __host__ __device__ constexpr size_t ent_words(int nr, int ne, int ew, int gr, int ty, int pt) {
   const size_t ent = (size_t)nr * ne * ew;
@@ -161,7 +171,7 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
                  const float* __restrict__ R, ptrdiff_t rs, int rcw, int rch,
                  int sx, int sy, int ne, int32_t* __restrict__ out, ptrdiff_t os, int ow, int oh,
                  int* __restrict__ flag_set, int* __restrict__ flag_clear,
-                 int gxt, int ntiles, int last_round) {
+                 int gxt, int ntiles, int last_round, int first_round, int stagger_ticks) {
   typedef Cfg<KX, KY, TY, WV> C;
   constexpr bool SPLIT = GR > 1;
   constexpr int NW = C::NW, EW = C::EW, NR = C::NR;
@@ -206,6 +216,19 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
   }
 #endif
 
+  // First-round hand-off (one-group grids of two rounds or more; `first_round` = number of workgroups of the first round of dispatch, 0 = off).
+  // The two first-round workgroups of a CU would stage together, all CUs at once, while no SIMD of the chip has anything to issue; the one
+  // taken for the second of its CU starts `stagger_ticks` of the 100 MHz wall clock later, so that its neighbour stages at the rate of one
+  // tile pair per CU and sweeps while this one stages.  Wave 0 times the wait and the others meet it at the barrier.  The wait reads the
+  // clock only — nothing that another workgroup writes — and is capped, so it ends wherever the workgroups were placed; dispatch order is
+  // not defined, and a wrong guess costs time, never a result.
+  if (!SPLIT && (int)blockIdx.x < first_round && sad_second_on_cu(blockIdx.x, first_round)) {
+    if (tid < 64) {
+      const u64 t_start = wall_clock64();
+      for (int it = 0; it < 512 && wall_clock64() - t_start < (u64)stagger_ticks; ++it) __builtin_amdgcn_s_sleep(8);
+    }
+    __syncthreads();
+  }
   // ---- LEFT: float tile -> u8 in LDS (borrowing the entry array) -> per-lane register windows ----
   // Both tiles are staged before anything else is live in registers (the LEFT tile borrows the entry array).
   // (both images' main loads in flight before the first conversion — one memory latency instead of two — was tried for the
@@ -574,7 +597,7 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
 }
 
 typedef void (*KernelFn)(const float*, ptrdiff_t, int, int, const float*, ptrdiff_t, int, int, int, int, int,
-                         int32_t*, ptrdiff_t, int, int, int*, int*, int, int, int);
+                         int32_t*, ptrdiff_t, int, int, int*, int*, int, int, int, int, int);
 struct Launch {
   int kx, ky, ty;
   int threads, twb, nr, ew, nw;
@@ -661,6 +684,11 @@ const Launch* pick_launch(int kx, int ky, int ow, int oh, int num_cu, int groups
 
 constexpr size_t kMaxLds = 80 * 1024;   // two workgroups per CU
 
+// Delay of the late first-round workgroup of a CU in ticks of the 100 MHz wall clock: 14 us.  Swept on the 4096^2 headline against the
+// parent in alternating runs (profiles/sad_first_round_handoff.md; medians of three): 6 us -0.5, 8 us -0.7, 10 us -1.7, 12 us -2.2 / -2.3,
+// 13 us -2.9, 14 us -2.9 / -3.8 / -3.1, 15 us -2.3, 16 us -2.2, 18 us -2.9, 22 us -1.6, 26 and 30 us +0.3, 40 us +2.4, 60 us +7.7 us.
+constexpr int kStaggerTicks = 1400;
+
 int entries_per_row(const Launch& l, int sx) { return l.twb / 4 + ((sx + 2) >> 2) + 1; }
 
 // em: the entry-major array (rows padded to an odd count), else the row-major one
@@ -690,7 +718,9 @@ int vwgpu_launch_bm_sad_u8(vwgpu_ctx* ctx,
   (void)rw; (void)rh;
   const int ow = lw - kx + 1, oh = lh - ky + 1;
   bool split = false;
-  const Launch* l = pick_launch(kx, ky, ow, oh, ctx->num_cu, ctx->sad_groups, &split);
+  // VWGPU_OPT_SAD_ROUND_SLOTS = n: the launcher plans for n workgroup slots, i.e. a device of n / 2 CUs — tile choice and rounds alike
+  const int plan_cu = ctx->sad_round_slots > 0 ? (ctx->sad_round_slots + 1) / 2 : ctx->num_cu;
+  const Launch* l = pick_launch(kx, ky, ow, oh, plan_cu, ctx->sad_groups, &split);
   if (!l) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "no packed-u8 kernel for %dx%d", kx, ky);
   const int rcw = lw + sx - 1, rch = lh + sy - 1;
   const int gx = (ow + l->twb - 1) / l->twb, gy = (oh + l->ty - 1) / l->ty;
@@ -715,8 +745,12 @@ int vwgpu_launch_bm_sad_u8(vwgpu_ctx* ctx,
   const unsigned grid1 = (unsigned)((gx * gy + 7) / 8 * 8);   // one tile per workgroup, see the XCD note in the kernel
   // the end balance of the one-group matcher (see the kernel): workgroups are dispatched in index order, and the last `slots` of a grid
   // of two rounds or more are its last round; INT_MAX turns it off (one round: the slots start together, nothing to balance)
-  const int slots = ctx->num_cu * ((l->ty <= 8 && l->kx <= 8) ? 3 : 2);
-  const int last_round = (!split && (int)grid1 >= 2 * slots) ? (int)grid1 - slots : INT_MAX;
+  const int resident = (l->ty <= 8 && l->kx <= 8) ? 3 : 2;
+  const int slots = ctx->sad_round_slots > 0 ? ctx->sad_round_slots : ctx->num_cu * resident;
+  const bool rounds = !split && (int)grid1 >= 2 * slots;
+  const int last_round = rounds ? (int)grid1 - slots : INT_MAX;
+  // the first-round hand-off (see the kernel): the first `slots` workgroups, two to a CU
+  const int first_round = (rounds && resident == 2) ? slots : 0;
   if (shmem > 64 * 1024)
     VWGPU_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(main_fn),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
@@ -724,7 +758,7 @@ int vwgpu_launch_bm_sad_u8(vwgpu_ctx* ctx,
     vwgpu_prof_scope ps(ctx, "bm_sad_u8");
     hipLaunchKernelGGL(main_fn, dim3(grid1), dim3(split ? l->split_groups * l->threads : l->threads), shmem, ctx->stream,
                        left, ls, lw, lh, right, rs, rcw, rch, sx, sy, ne, out, os, ow, oh,
-                       flag_set, flag_clear, gx, gx * gy, last_round);
+                       flag_set, flag_clear, gx, gx * gy, last_round, first_round, kStaggerTicks);
   }
   VWGPU_HIP(ctx, hipGetLastError());
   return VWGPU_OK;

@@ -279,6 +279,7 @@ static const struct { int id; int vwgpu_ctx::* field; int lo, hi; bool settable;
   {VWGPU_OPT_SAD_GROUPS, &vwgpu_ctx::sad_groups, 0, 3, true},
   {VWGPU_OPT_SAD_LAYOUT, &vwgpu_ctx::sad_layout, 0, 1, true},
   {VWGPU_OPT_SAD_LAST_LAUNCH, &vwgpu_ctx::sad_last_launch, 0, 0, false},
+  {VWGPU_OPT_SAD_ROUND_SLOTS, &vwgpu_ctx::sad_round_slots, 0, 1 << 20, true},
   {VWGPU_OPT_EXACT_SCRATCH_MB, &vwgpu_ctx::exact_scratch_mb, 16, 65536, true},
   {VWGPU_OPT_TRACE, &vwgpu_ctx::trace, 0, 7, true},
   {VWGPU_OPT_CERTIFY, &vwgpu_ctx::certify, 0, 1, true},

@@ -232,6 +232,47 @@ def test_deferred_mode_returns_the_reference_bits_or_says_it_returned_none(ctx, 
     finally:
         ctx.force_path(core.PATH_NONE)
     assert p == core.PATH_REFUSED
+    # ... from every forced packed path: 64 x 16 (one workgroup, a partial tile in both directions), 7x7, 9 disparities.  Inside the
+    # family's domain the forced id and the oracle's bits; one pixel outside it PATH_REFUSED; a second search row, which the three
+    # one-row families do not serve, NoImplErr.
+    rng = np.random.default_rng(78)
+    for path, costs, top, stray in [(core.PATH_DOT_U8, (SQ, NCC), 256, 100.5), (core.PATH_SAD_U16, (ABS,), 65536, -3.0),
+                                    (core.PATH_DOT_U16, (SQ, NCC), 4096, 4096.0)]:
+        left = np.floor(1 + rng.random((16, 64)) * (top - 1)).astype(np.float32)
+        right = np.floor(1 + rng.random((17, 72)) * (top - 1)).astype(np.float32)
+        right[:16, 4:68] = np.where(rng.random((16, 64)) < 0.7, left, right[:16, 4:68])
+        left[2, 3] = top - 1.0
+        bad = left.copy(); bad[5, 7] = stray
+        for cost in costs:
+            got, p = _gpu(ctx, cost, left, right[:16], (7, 7), (9, 1), path=path)
+            assert p == path, (path, cost, p)
+            assert np.array_equal(got, oracle.calc_disparity(cost, left, right[:16], (7, 7), (9, 1))), (path, cost)
+            _, p = _gpu(ctx, cost, bad, right[:16], (7, 7), (9, 1), path=path)
+            assert p == core.PATH_REFUSED, (path, cost, p)
+            with pytest.raises(vwa.NoImplErr):
+                _gpu(ctx, cost, left, right, (7, 7), (9, 2), path=path)
+
+
+def test_refused_bytes_reorder_the_attempts_and_bytes_restore_them(oracle):
+    """The order of the attempts after a refusal (measure_first): byte imagery takes the packed-u8 kernel; 16-bit imagery is refused by
+    it, served by the packed-u16 kernel, and makes the context measure the class first; the next byte pair is measured, takes the
+    packed-u8 kernel again and ends the measuring.  Every result is the oracle's.  64 x 16, 7x7, 9 disparities, default options."""
+    rng = np.random.default_rng(79)
+    pairs = []
+    for top in (256, 65536):
+        left = np.floor(rng.random((16, 64)) * top).astype(np.float32)
+        right = np.floor(rng.random((16, 72)) * top).astype(np.float32)
+        right[:, 4:68] = np.where(rng.random((16, 64)) < 0.7, left, right[:, 4:68])
+        left[2, 3] = top - 1.0
+        pairs.append((left, right, oracle.calc_disparity(ABS, left, right, (7, 7), (9, 1))))
+    c = vwa.Context(0)
+    try:
+        for (left, right, want), want_path in [(pairs[0], core.PATH_SAD_U8), (pairs[1], core.PATH_SAD_U16), (pairs[0], core.PATH_SAD_U8)]:
+            got, p = _gpu(c, ABS, left, right, (7, 7), (9, 1))
+            assert p == want_path, (want_path, p)
+            assert np.array_equal(got, want), want_path
+    finally:
+        c.close()
 
 
 def test_trim_gives_the_arenas_back(oracle):

@@ -18,8 +18,9 @@
 //             valid <=> they differ (Correlation.cc:121-133)
 //   NCC       the two-largest-keys scheme of bm_corr_u8.hip (fp32 score with the disparity in the low mantissa bits; pixels whose
 //             runner-up is within 2^-13 are evaluated in float64 by ncc_full_kernel)
-// Inputs outside the domain, or an all-zero window under NCC, raise the device flag; the caller then runs the float64 kernel.
-// One search row (sy == 1).
+// Inputs outside the domain, or an all-zero window under NCC, raise the device flag (vwgpu_bm_matcher, vwgpu_internal.h); the caller
+// then runs the float64 kernel.  One search row (sy == 1).  The pair staging is stage_pair_rows of packed_tile.h, the NCC scratch
+// vwgpu_ncc_plan.
 //
 // Roofline: HBM bound by the task's definition (20 B per output pixel); VALU-issue bound in fact: (TY+ky-1)/TY * (kx/2 + 1) dot2 +
 // 5 (SSD) / 9 (NCC) instruction slots per (pixel, disparity).
@@ -28,9 +29,11 @@
 #include <type_traits>
 
 #include "vwgpu_internal.h"
+#include "packed_tile.h"
 
 namespace {
 
+using namespace vwgpu_packed;
 typedef uint32_t u32;
 typedef uint64_t u64;
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
@@ -41,30 +44,6 @@ constexpr u32 UMAXV = 4095u;
 
 __device__ __forceinline__ u32 dot2(u32 a, u32 b, u32 c) {
   return __builtin_amdgcn_udot2(__builtin_bit_cast(us2, a), __builtin_bit_cast(us2, b), c, false);
-}
-
-// float -> u16 with the exactness test of the path: integer-valued and inside [0,4095]
-__device__ __forceinline__ u32 to_u12(float v, bool& bad) {
-  const float r = rintf(v);
-  bad |= !(r == v && v >= 0.0f && v <= (float)UMAXV);
-  return (u32)(int)fminf(fmaxf(r, 0.0f), (float)UMAXV);
-}
-
-// dst[r][g] = pixels (x0 + 2g, x0 + 2g + 1) of row y0 + r as a u16 pair, zero outside the image
-template <int NROWS>
-__device__ __forceinline__ void stage_u12_rows(const float* __restrict__ img, ptrdiff_t stride, int w, int h, int x0, int y0,
-                                               int npairs, u32* __restrict__ dst, int tid, bool& bad) {
-  for (int i = tid; i < NROWS * npairs; i += UTHREADS) {
-    const int r = i / npairs, gq = i - r * npairs;
-    const int x = x0 + 2 * gq, y = y0 + r;
-    u32 p = 0;
-    if (y < h) {
-      const float* row = img + (ptrdiff_t)y * stride;
-      if (x < w) p = to_u12(row[x], bad);
-      if (x + 1 < w) p |= to_u12(row[x + 1], bad) << 16;
-    }
-    dst[i] = p;
-  }
 }
 
 struct U16Geom {
@@ -99,8 +78,8 @@ bm_corr_u16_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
   if (tid == 0 && blockIdx.x == 0 && blockIdx.y == 0) *flag_clear = 0;     // the NEXT call's flag
 
   bool bad = false;
-  stage_u12_rows<NR>(L, ls, lw, lh, x0, y0, LPD, LW, tid, bad);
-  stage_u12_rows<NR>(R, rs, rcw, rch, x0, y0, rpd, XR, tid, bad);
+  stage_pair_rows<NR, UMAXV, UTHREADS>(L, ls, lw, lh, x0, y0, LPD, LW, tid, bad);
+  stage_pair_rows<NR, UMAXV, UTHREADS>(R, rs, rcw, rch, x0, y0, rpd, XR, tid, bad);
   __syncthreads();
   // ---- LEFT pairs of this lane's column: pixels x + 2n, x + 2n + 1; the dead pixel of the last pair is cleared ----
   u32 lwn[NR][NWF + 1];
@@ -308,7 +287,7 @@ bm_corr_u16_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
 
 typedef void (*Corr16Fn)(const float*, ptrdiff_t, int, int, const float*, ptrdiff_t, int, int, U16Geom, int32_t*, ptrdiff_t, int, int, int*, int*,
                          u32*, u32*, int, u32*, u32*, u32);
-struct Corr16Launch { int cost, kx, ky, ty; Corr16Fn fn; };
+typedef Launch<Corr16Fn> Corr16Launch;
 // rows per workgroup: the LEFT pairs of TY + ky - 1 rows are registers (kx/2 + 1 each); the tallest TY that compiles without scratch
 // (measured at 4096^2 x 129: 9x9 at TY 16 spills 324 B and takes 2.43 ms, at TY 12 1.46 ms; 11x11 at TY 12 2.16 ms, at TY 8 1.54 ms)
 #define VW_C16(C, KX, KY, TY) Corr16Launch{C, KX, KY, TY, bm_corr_u16_kernel<C, KX, KY, TY>}
@@ -319,12 +298,6 @@ const Corr16Launch kCorr16[] = {
     VW_C16(VWGPU_CROSS_CORRELATION, 9, 9, 12), VW_C16(VWGPU_CROSS_CORRELATION, 11, 11, 8),
 };
 #undef VW_C16
-
-const Corr16Launch* find_corr16(int cost, int kx, int ky) {
-  for (const Corr16Launch& l : kCorr16)
-    if (l.cost == cost && l.kx == kx && l.ky == ky) return &l;
-  return nullptr;
-}
 
 U16Geom corr16_geom(int kx, int sx) {
   U16Geom g;
@@ -341,51 +314,33 @@ size_t corr16_lds(const Corr16Launch& l, const U16Geom& g) {
   return ((size_t)nr * g.urp + xr + (size_t)nr * (UTW / 2 + l.kx / 2 + 2)) * sizeof(u32);
 }
 
-}  // namespace
-
-bool vwgpu_bm_corr_u16_supported(int cost_type, int kx, int ky, int sx, int sy) {
-  const Corr16Launch* l = find_corr16(cost_type, kx, ky);
-  if (!l || sy != 1 || sx > 256) return false;
-  return corr16_lds(*l, corr16_geom(kx, sx)) <= 80 * 1024;       // two workgroups per CU
+bool supported(const vwgpu_bm_args& a) {
+  const Corr16Launch* l = find_launch(kCorr16, a.cost_type, a.kx, a.ky);
+  if (!l || a.sy != 1 || a.sx > 256) return false;
+  return corr16_lds(*l, corr16_geom(a.kx, a.sx)) <= 80 * 1024;   // two workgroups per CU
 }
 
-int vwgpu_launch_bm_corr_u16(vwgpu_ctx* ctx, int cost_type, const float* left, int lw, int lh, ptrdiff_t ls,
-                             const float* right, int rw, int rh, ptrdiff_t rs, int kx, int ky, int sx, int sy,
-                             int32_t* out, ptrdiff_t os, int** d_fallback_flag) {
-  (void)rw; (void)rh; (void)sy;
-  const Corr16Launch* l = find_corr16(cost_type, kx, ky);
-  if (!l) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "no packed-u16 SSD / NCC kernel for %dx%d", kx, ky);
-  const int ow = lw - kx + 1, oh = lh - ky + 1;
-  const int rcw = lw + sx - 1, rch = lh;
-  const U16Geom g = corr16_geom(kx, sx);
-  int* flag_set = nullptr; int* flag_clear = nullptr;
-  int rc = vwgpu_next_flags(ctx, 0, &flag_set, &flag_clear, nullptr);
-  if (rc) return rc;
-  *d_fallback_flag = flag_set;
-  const bool ncc = cost_type == VWGPU_CROSS_CORRELATION;
-  u32 *a2 = nullptr, *b2 = nullptr, *full_list = nullptr, *full_count = nullptr;
-  const int b2w = rcw - kx + 1;
-  const u32 cap = (u32)std::max<size_t>(4096, (size_t)ow * oh / 32);     // as bm_corr_u8.hip
-  if (ncc) {
-    if ((size_t)ow * oh >= 0xffffffffull) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "bm_corr_u16: image too large");
-    const size_t na = vwgpu_align_up((size_t)ow * oh * 4, 256), nb = vwgpu_align_up((size_t)b2w * oh * 4, 256),
-                 nl = vwgpu_align_up((size_t)cap * 4 + 256, 256);
-    rc = vwgpu_arena_reserve(ctx, &ctx->scratch, na + nb + nl);
-    if (rc) return rc;
-    char* base = static_cast<char*>(ctx->scratch.base);
-    a2 = reinterpret_cast<u32*>(base); b2 = reinterpret_cast<u32*>(base + na);
-    full_count = reinterpret_cast<u32*>(base + na + nb); full_list = full_count + 64;
-    VWGPU_HIP(ctx, hipMemsetAsync(full_count, 0, 4, ctx->stream));
-  }
+int launch(vwgpu_ctx* ctx, const vwgpu_bm_args& a, int** d_flag) {
+  const Corr16Launch* l = find_launch(kCorr16, a.cost_type, a.kx, a.ky);
+  if (!l) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "no packed-u16 SSD / NCC kernel for %dx%d", a.kx, a.ky);
+  const U16Geom g = corr16_geom(a.kx, a.sx);
   const size_t shmem = corr16_lds(*l, g);
-  if (shmem > 64 * 1024)
-    VWGPU_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(l->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  vwgpu_flag_pair f;
+  int rc = vwgpu_packed_prologue(ctx, reinterpret_cast<const void*>(l->fn), shmem, d_flag, &f);
+  if (rc) return rc;
+  const bool ncc = a.cost_type == VWGPU_CROSS_CORRELATION;
+  vwgpu_ncc_plan p;
+  if (ncc && (rc = vwgpu_ncc_plan_reserve(ctx, a, "bm_corr_u16", &p))) return rc;
   {
     vwgpu_prof_scope ps(ctx, "bm_corr_u16");
-    hipLaunchKernelGGL(l->fn, dim3((ow + UTW - 1) / UTW, (oh + l->ty - 1) / l->ty), dim3(UTHREADS), shmem, ctx->stream,
-                       left, ls, lw, lh, right, rs, rcw, rch, g, out, os, ow, oh, flag_set, flag_clear, a2, b2, b2w, full_list, full_count, cap);
+    hipLaunchKernelGGL(l->fn, dim3((a.ow() + UTW - 1) / UTW, (a.oh() + l->ty - 1) / l->ty), dim3(UTHREADS), shmem, ctx->stream,
+                       a.left, a.ls, a.lw, a.lh, a.right, a.rs, a.lw + a.sx - 1, a.lh, g, a.out, a.os, a.ow(), a.oh(), f.set, f.clear,
+                       p.a2, p.b2, p.b2w, p.full_list, p.full_count, p.cap);
   }
   VWGPU_HIP(ctx, hipGetLastError());
-  if (ncc) return vwgpu_launch_ncc_full(ctx, left, ls, right, rs, kx, ky, sx, a2, b2, b2w, out, os, ow, flag_set, full_list, full_count, cap);
-  return VWGPU_OK;
+  return ncc ? vwgpu_launch_ncc_full(ctx, a, p, f.set) : VWGPU_OK;
 }
+
+}  // namespace
+
+vwgpu_bm_matcher vwgpu_bm_corr_u16 = {VWGPU_PATH_DOT_U16, 11, "packed-u16 SSD / NCC", supported, launch};

@@ -21,7 +21,8 @@
 //             winner's disparity is the reference's and the pixel is valid.  The other pixels (near ties, flat patches) are queued
 //             and ncc_full_kernel evaluates the float64 sequence for every disparity of them (Correlation.cc:91-133).
 // Inputs that are not integers in [0,255], or an all-zero window under NCC (1/0), raise the device flag and the float64
-// kernel recomputes the image (the protocol of bm_sad_u8.hip).  One search row (sy == 1).
+// kernel recomputes the image (the protocol of vwgpu_bm_matcher, vwgpu_internal.h).  One search row (sy == 1).  This file also holds what
+// the two integer NCC matchers share: the scratch plan (vwgpu_ncc_plan_reserve) and ncc_full_kernel.
 //
 // Roofline: HBM bound by the task's definition (20 B per output pixel), VALU-issue bound in fact: per evaluation
 // (TY + ky - 1) / TY * ceil(kx / 4) dot4 + 4 ops (SSD) or + 4 ops per sweep (NCC).
@@ -30,10 +31,12 @@
 
 #include "vwgpu_internal.h"
 #include "u8_tile.h"
+#include "packed_tile.h"
 
 namespace {
 
 using namespace vwgpu_u8;
+using namespace vwgpu_packed;
 typedef uint64_t u64;
 
 constexpr int CTW = 256;          // output columns per workgroup (lane = column)
@@ -45,11 +48,6 @@ struct CorrGeom {
   int rwd;       // aligned dwords per staged right row
   int urp;       // dwords per row of the every-byte word array
 };
-
-__device__ __forceinline__ u32 umin3(u32 a, u32 b, u32 c) { u32 r; asm("v_min3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ u32 umax3(u32 a, u32 b, u32 c) { u32 r; asm("v_max3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ float fmax3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ float fmin3(float a, float b, float c) { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 
 template <int COST, int KX, int KY, int TY>
 __global__ void __launch_bounds__(CTHREADS, 2)
@@ -357,7 +355,7 @@ ncc_full_kernel(const float* __restrict__ L, ptrdiff_t ls, const float* __restri
 
 typedef void (*CorrFn)(const float*, ptrdiff_t, int, int, const float*, ptrdiff_t, int, int, CorrGeom, int32_t*, ptrdiff_t, int, int, int*, int*,
                        u32*, u32*, int, u32*, u32*, u32);
-struct CorrLaunch { int cost, kx, ky, ty; CorrFn fn; };
+typedef Launch<CorrFn> CorrLaunch;
 #define VW_CORR(C, KX, KY, TY) CorrLaunch{C, KX, KY, TY, bm_corr_u8_kernel<C, KX, KY, TY>}
 const CorrLaunch kCorr[] = {
     VW_CORR(VWGPU_SQUARED_DIFFERENCE, 3, 3, 16), VW_CORR(VWGPU_SQUARED_DIFFERENCE, 5, 5, 16), VW_CORR(VWGPU_SQUARED_DIFFERENCE, 7, 7, 16),
@@ -366,12 +364,6 @@ const CorrLaunch kCorr[] = {
     VW_CORR(VWGPU_CROSS_CORRELATION, 9, 9, 16), VW_CORR(VWGPU_CROSS_CORRELATION, 11, 11, 16),
 };
 #undef VW_CORR
-
-const CorrLaunch* find_corr(int cost, int kx, int ky) {
-  for (const CorrLaunch& l : kCorr)
-    if (l.cost == cost && l.kx == kx && l.ky == ky) return &l;
-  return nullptr;
-}
 
 CorrGeom corr_geom(int kx, int sx) {
   CorrGeom g;
@@ -389,64 +381,60 @@ size_t corr_lds_bytes(const CorrLaunch& l, const CorrGeom& g) {
   return ((size_t)nr * g.urp + xr + (size_t)nr * (CTW / 4 + nw + 1)) * sizeof(u32);
 }
 
-}  // namespace
-
-bool vwgpu_bm_corr_u8_supported(int cost_type, int kx, int ky, int sx, int sy) {
-  const CorrLaunch* l = find_corr(cost_type, kx, ky);
-  if (!l || sy != 1 || sx > 256) return false;
-  return corr_lds_bytes(*l, corr_geom(kx, sx)) <= 80 * 1024;     // two workgroups per CU
+bool supported(const vwgpu_bm_args& a) {
+  const CorrLaunch* l = find_launch(kCorr, a.cost_type, a.kx, a.ky);
+  if (!l || a.sy != 1 || a.sx > 256) return false;
+  return corr_lds_bytes(*l, corr_geom(a.kx, a.sx)) <= 80 * 1024;   // two workgroups per CU
 }
 
-int vwgpu_launch_bm_corr_u8(vwgpu_ctx* ctx, int cost_type, const float* left, int lw, int lh, ptrdiff_t ls,
-                            const float* right, int rw, int rh, ptrdiff_t rs, int kx, int ky, int sx, int sy,
-                            int32_t* out, ptrdiff_t os, int** d_fallback_flag) {
-  (void)rw; (void)rh; (void)sy;
-  const CorrLaunch* l = find_corr(cost_type, kx, ky);
-  if (!l) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "no register-blocked SSD / NCC kernel for %dx%d", kx, ky);
-  const int ow = lw - kx + 1, oh = lh - ky + 1;
-  const int rcw = lw + sx - 1, rch = lh;
-  const CorrGeom g = corr_geom(kx, sx);
-  int* flag_set = nullptr; int* flag_clear = nullptr;
-  int rc = vwgpu_next_flags(ctx, 0, &flag_set, &flag_clear, nullptr);
-  if (rc) return rc;
-  *d_fallback_flag = flag_set;
-  const bool ncc = cost_type == VWGPU_CROSS_CORRELATION;
-  u32 *a2 = nullptr, *b2 = nullptr, *full_list = nullptr, *full_count = nullptr;
-  const int b2w = rcw - kx + 1;
-  // pixels evaluated over every disparity by ncc_full_kernel: at most ~3 % of the image, beyond that the float64 kernel is faster
-  const u32 cap = (u32)std::max<size_t>(4096, (size_t)ow * oh / 32);
-  if (ncc) {
-    if ((size_t)ow * oh >= 0xffffffffull) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "bm_corr_u8: image too large");
-    const size_t na = vwgpu_align_up((size_t)ow * oh * 4, 256), nb = vwgpu_align_up((size_t)b2w * oh * 4, 256),
-                 nl = vwgpu_align_up((size_t)cap * 4 + 256, 256);
-    rc = vwgpu_arena_reserve(ctx, &ctx->scratch, na + nb + nl);
-    if (rc) return rc;
-    char* base = static_cast<char*>(ctx->scratch.base);
-    a2 = reinterpret_cast<u32*>(base); b2 = reinterpret_cast<u32*>(base + na);
-    full_count = reinterpret_cast<u32*>(base + na + nb); full_list = full_count + 64;
-    VWGPU_HIP(ctx, hipMemsetAsync(full_count, 0, 4, ctx->stream));
-  }
+int launch(vwgpu_ctx* ctx, const vwgpu_bm_args& a, int** d_flag) {
+  const CorrLaunch* l = find_launch(kCorr, a.cost_type, a.kx, a.ky);
+  if (!l) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "no register-blocked SSD / NCC kernel for %dx%d", a.kx, a.ky);
+  const CorrGeom g = corr_geom(a.kx, a.sx);
   const size_t shmem = corr_lds_bytes(*l, g);
-  if (shmem > 64 * 1024)
-    VWGPU_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(l->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  vwgpu_flag_pair f;
+  int rc = vwgpu_packed_prologue(ctx, reinterpret_cast<const void*>(l->fn), shmem, d_flag, &f);
+  if (rc) return rc;
+  const bool ncc = a.cost_type == VWGPU_CROSS_CORRELATION;
+  vwgpu_ncc_plan p;
+  if (ncc && (rc = vwgpu_ncc_plan_reserve(ctx, a, "bm_corr_u8", &p))) return rc;
   {
     vwgpu_prof_scope ps(ctx, "bm_corr_u8");
-    hipLaunchKernelGGL(l->fn, dim3((ow + CTW - 1) / CTW, (oh + l->ty - 1) / l->ty), dim3(CTHREADS), shmem, ctx->stream,
-                       left, ls, lw, lh, right, rs, rcw, rch, g, out, os, ow, oh, flag_set, flag_clear, a2, b2, b2w, full_list, full_count, cap);
+    hipLaunchKernelGGL(l->fn, dim3((a.ow() + CTW - 1) / CTW, (a.oh() + l->ty - 1) / l->ty), dim3(CTHREADS), shmem, ctx->stream,
+                       a.left, a.ls, a.lw, a.lh, a.right, a.rs, a.lw + a.sx - 1, a.lh, g, a.out, a.os, a.ow(), a.oh(), f.set, f.clear,
+                       p.a2, p.b2, p.b2w, p.full_list, p.full_count, p.cap);
   }
   VWGPU_HIP(ctx, hipGetLastError());
-  if (ncc) return vwgpu_launch_ncc_full(ctx, left, ls, right, rs, kx, ky, sx, a2, b2, b2w, out, os, ow, flag_set, full_list, full_count, cap);
+  return ncc ? vwgpu_launch_ncc_full(ctx, a, p, f.set) : VWGPU_OK;
+}
+
+}  // namespace
+
+vwgpu_bm_matcher vwgpu_bm_corr_u8 = {VWGPU_PATH_DOT_U8, 7, "dot-product", supported, launch};
+
+int vwgpu_ncc_plan_reserve(vwgpu_ctx* ctx, const vwgpu_bm_args& a, const char* who, vwgpu_ncc_plan* p) {
+  const size_t ow = a.ow(), oh = a.oh();
+  if (ow * oh >= 0xffffffffull) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "%s: image too large", who);
+  p->b2w = a.lw + a.sx - 1 - a.kx + 1;
+  // pixels evaluated over every disparity by ncc_full_kernel: at most ~3 % of the image, beyond that the float64 kernel is faster
+  p->cap = (uint32_t)std::max<size_t>(4096, ow * oh / 32);
+  const size_t na = vwgpu_align_up(ow * oh * 4, 256), nb = vwgpu_align_up((size_t)p->b2w * oh * 4, 256),
+               nl = vwgpu_align_up((size_t)p->cap * 4 + 256, 256);
+  int rc = vwgpu_arena_reserve(ctx, &ctx->scratch, na + nb + nl);
+  if (rc) return rc;
+  char* base = static_cast<char*>(ctx->scratch.base);
+  p->a2 = reinterpret_cast<uint32_t*>(base); p->b2 = reinterpret_cast<uint32_t*>(base + na);
+  p->full_count = reinterpret_cast<uint32_t*>(base + na + nb); p->full_list = p->full_count + 64;
+  VWGPU_HIP(ctx, hipMemsetAsync(p->full_count, 0, 4, ctx->stream));
   return VWGPU_OK;
 }
 
 // The float64 sequence for the queued pixels of an integer NCC matcher (bm_corr_u8.hip, bm_corr_u16.hip: products and window sums below 2^32).
-int vwgpu_launch_ncc_full(vwgpu_ctx* ctx, const float* left, ptrdiff_t ls, const float* right, ptrdiff_t rs, int kx, int ky, int sx,
-                          const uint32_t* a2, const uint32_t* b2, int b2w, int32_t* out, ptrdiff_t os, int ow, int* flag,
-                          const uint32_t* full_list, const uint32_t* full_count, uint32_t cap) {
+int vwgpu_launch_ncc_full(vwgpu_ctx* ctx, const vwgpu_bm_args& a, const vwgpu_ncc_plan& p, int* flag) {
   vwgpu_prof_scope ps(ctx, "ncc_full");
-  const size_t full_lds = (size_t)4 * ((size_t)ky * (kx + sx - 1) + (size_t)ky * kx) * sizeof(uint32_t);      // kx, ky <= 11 (64 lanes cover a window row), sx <= 256: <= 49 KB
-  hipLaunchKernelGGL(ncc_full_kernel, dim3(2048), dim3(256), full_lds, ctx->stream, left, ls, right, rs, kx, ky, sx, a2, b2, b2w,
-                     out, os, ow, flag, full_list, full_count, cap);
+  const size_t full_lds = (size_t)4 * ((size_t)a.ky * (a.kx + a.sx - 1) + (size_t)a.ky * a.kx) * sizeof(uint32_t);      // kx, ky <= 11 (64 lanes cover a window row), sx <= 256: <= 49 KB
+  hipLaunchKernelGGL(ncc_full_kernel, dim3(2048), dim3(256), full_lds, ctx->stream, a.left, a.ls, a.right, a.rs, a.kx, a.ky, a.sx,
+                     p.a2, p.b2, p.b2w, a.out, a.os, a.ow(), flag, p.full_list, p.full_count, p.cap);
   VWGPU_HIP(ctx, hipGetLastError());
   return VWGPU_OK;
 }

@@ -13,8 +13,8 @@
 // the two operands comes from four byte-phase copies of each staged row in LDS (word w of phase p = bytes [4w+p, 4w+p+3]).
 // Per row the four waves exchange (best, index, worst) through LDS; validity = best != worst = "not all costs equal"
 // (Correlation.cc:91-133 reduces to that when no cost is NaN).  Tiles containing an all-zero window (NCC: 1/0) or inputs
-// that are not integers in [0,255] raise the device flag and the float64 kernel recomputes the image (same protocol as
-// bm_sad_u8.hip).  sy must be 1 (one search row); other shapes stay on the generic path.
+// that are not integers in [0,255] raise the device flag and the float64 kernel recomputes the image (the protocol of
+// vwgpu_bm_matcher, vwgpu_internal.h).  sy must be 1 (one search row); other shapes stay on the generic path.
 //
 // Roofline: LDS-bandwidth / VALU bound, not HBM: ~2*NW LDS word reads + 2*NW dot4 per (pixel, disparity), plus ~35 float64
 // instructions per evaluation for NCC.  Algorithmic HBM bytes are the same 20 B per output pixel as the SAD path.
@@ -270,33 +270,27 @@ DotFn pick(int nw, int dpt) {
 #undef VW_DOT
 }
 
-}  // namespace
-
-bool vwgpu_bm_dot_u8_supported(int cost_type, int kx, int ky, int sx, int sy) {
-  if (cost_type != VWGPU_SQUARED_DIFFERENCE && cost_type != VWGPU_CROSS_CORRELATION) return false;
-  if (sy != 1 || kx > 16 || ky > 31 || sx > 160 || TX + sx - 1 > 256) return false;
-  return dot_lds_bytes(make_geom(kx, ky, sx)) <= 120 * 1024;
+bool supported(const vwgpu_bm_args& a) {
+  if (a.cost_type != VWGPU_SQUARED_DIFFERENCE && a.cost_type != VWGPU_CROSS_CORRELATION) return false;
+  if (a.sy != 1 || a.kx > 16 || a.ky > 31 || a.sx > 160 || TX + a.sx - 1 > 256) return false;
+  return dot_lds_bytes(make_geom(a.kx, a.ky, a.sx)) <= 120 * 1024;
 }
 
-int vwgpu_launch_bm_dot_u8(vwgpu_ctx* ctx, int cost_type, const float* left, int lw, int lh, ptrdiff_t ls,
-                           const float* right, int rw, int rh, ptrdiff_t rs, int kx, int ky, int sx, int sy,
-                           int32_t* out, ptrdiff_t os, int** d_fallback_flag) {
-  (void)rw; (void)rh; (void)sy;
-  const int ow = lw - kx + 1, oh = lh - ky + 1;
-  const int rcw = lw + sx - 1, rch = lh;
-  const DotGeom g = make_geom(kx, ky, sx);
-  int* flag_set = nullptr; int* flag_clear = nullptr;
-  int rc = vwgpu_next_flags(ctx, 0, &flag_set, &flag_clear, nullptr);
-  if (rc) return rc;
-  *d_fallback_flag = flag_set;
+int launch(vwgpu_ctx* ctx, const vwgpu_bm_args& a, int** d_flag) {
+  const DotGeom g = make_geom(a.kx, a.ky, a.sx);
   const size_t shmem = dot_lds_bytes(g);
-  const int nw = (kx + 3) / 4, dpt = (sx + 3) / 4;
-  DotFn fn = cost_type == VWGPU_CROSS_CORRELATION ? pick<VWGPU_CROSS_CORRELATION>(nw, dpt) : pick<VWGPU_SQUARED_DIFFERENCE>(nw, dpt);
-  if (shmem > 64 * 1024)
-    VWGPU_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  const int nw = (a.kx + 3) / 4, dpt = (a.sx + 3) / 4;
+  DotFn fn = a.cost_type == VWGPU_CROSS_CORRELATION ? pick<VWGPU_CROSS_CORRELATION>(nw, dpt) : pick<VWGPU_SQUARED_DIFFERENCE>(nw, dpt);
+  vwgpu_flag_pair f;
+  int rc = vwgpu_packed_prologue(ctx, reinterpret_cast<const void*>(fn), shmem, d_flag, &f);
+  if (rc) return rc;
   vwgpu_prof_scope ps(ctx, "bm_dot_u8");
-  hipLaunchKernelGGL(fn, dim3((ow + TX - 1) / TX, (oh + TYR - 1) / TYR), dim3(NTHREADS), shmem, ctx->stream,
-                     left, ls, lw, lh, right, rs, rcw, rch, g, out, os, ow, oh, flag_set, flag_clear);
+  hipLaunchKernelGGL(fn, dim3((a.ow() + TX - 1) / TX, (a.oh() + TYR - 1) / TYR), dim3(NTHREADS), shmem, ctx->stream,
+                     a.left, a.ls, a.lw, a.lh, a.right, a.rs, a.lw + a.sx - 1, a.lh, g, a.out, a.os, a.ow(), a.oh(), f.set, f.clear);
   VWGPU_HIP(ctx, hipGetLastError());
   return VWGPU_OK;
 }
+
+}  // namespace
+
+vwgpu_bm_matcher vwgpu_bm_dot_u8 = {VWGPU_PATH_DOT_U8, 7, "dot-product", supported, launch};

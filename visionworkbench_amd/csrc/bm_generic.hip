@@ -40,8 +40,7 @@ __device__ __forceinline__ bool better(double c, double q) {
 
 // NCC side-car: prec(x,y) = 1.0 / sum_{ky x kx}(img^2) in float64 (NCCCost ctor, CostFunctions.h:214-219).
 __global__ void ncc_precision_kernel(const float* __restrict__ img, ptrdiff_t stride, int w, int h,
-                                     int kx, int ky, double* __restrict__ prec, const int* __restrict__ run_flag) {
-  if (run_flag && *run_flag == 0) return;  // the fast path already produced the result
+                                     int kx, int ky, double* __restrict__ prec) {
   const int ow = w - kx + 1, oh = h - ky + 1;
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   const int y = blockIdx.y * blockDim.y + threadIdx.y;
@@ -62,9 +61,7 @@ bm_generic_kernel(const float* __restrict__ left, ptrdiff_t ls, int lw, int lh,
                   const float* __restrict__ right, ptrdiff_t rs,
                   int kx, int ky, int sx, int sy,
                   const double* __restrict__ lprec, const double* __restrict__ rprec, int rpw,
-                  int32_t* __restrict__ out, ptrdiff_t os, int ow, int oh,
-                  const int* __restrict__ run_flag) {
-  if (run_flag && *run_flag == 0) return;  // the fast path already produced the result
+                  int32_t* __restrict__ out, ptrdiff_t os, int ow, int oh) {
   // Column sums of all GEN_TY output rows of one disparity go to an LDS plane at once: two barriers per disparity instead of
   // one per (disparity, row) with a global-load round trip inside each.  One 32 KB plane (not two alternating ones): four
   // workgroups per CU hide the LDS / global latency better than a saved barrier does.
@@ -155,19 +152,16 @@ bm_generic_kernel(const float* __restrict__ left, ptrdiff_t ls, int lw, int lh,
 
 }  // namespace
 
-int vwgpu_launch_bm_generic_flag(vwgpu_ctx* ctx, int cost_type,
-                                 const float* left, int lw, int lh, ptrdiff_t ls,
-                                 const float* right, int rw, int rh, ptrdiff_t rs,
-                                 int kx, int ky, int sx, int sy, int32_t* out, ptrdiff_t os,
-                                 const int* run_flag) {
-  (void)rw; (void)rh;
-  const int ow = lw - kx + 1, oh = lh - ky + 1;
+int vwgpu_launch_bm_generic(vwgpu_ctx* ctx, const vwgpu_bm_args& a) {
+  const float *left = a.left, *right = a.right;
+  const int lw = a.lw, lh = a.lh, kx = a.kx, ky = a.ky, sx = a.sx, sy = a.sy, ow = a.ow(), oh = a.oh();
+  const ptrdiff_t ls = a.ls, rs = a.rs;
   if (kx > GEN_THREADS / 2) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "kernel width %d > %d", kx, GEN_THREADS / 2);
 
   double* lprec = nullptr;
   double* rprec = nullptr;
   int rpw = 0;
-  if (cost_type == VWGPU_CROSS_CORRELATION) {
+  if (a.cost_type == VWGPU_CROSS_CORRELATION) {
     const int rcw = lw + sx - 1, rch = lh + sy - 1;
     rpw = rcw - kx + 1;
     const int rph = rch - ky + 1;
@@ -181,12 +175,12 @@ int vwgpu_launch_bm_generic_flag(vwgpu_ctx* ctx, int cost_type,
     {
       vwgpu_prof_scope ps(ctx, "ncc_precision_left");
       dim3 grd((ow + 63) / 64, (oh + 3) / 4);
-      hipLaunchKernelGGL(ncc_precision_kernel, grd, blk, 0, ctx->stream, left, ls, lw, lh, kx, ky, lprec, run_flag);
+      hipLaunchKernelGGL(ncc_precision_kernel, grd, blk, 0, ctx->stream, left, ls, lw, lh, kx, ky, lprec);
     }
     {
       vwgpu_prof_scope ps(ctx, "ncc_precision_right");
       dim3 grd((rpw + 63) / 64, (rph + 3) / 4);
-      hipLaunchKernelGGL(ncc_precision_kernel, grd, blk, 0, ctx->stream, right, rs, rcw, rch, kx, ky, rprec, run_flag);
+      hipLaunchKernelGGL(ncc_precision_kernel, grd, blk, 0, ctx->stream, right, rs, rcw, rch, kx, ky, rprec);
     }
   }
 
@@ -195,11 +189,11 @@ int vwgpu_launch_bm_generic_flag(vwgpu_ctx* ctx, int cost_type,
   dim3 blk(GEN_THREADS);
   vwgpu_prof_scope ps(ctx, "bm_generic");
 #define VW_GEN(C, K) hipLaunchKernelGGL((bm_generic_kernel<C, K>), grd, blk, 0, ctx->stream, \
-                                       left, ls, lw, lh, right, rs, kx, ky, sx, sy, lprec, rprec, rpw, out, os, ow, oh, run_flag)
+                                       left, ls, lw, lh, right, rs, kx, ky, sx, sy, lprec, rprec, rpw, a.out, a.os, ow, oh)
 #define VW_GEN_K(C) do { switch (kx) { case 3: VW_GEN(C, 3); break; case 5: VW_GEN(C, 5); break; case 7: VW_GEN(C, 7); break; \
                                       case 9: VW_GEN(C, 9); break; case 11: VW_GEN(C, 11); break; case 13: VW_GEN(C, 13); break; \
                                       case 15: VW_GEN(C, 15); break; default: VW_GEN(C, 0); break; } } while (0)
-  switch (cost_type) {
+  switch (a.cost_type) {
     case VWGPU_CROSS_CORRELATION: VW_GEN_K(VWGPU_CROSS_CORRELATION); break;
     case VWGPU_SQUARED_DIFFERENCE: VW_GEN_K(VWGPU_SQUARED_DIFFERENCE); break;
     default: VW_GEN_K(VWGPU_ABSOLUTE_DIFFERENCE); break;
@@ -208,12 +202,4 @@ int vwgpu_launch_bm_generic_flag(vwgpu_ctx* ctx, int cost_type,
 #undef VW_GEN
   VWGPU_HIP(ctx, hipGetLastError());
   return VWGPU_OK;
-}
-
-int vwgpu_launch_bm_generic(vwgpu_ctx* ctx, int cost_type,
-                            const float* left, int lw, int lh, ptrdiff_t ls,
-                            const float* right, int rw, int rh, ptrdiff_t rs,
-                            int kx, int ky, int sx, int sy, int32_t* out, ptrdiff_t os) {
-  return vwgpu_launch_bm_generic_flag(ctx, cost_type, left, lw, lh, ls, right, rw, rh, rs,
-                                      kx, ky, sx, sy, out, os, nullptr);
 }

@@ -15,48 +15,25 @@
 //   odd kx    the last pair of a window holds one live pixel; its RIGHT half is cleared (v_and), so the dead LEFT pixel adds
 //             the same value to every disparity of the pixel — argmin and the equality test do not see it (the trick of the
 //             u8 kernel's zero-padded last word)
-// Inputs outside the domain raise the device flag; the caller then runs the float64 kernel.  One search row (sy == 1).
+// Inputs outside the domain raise the device flag (vwgpu_bm_matcher, vwgpu_internal.h); the caller then runs the float64 kernel.  One
+// search row (sy == 1).  The pair staging is stage_pair_rows of packed_tile.h.
 //
 // Roofline: HBM bound by the task's definition (20 B per output pixel); VALU-issue bound in fact: (TY+ky-1)/TY * (ceil(kx/2)
 // + 1) + 4 instruction slots per (pixel, disparity).
 #include <algorithm>
 
 #include "vwgpu_internal.h"
+#include "packed_tile.h"
 
 namespace {
 
+using namespace vwgpu_packed;
 typedef uint32_t u32;
 
 constexpr int STW = 256;          // output columns per workgroup
 constexpr int STHREADS = 256;
 
-__device__ __forceinline__ u32 umin3(u32 a, u32 b, u32 c) { u32 r; asm("v_min3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ u32 umax3(u32 a, u32 b, u32 c) { u32 r; asm("v_max3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 __device__ __forceinline__ u32 sad_u16(u32 a, u32 b, u32 c) { u32 r; asm("v_sad_u16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-
-// float -> u16 with the exactness test of the path: integer-valued and inside [0,65535]
-__device__ __forceinline__ u32 to_u16(float v, bool& bad) {
-  const float r = rintf(v);
-  bad |= !(r == v && v >= 0.0f && v <= 65535.0f);
-  return (u32)(int)fminf(fmaxf(r, 0.0f), 65535.0f);
-}
-
-// dst[r][g] = pixels (x0 + 2g, x0 + 2g + 1) of row y0 + r as a u16 pair, zero outside the image
-template <int NROWS>
-__device__ __forceinline__ void stage_u16_rows(const float* __restrict__ img, ptrdiff_t stride, int w, int h, int x0, int y0,
-                                               int npairs, u32* __restrict__ dst, int tid, bool& bad) {
-  for (int i = tid; i < NROWS * npairs; i += STHREADS) {
-    const int r = i / npairs, gq = i - r * npairs;
-    const int x = x0 + 2 * gq, y = y0 + r;
-    u32 p = 0;
-    if (y < h) {
-      const float* row = img + (ptrdiff_t)y * stride;
-      if (x < w) p = to_u16(row[x], bad);
-      if (x + 1 < w) p |= to_u16(row[x + 1], bad) << 16;
-    }
-    dst[i] = p;
-  }
-}
 
 template <int KX, int KY, int TY>
 __global__ void __launch_bounds__(STHREADS, 2)
@@ -77,8 +54,8 @@ bm_sad_u16_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
   if (tid == 0 && blockIdx.x == 0 && blockIdx.y == 0) *flag_clear = 0;     // the NEXT call's flag
 
   bool bad = false;
-  stage_u16_rows<NR>(L, ls, lw, lh, x0, y0, LPD, LW, tid, bad);
-  stage_u16_rows<NR>(R, rs, rcw, rch, x0, y0, rpd, XR, tid, bad);
+  stage_pair_rows<NR, 65535u, STHREADS>(L, ls, lw, lh, x0, y0, LPD, LW, tid, bad);
+  stage_pair_rows<NR, 65535u, STHREADS>(R, rs, rcw, rch, x0, y0, rpd, XR, tid, bad);
   __syncthreads();
   // LEFT pairs of this lane's column: pixels x + 2n, x + 2n + 1
   u32 lwn[NR][NWF + 1];
@@ -172,16 +149,11 @@ bm_sad_u16_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
 }
 
 typedef void (*Sad16Fn)(const float*, ptrdiff_t, int, int, const float*, ptrdiff_t, int, int, int, int, int, int32_t*, ptrdiff_t, int, int, int*, int*);
-struct Sad16Launch { int kx, ky, ty; Sad16Fn fn; };
-#define VW_S16(KX, KY, TY) Sad16Launch{KX, KY, TY, bm_sad_u16_kernel<KX, KY, TY>}
+typedef Launch<Sad16Fn> Sad16Launch;
+#define VW_S16(KX, KY, TY) Sad16Launch{VWGPU_ABSOLUTE_DIFFERENCE, KX, KY, TY, bm_sad_u16_kernel<KX, KY, TY>}
 const Sad16Launch kSad16[] = {VW_S16(3, 3, 16), VW_S16(5, 5, 16), VW_S16(7, 7, 16), VW_S16(7, 5, 16), VW_S16(9, 9, 16), VW_S16(11, 11, 16)};
 #undef VW_S16
 
-const Sad16Launch* find_sad16(int kx, int ky) {
-  for (const Sad16Launch& l : kSad16)
-    if (l.kx == kx && l.ky == ky) return &l;
-  return nullptr;
-}
 void sad16_geom(int kx, int sx, int* urp, int* rpd) {
   *urp = STW + sx - 1 + kx + 1 + 16;                             // every pixel a window of a (clamped tail) quad can start a pair at
   *rpd = (*urp + 1) / 2 + 2;
@@ -193,33 +165,28 @@ size_t sad16_lds(const Sad16Launch& l, int sx) {
   return ((size_t)nr * urp + (size_t)nr * rpd + (size_t)nr * (STW / 2 + l.kx / 2 + 2)) * sizeof(u32);
 }
 
-}  // namespace
-
-bool vwgpu_bm_sad_u16_supported(int cost_type, int kx, int ky, int sx, int sy) {
-  if (cost_type != VWGPU_ABSOLUTE_DIFFERENCE || sy != 1 || sx > 256) return false;
-  const Sad16Launch* l = find_sad16(kx, ky);
-  return l && sad16_lds(*l, sx) <= 80 * 1024;
+bool supported(const vwgpu_bm_args& a) {
+  if (a.sy != 1 || a.sx > 256) return false;
+  const Sad16Launch* l = find_launch(kSad16, a.cost_type, a.kx, a.ky);
+  return l && sad16_lds(*l, a.sx) <= 80 * 1024;
 }
 
-int vwgpu_launch_bm_sad_u16(vwgpu_ctx* ctx, const float* left, int lw, int lh, ptrdiff_t ls,
-                            const float* right, int rw, int rh, ptrdiff_t rs, int kx, int ky, int sx, int sy,
-                            int32_t* out, ptrdiff_t os, int** d_fallback_flag) {
-  (void)rw; (void)rh; (void)sy;
-  const Sad16Launch* l = find_sad16(kx, ky);
-  if (!l) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "no packed-u16 SAD kernel for %dx%d", kx, ky);
-  const int ow = lw - kx + 1, oh = lh - ky + 1;
+int launch(vwgpu_ctx* ctx, const vwgpu_bm_args& a, int** d_flag) {
+  const Sad16Launch* l = find_launch(kSad16, a.cost_type, a.kx, a.ky);
+  if (!l) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "no packed-u16 SAD kernel for %dx%d", a.kx, a.ky);
   int urp, rpd;
-  sad16_geom(kx, sx, &urp, &rpd);
-  int* flag_set = nullptr; int* flag_clear = nullptr;
-  int rc = vwgpu_next_flags(ctx, 0, &flag_set, &flag_clear, nullptr);
+  sad16_geom(a.kx, a.sx, &urp, &rpd);
+  const size_t shmem = sad16_lds(*l, a.sx);
+  vwgpu_flag_pair f;
+  int rc = vwgpu_packed_prologue(ctx, reinterpret_cast<const void*>(l->fn), shmem, d_flag, &f);
   if (rc) return rc;
-  *d_fallback_flag = flag_set;
-  const size_t shmem = sad16_lds(*l, sx);
-  if (shmem > 64 * 1024)
-    VWGPU_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(l->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
   vwgpu_prof_scope ps(ctx, "bm_sad_u16");
-  hipLaunchKernelGGL(l->fn, dim3((ow + STW - 1) / STW, (oh + l->ty - 1) / l->ty), dim3(STHREADS), shmem, ctx->stream,
-                     left, ls, lw, lh, right, rs, lw + sx - 1, lh, sx, urp, rpd, out, os, ow, oh, flag_set, flag_clear);
+  hipLaunchKernelGGL(l->fn, dim3((a.ow() + STW - 1) / STW, (a.oh() + l->ty - 1) / l->ty), dim3(STHREADS), shmem, ctx->stream,
+                     a.left, a.ls, a.lw, a.lh, a.right, a.rs, a.lw + a.sx - 1, a.lh, a.sx, urp, rpd, a.out, a.os, a.ow(), a.oh(), f.set, f.clear);
   VWGPU_HIP(ctx, hipGetLastError());
   return VWGPU_OK;
 }
+
+}  // namespace
+
+vwgpu_bm_matcher vwgpu_bm_sad_u16 = {VWGPU_PATH_SAD_U16, 15, "packed-u16", supported, launch};

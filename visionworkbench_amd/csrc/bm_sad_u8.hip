@@ -7,8 +7,8 @@
 // domain |a-b| in float, the float64 box sums and the strict `<` compares are all exact, so the result only
 // depends on (cost, dy, dx) lexicographic order ("strict compare, first wins" == smallest (cost, dy, dx)),
 // which is what this kernel tracks.  It reads the float32 images directly (4 B/px, once per tile), checks
-// the domain on the fly and raises a device flag otherwise; the generic float64 kernel (bm_generic.hip)
-// then recomputes the image.
+// the domain on the fly and raises a device flag otherwise (vwgpu_bm_matcher, vwgpu_internal.h; the flags
+// alternate between calls, vwgpu_packed_prologue); a float64 path then recomputes the image.
 //
 // Issue-bound, not HBM-bound: 4096^2 x 129 disparities = 2.16 G (pixel, disparity) evaluations against
 // 337 MB of compulsory HBM traffic (42 us).  Measured on MI355X (profiles/r01_ubench_valu.txt): an ordinary
@@ -700,43 +700,29 @@ size_t lds_bytes(const Launch& l, int sx, int groups, bool em) {
   return ((ent > left ? ent : left) + base) * sizeof(u32);
 }
 
-}  // namespace
-
-bool vwgpu_bm_sad_u8_supported(int cost_type, int kx, int ky, int sx, int sy) {
-  if (cost_type != VWGPU_ABSOLUTE_DIFFERENCE) return false;
-  const Launch* l = find_launch(kx, ky);
+bool supported(const vwgpu_bm_args& a) {
+  if (a.cost_type != VWGPU_ABSOLUTE_DIFFERENCE) return false;
+  const Launch* l = find_launch(a.kx, a.ky);
   if (!l) return false;
-  if ((long long)sx * sy > 65535) return false;
-  return lds_bytes(*l, sx, l->split_fn ? l->split_groups : 1, false) <= kMaxLds;    // (the row-major array is the smaller one)
+  if ((long long)a.sx * a.sy > 65535) return false;
+  return lds_bytes(*l, a.sx, l->split_fn ? l->split_groups : 1, false) <= kMaxLds;    // (the row-major array is the smaller one)
 }
 
-int vwgpu_launch_bm_sad_u8(vwgpu_ctx* ctx,
-                           const float* left, int lw, int lh, ptrdiff_t ls,
-                           const float* right, int rw, int rh, ptrdiff_t rs,
-                           int kx, int ky, int sx, int sy, int32_t* out, ptrdiff_t os,
-                           int** d_fallback_flag) {
-  (void)rw; (void)rh;
-  const int ow = lw - kx + 1, oh = lh - ky + 1;
+int launch(vwgpu_ctx* ctx, const vwgpu_bm_args& a, int** d_flag) {
+  const int kx = a.kx, sx = a.sx, sy = a.sy, ow = a.ow(), oh = a.oh();
   bool split = false;
   // VWGPU_OPT_SAD_ROUND_SLOTS = n: the launcher plans for n workgroup slots, i.e. a device of n / 2 CUs — tile choice and rounds alike
   const int plan_cu = ctx->sad_round_slots > 0 ? (ctx->sad_round_slots + 1) / 2 : ctx->num_cu;
-  const Launch* l = pick_launch(kx, ky, ow, oh, plan_cu, ctx->sad_groups, &split);
-  if (!l) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "no packed-u8 kernel for %dx%d", kx, ky);
-  const int rcw = lw + sx - 1, rch = lh + sy - 1;
+  const Launch* l = pick_launch(kx, a.ky, ow, oh, plan_cu, ctx->sad_groups, &split);
+  if (!l) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "no packed-u8 kernel for %dx%d", kx, a.ky);
+  const int rcw = a.lw + sx - 1, rch = a.lh + sy - 1;
   const int gx = (ow + l->twb - 1) / l->twb, gy = (oh + l->ty - 1) / l->ty;
   const int ne = entries_per_row(*l, sx);
-
-  // Two alternating device flags: call n raises flags[n&1] on unsuitable input and clears flags[(n+1)&1]
-  // for the next call, so no memset launch is needed (stream order makes this race free).
-  int *flag_set = nullptr, *flag_clear = nullptr;
-  int rc = vwgpu_next_flags(ctx, 0, &flag_set, &flag_clear, nullptr);
-  if (rc) return rc;
-  *d_fallback_flag = flag_set;
   // entry-major word groups wherever the padded array fits the budget the size was admitted with (7x7 at 1024 x 16: up to 173 disparities with one group, 169 with two, of the
   // 209 the kernel serves); VWGPU_OPT_SAD_LAYOUT = 1 pins the row-major array (same results)
   const int groups = split ? l->split_groups : 1;
   const size_t ctr_bytes = split ? 64 : 0;            // the item counters of the split variant
-  // (the counters count against the padded array; the row-major one was admitted without them by vwgpu_bm_sad_u8_supported and
+  // (the counters count against the padded array; the row-major one was admitted without them by supported() and
   // may exceed the constant by those 64 bytes, as it always could: a split workgroup has its CU to itself)
   const bool em = ctx->sad_layout == 0 && lds_bytes(*l, sx, groups, true) + ctr_bytes <= kMaxLds;
   const size_t shmem = lds_bytes(*l, sx, groups, em) + ctr_bytes;
@@ -751,15 +737,19 @@ int vwgpu_launch_bm_sad_u8(vwgpu_ctx* ctx,
   const int last_round = rounds ? (int)grid1 - slots : INT_MAX;
   // the first-round hand-off (see the kernel): the first `slots` workgroups, two to a CU
   const int first_round = (rounds && resident == 2) ? slots : 0;
-  if (shmem > 64 * 1024)
-    VWGPU_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(main_fn),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  vwgpu_flag_pair f;
+  int rc = vwgpu_packed_prologue(ctx, reinterpret_cast<const void*>(main_fn), shmem, d_flag, &f);
+  if (rc) return rc;
   {
     vwgpu_prof_scope ps(ctx, "bm_sad_u8");
     hipLaunchKernelGGL(main_fn, dim3(grid1), dim3(split ? l->split_groups * l->threads : l->threads), shmem, ctx->stream,
-                       left, ls, lw, lh, right, rs, rcw, rch, sx, sy, ne, out, os, ow, oh,
-                       flag_set, flag_clear, gx, gx * gy, last_round, first_round, kStaggerTicks);
+                       a.left, a.ls, a.lw, a.lh, a.right, a.rs, rcw, rch, sx, sy, ne, a.out, a.os, ow, oh,
+                       f.set, f.clear, gx, gx * gy, last_round, first_round, kStaggerTicks);
   }
   VWGPU_HIP(ctx, hipGetLastError());
   return VWGPU_OK;
 }
+
+}  // namespace
+
+vwgpu_bm_matcher vwgpu_bm_sad_u8 = {VWGPU_PATH_SAD_U8, 7, "packed-u8", supported, launch};

@@ -140,9 +140,9 @@ static void prof_clear(vwgpu_ctx* ctx) {
 // ---- context ------------------------------------------------------------------------------------------
 
 // Two alternating device flags: call n raises flags[n&1] on unsuitable input and clears flags[(n+1)&1] for the next call, so
-// no memset launch is needed (stream order makes this race free).  `extra` (optional) = extra_ints ints after the flags.
-int vwgpu_next_flags(vwgpu_ctx* ctx, size_t extra_ints, int** flag_set, int** flag_clear, int** extra) {
-  int rc = vwgpu_arena_reserve(ctx, &ctx->flags, 256 + extra_ints * sizeof(int));
+// no memset launch is needed (stream order makes this race free).
+static int vwgpu_next_flags(vwgpu_ctx* ctx, vwgpu_flag_pair* f) {
+  int rc = vwgpu_arena_reserve(ctx, &ctx->flags, 256);
   if (rc) return rc;
   int* flags = static_cast<int*>(ctx->flags.base);
   if (ctx->flags_base_seen != ctx->flags.base) { ctx->flags_init = false; ctx->flags_base_seen = ctx->flags.base; ctx->last_flag = nullptr; }
@@ -150,12 +150,23 @@ int vwgpu_next_flags(vwgpu_ctx* ctx, size_t extra_ints, int** flag_set, int** fl
     VWGPU_HIP(ctx, hipMemsetAsync(flags, 0, 256, ctx->stream));
     ctx->flags_init = true;
   }
-  *flag_set = flags + (ctx->flag_parity & 1);
-  *flag_clear = flags + ((ctx->flag_parity + 1) & 1);
+  f->set = flags + (ctx->flag_parity & 1);
+  f->clear = flags + ((ctx->flag_parity + 1) & 1);
   ctx->flag_parity ^= 1;
-  if (extra) *extra = flags + 64;
   return VWGPU_OK;
 }
+
+int vwgpu_packed_prologue(vwgpu_ctx* ctx, const void* kernel, size_t shmem, int** d_flag, vwgpu_flag_pair* flags) {
+  int rc = vwgpu_next_flags(ctx, flags);
+  if (rc) return rc;
+  *d_flag = flags->set;
+  if (shmem > 64 * 1024) VWGPU_HIP(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  return VWGPU_OK;
+}
+
+// The packed-integer matchers in dispatch order: the byte class (max_hi 7), of which a call takes the first that serves it — so
+// VWGPU_PATH_DOT_U8 means bm_corr_u8 where instantiated, else bm_dot_u8 — then the wider classes the classified path may try, one by one.
+static const vwgpu_bm_matcher* const kPacked[] = {&vwgpu_bm_sad_u8, &vwgpu_bm_corr_u8, &vwgpu_bm_dot_u8, &vwgpu_bm_sad_u16, &vwgpu_bm_corr_u16};
 
 extern "C" {
 
@@ -335,7 +346,9 @@ int vwgpu_get_option(const vwgpu_ctx* ctx, int option, int* value) {
 int vwgpu_last_path(const vwgpu_ctx* cctx) {
   vwgpu_ctx* ctx = const_cast<vwgpu_ctx*>(cctx);
   if (!ctx) return VWGPU_PATH_NONE;
-  if ((ctx->last_path == VWGPU_PATH_SAD_U8 || ctx->last_path == VWGPU_PATH_DOT_U8 || ctx->last_path == VWGPU_PATH_SAD_U16 || ctx->last_path == VWGPU_PATH_DOT_U16) && ctx->last_flag) {
+  bool packed = false;
+  for (const vwgpu_bm_matcher* m : kPacked) packed |= m->path == ctx->last_path;
+  if (packed && ctx->last_flag) {
     // A packed kernel was queued without waiting for its verdict (a forced path, or VWGPU_OPT_DEFER_EXACTNESS): it reports input
     // outside its domain through a device flag, and NOTHING recomputed the image then — the call has no result.
     int flag = 0;
@@ -376,12 +389,12 @@ int vwgpu_profile_read(vwgpu_ctx* ctx, const char** names, float* ms, int cap) {
 
 // ---- calc_disparity -----------------------------------------------------------------------------------
 
-static int check_bm_args(vwgpu_ctx* ctx, int cost_type, const void* l, int lw, int lh, ptrdiff_t ls,
-                         const void* r, int rw, int rh, ptrdiff_t rs, int kx, int ky, int sx, int sy,
-                         const void* out, ptrdiff_t os) {
+static int check_bm_args(vwgpu_ctx* ctx, const vwgpu_bm_args& a) {
+  const int cost_type = a.cost_type, lw = a.lw, lh = a.lh, rw = a.rw, rh = a.rh, kx = a.kx, ky = a.ky, sx = a.sx, sy = a.sy;
+  const ptrdiff_t ls = a.ls, rs = a.rs, os = a.os;
   if (!ctx) return VWGPU_ERR_ARGUMENT;
   ctx->err.clear();
-  if (!l || !r || !out) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "calc_disparity: null image pointer");
+  if (!a.left || !a.right || !a.out) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "calc_disparity: null image pointer");
   if (cost_type < VWGPU_ABSOLUTE_DIFFERENCE || cost_type > VWGPU_CROSS_CORRELATION)
     return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "calc_disparity: cost type %d is not a block-matching cost", cost_type);
   // The reference's checks (src/vw/Stereo/Correlation.cc:341-351, Algorithms.h:45-46), always on here.
@@ -405,9 +418,30 @@ static int check_bm_args(vwgpu_ctx* ctx, int cost_type, const void* l, int lw, i
 // representable (any order returns the reference's bits), the reference's serial summation order otherwise.
 struct Grain { bool known = false; int lo = 0, hi = 0, nonfinite = 0; };
 
-static int calc_disparity_classified(vwgpu_ctx* ctx, int cost_type, const float* d_left, int lw, int lh, ptrdiff_t ls,
-                                     const float* d_right, int rw, int rh, ptrdiff_t rs, int kx, int ky, int sx, int sy,
-                                     int32_t* d_out, ptrdiff_t os, Grain gr = Grain()) {
+// Queues a packed matcher.  accepted == nullptr (a forced path, VWGPU_OPT_DEFER_EXACTNESS): no wait, the call returns with last_flag
+// set and vwgpu_last_path() reads the verdict.  Otherwise the flag is copied back behind the kernel and *accepted says whether the
+// result stands.
+static int try_packed(vwgpu_ctx* ctx, const vwgpu_bm_matcher& m, const vwgpu_bm_args& a, bool* accepted) {
+  int* d_flag = nullptr;
+  int rc = m.launch(ctx, a, &d_flag);
+  if (rc) return rc;
+  ctx->last_path = m.path;
+  ctx->last_flag = d_flag;
+  if (!accepted) return VWGPU_OK;
+  int flag = 0;
+  VWGPU_HIP(ctx, hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
+  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->last_flag = nullptr;
+  *accepted = flag == 0;
+  return VWGPU_OK;
+}
+
+// Automatic dispatch past the byte class, and the forced float64 / exact-order paths.
+static int calc_disparity_classified(vwgpu_ctx* ctx, const vwgpu_bm_args& a, Grain gr = Grain()) {
+  const int cost_type = a.cost_type, lw = a.lw, lh = a.lh, rw = a.rw, rh = a.rh, kx = a.kx, ky = a.ky, sx = a.sx, sy = a.sy;
+  const float *d_left = a.left, *d_right = a.right;
+  const ptrdiff_t ls = a.ls, rs = a.rs, os = a.os;
+  int32_t* d_out = a.out;
   bool exact = ctx->forced_path == VWGPU_PATH_EXACT_ORDER;
   ctx->last_flag = nullptr;
   int g_lo = INT_MAX, g_hi = INT_MIN, g_nonfinite = 1;
@@ -417,42 +451,15 @@ static int calc_disparity_classified(vwgpu_ctx* ctx, int cost_type, const float*
     if (rc) return rc;
     g_lo = lo; g_hi = hi; g_nonfinite = nonfinite;
     exact = !vwgpu_sums_order_free(cost_type, kx, ky, lo, hi, nonfinite);      // never the tile-local sums on data whose roundings depend on the order
-    // integers below 2^16 (16-bit imagery): the packed-u16 SAD kernel; it checks the sign itself and raises its flag
-    if (!exact && !nonfinite && lo != INT_MAX && lo >= 0 && hi <= 15 && vwgpu_bm_sad_u16_supported(cost_type, kx, ky, sx, sy)) {   // (nonfinite bit 1 = negative pixels)
-      int* d_flag = nullptr;
-      rc = vwgpu_launch_bm_sad_u16(ctx, d_left, lw, lh, ls, d_right, rw, rh, rs, kx, ky, sx, sy, d_out, os, &d_flag);
-      if (rc) return rc;
-      int flag = 0;
-      VWGPU_HIP(ctx, hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
-      VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      if (!flag) { ctx->last_path = VWGPU_PATH_SAD_U16; return VWGPU_OK; }
-    }
-    // integers below 2^12 (11- / 12-bit imagery): float32 products and squared differences are exact, SSD / NCC on v_dot2_u32_u16
-    if (!exact && !nonfinite && lo != INT_MAX && lo >= 0 && hi <= 11 && vwgpu_bm_corr_u16_supported(cost_type, kx, ky, sx, sy)) {
-      int* d_flag = nullptr;
-      rc = vwgpu_launch_bm_corr_u16(ctx, cost_type, d_left, lw, lh, ls, d_right, rw, rh, rs, kx, ky, sx, sy, d_out, os, &d_flag);
-      if (rc) return rc;
-      int flag = 0;
-      VWGPU_HIP(ctx, hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
-      VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      if (!flag) { ctx->last_path = VWGPU_PATH_DOT_U16; return VWGPU_OK; }
-    }
-  } else if (ctx->forced_path == VWGPU_PATH_DOT_U16) {
-    if (!vwgpu_bm_corr_u16_supported(cost_type, kx, ky, sx, sy))
-      return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "calc_disparity: no packed-u16 SSD / NCC path for cost %d kernel %dx%d search %dx%d", cost_type, kx, ky, sx, sy);
-    int* d_flag = nullptr;
-    int rc = vwgpu_launch_bm_corr_u16(ctx, cost_type, d_left, lw, lh, ls, d_right, rw, rh, rs, kx, ky, sx, sy, d_out, os, &d_flag);
-    ctx->last_path = VWGPU_PATH_DOT_U16;
-    ctx->last_flag = d_flag;
-    return rc;
-  } else if (ctx->forced_path == VWGPU_PATH_SAD_U16) {
-    if (!vwgpu_bm_sad_u16_supported(cost_type, kx, ky, sx, sy))
-      return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "calc_disparity: no packed-u16 path for cost %d kernel %dx%d search %dx%d", cost_type, kx, ky, sx, sy);
-    int* d_flag = nullptr;
-    int rc = vwgpu_launch_bm_sad_u16(ctx, d_left, lw, lh, ls, d_right, rw, rh, rs, kx, ky, sx, sy, d_out, os, &d_flag);
-    ctx->last_path = VWGPU_PATH_SAD_U16;
-    ctx->last_flag = d_flag;
-    return rc;
+    // Non-negative integers of a wider class than bytes, each matcher of the table whose class holds them, in its order: below 2^16
+    // (16-bit imagery) the packed-u16 SAD kernel — it checks the sign itself and raises its flag (nonfinite bit 1 = negative pixels);
+    // below 2^12 (11- / 12-bit imagery) float32 products and squared differences are exact, SSD / NCC on v_dot2_u32_u16.
+    if (!exact && !nonfinite && lo != INT_MAX && lo >= 0)
+      for (const vwgpu_bm_matcher* m : kPacked) {
+        if (m->max_hi <= 7 || hi > m->max_hi || !m->supported(a)) continue;
+        bool accepted = false;
+        if ((rc = try_packed(ctx, *m, a, &accepted)) || accepted) return rc;
+      }
   }
   // Float imagery outside the packed classes, automatic dispatch: the tile-parallel zone matcher (bm_zones.hip) with the whole raster as its
   // one zone — the kernel family the pyramid levels run on, several times faster than bm_generic's column-sum tiles and than the
@@ -522,70 +529,60 @@ static int calc_disparity_classified(vwgpu_ctx* ctx, int cost_type, const float*
     return vwgpu_launch_bm_exact(ctx, cost_type, d_left, lw, lh, ls, d_right, rw, rh, rs, kx, ky, &z, 1, d_out);
   }
   ctx->last_path = VWGPU_PATH_GENERIC_F64;
-  return vwgpu_launch_bm_generic(ctx, cost_type, d_left, lw, lh, ls, d_right, rw, rh, rs, kx, ky, sx, sy, d_out, os);
+  return vwgpu_launch_bm_generic(ctx, a);
 }
 
 int vwgpu_calc_disparity_dev(vwgpu_ctx* ctx, int cost_type,
                              const float* d_left, int lw, int lh, ptrdiff_t ls,
                              const float* d_right, int rw, int rh, ptrdiff_t rs,
                              int kx, int ky, int sx, int sy, int32_t* d_out, ptrdiff_t os) {
-  int rc = check_bm_args(ctx, cost_type, d_left, lw, lh, ls, d_right, rw, rh, rs, kx, ky, sx, sy, d_out, os);
+  const vwgpu_bm_args a{cost_type, d_left, lw, lh, ls, d_right, rw, rh, rs, kx, ky, sx, sy, d_out, os ? os : lw - kx + 1};
+  int rc = check_bm_args(ctx, a);
   if (rc) return rc;
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  if (os == 0) os = lw - kx + 1;
-  if (os > INT32_MAX) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "calc_disparity: output stride too large");
+  if (a.os > INT32_MAX) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "calc_disparity: output stride too large");
 
-  const bool sad_ok = vwgpu_bm_sad_u8_supported(cost_type, kx, ky, sx, sy);
-  const bool corr_ok = !sad_ok && vwgpu_bm_corr_u8_supported(cost_type, kx, ky, sx, sy);
-  const bool dot_ok = !sad_ok && (corr_ok || vwgpu_bm_dot_u8_supported(cost_type, kx, ky, sx, sy));
-  if (ctx->forced_path == VWGPU_PATH_SAD_U8 && !sad_ok)
-    return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "calc_disparity: no packed-u8 path for cost %d kernel %dx%d search %dx%d",
-                      cost_type, kx, ky, sx, sy);
-  if (ctx->forced_path == VWGPU_PATH_DOT_U8 && !dot_ok)
-    return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "calc_disparity: no dot-product path for cost %d kernel %dx%d search %dx%d",
-                      cost_type, kx, ky, sx, sy);
-  const bool try_packed = (sad_ok && (ctx->forced_path == VWGPU_PATH_NONE || ctx->forced_path == VWGPU_PATH_SAD_U8)) ||
-                          (dot_ok && (ctx->forced_path == VWGPU_PATH_NONE || ctx->forced_path == VWGPU_PATH_DOT_U8));
-  if (!try_packed)
-    return calc_disparity_classified(ctx, cost_type, d_left, lw, lh, ls, d_right, rw, rh, rs, kx, ky, sx, sy, d_out, os);
+  // The packed matcher of this call: forced, the first of the table with that path id that serves the configuration; automatic, of the byte class.
+  const int forced = ctx->forced_path;
+  const vwgpu_bm_matcher* m = nullptr;
+  const char* what = nullptr;
+  for (const vwgpu_bm_matcher* c : kPacked) {
+    if (forced != VWGPU_PATH_NONE ? c->path != forced : c->max_hi != 7) continue;
+    what = c->what;
+    if (!m && c->supported(a)) m = c;
+  }
+  if (forced != VWGPU_PATH_NONE && what) {                       // a forced packed path: caller inspects vwgpu_last_path()
+    if (!m) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "calc_disparity: no %s path for cost %d kernel %dx%d search %dx%d", what, cost_type, kx, ky, sx, sy);
+    return try_packed(ctx, *m, a, nullptr);
+  }
+  if (!m) return calc_disparity_classified(ctx, a);
 
   // A context whose previous call was not byte imagery measures the class first (0.1 ms at 4096^2) instead of spending a packed-u8
   // launch on data that will be refused again; the order of the attempts is all this changes.
-  if (ctx->forced_path == VWGPU_PATH_NONE && !ctx->defer_exact && ctx->measure_first) {
+  if (!ctx->defer_exact && ctx->measure_first) {
     Grain gr;
     rc = vwgpu_float_grain(ctx, d_left, lw, lh, ls, d_right, lw + sx - 1, lh + sy - 1, rs, &gr.lo, &gr.hi, &gr.nonfinite);
     if (rc) return rc;
     gr.known = true;
     const bool bytes = !gr.nonfinite && (gr.lo == INT_MAX || (gr.lo >= 0 && gr.hi <= 7));
-    if (!bytes) return calc_disparity_classified(ctx, cost_type, d_left, lw, lh, ls, d_right, rw, rh, rs, kx, ky, sx, sy, d_out, os, gr);
+    if (!bytes) return calc_disparity_classified(ctx, a, gr);
   }
   // Integer-valued inputs in [0,255]: the packed kernels; they check the domain while converting and raise a device flag.
-  int* d_flag = nullptr;
-  if (sad_ok) rc = vwgpu_launch_bm_sad_u8(ctx, d_left, lw, lh, ls, d_right, rw, rh, rs, kx, ky, sx, sy, d_out, os, &d_flag);
-  else if (corr_ok) rc = vwgpu_launch_bm_corr_u8(ctx, cost_type, d_left, lw, lh, ls, d_right, rw, rh, rs, kx, ky, sx, sy, d_out, os, &d_flag);
-  else rc = vwgpu_launch_bm_dot_u8(ctx, cost_type, d_left, lw, lh, ls, d_right, rw, rh, rs, kx, ky, sx, sy, d_out, os, &d_flag);
-  if (rc) return rc;
-  ctx->last_path = sad_ok ? VWGPU_PATH_SAD_U8 : VWGPU_PATH_DOT_U8;
-  ctx->last_flag = d_flag;
-  if (ctx->forced_path != VWGPU_PATH_NONE) return VWGPU_OK;       // caller inspects vwgpu_last_path()
-  // Pipelined callers: ONE launch and no host round trip.  Nothing runs behind the flag (rounds 1-3 queued the float64 tile kernel
-  // there, which is not the reference's arithmetic on data whose sums round): input outside the packed kernel's domain leaves
-  // the call without a result, vwgpu_last_path() says VWGPU_PATH_REFUSED, and the caller repeats it with the option off.
-  if (ctx->defer_exact) return VWGPU_OK;
-  int flag = 0;
-  VWGPU_HIP(ctx, hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
-  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->last_flag = nullptr;
-  ctx->measure_first = flag != 0;
-  if (!flag) return VWGPU_OK;
-  return calc_disparity_classified(ctx, cost_type, d_left, lw, lh, ls, d_right, rw, rh, rs, kx, ky, sx, sy, d_out, os);
+  // Pipelined callers (VWGPU_OPT_DEFER_EXACTNESS): ONE launch and no host round trip.  Nothing runs behind the flag (rounds 1-3 queued
+  // the float64 tile kernel there, which is not the reference's arithmetic on data whose sums round): input outside the packed kernel's
+  // domain leaves the call without a result, vwgpu_last_path() says VWGPU_PATH_REFUSED, and the caller repeats it with the option off.
+  bool accepted = false;
+  rc = try_packed(ctx, *m, a, ctx->defer_exact ? nullptr : &accepted);
+  if (rc || ctx->defer_exact) return rc;
+  ctx->measure_first = !accepted;
+  return accepted ? VWGPU_OK : calc_disparity_classified(ctx, a);
 }
 
 int vwgpu_calc_disparity(vwgpu_ctx* ctx, int cost_type,
                          const float* left, int lw, int lh, ptrdiff_t ls,
                          const float* right, int rw, int rh, ptrdiff_t rs,
                          int kx, int ky, int sx, int sy, int32_t* out, ptrdiff_t os) {
-  int rc = check_bm_args(ctx, cost_type, left, lw, lh, ls, right, rw, rh, rs, kx, ky, sx, sy, out, os);
+  int rc = check_bm_args(ctx, vwgpu_bm_args{cost_type, left, lw, lh, ls, right, rw, rh, rs, kx, ky, sx, sy, out, os});
   if (rc) return rc;
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
   const int ow = lw - kx + 1, oh = lh - ky + 1;

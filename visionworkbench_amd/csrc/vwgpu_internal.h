@@ -141,52 +141,51 @@ struct vwgpu_stage {
 // ---- kernel-family launchers (each in its own .hip) ------------------------------------------------
 // All pointers are device pointers; every launcher enqueues on ctx->stream and returns a vwgpu_status.
 
-int vwgpu_launch_bm_generic(vwgpu_ctx* ctx, int cost_type,
-                            const float* left, int lw, int lh, ptrdiff_t ls,
-                            const float* right, int rw, int rh, ptrdiff_t rs,
-                            int kx, int ky, int sx, int sy, int32_t* out, ptrdiff_t os);
+// The operands of one whole-raster block-matching call, as vwgpu_calc_disparity_dev received them (os defaulted).
+struct vwgpu_bm_args {
+  int cost_type;
+  const float* left; int lw, lh; ptrdiff_t ls;
+  const float* right; int rw, rh; ptrdiff_t rs;
+  int kx, ky, sx, sy;
+  int32_t* out; ptrdiff_t os;
+  int ow() const { return lw - kx + 1; }
+  int oh() const { return lh - ky + 1; }
+};
 
-// Same, but the kernel returns immediately when run_flag != NULL and *run_flag == 0 (device memory).
-int vwgpu_launch_bm_generic_flag(vwgpu_ctx* ctx, int cost_type,
-                                 const float* left, int lw, int lh, ptrdiff_t ls,
-                                 const float* right, int rw, int rh, ptrdiff_t rs,
-                                 int kx, int ky, int sx, int sy, int32_t* out, ptrdiff_t os,
-                                 const int* run_flag);
+int vwgpu_launch_bm_generic(vwgpu_ctx* ctx, const vwgpu_bm_args& a);
 
-// Returns VWGPU_ERR_NOIMPL (without touching `out`) if this configuration has no u8 fast path;
-// otherwise enqueues pack + match.  *d_fallback_flag (device int) is nonzero afterwards if the inputs were
-// not integer-valued in [0,255] — the caller must then run the generic path.
-bool vwgpu_bm_sad_u8_supported(int cost_type, int kx, int ky, int sx, int sy);
-int vwgpu_launch_bm_sad_u8(vwgpu_ctx* ctx,
-                           const float* left, int lw, int lh, ptrdiff_t ls,
-                           const float* right, int rw, int rh, ptrdiff_t rs,
-                           int kx, int ky, int sx, int sy, int32_t* out, ptrdiff_t os,
-                           int** d_fallback_flag);
+// A packed-integer matcher: exact on integer-valued pixels of its class, and it checks the class itself while converting — input
+// outside it leaves *d_flag (device int) nonzero once the launch has run, and the caller must then take another path.
+//   bm_sad_u8.hip    SAD, [0,255] (v_qsad_pk_u16_u8)
+//   bm_corr_u8.hip   SSD / NCC, [0,255], register-blocked v_dot4_u32_u8 (preferred over bm_dot_u8 where instantiated)
+//   bm_dot_u8.hip    SSD / NCC, [0,255], v_dot4_u32_u8
+//   bm_sad_u16.hip   SAD, [0,65535] (v_sad_u16 on pixel pairs)
+//   bm_corr_u16.hip  SSD / NCC, [0,4095] (v_dot2_u32_u16 on pixel pairs)
+struct vwgpu_bm_matcher {
+  int path;           // what vwgpu_last_path reports
+  int max_hi;         // the largest `hi` exponent of vwgpu_float_grain inside the class
+  const char* what;   // names the path in the NOIMPL text of a forced call
+  bool (*supported)(const vwgpu_bm_args& a);                              // false: this configuration has no such kernel
+  int (*launch)(vwgpu_ctx* ctx, const vwgpu_bm_args& a, int** d_flag);
+};
+// (Not const objects: the device compilation would emit a constant-initialised const object too, and has no such host functions.)
+extern vwgpu_bm_matcher vwgpu_bm_sad_u8, vwgpu_bm_corr_u8, vwgpu_bm_dot_u8, vwgpu_bm_sad_u16, vwgpu_bm_corr_u16;
 
-// bm_dot_u8.hip: SSD / NCC on integer-valued [0,255] inputs (v_dot4_u32_u8); same fallback-flag protocol as the SAD path
-bool vwgpu_bm_dot_u8_supported(int cost_type, int kx, int ky, int sx, int sy);
-int vwgpu_launch_bm_dot_u8(vwgpu_ctx* ctx, int cost_type, const float* left, int lw, int lh, ptrdiff_t ls,
-                           const float* right, int rw, int rh, ptrdiff_t rs, int kx, int ky, int sx, int sy,
-                           int32_t* out, ptrdiff_t os, int** d_fallback_flag);
-int vwgpu_next_flags(vwgpu_ctx* ctx, size_t extra_ints, int** flag_set, int** flag_clear, int** extra);
-// bm_sad_u16.hip: SAD for integer-valued imagery in [0,65535] (v_sad_u16 on pixel pairs); same fallback-flag protocol
-bool vwgpu_bm_sad_u16_supported(int cost_type, int kx, int ky, int sx, int sy);
-int vwgpu_launch_bm_sad_u16(vwgpu_ctx* ctx, const float* left, int lw, int lh, ptrdiff_t ls,
-                            const float* right, int rw, int rh, ptrdiff_t rs, int kx, int ky, int sx, int sy,
-                            int32_t* out, ptrdiff_t os, int** d_fallback_flag);
-// bm_corr_u8.hip: register-blocked SSD / NCC for the same inputs (preferred over bm_dot_u8 where instantiated)
-bool vwgpu_bm_corr_u8_supported(int cost_type, int kx, int ky, int sx, int sy);
-int vwgpu_launch_bm_corr_u8(vwgpu_ctx* ctx, int cost_type, const float* left, int lw, int lh, ptrdiff_t ls,
-                            const float* right, int rw, int rh, ptrdiff_t rs, int kx, int ky, int sx, int sy,
-                            int32_t* out, ptrdiff_t os, int** d_fallback_flag);
-int vwgpu_launch_ncc_full(vwgpu_ctx* ctx, const float* left, ptrdiff_t ls, const float* right, ptrdiff_t rs, int kx, int ky, int sx,
-                          const uint32_t* a2, const uint32_t* b2, int b2w, int32_t* out, ptrdiff_t os, int ow, int* flag,
-                          const uint32_t* full_list, const uint32_t* full_count, uint32_t cap);
-// bm_corr_u16.hip: SSD / NCC for integer-valued imagery in [0,4095] (v_dot2_u32_u16 on pixel pairs); same fallback-flag protocol
-bool vwgpu_bm_corr_u16_supported(int cost_type, int kx, int ky, int sx, int sy);
-int vwgpu_launch_bm_corr_u16(vwgpu_ctx* ctx, int cost_type, const float* left, int lw, int lh, ptrdiff_t ls,
-                             const float* right, int rw, int rh, ptrdiff_t rs, int kx, int ky, int sx, int sy,
-                             int32_t* out, ptrdiff_t os, int** d_fallback_flag);
+// The start of every packed launcher: the call's two alternating flags (*d_flag = the one this call raises, `clear` the next call's)
+// and, for a request of more than 64 KiB, the dynamic-LDS limit of the kernel.
+struct vwgpu_flag_pair { int* set = nullptr; int* clear = nullptr; };
+int vwgpu_packed_prologue(vwgpu_ctx* ctx, const void* kernel, size_t shmem, int** d_flag, vwgpu_flag_pair* flags);
+
+// Scratch of the integer NCC matchers (bm_corr_u8.hip, bm_corr_u16.hip) in ctx->scratch: the window sums of squares of both images and
+// the queue of pixels that ncc_full_kernel evaluates over every disparity in float64 (the count zeroed).  `who` names the caller in errors.
+struct vwgpu_ncc_plan {
+  uint32_t *a2 = nullptr, *b2 = nullptr;
+  int b2w = 0;
+  uint32_t *full_list = nullptr, *full_count = nullptr;
+  uint32_t cap = 0;
+};
+int vwgpu_ncc_plan_reserve(vwgpu_ctx* ctx, const vwgpu_bm_args& a, const char* who, vwgpu_ncc_plan* p);
+int vwgpu_launch_ncc_full(vwgpu_ctx* ctx, const vwgpu_bm_args& a, const vwgpu_ncc_plan& p, int* flag);
 
 // bm_exact.hip: the reference's own summation order (serial column / row chains of fast_box_sum) for inputs whose
 // partial sums are not exactly representable; see the file header.

@@ -763,17 +763,37 @@ int vwgpu_intersect_mask_and_data(vwgpu_ctx* ctx, int type, const void* data, pt
  *                            point, its 19 passes, its best-so-far fallbacks and its 1e-9 stop on the step; fu or fv
  *                            below 1e-300 gives HUGE_VAL.
  *   VWGPU_CAMERA_CAHV     CAHVModel::pixel_to_vector / camera_center (src/vw/Camera/CAHVModel.cc:173-189):
- *                         normalize(cross(V - y A, H - x A)), times -1.0 when dot(cross(V, H), A) < 0, from C = `center`. */
-typedef enum vwgpu_camera_kind { VWGPU_CAMERA_PINHOLE = 0, VWGPU_CAMERA_CAHV = 1 } vwgpu_camera_kind;
+ *                         normalize(cross(V - y A, H - x A)), times -1.0 when dot(cross(V, H), A) < 0, from C = `center`.
+ *   VWGPU_CAMERA_CAHVOR   CAHVORModel::pixel_to_vector and point_to_pixel without partials (src/vw/Camera/CAHVORModel.cc:297-348,
+ *                         :431-448): radial distortion about the axis O with the coefficients R.  The Newton loop on
+ *                         k5 u^5 + k3 u^3 + k1 u = 1 keeps its exits (20 passes, deriv <= 0, |du| < 1e-6 after the step); none
+ *                         of them is a failure.  Only + - * / sqrt fabs: the reference's bits.
+ *   VWGPU_CAMERA_CAHVORE  CAHVOREModel::pixel_to_vector and point_to_pixel (src/vw/Camera/CAHVOREModel.cc:167-301): fisheye
+ *                         with the linearity P (1 perspective, 0 fisheye) and the moving entrance pupil E.  Where the
+ *                         reference throws ("Did not converge." after 101 Newton steps, "Theta out of bounds.") the pixel
+ *                         counts as failed, as below.  sin, cos, tan, atan, atan2 and asin are the device library's.
+ * The kinds 3 and 4 follow 1: the value 2 was refused with VWGPU_ERR_ARGUMENT before they existed, callers and tests rely on
+ * that, and it stays unassigned and refused.
+ * The descriptor keeps its 256 bytes.  For a CAHVOR or CAHVORE camera center, A, H, V mean what they mean for CAHV, and
+ * O, R, E and P live in storage only a pinhole uses:
+ *   inv_camera_transform[0..2] = O, [3..5] = R, [6..8] = E (CAHVORE);  distortion[0] = P (CAHVORE).
+ * Callers do not write these by hand: vwgpu_cahvor_camera and vwgpu_cahvore_camera fill a descriptor.
+ * Pairs that have a kernel: vwgpu_camera_transform* with one CAHVOR or CAHVORE camera and one CAHV camera, in either role;
+ * triangulation and the convergence angle with two CAHVOR or two CAHVORE cameras.  Every other pair with a CAHVOR or
+ * CAHVORE camera (with a pinhole, CAHVOR with CAHVORE, two of them in a camera transform, one of them beside another kind
+ * in triangulation) is VWGPU_ERR_NOIMPL with a message that names the pair, before any device work. */
+typedef enum vwgpu_camera_kind {
+  VWGPU_CAMERA_PINHOLE = 0, VWGPU_CAMERA_CAHV = 1, VWGPU_CAMERA_CAHVOR = 3, VWGPU_CAMERA_CAHVORE = 4
+} vwgpu_camera_kind;
 typedef enum vwgpu_distortion_kind { VWGPU_DISTORTION_NULL = 0, VWGPU_DISTORTION_TSAI = 1 } vwgpu_distortion_kind;
 typedef struct vwgpu_camera {
   int kind;                          /* vwgpu_camera_kind */
   int distortion_kind;               /* vwgpu_distortion_kind (pinhole) */
-  double center[3];                  /* camera centre (pinhole), C (CAHV) */
-  double inv_camera_transform[9];    /* pinhole */
+  double center[3];                  /* camera centre (pinhole), C (CAHV, CAHVOR, CAHVORE) */
+  double inv_camera_transform[9];    /* pinhole; O, R, E of CAHVOR / CAHVORE */
   double pixel_pitch, fu, fv, cu, cv;
-  double distortion[5];
-  double A[3], H[3], V[3];           /* CAHV */
+  double distortion[5];              /* pinhole; [0] = P of CAHVORE */
+  double A[3], H[3], V[3];           /* CAHV, CAHVOR, CAHVORE */
 } vwgpu_camera;
 
 /* Fills a pinhole descriptor the way PinholeModel::rebuild_camera_matrix does (src/vw/Camera/PinholeModel.cc:553-605):
@@ -786,6 +806,22 @@ typedef struct vwgpu_camera {
 int vwgpu_pinhole_camera(const double* center, const double* rotation, double fu, double fv, double cu, double cv,
                          const double* u_dir, const double* v_dir, const double* w_dir, double pixel_pitch, int distortion_kind,
                          const double* distortion, vwgpu_camera* out);
+
+/* CAHVORModel(C, A, H, V, O, R) and CAHVOREModel(C, A, H, V, O, R, E, T, P) (src/vw/Camera/CAHVOREModel.cc:111-124) into a
+ * descriptor; every vector is double[3].  type (T) 1 sets P = 1, 2 sets P = 0, 3 takes P in [0, 1]; any other type or P:
+ * VWGPU_ERR_ARGUMENT, as a null pointer.  Pure host arithmetic, no context. */
+int vwgpu_cahvor_camera(const double* C, const double* A, const double* H, const double* V, const double* O, const double* R,
+                        vwgpu_camera* out);
+int vwgpu_cahvore_camera(const double* C, const double* A, const double* H, const double* V, const double* O, const double* R,
+                         const double* E, int type, double P, vwgpu_camera* out);
+
+/* linearize_camera(CAHVORModel | CAHVOREModel, input size, output size) (src/vw/Camera/CAHVORModel.cc:460-547,
+ * src/vw/Camera/CAHVOREModel.cc:303-381): the CAHV camera with the same centre that sees the common field of view of the
+ * six landmarks on each pair of edges of an in_w x in_h frame, for an out_w x out_h image.  Reproduced as it is, with the
+ * reference's integer and real midpoints (an even and an odd width differ by more than the half pixel).  It runs the
+ * model functions of the kernels on the host.  src of another kind, a size <= 0, a null pointer: VWGPU_ERR_ARGUMENT; a
+ * CAHVORE landmark ray that does not converge: VWGPU_ERR_LOGIC.  dst may be src.  Pure host arithmetic, no context. */
+int vwgpu_linearize_camera(const vwgpu_camera* src, int in_w, int in_h, int out_w, int out_h, vwgpu_camera* dst);
 
 /* How the right pixel of a pair is formed (the two entry points of the reference differ, and the difference is kept):
  *   VWGPU_TRIANGULATE_VIEW   StereoView::operator() (src/vw/Stereo/StereoView.h:91-99): Vector2(i, j) + Vector2((double)dx,
@@ -825,8 +861,10 @@ typedef struct vwgpu_triangulate_stats {
  * camera.  error = norm_2(errvec).  An invalid disparity pixel gives a zero point, error and error vector.
  *   xyz     w x h x 3 double (stride in pixels); error (optional) w x h double; errvec (optional) w x h x 3 double.
  *   stats   optional vwgpu_triangulate_stats: a DEVICE pointer for _dev (no synchronisation), a host pointer otherwise.
+ * A CAHVORE ray that does not converge gives the zero point and error vector (the catch of PixelToRayErr, :144-146).
  * Null disp / xyz / cameras, w or h <= 0, a stride below the width, type, camera kind, distortion kind, semantics or layout
- * out of range, NaN angle_tol: VWGPU_ERR_ARGUMENT before any device work.  Outputs must not alias each other. */
+ * out of range, NaN angle_tol: VWGPU_ERR_ARGUMENT before any device work; a CAHVOR or CAHVORE camera beside a camera of
+ * another kind: VWGPU_ERR_NOIMPL.  Outputs must not alias each other. */
 int vwgpu_stereo_triangulate_dev(vwgpu_ctx* ctx, int type, const void* d_disp, int w, int h, ptrdiff_t dstride, int x0, int y0,
                                  const vwgpu_camera* cam1, const vwgpu_camera* cam2, double angle_tol, int semantics, double* d_xyz,
                                  ptrdiff_t xstride, double* d_error, ptrdiff_t estride, double* d_errvec, ptrdiff_t vstride,
@@ -839,7 +877,7 @@ int vwgpu_stereo_triangulate(vwgpu_ctx* ctx, int type, const void* disp, int w, 
 /* Replaces StereoModel::convergence_angle (src/vw/Stereo/StereoModel.cc:174-177) over a disparity map: out is w x h double,
  * acos(dot(cam1.pixel_to_vector(pix1), cam2.pixel_to_vector(pix2))) with the pixel pair formed as above (no pixel is
  * skipped: a NaN pixel gives a NaN angle); invalid disparity pixels give 0.  The dot product is the reference's bits, acos
- * is the device library's. */
+ * is the device library's.  A CAHVORE ray that does not converge (the reference throws) gives a NaN angle. */
 int vwgpu_convergence_angle_dev(vwgpu_ctx* ctx, int type, const void* d_disp, int w, int h, ptrdiff_t dstride, int x0, int y0,
                                 const vwgpu_camera* cam1, const vwgpu_camera* cam2, int semantics, double* d_out, ptrdiff_t ostride);
 int vwgpu_convergence_angle(vwgpu_ctx* ctx, int type, const void* disp, int w, int h, ptrdiff_t dstride, int x0, int y0,
@@ -886,7 +924,7 @@ int vwgpu_epipolar_cahv(const vwgpu_camera* src0, const vwgpu_camera* src1, vwgp
 /* Replaces rasterising camera_transform(image, src_camera, dst_camera, size, edge, BilinearInterpolation())
  * (src/vw/Camera/CameraTransform.h:43-183) for a float image with an optional validity mask (PixelMask<float>).
  *   src          sw x sh floats; src_mask optional uint8 of the same size (0 = invalid); strides in elements, 0 = packed
- *   src_matrix, dst_matrix   vwgpu_pinhole_camera_matrix of a pinhole camera; NULL for a CAHV camera
+ *   src_matrix, dst_matrix   vwgpu_pinhole_camera_matrix of a pinhole camera; NULL for a CAHV, CAHVOR or CAHVORE camera
  *   w, h         output size; x0, y0 the image coordinates of output pixel (0, 0): a tile equals that region of the whole call
  *   edge_value, edge_valid   the ValueEdgeExtension pixel; 0, 0 is ZeroEdgeExtension
  *   check        PinholeModel::set_do_point_to_pixel_check of the source camera (the reference's default is on)
@@ -903,7 +941,10 @@ int vwgpu_epipolar_cahv(const vwgpu_camera* src0, const vwgpu_camera* src1, vwgp
  * (src/vw/Image/PixelMask.h:321-345, :424-433).  Where the reference throws PointToPixelErr (the round trip of
  * PinholeModel.cc:378-394, ERROR_THRESHOLD 0.01) the pixel is written as the edge pixel and counted; the host-pointer
  * entry then returns VWGPU_ERR_LOGIC with the reference's message and the count in vwgpu_last_error (the images are
- * complete), the _dev entry only writes the count.
+ * complete), the _dev entry only writes the count.  The throws of a CAHVORE camera are treated the same way, a dst ray
+ * that does not converge (PixelToRayErr) and a src projection that does not converge or whose theta is out of bounds: the
+ * message is "CAHVOREModel: Did not converge." if any pixel did not converge, else "CAHVOREModel: Theta out of bounds.".
+ * A CAHVOR or CAHVORE camera goes with a CAHV camera only, in either role: any other pair is VWGPU_ERR_NOIMPL.
  * Cameras whose centres differ: VWGPU_ERR_LOGIC (the reference's assert) before any device work.  Null src / out /
  * cameras, sizes <= 0, a stride below the width, a camera or lens kind out of range, a pinhole without its matrix, out or
  * out_mask aliasing an input or each other, a NaN edge_value with edge_valid: VWGPU_ERR_ARGUMENT before any device work. */

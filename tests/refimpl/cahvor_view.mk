@@ -1,0 +1,14 @@
+# cahvor_view: a vwlite program over libvwgpu.so (test infrastructure only); make -f cahvor_view.mk.
+CXX ?= g++
+ROOT := ../..
+LIBDIR := $(abspath $(ROOT)/visionworkbench_amd/lib)
+ROCM_LIB ?= /opt/rocm/lib
+CXXFLAGS ?= -O1 -std=c++17 -Wall -ffp-contract=off
+
+all: cahvor_view
+
+cahvor_view: cahvor_view.cc $(ROOT)/visionworkbench_amd/vwlite/vw/Camera.h $(ROOT)/visionworkbench_amd/vwlite/vw/CameraTransform.h $(ROOT)/include/vwgpu.h
+	$(CXX) $(CXXFLAGS) -I$(ROOT)/include -I$(ROOT)/visionworkbench_amd/vwlite -o $@ cahvor_view.cc -L$(LIBDIR) -lvwgpu -Wl,-rpath,$(LIBDIR) -Wl,-rpath,$(ROCM_LIB) -pthread
+
+clean:
+	rm -f cahvor_view

@@ -7,7 +7,8 @@ calls after a warm-up call, divided by the count; the median of `--windows` such
 bytes per pixel over that time (4 read + 4 written, 5 + 5 with masks), and the ratio to a device-to-device copy of the
 SAME number of bytes timed in the same run, which is the yardstick (no data-sheet number enters).  Cases: pinhole ->
 pinhole with the point-to-pixel check on and off, a Tsai source with the check on (the Newton loop) and off, CAHV -> CAHV,
-and the masked form.  VWGPU_LIBRARY selects another build of the library (make -C visionworkbench_amd/csrc ct16: the
+the masked form, and a CAHVOR and a CAHVORE source (the reference's test cameras scaled to the frame) into their own
+linearisation, masked and not, with the re-distortion (CAHV -> CAHVOR / CAHVORE) beside them.  VWGPU_LIBRARY selects another build of the library (make -C visionworkbench_amd/csrc ct16: the
 16 x 16 workgroup footprint).
 usage: python tools/time_camera_transform.py [--size 4096] [--repeat 20] [--windows 5]"""
 import argparse
@@ -102,6 +103,14 @@ def main():
     report("Tsai src -> pinhole, check off", gpu(transform(src_tsai, dst, False, False)), 8)
     report("CAHV -> CAHV", gpu(transform(tri.cahv_of(src), tri.cahv_of(dst), True, False)), 8)
     report("pinhole -> pinhole, check on, masked", gpu(transform(src, dst, True, True)), 10)
+    # CAHVOR / CAHVORE: the fixture cameras of the tests (1024^2 frames) scaled to n, into their own linearisation
+    import cahvor_ref
+    for name, make in (("CAHVOR", cahvor_ref.cahvor), ("CAHVORE", cahvor_ref.cahvore)):
+        raw = make(n / 1024.0)
+        lin = camera.linearize_camera(raw, (n, n))
+        report("%s -> CAHV" % name, gpu(transform(raw, lin, True, False)), 8)
+        report("%s -> CAHV, masked" % name, gpu(transform(raw, lin, True, True)), 10)
+        report("CAHV -> %s" % name, gpu(transform(lin, raw, True, False)), 8)
     ctx.close()
 
 

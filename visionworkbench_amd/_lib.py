@@ -37,6 +37,7 @@ SYMBOLS = [
     "vwgpu_convergence_angle_dev", "vwgpu_convergence_angle", "vwgpu_universe_radius_dev", "vwgpu_universe_radius",
     "vwgpu_pinhole_camera_matrix", "vwgpu_epipolar_pinhole", "vwgpu_epipolar_cahv",
     "vwgpu_camera_transform_dev", "vwgpu_camera_transform", "vwgpu_camera_transform_points_dev", "vwgpu_camera_transform_points",
+    "vwgpu_cahvor_camera", "vwgpu_cahvore_camera", "vwgpu_linearize_camera",
     "vwgpu_disparity_filter_dev", "vwgpu_disparity_filter",
     "vwgpu_disparity_mask_dev", "vwgpu_disparity_mask",
     "vwgpu_subdivide_regions",
@@ -232,6 +233,9 @@ def load():
     lib.vwgpu_pinhole_camera_matrix.argtypes = [P, P, D, D, D, D, P, P, P, D, I, P, P]
     lib.vwgpu_epipolar_pinhole.argtypes = [P, P, P, P, D, P, P, P, P, D, P, P, P, P]
     lib.vwgpu_epipolar_cahv.argtypes = [CP, CP, CP, CP]
+    lib.vwgpu_cahvor_camera.argtypes = [P, P, P, P, P, P, CP]
+    lib.vwgpu_cahvore_camera.argtypes = [P, P, P, P, P, P, P, I, D, CP]
+    lib.vwgpu_linearize_camera.argtypes = [CP, I, I, I, I, CP]
     ctr = [P, P, I, I, PD, P, PD, CP, P, CP, P, I, I, I, I, F, I, I, P, PD, P, PD, P]
     lib.vwgpu_camera_transform_dev.argtypes = ctr
     lib.vwgpu_camera_transform.argtypes = ctr

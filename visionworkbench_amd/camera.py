@@ -1,5 +1,6 @@
 """The part of vw::camera that triangulation and epipolar rectification need: PinholeModel with the null or the Tsai lens
-distortion and CAHVModel, epipolar(), resize_epipolar_cameras_to_fit, CameraTransform and camera_transform.
+distortion, CAHVModel, CAHVORModel and CAHVOREModel, epipolar(), linearize_camera, resize_epipolar_cameras_to_fit,
+CameraTransform and camera_transform.
 
 Each model is a host object that produces the flat camera descriptor of the C ABI (struct vwgpu_camera, include/vwgpu.h)
 and, for a pinhole, the 3 x 4 camera matrix that travels beside it; the rays and projections themselves are computed on
@@ -7,14 +8,15 @@ the device (stereo.stereo_triangulate, camera_transform, CameraTransform).  poin
 (scene building, tests); the models and epipolar() need no GPU.
 """
 import ctypes
+import re
 
 import numpy as np
 
 from . import _lib
 from ._operands import Operands
-from .core import ArgumentErr, BBox2i
+from .core import ArgumentErr, BBox2i, IOErr, LogicErr
 
-CAMERA_PINHOLE, CAMERA_CAHV = 0, 1
+CAMERA_PINHOLE, CAMERA_CAHV, CAMERA_CAHVOR, CAMERA_CAHVORE = 0, 1, 3, 4      # 2 is unassigned and refused (include/vwgpu.h)
 DISTORTION_NULL, DISTORTION_TSAI = 0, 1
 
 
@@ -130,18 +132,242 @@ class CAHVModel(object):
         return np.array([p @ self.H / d, p @ self.V / d])
 
 
+def _read_vectors(path, names, who):
+    """The `X = a b c` lines of the reference's camera files in the order `names`, after anything that precedes `C =`
+    (src/vw/Camera/CAHVORModel.cc:30-78)."""
+    try:
+        with open(path) as f:
+            text = f.read()
+    except OSError as e:
+        raise IOErr("%s: Could not read file: %s (%s)" % (who, path, e))
+    start = re.search(r"C\s*=", text)
+    if start is None:
+        raise IOErr("%s: Could not read file: %s" % (who, path))
+    tokens = text[start.start():].replace("=", " = ").split()
+    out, k = {}, 0
+    for name, count in names:
+        if tokens[k:k + 2] != [name, "="] or len(tokens) < k + 2 + count:
+            raise IOErr("%s: Could not read %s vector" % (who, name))
+        try:
+            out[name] = [float(t) for t in tokens[k + 2:k + 2 + count]]
+        except ValueError:
+            raise IOErr("%s: Could not read %s vector" % (who, name))
+        k += 2 + count
+    return out
+
+
+def _g20(v):
+    return "%.20g" % v          # std::ofstream with precision(20)
+
+
+def _write_vectors(path, rows, who):
+    try:
+        with open(path, "w") as f:
+            for name, v in rows:
+                f.write("%s = %s\n" % (name, " ".join(_g20(x) for x in np.atleast_1d(v))))
+    except OSError as e:
+        raise IOErr("%s: Could not write file: %s (%s)" % (who, path, e))
+
+
+def _normalize(v):
+    return v / np.sqrt(v @ v)
+
+
+class CAHVORModel(object):
+    """vw::camera::CAHVORModel(C, A, H, V, O, R) (src/vw/Camera/CAHVORModel.h): CAHV with radial distortion about the axis O
+    with the coefficients R.  The rays and projections of the device are the reference's bits; pixel_to_vector and
+    point_to_pixel here are a host convenience in numpy."""
+
+    def __init__(self, C, A, H, V, O, R):
+        self.C, self.A, self.H, self.V, self.O, self.R = (_vec3(x, "CAHVORModel: " + n) for x, n in zip((C, A, H, V, O, R), "CAHVOR"))
+        self.descriptor = _lib.Camera()
+        rc = _lib.load().vwgpu_cahvor_camera(self.C.ctypes.data, self.A.ctypes.data, self.H.ctypes.data, self.V.ctypes.data,
+                                             self.O.ctypes.data, self.R.ctypes.data, ctypes.byref(self.descriptor))
+        if rc != 0:
+            raise ArgumentErr("CAHVORModel: bad arguments")
+
+    def type(self):
+        return "CAHVOR"
+
+    def camera_center(self, pix=None):
+        return self.C.copy()
+
+    def pixel_to_vector(self, pix):
+        """CAHVORModel::pixel_to_vector (src/vw/Camera/CAHVORModel.cc:297-348)."""
+        rr = _normalize(np.cross(self.V - pix[1] * self.A, self.H - pix[0] * self.A))
+        if np.cross(self.V, self.H) @ self.A < 0:
+            rr = -rr
+        omega = rr @ self.O
+        lam = rr - omega * self.O
+        tau = lam @ lam / (omega * omega)
+        k1, k3, k5 = 1 + self.R[0], self.R[1] * tau, self.R[2] * tau * tau
+        u = 1.0 - (self.R[0] + k3 + k5)
+        for _ in range(20):
+            u2 = u * u
+            poly = ((k5 * u2 + k3) * u2 + k1) * u - 1
+            deriv = (5 * k5 * u2 + 3 * k3) * u2 + k1
+            if deriv <= 0:
+                break
+            du = poly / deriv
+            u -= du
+            if abs(du) < 1e-6:
+                break
+        return _normalize(rr - (1 - u) * lam)
+
+    def point_to_pixel(self, point):
+        """CAHVORModel::point_to_pixel (src/vw/Camera/CAHVORModel.cc:431-448)."""
+        vec = _vec3(point, "point_to_pixel: the point") - self.C
+        omega = vec @ self.O
+        lam = vec - omega * self.O
+        tau = lam @ lam / (omega * omega)
+        mu = self.R[0] + self.R[1] * tau + self.R[2] * tau * tau
+        pp = vec + mu * lam
+        alpha = pp @ self.A
+        return np.array([pp @ self.H / alpha, pp @ self.V / alpha])
+
+    @classmethod
+    def read(cls, path):
+        """CAHVORModel(filename) (src/vw/Camera/CAHVORModel.cc:30-78)."""
+        v = _read_vectors(path, [(n, 3) for n in "CAHVOR"], "CAHVORModel")
+        return cls(*(v[n] for n in "CAHVOR"))
+
+    def write(self, path):
+        """CAHVORModel::write (src/vw/Camera/CAHVORModel.cc:93-112): 20 significant digits."""
+        _write_vectors(path, [(n, getattr(self, n)) for n in "CAHVOR"], "CAHVORModel")
+
+
+class CAHVOREModel(object):
+    """vw::camera::CAHVOREModel(C, A, H, V, O, R, E, T, P) (src/vw/Camera/CAHVOREModel.cc:105-132): the fisheye member of the
+    family, with the moving entrance pupil E and the linearity P.  T = 1 (perspective) sets P = 1, T = 2 (fisheye) sets
+    P = 0, T = 3 (general) takes P; without T, P itself is given.  P outside [0, 1] or another T raises ArgumentErr."""
+
+    def __init__(self, C, A, H, V, O, R, E, T=None, P=1.0):
+        names = "CAHVORE"
+        self.C, self.A, self.H, self.V, self.O, self.R, self.E = (_vec3(x, "CAHVOREModel: " + n) for x, n in zip((C, A, H, V, O, R, E), names))
+        T = 3 if T is None else T
+        if T not in (1, 2, 3):
+            raise ArgumentErr("Unknown CAHVORE type: %r" % (T,))
+        self.descriptor = _lib.Camera()
+        rc = _lib.load().vwgpu_cahvore_camera(self.C.ctypes.data, self.A.ctypes.data, self.H.ctypes.data, self.V.ctypes.data,
+                                              self.O.ctypes.data, self.R.ctypes.data, self.E.ctypes.data, int(T), float(P),
+                                              ctypes.byref(self.descriptor))
+        if rc != 0:
+            raise ArgumentErr("Invalid P value: %r" % (P,))
+        self.P = float(self.descriptor.distortion[0])
+
+    def type(self):
+        return "CAHVORE"
+
+    def camera_center(self, pix=None):
+        return self.C.copy()
+
+    def pixel_to_vector(self, pix):
+        """CAHVOREModel::pixel_to_vector (src/vw/Camera/CAHVOREModel.cc:167-228); LogicErr where it does not converge."""
+        w3 = np.cross(self.V - pix[1] * self.A, self.H - pix[0] * self.A)
+        rp = w3 / (self.A @ np.cross(self.V, self.H))
+        zetap = rp @ self.O
+        lam3 = rp - zetap * self.O
+        chip = np.sqrt(lam3 @ lam3) / zetap
+        if chip < 1e-8:
+            return self.O.copy()
+        chi, dchi, R = chip, 1.0, self.R
+        for n in range(102):
+            if n > 100:
+                raise LogicErr("CAHVOREModel: Did not converge.")
+            if abs(dchi) < 1e-8:
+                break
+            with np.errstate(all="ignore"):
+                deriv = (1 + R[0]) + 3 * R[1] * chi ** 2 + 5 * R[2] * chi ** 4
+                dchi = ((1 + R[0]) * chi + R[1] * chi ** 3 + R[2] * chi ** 5 - chip) / deriv
+            chi -= dchi
+        P = self.P
+        theta = np.arcsin(P * chi) / P if P < -1e-15 else np.arctan(P * chi) / P if P > 1e-15 else chi
+        return np.sin(theta) * _normalize(lam3) + np.cos(theta) * self.O
+
+    def point_to_pixel(self, point):
+        """CAHVOREModel::point_to_pixel (src/vw/Camera/CAHVOREModel.cc:232-301); LogicErr where it throws."""
+        p_c = _vec3(point, "point_to_pixel: the point") - self.C
+        zeta = p_c @ self.O
+        lam3 = p_c - zeta * self.O
+        lam = np.sqrt(lam3 @ lam3)
+        theta, dtheta, E, R, P = np.arctan2(lam, zeta), 1.0, self.E, self.R, self.P
+        for n in range(102):
+            if n > 100:
+                raise LogicErr("CAHVOREModel: Did not converge.")
+            if abs(dtheta) < 1e-8:
+                break
+            c, s, t2, t3, t4 = np.cos(theta), np.sin(theta), theta ** 2, theta ** 3, theta ** 4
+            ups = zeta * c + lam * s - (1 - c) * (E[0] + E[1] * t2 + E[2] * t4) - (theta - s) * (2 * E[1] * theta + 4 * E[2] * t3)
+            dtheta = (zeta * s - lam * c - (theta - s) * (E[0] + E[1] * t2 + E[2] * t4)) / ups
+            theta -= dtheta
+        if theta * abs(P) > np.pi / 2:
+            raise LogicErr("CAHVOREModel: Theta out of bounds.")
+        if theta < 1e-8:
+            rp = p_c
+        else:
+            chi = np.sin(P * theta) / P if P < -1e-15 else np.tan(P * theta) / P if P > 1e-15 else theta
+            mu = R[0] + chi * chi * (R[1] + chi * chi * R[2])
+            rp = (lam / chi) * self.O + (1 + mu) * lam3
+        alpha = rp @ self.A
+        return np.array([rp @ self.H / alpha, rp @ self.V / alpha])
+
+    @classmethod
+    def read(cls, path):
+        """CAHVOREModel(filename) (src/vw/Camera/CAHVOREModel.cc:38-103)."""
+        v = _read_vectors(path, [(n, 3) for n in "CAHVORE"] + [("T", 1), ("P", 1)], "CAHVOREModel")
+        t = v["T"][0]
+        if t != int(t):
+            raise IOErr("CAHVOREModel: could not read T element")
+        return cls(*(v[n] for n in "CAHVORE"), T=int(t), P=v["P"][0])
+
+    def write(self, path):
+        """CAHVOREModel::write (src/vw/Camera/CAHVOREModel.cc:139-165): the T line follows P (0 -> 2, 1 -> 1, else 3)."""
+        t = 2 if self.P == 0 else 1 if self.P == 1 else 3
+        _write_vectors(path, [(n, getattr(self, n)) for n in "CAHVORE"] + [("T", t), ("P", self.P)], "CAHVOREModel")
+
+
+def linearize_camera(model, in_size, out_size=None):
+    """vw::camera::linearize_camera(model, in_size, out_size) for a CAHVORModel (src/vw/Camera/CAHVORModel.cc:460-547) or a
+    CAHVOREModel (src/vw/Camera/CAHVOREModel.cc:303-381): the CAHVModel with the same centre that covers the common field
+    of view of a frame of in_size = (cols, rows), for an image of out_size (in_size by default).  A CAHVORE landmark ray
+    that does not converge raises LogicErr.  Host arithmetic in the library, no GPU."""
+    if not isinstance(model, (CAHVORModel, CAHVOREModel)):
+        raise ArgumentErr("linearize_camera: expected a CAHVORModel or a CAHVOREModel")
+    out_size = in_size if out_size is None else out_size
+    d = _lib.Camera()
+    rc = _lib.load().vwgpu_linearize_camera(ctypes.byref(model.descriptor), int(in_size[0]), int(in_size[1]), int(out_size[0]),
+                                            int(out_size[1]), ctypes.byref(d))
+    if rc == -5:
+        raise LogicErr("CAHVOREModel: Did not converge.")
+    if rc != 0:
+        raise ArgumentErr("linearize_camera: the sizes must be positive")
+    return CAHVModel(list(d.center), list(d.A), list(d.H), list(d.V))
+
+
+def linearize_camera_transform(image, src, mask=None, edge=(0, False), ctx=None):
+    """linearize_camera_transform(image, src_camera, edge, BilinearInterpolation()) (src/vw/Camera/CameraTransform.h:185-225):
+    the image of a CAHVORModel or CAHVOREModel as its own linearisation at the image's size sees it.  Returns
+    (image, cahv) or, with a mask, (image, mask, cahv)."""
+    if image.ndim != 2:
+        raise ArgumentErr("linearize_camera_transform: the image must be (rows, cols)")
+    size = (int(image.shape[1]), int(image.shape[0]))
+    cahv = linearize_camera(src, size, size)
+    out = camera_transform(image, src, cahv, mask=mask, edge=edge, ctx=ctx)
+    return out + (cahv,) if mask is not None else (out, cahv)
+
+
 def descriptor_of(camera):
     """The struct vwgpu_camera of a camera model, or the structure itself."""
     if isinstance(camera, _lib.Camera):
         return camera
     d = getattr(camera, "descriptor", None)
     if not isinstance(d, _lib.Camera):
-        raise ArgumentErr("expected a PinholeModel, a CAHVModel or a camera descriptor, not %r" % (camera,))
+        raise ArgumentErr("expected a PinholeModel, a CAHV, CAHVOR or CAHVORE model or a camera descriptor, not %r" % (camera,))
     return d
 
 
 def matrix_of(camera):
-    """The camera matrix that goes beside a descriptor: a (3, 4) float64 array for a PinholeModel, None for a CAHVModel."""
+    """The camera matrix that goes beside a descriptor: a (3, 4) float64 array for a PinholeModel, None for the CAHV family."""
     return getattr(camera, "matrix", None)
 
 
@@ -215,6 +441,8 @@ def camera_transform(image, src, dst, size=None, mask=None, edge=(0, False), x0=
     is.  edge = (value, valid): the ValueEdgeExtension pixel; (0, False) is ZeroEdgeExtension.  check: the source
     PinholeModel's point-to-pixel check (on by default, as in the reference); a failing pixel becomes the edge pixel, and
     a numpy call then raises LogicErr with the reference's message, where a tensor call goes on without synchronising.
+    The same holds where a CAHVOREModel on either side throws (no convergence, theta out of bounds).  A CAHVORModel or
+    CAHVOREModel goes with a CAHVModel, in either role; any other pair with one of them raises NoImplErr.
     failed: an int64[1] CUDA tensor that receives the count of such pixels.  numpy in -> numpy out, CUDA tensors in -> CUDA
     tensors out on the current torch stream."""
     ops = Operands("camera_transform", image, ctx)
@@ -286,5 +514,6 @@ def resize_epipolar_cameras_to_fit(cam1, cam2, epi1, epi2, roi1, roi2, ctx=None)
     return new[0], new[1], sizes[0], sizes[1]
 
 
-__all__ = ["PinholeModel", "TsaiLensDistortion", "CAHVModel", "descriptor_of", "matrix_of", "epipolar", "CameraTransform",
+__all__ = ["PinholeModel", "TsaiLensDistortion", "CAHVModel", "CAHVORModel", "CAHVOREModel", "linearize_camera",
+           "linearize_camera_transform", "descriptor_of", "matrix_of", "epipolar", "CameraTransform",
            "camera_transform", "compute_transformed_bbox_fast", "resize_epipolar_cameras_to_fit", "BBox2i"]

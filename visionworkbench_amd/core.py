@@ -26,6 +26,10 @@ class LogicErr(VWException):
     """vw::LogicErr"""
 
 
+class IOErr(VWException):
+    """vw::IOErr"""
+
+
 class CostFunctionType(enum.IntEnum):
     """vw::stereo::CostFunctionType, src/vw/Stereo/CostFunctions.h:143-149."""
     ABSOLUTE_DIFFERENCE = 0

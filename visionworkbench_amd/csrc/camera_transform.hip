@@ -11,7 +11,9 @@
 // cameras and the source's camera matrix arrive by value and are read through scalar loads.  A lane gathers up to four
 // taps of the source and writes one float (and one mask byte); a wavefront's stores are row-contiguous.  The rays are
 // those of triangulate.hip (camera_rays.h).  A kernel is instantiated per (dst code, src code, masked): only a dst with
-// a lens, or a src with a lens whose round-trip check is on, carries the Newton loop.
+// a lens, or a src with a lens whose round-trip check is on, carries the Newton loop.  CAHVOR and CAHVORE
+// (camera_rays.h) are paired with CAHV alone, in either role: eight more image kernels and four more point kernels.
+// linearize_camera (CAHVORModel.cc:460-547, CAHVOREModel.cc:303-381) is host arithmetic over the same model functions.
 //
 // Everything up to the source position is double in the reference's expression order (-ffp-contract=off); the tap is
 // float, every product and sum rounded on its own.
@@ -32,8 +34,9 @@ constexpr int CT_COUNTERS = 1024;
 
 // how a kernel projects into a camera (point_to_pixel): a pinhole without the round-trip check (the lens kind is read at
 // run time: distorted_coordinates is closed form), a pinhole without lens with the check, a pinhole whose lens kind is
-// read at run time with the check (the Newton loop), CAHV (has no check)
-enum { CT_TO_PINHOLE_NOCHECK = 0, CT_TO_PINHOLE_NULL_CHECK = 1, CT_TO_PINHOLE_CHECK = 2, CT_TO_CAHV = 3 };
+// read at run time with the check (the Newton loop), CAHV (has no check), CAHVOR (closed form), CAHVORE (a Newton loop
+// and two ways to throw)
+enum { CT_TO_PINHOLE_NOCHECK = 0, CT_TO_PINHOLE_NULL_CHECK = 1, CT_TO_PINHOLE_CHECK = 2, CT_TO_CAHV = 3, CT_TO_CAHVOR = 4, CT_TO_CAHVORE = 5 };
 
 struct ct_mat { double m[12]; };   // m_camera_matrix, row-major 3 x 4
 
@@ -76,13 +79,36 @@ __device__ inline bool ct_point_to_pixel(const vwgpu_camera& c, const ct_mat& M,
   return !(diff >= ERROR_THRESHOLD || diff != diff);
 }
 
-// CameraTransform::reverse / forward (CameraTransform.h:52-74): a pixel of `from` to the pixel of `to` that sees the same ray
+// CameraTransform::reverse / forward (CameraTransform.h:52-74): a pixel of `from` to the pixel of `to` that sees the same
+// ray.  TR_OK, or why the reference throws: TR_NOT_CONVERGED also stands for the pinhole's failed round trip.
 template <int FROM, int TO>
-__device__ inline bool ct_transform(const vwgpu_camera& from, bool flip_from, const vwgpu_camera& to, const ct_mat& Mto, const tr_v2& p,
-                                    tr_v2& q) {
-  const tr_v3 vec = tr_ray<FROM>(from, p, flip_from);
+__device__ inline int ct_transform(const vwgpu_camera& from, bool flip_from, const vwgpu_camera& to, const ct_mat& Mto, const tr_v2& p,
+                                   tr_v2& q) {
+  tr_v3 vec;
+  const int ray = tr_ray_status<FROM>(from, p, flip_from, vec);
+  if (ray != TR_OK) return ray;   // PixelToRayErr
   const tr_v3 point{vec.x + from.center[0], vec.y + from.center[1], vec.z + from.center[2]};
-  return ct_point_to_pixel<TO>(to, Mto, false, point, q);
+  if (TO == CT_TO_CAHVORE) return tr_cahvore_project(to, point, q);
+  if (TO == CT_TO_CAHVOR) {
+    q = tr_cahvor_project(to, point);
+    return TR_OK;
+  }
+  return ct_point_to_pixel<TO>(to, Mto, false, point, q) ? TR_OK : TR_NOT_CONVERGED;
+}
+// whether a kernel counts failures: the pinhole's check, or a CAHVORE on either side
+template <int FROM, int TO>
+__device__ constexpr bool ct_kernel_counts() {
+  return TO == CT_TO_PINHOLE_NULL_CHECK || TO == CT_TO_PINHOLE_CHECK || TO == CT_TO_CAHVORE || FROM == TR_CAM_CAHVORE;
+}
+// the failures of a workgroup into bank 0 of the counters, those by theta out of bounds into bank 1 as well
+template <int TO>
+__device__ inline void ct_count(unsigned long long* counters, unsigned slot, bool failed, bool theta) {
+  const int n = __syncthreads_count(failed);
+  if (n != 0 && threadIdx.x == 0 && threadIdx.y == 0) atomicAdd(counters + slot, (unsigned long long)n);
+  if (TO == CT_TO_CAHVORE) {
+    const int nt = __syncthreads_count(theta);
+    if (nt != 0 && threadIdx.x == 0 && threadIdx.y == 0) atomicAdd(counters + CT_COUNTERS + slot, (unsigned long long)nt);
+  }
 }
 
 // ---- the image ---------------------------------------------------------------------------------------------------------
@@ -94,14 +120,14 @@ struct ct_args {
   long long mstride;
   int w, h;
   int x0, y0;
-  int flip_dst;        // a CAHV dst: dot(cross(V, H), A) < 0
+  int flip_dst;        // a CAHV or CAHVOR dst: dot(cross(V, H), A) < 0
   float edge_value;
   int edge_valid;
   float* out;
   long long ostride;
   uint8_t* omask;
   long long omstride;
-  unsigned long long* failed;   // CT_COUNTERS words, or nullptr
+  unsigned long long* failed;   // two banks of CT_COUNTERS words, or nullptr
 };
 
 // a pixel of the edge-extended source: ValueEdgeExtension(PixelMask<float>(edge_value) [invalidated])
@@ -128,13 +154,14 @@ template <int DST, int SRC, bool MASKED>
 __global__ __launch_bounds__(CT_THREADS) void ct_image_kernel(ct_args a, vwgpu_camera dst, vwgpu_camera src, ct_mat Msrc) {
   int x, y;
   long long band;
-  bool failed = false;
+  bool failed = false, theta = false;
   if (ct_position(a.w, a.h, x, y, band)) {
     const tr_v2 p{(double)((long long)a.x0 + x), (double)((long long)a.y0 + y)};
     tr_v2 q;
     float res = a.edge_value;
     bool valid = a.edge_valid != 0;
-    if (ct_transform<DST, SRC>(dst, a.flip_dst != 0, src, Msrc, p, q)) {
+    const int status = ct_transform<DST, SRC>(dst, a.flip_dst != 0, src, Msrc, p, q);
+    if (status == TR_OK) {
       // BilinearInterpolationImpl (Image/Interpolation.h:83-105).  Beyond 2^30 (or NaN) _floor's conversion to int32 is
       // undefined: the result is 0 by definition, and the masked pixel is {0, invalid}.
       const double lim = 1073741824.0;
@@ -157,16 +184,13 @@ __global__ __launch_bounds__(CT_THREADS) void ct_image_kernel(ct_args a, vwgpu_c
         }
       }
     } else {
-      failed = true;   // PointToPixelErr: the edge pixel, counted
+      failed = true;   // PointToPixelErr, PixelToRayErr: the edge pixel, counted
+      theta = status == TR_THETA_OUT_OF_BOUNDS;
     }
     a.out[(long long)y * a.ostride + x] = res;
     if (MASKED && a.omask) a.omask[(long long)y * a.omstride + x] = valid ? 255 : 0;
   }
-  if (SRC == CT_TO_PINHOLE_NULL_CHECK || SRC == CT_TO_PINHOLE_CHECK) {
-    const int n = __syncthreads_count(failed);
-    if (n != 0 && threadIdx.x == 0 && threadIdx.y == 0)
-      atomicAdd(a.failed + (unsigned)((band * gridDim.x + blockIdx.x) % CT_COUNTERS), (unsigned long long)n);
-  }
+  if (ct_kernel_counts<DST, SRC>()) ct_count<SRC>(a.failed, (unsigned)((band * gridDim.x + blockIdx.x) % CT_COUNTERS), failed, theta);
 }
 
 // ---- points ------------------------------------------------------------------------------------------------------------
@@ -180,34 +204,34 @@ struct ct_points_args {
 template <int FROM, int TO, bool UNUSED>
 __global__ __launch_bounds__(CT_THREADS) void ct_points_kernel(ct_points_args a, vwgpu_camera from, vwgpu_camera to, ct_mat Mto) {
   const long long i = (long long)blockIdx.x * CT_THREADS + threadIdx.y * CT_BX + threadIdx.x;
-  bool failed = false;
+  bool failed = false, theta = false;
   if (i < a.n) {
     const tr_v2 p{a.in[2 * i], a.in[2 * i + 1]};
     tr_v2 q;
-    if (!ct_transform<FROM, TO>(from, a.flip_from != 0, to, Mto, p, q)) {
-      failed = true;   // PointToPixelErr: a NaN pair, counted
+    const int status = ct_transform<FROM, TO>(from, a.flip_from != 0, to, Mto, p, q);
+    if (status != TR_OK) {
+      failed = true;   // PointToPixelErr, PixelToRayErr: a NaN pair, counted
+      theta = status == TR_THETA_OUT_OF_BOUNDS;
       q = tr_v2{__longlong_as_double(0x7ff8000000000000LL), __longlong_as_double(0x7ff8000000000000LL)};
     }
     a.out[2 * i] = q.x;
     a.out[2 * i + 1] = q.y;
   }
-  if (TO == CT_TO_PINHOLE_NULL_CHECK || TO == CT_TO_PINHOLE_CHECK) {
-    const int n = __syncthreads_count(failed);
-    if (n != 0 && threadIdx.x == 0 && threadIdx.y == 0) atomicAdd(a.failed + (blockIdx.x % CT_COUNTERS), (unsigned long long)n);
-  }
+  if (ct_kernel_counts<FROM, TO>()) ct_count<TO>(a.failed, blockIdx.x % CT_COUNTERS, failed, theta);
 }
 
-// the sum of the CT_COUNTERS words into word 0 (integers: any order)
+// the sum of the CT_COUNTERS words of bank blockIdx.x into its word 0 (integers: any order)
 __global__ __launch_bounds__(CT_THREADS) void ct_count_fold_kernel(unsigned long long* counters) {
   __shared__ unsigned long long lds[CT_THREADS];
   const int tid = threadIdx.x;
+  unsigned long long* bank = counters + (size_t)blockIdx.x * CT_COUNTERS;
   unsigned long long s = 0;
-  for (int k = tid; k < CT_COUNTERS; k += CT_THREADS) s += counters[k];
+  for (int k = tid; k < CT_COUNTERS; k += CT_THREADS) s += bank[k];
   lds[tid] = s;
   __syncthreads();
   if (tid == 0) {
     for (int k = 1; k < CT_THREADS; ++k) s += lds[k];
-    counters[0] = s;
+    bank[0] = s;
   }
 }
 
@@ -219,18 +243,26 @@ dim3 ct_grid(int w, int h) {
   return dim3((unsigned)((w + CT_BX - 1) / CT_BX), (unsigned)gy, (unsigned)((bands + gy - 1) / gy));
 }
 
-int ct_cahv_flip(const vwgpu_camera& c) {
-  return c.kind == VWGPU_CAMERA_CAHV && tr_dot(tr_cross(tr_load3(c.V), tr_load3(c.H)), tr_load3(c.A)) < 0.0;   // CAHVModel.cc:182
+int ct_cahv_flip(const vwgpu_camera& c) {   // CAHVORModel.cc:306 is the same test
+  return (c.kind == VWGPU_CAMERA_CAHV || c.kind == VWGPU_CAMERA_CAHVOR) && tr_dot(tr_cross(tr_load3(c.V), tr_load3(c.H)), tr_load3(c.A)) < 0.0;   // CAHVModel.cc:182
 }
 
 int ct_camera_check(vwgpu_ctx* ctx, const char* name, const char* which, const vwgpu_camera* c, const double* matrix) {
   if (!c) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: null %s camera", name, which);
-  if (c->kind != VWGPU_CAMERA_PINHOLE && c->kind != VWGPU_CAMERA_CAHV)
+  if (c->kind != VWGPU_CAMERA_PINHOLE && c->kind != VWGPU_CAMERA_CAHV && !tr_new_kind(*c))
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: unknown camera kind %d", name, c->kind);
   if (c->kind == VWGPU_CAMERA_PINHOLE && c->distortion_kind != VWGPU_DISTORTION_NULL && c->distortion_kind != VWGPU_DISTORTION_TSAI)
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: unknown lens distortion kind %d", name, c->distortion_kind);
   if (c->kind == VWGPU_CAMERA_PINHOLE && !matrix)
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: the %s camera is a pinhole and has no camera matrix", name, which);
+  return VWGPU_OK;
+}
+
+// CAHVOR and CAHVORE are paired with CAHV alone (in either role); every other pair with one of them has no kernel
+int ct_pair_check(vwgpu_ctx* ctx, const char* name, const vwgpu_camera* src, const vwgpu_camera* dst) {
+  if ((tr_new_kind(*src) && dst->kind != VWGPU_CAMERA_CAHV) || (tr_new_kind(*dst) && src->kind != VWGPU_CAMERA_CAHV))
+    return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "%s: no kernel for the pair %s -> %s: CAHVOR and CAHVORE go with CAHV only", name,
+                      tr_kind_name(*src), tr_kind_name(*dst));
   return VWGPU_OK;
 }
 
@@ -242,14 +274,18 @@ int ct_same_center(vwgpu_ctx* ctx, const vwgpu_camera* src, const vwgpu_camera* 
 
 // the code a kernel carries for the camera whose rays it forms / for the camera it projects into
 int ct_from_code(const vwgpu_camera& c) {
+  if (tr_new_kind(c)) return c.kind == VWGPU_CAMERA_CAHVOR ? TR_CAM_CAHVOR : TR_CAM_CAHVORE;
   return c.kind == VWGPU_CAMERA_CAHV ? TR_CAM_CAHV : c.distortion_kind == VWGPU_DISTORTION_NULL ? TR_CAM_PINHOLE_NULL : TR_CAM_PINHOLE;
 }
 int ct_to_code(const vwgpu_camera& c, int check) {
+  if (tr_new_kind(c)) return c.kind == VWGPU_CAMERA_CAHVOR ? CT_TO_CAHVOR : CT_TO_CAHVORE;
   if (c.kind == VWGPU_CAMERA_CAHV) return CT_TO_CAHV;
   if (!check) return CT_TO_PINHOLE_NOCHECK;
   return c.distortion_kind == VWGPU_DISTORTION_NULL ? CT_TO_PINHOLE_NULL_CHECK : CT_TO_PINHOLE_CHECK;
 }
-bool ct_counts(int to) { return to == CT_TO_PINHOLE_NULL_CHECK || to == CT_TO_PINHOLE_CHECK; }
+bool ct_counts(int from, int to) {
+  return to == CT_TO_PINHOLE_NULL_CHECK || to == CT_TO_PINHOLE_CHECK || to == CT_TO_CAHVORE || from == TR_CAM_CAHVORE;
+}
 
 ct_mat ct_matrix(const double* m) {
   ct_mat M{};
@@ -275,10 +311,20 @@ ct_mat ct_matrix(const double* m) {
     }                                                                                                            \
   } while (0)
 
+// the four pairs with a CAHVOR or CAHVORE camera: the other one is CAHV (ct_pair_check)
+#define CT_LAUNCH_NEW(KERNEL, FROM, TO, FLAG, GRID, ...)                                                                                    \
+  do {                                                                                                                                      \
+    if (FROM == TR_CAM_CAHVOR) hipLaunchKernelGGL((KERNEL<TR_CAM_CAHVOR, CT_TO_CAHV, FLAG>), (GRID), ct_block, 0, ctx->stream, __VA_ARGS__);  \
+    else if (FROM == TR_CAM_CAHVORE) hipLaunchKernelGGL((KERNEL<TR_CAM_CAHVORE, CT_TO_CAHV, FLAG>), (GRID), ct_block, 0, ctx->stream, __VA_ARGS__); \
+    else if (TO == CT_TO_CAHVOR) hipLaunchKernelGGL((KERNEL<TR_CAM_CAHV, CT_TO_CAHVOR, FLAG>), (GRID), ct_block, 0, ctx->stream, __VA_ARGS__); \
+    else hipLaunchKernelGGL((KERNEL<TR_CAM_CAHV, CT_TO_CAHVORE, FLAG>), (GRID), ct_block, 0, ctx->stream, __VA_ARGS__);                      \
+  } while (0)
+bool ct_new_pair(int from, int to) { return from == TR_CAM_CAHVOR || from == TR_CAM_CAHVORE || to == CT_TO_CAHVOR || to == CT_TO_CAHVORE; }
+
 // the counters of a call, zeroed; nullptr in *d_counter when the kernel does not count
 int ct_counters(vwgpu_ctx* ctx, bool counts, unsigned long long** d_counter) {
   *d_counter = nullptr;
-  const size_t bytes = CT_COUNTERS * sizeof(unsigned long long);
+  const size_t bytes = 2 * CT_COUNTERS * sizeof(unsigned long long);   // bank 0: every failure; bank 1: theta out of bounds
   int rc = vwgpu_arena_reserve(ctx, &ctx->scratch, bytes);
   if (rc) return rc;
   *d_counter = static_cast<unsigned long long*>(ctx->scratch.base);
@@ -287,22 +333,31 @@ int ct_counters(vwgpu_ctx* ctx, bool counts, unsigned long long** d_counter) {
   return VWGPU_OK;
 }
 
+// what a host-pointer call learns: the failures, and how many of them were CAHVORE's theta out of bounds
+struct ct_failures { long long failed, theta; bool cahvore; };
+
 // after the kernel: fold the counters; d_failed (device, optional) receives the count, *h_failed (host, optional) too (synchronises)
-int ct_count_out(vwgpu_ctx* ctx, bool counts, unsigned long long* d_counter, long long* d_failed, long long* h_failed) {
-  if (counts) hipLaunchKernelGGL(ct_count_fold_kernel, dim3(1), dim3(CT_THREADS), 0, ctx->stream, d_counter);
+int ct_count_out(vwgpu_ctx* ctx, int from, int to, unsigned long long* d_counter, long long* d_failed, ct_failures* h_failed) {
+  const bool counts = ct_counts(from, to), theta = to == CT_TO_CAHVORE;
+  if (counts) hipLaunchKernelGGL(ct_count_fold_kernel, dim3(theta ? 2 : 1), dim3(CT_THREADS), 0, ctx->stream, d_counter);
   VWGPU_HIP(ctx, hipGetLastError());
   if (d_failed) VWGPU_HIP(ctx, hipMemcpyAsync(d_failed, d_counter, 8, hipMemcpyDeviceToDevice, ctx->stream));
   if (h_failed) {
-    unsigned long long cnt = 0;
+    unsigned long long cnt = 0, cnt_theta = 0;
     VWGPU_HIP(ctx, hipMemcpyAsync(&cnt, d_counter, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (theta) VWGPU_HIP(ctx, hipMemcpyAsync(&cnt_theta, d_counter + CT_COUNTERS, 8, hipMemcpyDeviceToHost, ctx->stream));
     VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *h_failed = (long long)cnt;
+    *h_failed = ct_failures{(long long)cnt, (long long)cnt_theta, to == CT_TO_CAHVORE || from == TR_CAM_CAHVORE};
   }
   return VWGPU_OK;
 }
 
-int ct_inaccurate(vwgpu_ctx* ctx, long long failed) {
-  return vwgpu_fail(ctx, VWGPU_ERR_LOGIC, "PinholeModel: Projection into pinhole camera is inaccurate. (%lld pixels)", failed);
+// the reference's message for what it would have thrown.  It throws at the first failing pixel in raster order; here the
+// message names non-convergence when any pixel did not converge, and theta otherwise.
+int ct_inaccurate(vwgpu_ctx* ctx, const ct_failures& f) {
+  if (!f.cahvore) return vwgpu_fail(ctx, VWGPU_ERR_LOGIC, "PinholeModel: Projection into pinhole camera is inaccurate. (%lld pixels)", f.failed);
+  if (f.theta == f.failed) return vwgpu_fail(ctx, VWGPU_ERR_LOGIC, "CAHVOREModel: Theta out of bounds. (%lld pixels)", f.failed);
+  return vwgpu_fail(ctx, VWGPU_ERR_LOGIC, "CAHVOREModel: Did not converge. (%lld pixels)", f.failed);
 }
 
 struct ct_image_call {
@@ -335,16 +390,17 @@ int ct_image_check(vwgpu_ctx* ctx, ct_image_call& c) {
       (c.omask && ((const void*)c.omask == (const void*)c.src || c.omask == c.smask || (const void*)c.omask == (const void*)c.out)))
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: an output must not be an input or the other output", name);
   if (c.edge_valid && std::isnan(c.edge_value)) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: a valid edge pixel must not be NaN", name);
+  if ((rc = ct_pair_check(ctx, name, c.src_cam, c.dst_cam))) return rc;
   return ct_same_center(ctx, c.src_cam, c.dst_cam);
 }
 
 // all pointers of `c` are device pointers here
-int ct_image_run(vwgpu_ctx* ctx, const ct_image_call& c, long long* d_failed, long long* h_failed) {
+int ct_image_run(vwgpu_ctx* ctx, const ct_image_call& c, long long* d_failed, ct_failures* h_failed) {
   const int from = ct_from_code(*c.dst_cam), to = ct_to_code(*c.src_cam, c.check);
   unsigned long long* d_counter = nullptr;
   const bool want = d_failed || h_failed;
-  if (ct_counts(to) || want) {
-    int rc = ct_counters(ctx, ct_counts(to), &d_counter);
+  if (ct_counts(from, to) || want) {
+    int rc = ct_counters(ctx, ct_counts(from, to), &d_counter);
     if (rc) return rc;
   }
   ct_args a{c.src, (long long)c.sstride, c.sw, c.sh, c.smask, (long long)c.mstride, c.w, c.h, c.x0, c.y0, ct_cahv_flip(*c.dst_cam),
@@ -353,12 +409,18 @@ int ct_image_run(vwgpu_ctx* ctx, const ct_image_call& c, long long* d_failed, lo
   const bool masked = c.smask || c.omask;
   {
     vwgpu_prof_scope ps(ctx, "camera_transform");
-    if (masked) CT_LAUNCH_FROM(ct_image_kernel, from, to, true, ct_grid(c.w, c.h), a, *c.dst_cam, *c.src_cam, M);
-    else CT_LAUNCH_FROM(ct_image_kernel, from, to, false, ct_grid(c.w, c.h), a, *c.dst_cam, *c.src_cam, M);
+    if (ct_new_pair(from, to)) {
+      if (masked) CT_LAUNCH_NEW(ct_image_kernel, from, to, true, ct_grid(c.w, c.h), a, *c.dst_cam, *c.src_cam, M);
+      else CT_LAUNCH_NEW(ct_image_kernel, from, to, false, ct_grid(c.w, c.h), a, *c.dst_cam, *c.src_cam, M);
+    } else if (masked) {
+      CT_LAUNCH_FROM(ct_image_kernel, from, to, true, ct_grid(c.w, c.h), a, *c.dst_cam, *c.src_cam, M);
+    } else {
+      CT_LAUNCH_FROM(ct_image_kernel, from, to, false, ct_grid(c.w, c.h), a, *c.dst_cam, *c.src_cam, M);
+    }
     VWGPU_HIP(ctx, hipGetLastError());
   }
   if (!want) return VWGPU_OK;
-  return ct_count_out(ctx, ct_counts(to), d_counter, d_failed, h_failed);
+  return ct_count_out(ctx, from, to, d_counter, d_failed, h_failed);
 }
 
 int ct_points_check(vwgpu_ctx* ctx, const vwgpu_camera* src, const double* src_matrix, const vwgpu_camera* dst, const double* dst_matrix,
@@ -372,19 +434,20 @@ int ct_points_check(vwgpu_ctx* ctx, const vwgpu_camera* src, const double* src_m
   int rc = ct_camera_check(ctx, name, "source", src, src_matrix);
   if (rc) return rc;
   if ((rc = ct_camera_check(ctx, name, "destination", dst, dst_matrix))) return rc;
+  if ((rc = ct_pair_check(ctx, name, src, dst))) return rc;
   return ct_same_center(ctx, src, dst);
 }
 
 int ct_points_run(vwgpu_ctx* ctx, const vwgpu_camera* src, const double* src_matrix, const vwgpu_camera* dst, const double* dst_matrix,
-                  int direction, int check, const double* d_points, long long n, double* d_out, long long* d_failed, long long* h_failed) {
+                  int direction, int check, const double* d_points, long long n, double* d_out, long long* d_failed, ct_failures* h_failed) {
   const bool fwd = direction == VWGPU_CAMERA_TRANSFORM_FORWARD;
   const vwgpu_camera& cfrom = fwd ? *src : *dst;
   const vwgpu_camera& cto = fwd ? *dst : *src;
   const int from = ct_from_code(cfrom), to = ct_to_code(cto, check);
   unsigned long long* d_counter = nullptr;
   const bool want = d_failed || h_failed;
-  if (ct_counts(to) || want) {
-    int rc = ct_counters(ctx, ct_counts(to), &d_counter);
+  if (ct_counts(from, to) || want) {
+    int rc = ct_counters(ctx, ct_counts(from, to), &d_counter);
     if (rc) return rc;
   }
   ct_points_args a{d_points, d_out, n, ct_cahv_flip(cfrom), d_counter};
@@ -392,11 +455,12 @@ int ct_points_run(vwgpu_ctx* ctx, const vwgpu_camera* src, const double* src_mat
   const dim3 grid((unsigned)((n + CT_THREADS - 1) / CT_THREADS));
   {
     vwgpu_prof_scope ps(ctx, "camera_transform_points");
-    CT_LAUNCH_FROM(ct_points_kernel, from, to, false, grid, a, cfrom, cto, M);
+    if (ct_new_pair(from, to)) CT_LAUNCH_NEW(ct_points_kernel, from, to, false, grid, a, cfrom, cto, M);
+    else CT_LAUNCH_FROM(ct_points_kernel, from, to, false, grid, a, cfrom, cto, M);
     VWGPU_HIP(ctx, hipGetLastError());
   }
   if (!want) return VWGPU_OK;
-  return ct_count_out(ctx, ct_counts(to), d_counter, d_failed, h_failed);
+  return ct_count_out(ctx, from, to, d_counter, d_failed, h_failed);
 }
 
 // ---- host arithmetic -----------------------------------------------------------------------------------------------------
@@ -467,6 +531,33 @@ tr_v3 ct_scale(const tr_v3& a, double s) { return tr_v3{a.x * s, a.y * s, a.z * 
 tr_v3 ct_div(const tr_v3& a, double s) { return tr_v3{a.x / s, a.y / s, a.z / s}; }
 tr_v3 ct_add(const tr_v3& a, const tr_v3& b) { return tr_v3{a.x + b.x, a.y + b.y, a.z + b.z}; }
 void ct_store3(const tr_v3& a, double* p) { p[0] = a.x; p[1] = a.y; p[2] = a.z; }
+
+// pixel_to_vector of a CAHVOR or CAHVORE descriptor on the host: the text the kernels run
+int ct_host_ray(const vwgpu_camera& c, double x, double y, tr_v3& vec) {
+  if (c.kind == VWGPU_CAMERA_CAHVORE) return tr_cahvore_ray(c, tr_v2{x, y}, vec);
+  vec = tr_cahvor_ray(c, tr_v2{x, y}, ct_cahv_flip(c) != 0);
+  return TR_OK;
+}
+
+// the six landmarks on the left and right edge (hpts) and on the top and bottom edge (vpts) of linearize_camera.  The
+// midpoints are the reference's: CAHVOR halves in double but for vpts[4] (CAHVORModel.cc:472-484), CAHVORE divides the
+// integers everywhere (CAHVOREModel.cc:314-326).
+void ct_landmarks(bool cahvore, int w, int h, tr_v2* hpts, tr_v2* vpts) {
+  const double xe = w - 1, ye = h - 1;
+  const double ymid = cahvore ? (double)((h - 1) / 2) : (h - 1) / 2.0;
+  const double xmid1 = cahvore ? (double)((w - 1) / 2) : (w - 1) / 2.0;
+  const double xmid4 = (double)((w - 1) / 2);
+  hpts[0] = tr_v2{0, 0}; hpts[1] = tr_v2{0, ymid}; hpts[2] = tr_v2{0, ye};
+  hpts[3] = tr_v2{xe, 0}; hpts[4] = tr_v2{xe, ymid}; hpts[5] = tr_v2{xe, ye};
+  vpts[0] = tr_v2{0, 0}; vpts[1] = tr_v2{xmid1, 0}; vpts[2] = tr_v2{xe, 0};
+  vpts[3] = tr_v2{0, ye}; vpts[4] = tr_v2{xmid4, ye}; vpts[5] = tr_v2{xe, ye};
+}
+
+// u3 - dot(d, u3) * d, normalised
+tr_v3 ct_reject(const tr_v3& u3, const tr_v3& d) {
+  const double s = tr_dot(d, u3);
+  return tr_normalize(tr_v3{u3.x - s * d.x, u3.y - s * d.y, u3.z - s * d.z});
+}
 
 }  // namespace
 
@@ -564,6 +655,105 @@ int vwgpu_epipolar_cahv(const vwgpu_camera* src0, const vwgpu_camera* src1, vwgp
   return VWGPU_OK;
 }
 
+int vwgpu_cahvor_camera(const double* C, const double* A, const double* H, const double* V, const double* O, const double* R,
+                        vwgpu_camera* out) {
+  if (!C || !A || !H || !V || !O || !R || !out) return VWGPU_ERR_ARGUMENT;
+  std::memset(out, 0, sizeof(*out));
+  out->kind = VWGPU_CAMERA_CAHVOR;
+  std::memcpy(out->center, C, sizeof(out->center));
+  std::memcpy(out->A, A, sizeof(out->A));
+  std::memcpy(out->H, H, sizeof(out->H));
+  std::memcpy(out->V, V, sizeof(out->V));
+  std::memcpy(out->inv_camera_transform, O, 3 * sizeof(double));
+  std::memcpy(out->inv_camera_transform + 3, R, 3 * sizeof(double));
+  return VWGPU_OK;
+}
+
+int vwgpu_cahvore_camera(const double* C, const double* A, const double* H, const double* V, const double* O, const double* R,
+                         const double* E, int type, double P, vwgpu_camera* out) {
+  if (!E) return VWGPU_ERR_ARGUMENT;
+  // CAHVOREModel(C, A, H, V, O, R, E, T, P) (CAHVOREModel.cc:111-124)
+  switch (type) {
+    case 1: P = 1.0; break;
+    case 2: P = 0.0; break;
+    case 3:
+      if (P < 0 || P > 1 || P != P) return VWGPU_ERR_ARGUMENT;
+      break;
+    default: return VWGPU_ERR_ARGUMENT;
+  }
+  int rc = vwgpu_cahvor_camera(C, A, H, V, O, R, out);
+  if (rc) return rc;
+  out->kind = VWGPU_CAMERA_CAHVORE;
+  std::memcpy(out->inv_camera_transform + 6, E, 3 * sizeof(double));
+  out->distortion[0] = P;
+  return VWGPU_OK;
+}
+
+int vwgpu_linearize_camera(const vwgpu_camera* src, int in_w, int in_h, int out_w, int out_h, vwgpu_camera* dst) {
+  if (!src || !dst || !tr_new_kind(*src) || in_w <= 0 || in_h <= 0 || out_w <= 0 || out_h <= 0) return VWGPU_ERR_ARGUMENT;
+  const vwgpu_camera cam = *src;   // dst may be src
+  const bool cahvore = cam.kind == VWGPU_CAMERA_CAHVORE;
+  tr_v2 hpts[6], vpts[6];
+  ct_landmarks(cahvore, in_w, in_h, hpts, vpts);
+  tr_v3 hray[6], vray[6];
+  for (int k = 0; k < 6; ++k)
+    if (ct_host_ray(cam, hpts[k].x, hpts[k].y, hray[k]) != TR_OK || ct_host_ray(cam, vpts[k].x, vpts[k].y, vray[k]) != TR_OK) return VWGPU_ERR_LOGIC;
+  tr_v3 A{0.0, 0.0, 0.0};
+  if (cahvore) {
+    // the ray of the real-valued centre (CAHVOREModel.cc:329-330)
+    if (ct_host_ray(cam, (in_w - 1) / 2.0, (in_h - 1) / 2.0, A) != TR_OK) return VWGPU_ERR_LOGIC;
+  } else {
+    // the normalised sum over vpts, then hpts (CAHVORModel.cc:486-492)
+    for (int k = 0; k < 6; ++k) A = ct_add(A, vray[k]);
+    for (int k = 0; k < 6; ++k) A = ct_add(A, hray[k]);
+    A = tr_normalize(A);
+  }
+  // the original right and down vectors, made orthogonal to the new axis
+  const tr_v3 srcA = tr_load3(cam.A), srcH = tr_load3(cam.H);
+  tr_v3 dn = tr_cross(srcA, srcH);
+  tr_v3 rt = tr_normalize(tr_cross(dn, srcA));
+  dn = tr_normalize(dn);
+  rt = tr_cross(dn, A);
+  dn = tr_normalize(tr_cross(A, rt));
+  rt = tr_normalize(rt);
+  double hmin = 1, hmax = -1, vmin = 1, vmax = -1;
+  for (int k = 0; k < 6; ++k) {
+    const tr_v3 n = ct_reject(hray[k], dn);
+    const double v = cahvore ? tr_dot(A, n) : tr_norm(tr_cross(A, n));
+    if (hmin > v) hmin = v;
+    if (hmax < v) hmax = v;
+  }
+  for (int k = 0; k < 6; ++k) {
+    const tr_v3 n = ct_reject(vray[k], rt);
+    const double v = cahvore ? tr_dot(A, n) : tr_norm(tr_cross(A, n));
+    if (vmin > v) vmin = v;
+    if (vmax < v) vmax = v;
+  }
+  double scale[2], centre[2] = {(out_w - 1) / 2.0, (out_h - 1) / 2.0};
+  if (cahvore) {
+    // minfov: the larger cosines, limited to a field of view of 135 degrees (CAHVOREModel.cc:359-371)
+    const double limfov = 3.14159265358979323846 * 3 / 4;
+    double cosines[2] = {hmax, vmax};
+    if (acos(cosines[0]) > limfov) cosines[0] = cos(limfov);
+    if (acos(cosines[1]) > limfov) cosines[1] = cos(limfov);
+    scale[0] = (out_w / 2.0 * cosines[0]) / sqrt(1 - cosines[0] * cosines[0]);
+    scale[1] = (out_h / 2.0 * cosines[1]) / sqrt(1 - cosines[1] * cosines[1]);
+  } else {
+    // minfov: the smaller sines (CAHVORModel.cc:527-534)
+    const double c2[2] = {centre[0] * centre[0], centre[1] * centre[1]};
+    scale[0] = sqrt(c2[0] / (hmin * hmin) - c2[0]);
+    scale[1] = sqrt(c2[1] / (vmin * vmin) - c2[1]);
+  }
+  vwgpu_camera out{};
+  out.kind = VWGPU_CAMERA_CAHV;
+  std::memcpy(out.center, cam.center, sizeof(out.center));
+  ct_store3(A, out.A);
+  ct_store3(ct_add(ct_scale(rt, scale[0]), ct_scale(A, centre[0])), out.H);
+  ct_store3(ct_add(ct_scale(dn, scale[1]), ct_scale(A, centre[1])), out.V);
+  *dst = out;
+  return VWGPU_OK;
+}
+
 int vwgpu_camera_transform_dev(vwgpu_ctx* ctx, const float* d_src, int sw, int sh, ptrdiff_t sstride, const uint8_t* d_src_mask,
                                ptrdiff_t mstride, const vwgpu_camera* src_camera, const double* src_matrix,
                                const vwgpu_camera* dst_camera, const double* dst_matrix, int w, int h, int x0, int y0, float edge_value,
@@ -595,11 +785,11 @@ int vwgpu_camera_transform(vwgpu_ctx* ctx, const float* src, int sw, int sh, ptr
   d.smask = st.dev<uint8_t>(pm); d.mstride = sw;
   d.out = st.dev<float>(po); d.ostride = w;
   d.omask = st.dev<uint8_t>(pk); d.omstride = w;
-  long long count = 0;
+  ct_failures count{};
   if ((rc = ct_image_run(ctx, d, nullptr, &count))) return rc;
   if ((rc = st.finish())) return rc;
-  if (failed) *failed = count;
-  return count != 0 ? ct_inaccurate(ctx, count) : VWGPU_OK;
+  if (failed) *failed = count.failed;
+  return count.failed != 0 ? ct_inaccurate(ctx, count) : VWGPU_OK;
 }
 
 int vwgpu_camera_transform_points_dev(vwgpu_ctx* ctx, const vwgpu_camera* src_camera, const double* src_matrix,
@@ -621,13 +811,13 @@ int vwgpu_camera_transform_points(vwgpu_ctx* ctx, const vwgpu_camera* src_camera
   vwgpu_stage st(ctx);
   const int pi = st.add(points, (int)n, 1, 16, n, VWGPU_STAGE_IN), po = st.add(out, (int)n, 1, 16, n, VWGPU_STAGE_OUT);
   if ((rc = st.commit())) return rc;
-  long long count = 0;
+  ct_failures count{};
   if ((rc = ct_points_run(ctx, src_camera, src_matrix, dst_camera, dst_matrix, direction, check, st.dev<double>(pi), n, st.dev<double>(po),
                           nullptr, &count)))
     return rc;
   if ((rc = st.finish())) return rc;
-  if (failed) *failed = count;
-  return count != 0 ? ct_inaccurate(ctx, count) : VWGPU_OK;
+  if (failed) *failed = count.failed;
+  return count.failed != 0 ? ct_inaccurate(ctx, count) : VWGPU_OK;
 }
 
 }  // extern "C"

@@ -11,7 +11,8 @@
 // statistics variant keeps one partial per wavefront there).  The cameras arrive by value: they are uniform and are read
 // through scalar loads.  A lane reads the 12 bytes of its pixel and writes 24 contiguous bytes of xyz, so a wavefront's
 // stores cover 1536 contiguous bytes.  The null-distortion pinhole pair, the other pinhole pairs and the three pairs
-// with a CAHV camera are separate instantiations: the common case carries no Newton loop.
+// with a CAHV camera are separate instantiations: the common case carries no Newton loop.  Two CAHVOR and two CAHVORE
+// cameras (camera_rays.h) are one instantiation each; a CAHVORE ray that does not converge gives the zero point.
 //
 // Everything is double in the reference's expression order; the Makefile's -ffp-contract=off keeps products and sums
 // apart, and fp64 division and square root are correctly rounded on the device.  Sums written `0.0 + ...` are the
@@ -39,7 +40,7 @@ struct tr_args {
   int w, h;
   int x0, y0;
   int int_type, layout, model;
-  int flip1, flip2;   // CAHV cameras: dot(cross(V, H), A) < 0
+  int flip1, flip2;   // CAHV and CAHVOR cameras: dot(cross(V, H), A) < 0
   double tol;
   double* xyz;
   long long xstride;
@@ -108,7 +109,11 @@ __device__ inline tr_v3 tr_triangulate(const tr_args& a, const vwgpu_camera& cam
   if (tr_pixel_skipped(pix1) || tr_pixel_skipped(pix2)) return zero;   // fewer than two rays
   // a ray with a Newton loop first: fewer scalar registers stay live across the loop (the values do not depend on the order)
   tr_v3 dir0, dir1;
-  if (CAM1 == TR_CAM_CAHV && CAM2 == TR_CAM_PINHOLE) {
+  if (CAM1 == TR_CAM_CAHVOR || CAM1 == TR_CAM_CAHVORE) {
+    // catch (PixelToRayErr) (:144-146): the zero point and the zero error vector
+    const int s0 = tr_ray_status<CAM1>(cam1, pix1, a.flip1 != 0, dir0), s1 = tr_ray_status<CAM2>(cam2, pix2, a.flip2 != 0, dir1);
+    if (s0 != TR_OK || s1 != TR_OK) return zero;
+  } else if (CAM1 == TR_CAM_CAHV && CAM2 == TR_CAM_PINHOLE) {
     dir1 = tr_ray<CAM2>(cam2, pix2, false);
     dir0 = tr_ray<CAM1>(cam1, pix1, a.flip1 != 0);
   } else {
@@ -255,7 +260,10 @@ __global__ __launch_bounds__(TR_THREADS) void tr_angle_kernel(tr_args a, vwgpu_c
   if (tr_load_disp(a, x, y, da, db)) {
     tr_v2 pix1, pix2;
     tr_pixel_pair(a, x, y, da, db, pix1, pix2);
-    ang = acos(tr_dot(tr_ray<CAM1>(cam1, pix1, a.flip1 != 0), tr_ray<CAM2>(cam2, pix2, a.flip2 != 0)));
+    tr_v3 dir0, dir1;
+    const int s0 = tr_ray_status<CAM1>(cam1, pix1, a.flip1 != 0, dir0), s1 = tr_ray_status<CAM2>(cam2, pix2, a.flip2 != 0, dir1);
+    // where CAHVOREModel::pixel_to_vector throws the reference has no angle: NaN
+    ang = s0 == TR_OK && s1 == TR_OK ? acos(tr_dot(dir0, dir1)) : __longlong_as_double(0x7ff8000000000000LL);
   }
   a.error[(long long)y * a.estride + x] = ang;
 }
@@ -324,7 +332,7 @@ int tr_elem_words(int layout) {
 
 int tr_camera_check(vwgpu_ctx* ctx, const char* name, const vwgpu_camera* c) {
   if (!c) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: null camera", name);
-  if (c->kind != VWGPU_CAMERA_PINHOLE && c->kind != VWGPU_CAMERA_CAHV)
+  if (c->kind != VWGPU_CAMERA_PINHOLE && c->kind != VWGPU_CAMERA_CAHV && !tr_new_kind(*c))
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: unknown camera kind %d", name, c->kind);
   if (c->kind == VWGPU_CAMERA_PINHOLE && c->distortion_kind != VWGPU_DISTORTION_NULL && c->distortion_kind != VWGPU_DISTORTION_TSAI)
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: unknown lens distortion kind %d", name, c->distortion_kind);
@@ -332,8 +340,10 @@ int tr_camera_check(vwgpu_ctx* ctx, const char* name, const vwgpu_camera* c) {
 }
 
 // the instantiation for a camera pair, as 3 * (code of cam1) + (code of cam2): (0, 0) for two pinholes without lens
-// distortion, (1, 1) for other pinhole pairs, and the three pairs with a CAHV camera
+// distortion, (1, 1) for other pinhole pairs, the three pairs with a CAHV camera, (3, 3) for two CAHVOR and (4, 4) for
+// two CAHVORE cameras (tr_check refuses every other pair with one of those)
 int tr_cams_of(const vwgpu_camera& c1, const vwgpu_camera& c2) {
+  if (tr_new_kind(c1)) return c1.kind == VWGPU_CAMERA_CAHVOR ? 3 * TR_CAM_CAHVOR + TR_CAM_CAHVOR : 3 * TR_CAM_CAHVORE + TR_CAM_CAHVORE;
   const bool cahv1 = c1.kind == VWGPU_CAMERA_CAHV, cahv2 = c2.kind == VWGPU_CAMERA_CAHV;
   if (!cahv1 && !cahv2 && c1.distortion_kind == VWGPU_DISTORTION_NULL && c2.distortion_kind == VWGPU_DISTORTION_NULL) return 0;
   return 3 * (cahv1 ? TR_CAM_CAHV : TR_CAM_PINHOLE) + (cahv2 ? TR_CAM_CAHV : TR_CAM_PINHOLE);
@@ -353,6 +363,9 @@ int tr_check(vwgpu_ctx* ctx, const char* name, int type, const void* disp, int w
   int rc = tr_camera_check(ctx, name, cam1);
   if (rc) return rc;
   if ((rc = tr_camera_check(ctx, name, cam2))) return rc;
+  if ((tr_new_kind(*cam1) || tr_new_kind(*cam2)) && cam1->kind != cam2->kind)
+    return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "%s: no kernel for the pair %s + %s: a CAHVOR or CAHVORE camera goes with one of its own kind", name,
+                      tr_kind_name(*cam1), tr_kind_name(*cam2));
   if (dstride == 0) dstride = w;
   if (dstride < w) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: row stride smaller than row width", name);
   return VWGPU_OK;
@@ -381,8 +394,8 @@ int triangulate_check(vwgpu_ctx* ctx, int type, const void* disp, int w, int h, 
   return tr_out_stride(ctx, name, errvec, vstride, w);
 }
 
-int tr_cahv_flip(const vwgpu_camera& c) {
-  return c.kind == VWGPU_CAMERA_CAHV && tr_dot(tr_cross(tr_load3(c.V), tr_load3(c.H)), tr_load3(c.A)) < 0.0;   // CAHVModel.cc:182
+int tr_cahv_flip(const vwgpu_camera& c) {   // CAHVORModel.cc:306 is the same test
+  return (c.kind == VWGPU_CAMERA_CAHV || c.kind == VWGPU_CAMERA_CAHVOR) && tr_dot(tr_cross(tr_load3(c.V), tr_load3(c.H)), tr_load3(c.A)) < 0.0;   // CAHVModel.cc:182
 }
 
 tr_args tr_make_args(int type, const void* d_disp, int w, int h, ptrdiff_t dstride, int x0, int y0, int semantics, const vwgpu_camera& cam1,
@@ -407,6 +420,8 @@ tr_args tr_make_args(int type, const void* d_disp, int w, int h, ptrdiff_t dstri
       case 4: TR_LAUNCH_ONE(KERNEL, TR_CAM_PINHOLE, TR_CAM_PINHOLE, GRID, __VA_ARGS__); break;                     \
       case 5: TR_LAUNCH_ONE(KERNEL, TR_CAM_PINHOLE, TR_CAM_CAHV, GRID, __VA_ARGS__); break;                        \
       case 7: TR_LAUNCH_ONE(KERNEL, TR_CAM_CAHV, TR_CAM_PINHOLE, GRID, __VA_ARGS__); break;                        \
+      case 12: TR_LAUNCH_ONE(KERNEL, TR_CAM_CAHVOR, TR_CAM_CAHVOR, GRID, __VA_ARGS__); break;                      \
+      case 16: TR_LAUNCH_ONE(KERNEL, TR_CAM_CAHVORE, TR_CAM_CAHVORE, GRID, __VA_ARGS__); break;                    \
       default: TR_LAUNCH_ONE(KERNEL, TR_CAM_CAHV, TR_CAM_CAHV, GRID, __VA_ARGS__); break;                          \
     }                                                                                                              \
     VWGPU_HIP(ctx, hipGetLastError());                                                                             \

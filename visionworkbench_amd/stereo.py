@@ -950,7 +950,8 @@ def stereo_triangulate(disparity, cam1, cam2, x0=0, y0=0, error=False, error_vec
     (rows, cols, 3) float64 point image; the right pixel of a pair is Vector2(i, j) + Vector2((double)dx, (double)dy).
     Invalid disparities, pixel pairs with fewer than two rays and nearly parallel rays give (0, 0, 0); points behind a
     camera are reflected (StereoModel::operator(), src/vw/Stereo/StereoModel.cc:97-147).  cam1, cam2: camera.PinholeModel /
-    camera.CAHVModel.  x0, y0: the image coordinates of pixel (0, 0) of `disparity` (a tile of a larger map).
+    camera.CAHVModel in any combination, or two camera.CAHVORModel, or two camera.CAHVOREModel (a CAHVORE ray that does not
+    converge gives (0, 0, 0); any other pair with one of these raises NoImplErr).  x0, y0: the image coordinates of pixel (0, 0) of `disparity` (a tile of a larger map).
     error=True adds the (rows, cols) ray-intersection error norm_2(error vector), error_vector=True the (rows, cols, 3)
     vector between the closest points; the result is then a tuple (xyz[, error][, error_vector]).  StereoView::error() has
     no definition behind it in the reference; the error here is StereoModel's.
@@ -1034,14 +1035,25 @@ def epipolar_transformed_images(left, right, cam_l, cam_r, left_mask=None, right
     for pinholes resize_epipolar_cameras_to_fit over the whole frames, and one camera_transform per image.  Returns
     (left_out, right_out, epi_l, epi_r), or with masks (left_out, left_out_mask, right_out, right_out_mask, epi_l, epi_r);
     epi_l, epi_r are the rectified cameras stereo_triangulate takes for a disparity map of the aligned pair.
-    cam_l, cam_r: two camera.PinholeModel (null or Tsai lens) or two camera.CAHVModel.  (A distorted source against a CAHV
-    pair, the epipolar_transformed_cahv_images case, is two camera.camera_transform calls.)  The frames start at (0, 0):
-    there is no AdjustedCameraModel for cropped inputs.
+    cam_l, cam_r: two camera.PinholeModel (null or Tsai lens), two camera.CAHVModel, two camera.CAHVORModel or two
+    camera.CAHVOREModel.  A CAHVOR or CAHVORE pair takes the .cahvor / .cahvore branch of epipolar_transformed_cahv_images
+    (:173-188): each model is linearised at its frame's size (linearize_camera), epipolar() aligns the two CAHV results,
+    and every frame goes from its raw model straight to its rectified CAHV camera.  (A distorted pinhole against a CAHV
+    pair is two camera.camera_transform calls.)  The frames start at (0, 0): there is no AdjustedCameraModel for cropped
+    inputs.
     sizes: ((cols, rows), (cols, rows)) of the results; by default what resize_epipolar_cameras_to_fit returns for
-    pinholes, and the frames' own sizes for CAHV models.  edge, check: as in camera.camera_transform."""
+    pinholes, and the frames' own sizes for the CAHV family.  edge, check: as in camera.camera_transform."""
     if left.ndim != 2 or right.ndim != 2:
         raise ArgumentErr("epipolar_transformed_images: the images must be (rows, cols)")
-    epi_l, epi_r = camera.epipolar(cam_l, cam_r)
+    distorted = (camera.CAHVORModel, camera.CAHVOREModel)
+    if isinstance(cam_l, distorted) or isinstance(cam_r, distorted):
+        if type(cam_l) is not type(cam_r):
+            raise ArgumentErr("epipolar_transformed_images: expected two CAHVORModels or two CAHVOREModels")
+        lin_l = camera.linearize_camera(cam_l, (int(left.shape[1]), int(left.shape[0])))
+        lin_r = camera.linearize_camera(cam_r, (int(right.shape[1]), int(right.shape[0])))
+        epi_l, epi_r = camera.epipolar(lin_l, lin_r)
+    else:
+        epi_l, epi_r = camera.epipolar(cam_l, cam_r)
     if isinstance(cam_l, camera.PinholeModel):
         roi_l = BBox2i(0, 0, int(left.shape[1]), int(left.shape[0]))
         roi_r = BBox2i(0, 0, int(right.shape[1]), int(right.shape[0]))

@@ -1,6 +1,7 @@
 // vw/Camera.h — the part of vw::camera that triangulation and epipolar rectification need: PinholeModel with the null or
 // the Tsai lens distortion (src/vw/Camera/PinholeModel.{h,cc}, LensDistortion.{h,cc}), CAHVModel
-// (src/vw/Camera/CAHVModel.{h,cc}) and epipolar() for both.  Each model carries the flat camera descriptor of the C ABI
+// (src/vw/Camera/CAHVModel.{h,cc}) and epipolar() for both, CAHVORModel and CAHVOREModel (src/vw/Camera/CAHVORModel.{h,cc},
+// CAHVOREModel.{h,cc}) and linearize_camera() for those.  Each model carries the flat camera descriptor of the C ABI
 // (struct vwgpu_camera, include/vwgpu.h) and, for a pinhole, the 3 x 4 camera matrix beside it, which is what the engine's
 // kernels read; pixel_to_vector, camera_center and point_to_pixel are host code for single pixels, with the reference's
 // expressions (whole images are computed on the device: vw/Stereo.h, vw/CameraTransform.h).
@@ -10,6 +11,7 @@
 #include <cmath>
 #include <limits>
 #include <memory>
+#include <string>
 
 #include "Core.h"
 #include "Math.h"
@@ -161,6 +163,167 @@ public:
   }
   Vector3 camera_center(Vector2 const& = Vector2()) const { return C; }
 };
+
+/// What the CAHVORE model throws (src/vw/Camera/CameraModel.h).
+VWLITE_EXCEPTION(PixelToRayErr, Exception);
+VWLITE_EXCEPTION(PointToPixelErr, Exception);
+
+/// CAHVORModel(C, A, H, V, O, R) (CAHVORModel.h): CAHV with radial distortion about the axis O.  The single-pixel functions
+/// are host code in the reference's expressions (CAHVORModel.cc:297-348, :431-448); images and arrays of points go through
+/// the engine (vw/CameraTransform.h, vw/Stereo.h).
+class CAHVORModel : public CameraModel {
+public:
+  typedef CAHVModel linearized_type;
+  Vector3 C, A, H, V, O, R;
+  CAHVORModel() : CAHVORModel(Vector3(0, 0, 0), Vector3(0, 0, 1), Vector3(1, 0, 0), Vector3(0, 1, 0), Vector3(0, 0, 1), Vector3(0, 0, 0)) {}
+  CAHVORModel(Vector3 const& c, Vector3 const& a, Vector3 const& h, Vector3 const& v, Vector3 const& o, Vector3 const& r)
+      : C(c), A(a), H(h), V(v), O(o), R(r) {
+    const int rc = vwgpu_cahvor_camera(&C[0], &A[0], &H[0], &V[0], &O[0], &R[0], &m_desc);
+    VW_ASSERT(rc == VWGPU_OK, ArgumentErr() << "CAHVORModel: bad arguments.");
+  }
+  std::string type() const { return "CAHVOR"; }
+  Vector3 pixel_to_vector(Vector2 const& pix) const {
+    Vector3 rr = detail::normalize3(detail::cross3(V - pix[1] * A, H - pix[0] * A));
+    if (detail::dot3(detail::cross3(V, H), A) < 0) rr = -1.0 * rr;
+    const double omega = detail::dot3(rr, O);
+    const Vector3 lambda = rr - omega * O;
+    const double tau = detail::dot3(lambda, lambda) / (omega * omega);
+    const double k1 = 1 + R[0], k3 = R[1] * tau, k5 = R[2] * tau * tau;
+    double u = 1.0 - (R[0] + k3 + k5);
+    for (int i = 0; i < 20; ++i) {
+      const double u_2 = u * u;
+      const double poly = ((k5 * u_2 + k3) * u_2 + k1) * u - 1;
+      const double deriv = (5 * k5 * u_2 + 3 * k3) * u_2 + k1;
+      if (deriv <= 0) break;
+      const double du = poly / deriv;
+      u -= du;
+      if (std::fabs(du) < 1.0e-6) break;
+    }
+    return detail::normalize3(rr - (1 - u) * lambda);
+  }
+  Vector2 point_to_pixel(Vector3 const& point) const {
+    const Vector3 vec = point - C;
+    const double omega = detail::dot3(vec, O);
+    const Vector3 lambda = vec - omega * O;
+    const double tau = detail::dot3(lambda, lambda) / (omega * omega);
+    const double mu = R[0] + (R[1] * tau) + (R[2] * tau * tau);
+    const Vector3 pp_c = vec + mu * lambda;
+    const double alpha = detail::dot3(pp_c, A);
+    return Vector2(detail::dot3(pp_c, H) / alpha, detail::dot3(pp_c, V) / alpha);
+  }
+  Vector3 camera_center(Vector2 const& = Vector2()) const { return C; }
+};
+
+/// CAHVOREModel(C, A, H, V, O, R, E[, T, P | P]) (CAHVOREModel.h, CAHVOREModel.cc:105-132): the fisheye member of the family.
+/// T = 1 sets P = 1, T = 2 sets P = 0, T = 3 takes P in [0, 1]; anything else throws ArgumentErr.
+class CAHVOREModel : public CameraModel {
+  void fill(int type) {
+    const int rc = vwgpu_cahvore_camera(&C[0], &A[0], &H[0], &V[0], &O[0], &R[0], &E[0], type, P, &m_desc);
+    VW_ASSERT(rc == VWGPU_OK, ArgumentErr() << (type >= 1 && type <= 3 ? "Invalid P value: " : "Unknown CAHVORE type: ") << (type >= 1 && type <= 3 ? P : (double)type));
+    P = m_desc.distortion[0];
+  }
+public:
+  typedef CAHVModel linearized_type;
+  Vector3 C, A, H, V, O, R, E;
+  double P;
+  CAHVOREModel() : CAHVOREModel(Vector3(0, 0, 0), Vector3(0, 0, 1), Vector3(1, 0, 0), Vector3(0, 1, 0), Vector3(0, 0, 1), Vector3(0, 0, 0), Vector3(0, 0, 0)) {}
+  CAHVOREModel(Vector3 const& c, Vector3 const& a, Vector3 const& h, Vector3 const& v, Vector3 const& o, Vector3 const& r, Vector3 const& e)
+      : C(c), A(a), H(h), V(v), O(o), R(r), E(e), P(1.0) { fill(3); }
+  CAHVOREModel(Vector3 const& c, Vector3 const& a, Vector3 const& h, Vector3 const& v, Vector3 const& o, Vector3 const& r, Vector3 const& e,
+               int T, double P_v)
+      : C(c), A(a), H(h), V(v), O(o), R(r), E(e), P(P_v) { fill(T); }
+  CAHVOREModel(Vector3 const& c, Vector3 const& a, Vector3 const& h, Vector3 const& v, Vector3 const& o, Vector3 const& r, Vector3 const& e,
+               double P_v)
+      : C(c), A(a), H(h), V(v), O(o), R(r), E(e), P(P_v) { fill(3); }
+  std::string type() const { return "CAHVORE"; }
+  /// CAHVOREModel::pixel_to_vector (CAHVOREModel.cc:167-228)
+  Vector3 pixel_to_vector(Vector2 const& pix) const {
+    const Vector3 w3 = detail::cross3(V - pix[1] * A, H - pix[0] * A);
+    const Vector3 rp = (1 / detail::dot3(A, detail::cross3(V, H))) * w3;
+    const double zetap = detail::dot3(rp, O);
+    const Vector3 lambdap3 = rp - zetap * O;
+    const double lambdap = std::sqrt(detail::dot3(lambdap3, lambdap3));
+    const double chip = lambdap / zetap;
+    if (chip < 1e-8) return O;
+    double chi = chip, dchi = 1;
+    for (int32 n = 0;; ++n) {
+      if (n > 100) vw_throw(PixelToRayErr() << "CAHVOREModel: Did not converge.\n");
+      if (std::fabs(dchi) < 1e-8) break;
+      const double chi2 = chi * chi, chi3 = chi * chi2, chi4 = chi * chi3, chi5 = chi * chi4;
+      const double deriv = (1 + R[0]) + 3 * R[1] * chi2 + 5 * R[2] * chi4;
+      dchi = ((1 + R[0]) * chi + R[1] * chi3 + R[2] * chi5 - chip) / deriv;
+      chi -= dchi;
+    }
+    const double linchi = P * chi;
+    double theta;
+    if (P < -1e-15) theta = std::asin(linchi) / P;
+    else if (P > 1e-15) theta = std::atan(linchi) / P;
+    else theta = chi;
+    return std::sin(theta) * detail::normalize3(lambdap3) + std::cos(theta) * O;
+  }
+  /// CAHVOREModel::point_to_pixel (CAHVOREModel.cc:232-301)
+  Vector2 point_to_pixel(Vector3 const& point) const {
+    const Vector3 p_c = point - C;
+    const double zeta = detail::dot3(p_c, O);
+    const Vector3 lambda3 = p_c - zeta * O;
+    const double lambda = std::sqrt(detail::dot3(lambda3, lambda3));
+    double theta = std::atan2(lambda, zeta), dtheta = 1;
+    for (int32 n = 0;; ++n) {
+      if (n > 100) vw_throw(PointToPixelErr() << "CAHVOREModel: Did not converge.\n");
+      if (std::fabs(dtheta) < 1e-8) break;
+      const double costh = std::cos(theta), sinth = std::sin(theta);
+      const double theta2 = theta * theta, theta3 = theta * theta2, theta4 = theta * theta3;
+      const double upsilon = zeta * costh + lambda * sinth - (1 - costh) * (E[0] + E[1] * theta2 + E[2] * theta4) -
+                             (theta - sinth) * (2 * E[1] * theta + 4 * E[2] * theta3);
+      dtheta = (zeta * sinth - lambda * costh - (theta - sinth) * (E[0] + E[1] * theta2 + E[2] * theta4)) / upsilon;
+      theta -= dtheta;
+    }
+    if ((theta * std::fabs(P)) > 3.14159265358979323846 / 2) vw_throw(PointToPixelErr() << "CAHVOREModel: Theta out of bounds.\n");
+    Vector3 rp;
+    if (theta < 1e-8) {
+      rp = p_c;
+    } else {
+      const double linth = P * theta;
+      double chi;
+      if (P < -1e-15) chi = std::sin(linth) / P;
+      else if (P > 1e-15) chi = std::tan(linth) / P;
+      else chi = theta;
+      const double chi2 = chi * chi;
+      double mu = R[2];
+      mu = R[1] + chi2 * mu;
+      mu = R[0] + chi2 * mu;
+      rp = (lambda / chi) * O + (1 + mu) * lambda3;
+    }
+    const double alpha = detail::dot3(rp, A);
+    return Vector2(detail::dot3(rp, H) / alpha, detail::dot3(rp, V) / alpha);
+  }
+  Vector3 camera_center(Vector2 const& = Vector2()) const { return C; }
+};
+
+/// linearize_camera(model, input size, output size) for a CAHVORModel (CAHVORModel.cc:460-547) or a CAHVOREModel
+/// (CAHVOREModel.cc:303-381): host arithmetic in the engine (vwgpu_linearize_camera).  A CAHVORE landmark ray that does not
+/// converge throws PixelToRayErr.
+namespace detail {
+inline CAHVModel linearize(CameraModel const& camera_model, int32 ix, int32 iy, int32 ox, int32 oy) {
+  vwgpu_camera d;
+  const int rc = vwgpu_linearize_camera(&camera_model.descriptor(), ix, iy, ox, oy, &d);
+  if (rc == VWGPU_ERR_LOGIC) vw_throw(PixelToRayErr() << "CAHVOREModel: Did not converge.\n");
+  VW_ASSERT(rc == VWGPU_OK, ArgumentErr() << "linearize_camera: the image sizes must be positive.");
+  return CAHVModel(d);
+}
+}  // namespace detail
+inline CAHVModel linearize_camera(CAHVORModel const& camera_model, Vector2i const& cahvor_image_size, Vector2i const& cahv_image_size) {
+  return detail::linearize(camera_model, cahvor_image_size[0], cahvor_image_size[1], cahv_image_size[0], cahv_image_size[1]);
+}
+inline CAHVModel linearize_camera(CAHVORModel const& camera_model, int32 ix, int32 iy, int32 ox, int32 oy) {
+  return detail::linearize(camera_model, ix, iy, ox, oy);
+}
+inline CAHVModel linearize_camera(CAHVOREModel const& camera_model, Vector2i const& cahvore_image_size, Vector2i const& cahv_image_size) {
+  return detail::linearize(camera_model, cahvore_image_size[0], cahvore_image_size[1], cahv_image_size[0], cahv_image_size[1]);
+}
+inline CAHVModel linearize_camera(CAHVOREModel const& camera_model, int32 ix, int32 iy, int32 ox, int32 oy) {
+  return detail::linearize(camera_model, ix, iy, ox, oy);
+}
 
 /// epipolar(src0, src1, dst0, dst1) for two pinholes (PinholeModel.cc:679-732): host arithmetic in the engine
 /// (vwgpu_epipolar_pinhole); cameras without a baseline throw ArgumentErr.

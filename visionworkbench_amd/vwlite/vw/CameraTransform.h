@@ -1,6 +1,6 @@
 // vw/CameraTransform.h — resampling an image from one camera into another at the same centre
-// (src/vw/Camera/CameraTransform.h:43-183): CameraTransform<Src, Dst>, camera_transform(image, src, dst[, size][, edge,
-// interp]) and resize_epipolar_cameras_to_fit (src/vw/Camera/EpipolarUtils.cc:37-76) over compute_transformed_bbox_fast
+// (src/vw/Camera/CameraTransform.h:43-225): CameraTransform<Src, Dst>, camera_transform(image, src, dst[, size][, edge,
+// interp]), linearize_camera_transform(image, src[, edge, interp]) and resize_epipolar_cameras_to_fit (src/vw/Camera/EpipolarUtils.cc:37-76) over compute_transformed_bbox_fast
 // (src/vw/Image/Transform.h:272-315).  The view is lazy: rasterize(dest, bbox) is one vwgpu_camera_transform call with the
 // box's origin as x0, y0, so any tiling gives the pixels of the whole image; points go through
 // vwgpu_camera_transform_points.  Pixel types: float, PixelGray<float> and PixelMask<float>; bilinear interpolation only.
@@ -114,6 +114,8 @@ public:
   int32 cols() const { return m_cols; }
   int32 rows() const { return m_rows; }
   int32 planes() const { return 1; }
+  SrcCameraT const& src_camera() const { return m_src_camera; }
+  DstCameraT const& dst_camera() const { return m_dst_camera; }
 
   /// the box as an image of its own; it may leave [0, cols) x [0, rows), like any TransformView
   ImageView<pixel_type> box(BBox2i const& bbox) const {
@@ -165,6 +167,22 @@ template <class ImageT, class SrcCameraT, class DstCameraT>
 CameraTransformView<ImageT, SrcCameraT, DstCameraT> camera_transform(ImageViewBase<ImageT> const& image, SrcCameraT const& src_camera,
                                                                      DstCameraT const& dst_camera) {
   return camera_transform(image, src_camera, dst_camera, Vector2i(image.impl().cols(), image.impl().rows()));
+}
+
+/// linearize_camera_transform(image, src_camera[, edge][, interp]) (CameraTransform.h:185-225): the image of a CAHVORModel or
+/// CAHVOREModel as its own linearisation at the image's size sees it; view.dst_camera() is the CAHVModel that goes with it.
+template <class ImageT, class SrcCameraT>
+CameraTransformView<ImageT, SrcCameraT, typename SrcCameraT::linearized_type>
+linearize_camera_transform(ImageViewBase<ImageT> const& image, SrcCameraT const& src_camera,
+                           ValueEdgeExtension<typename ImageT::pixel_type> const& edge_func, BilinearInterpolation const& = BilinearInterpolation()) {
+  const Vector2i size(image.impl().cols(), image.impl().rows());
+  return camera_transform(image, src_camera, linearize_camera(src_camera, size, size), size, edge_func);
+}
+template <class ImageT, class SrcCameraT>
+CameraTransformView<ImageT, SrcCameraT, typename SrcCameraT::linearized_type> linearize_camera_transform(ImageViewBase<ImageT> const& image,
+                                                                                                         SrcCameraT const& src_camera) {
+  const Vector2i size(image.impl().cols(), image.impl().rows());
+  return camera_transform(image, src_camera, linearize_camera(src_camera, size, size), size);
 }
 
 /// compute_transformed_bbox_fast(roi, transform) (Image/Transform.h:272-315): min and max of the BBox2f grown by the

@@ -31,6 +31,7 @@ public:
 template <class T, int N> Vector<T, N> operator+(Vector<T, N> a, Vector<T, N> const& b) { return a += b; }
 template <class T, int N> Vector<T, N> operator-(Vector<T, N> a, Vector<T, N> const& b) { return a -= b; }
 template <class T, int N> Vector<T, N> operator*(Vector<T, N> a, T s) { for (int i = 0; i < N; ++i) a[i] *= s; return a; }
+template <class T, int N> Vector<T, N> operator*(T s, Vector<T, N> a) { for (int i = 0; i < N; ++i) a[i] = s * a[i]; return a; }
 template <class T, int N> Vector<T, N> operator/(Vector<T, N> a, T s) { for (int i = 0; i < N; ++i) a[i] /= s; return a; }
 template <class T, int N> T prod(Vector<T, N> const& v) { T p = 1; for (int i = 0; i < N; ++i) p *= v[i]; return p; }
 template <class T, int N> std::ostream& operator<<(std::ostream& o, Vector<T, N> const& v) {

@@ -785,7 +785,33 @@ int vwgpu_intersect_mask_and_data(vwgpu_ctx* ctx, int type, const void* data, pt
 typedef enum vwgpu_camera_kind {
   VWGPU_CAMERA_PINHOLE = 0, VWGPU_CAMERA_CAHV = 1, VWGPU_CAMERA_CAHVOR = 3, VWGPU_CAMERA_CAHVORE = 4
 } vwgpu_camera_kind;
-typedef enum vwgpu_distortion_kind { VWGPU_DISTORTION_NULL = 0, VWGPU_DISTORTION_TSAI = 1 } vwgpu_distortion_kind;
+/* The lenses of a pinhole beyond null and Tsai (src/vw/Camera/LensDistortion.cc).  The 14 doubles
+ * from distortion[0] to V[2] are contiguous, a pinhole uses none of A, H, V, and they hold the lens words L[0..13], which
+ * only vwgpu_camera_set_lens fills:
+ *   VWGPU_DISTORTION_FOV              FovLensDistortion (:462-515), both directions closed form.  L0 = k1, L1 = 1 / k1,
+ *                                     L2 = 2 tan(k1 / 2), the reference's two precomputed members.
+ *   VWGPU_DISTORTION_FISHEYE          FisheyeLensDistortion (:573-658).  L0..3 = k1..k4.  undistorted_coordinates is
+ *                                     NewtonRaphson::solve with the numerical Jacobian (src/vw/Math/NewtonRaphson.cc:27-47,
+ *                                     step 1e-6, tol 1e-9), with every exit of the solver.
+ *   VWGPU_DISTORTION_BROWN_CONRADY    BrownConradyDistortion (:731-744).  L0..7 = xp, yp, k1, k2, k3, p1, p2, phi, L8 =
+ *                                     sin(phi), L9 = cos(phi).  distorted_coordinates is the base class's (:175-195):
+ *                                     levenberg_marquardtFixed (src/vw/Math/LevenbergMarquardt.h:389-561) for the 2 x 2
+ *                                     case with tolerances 1e-16 and 100 passes, then the 1e-10 test whose failure is the
+ *                                     reference's throw "LensDistortion: Did not converge.".
+ *   VWGPU_DISTORTION_ADJUSTABLE_TSAI  AdjustableTsaiLensDistortion (:799-880).  L0..n-1 = the n coefficients (n - 3
+ *                                     radial, two tangential, alpha), L13 = n, 4 <= n <= 13.  The same Newton solver.
+ *   VWGPU_DISTORTION_PHOTOMETRIX      PhotometrixLensDistortion (:961-999).  L0..8 = xp, yp, k1, k2, k3, p1, p2, b1, b2
+ *                                     (b1, b2 unused, as in the reference).  The same Levenberg-Marquardt solver.
+ * fu or fv below 1e-300 gives HUGE_VAL for FOV, fisheye and adjustable Tsai.  FOV and fisheye call the device library's
+ * atan and tan; the other three use + - * / sqrt fabs alone.  Every entry that takes a camera accepts these kinds on a
+ * pinhole, in any combination on the two cameras.  A pixel whose projection fails the 1e-10 test counts as failed like a
+ * pixel that fails the pinhole's round-trip check, whether that check is on or off.
+ * The value 5 is unassigned and refused with VWGPU_ERR_ARGUMENT: callers and tests rely on it as a kind out of range.
+ * RPCLensDistortion has no kind: its coefficients do not fit the descriptor. */
+typedef enum vwgpu_distortion_kind {
+  VWGPU_DISTORTION_NULL = 0, VWGPU_DISTORTION_TSAI = 1, VWGPU_DISTORTION_FOV = 2, VWGPU_DISTORTION_FISHEYE = 3,
+  VWGPU_DISTORTION_BROWN_CONRADY = 4, VWGPU_DISTORTION_ADJUSTABLE_TSAI = 6, VWGPU_DISTORTION_PHOTOMETRIX = 7
+} vwgpu_distortion_kind;
 typedef struct vwgpu_camera {
   int kind;                          /* vwgpu_camera_kind */
   int distortion_kind;               /* vwgpu_distortion_kind (pinhole) */
@@ -806,6 +832,22 @@ typedef struct vwgpu_camera {
 int vwgpu_pinhole_camera(const double* center, const double* rotation, double fu, double fv, double cu, double cv,
                          const double* u_dir, const double* v_dir, const double* w_dir, double pixel_pitch, int distortion_kind,
                          const double* distortion, vwgpu_camera* out);
+
+/* Sets the lens of a pinhole descriptor that vwgpu_pinhole_camera built: the distortion kind and the lens words.  params
+ * holds n doubles in the order of the reference's distortion_parameters(): none for NULL, {k1, k2, p1, p2, k3} for TSAI
+ * (n = 5, or 4 with k3 = 0), {k1} for FOV, {k1..k4} for FISHEYE, {xp, yp, k1, k2, k3, p1, p2, phi} for BROWN_CONRADY, 4 to
+ * 13 coefficients for ADJUSTABLE_TSAI, {xp, yp, k1, k2, k3, p1, p2, b1, b2} for PHOTOMETRIX.  The words the kind does not use
+ * become 0.  A camera that is no pinhole, a null pointer, kind 5 or an unknown kind, a wrong n, FOV with k1 <= 0 (the
+ * reference's IOErr) or a parameter that is not finite: VWGPU_ERR_ARGUMENT, the descriptor unchanged.  Pure host
+ * arithmetic, no context. */
+int vwgpu_camera_set_lens(vwgpu_camera* cam, int distortion_kind, const double* params, int n);
+
+/* distorted_coordinates (direction 0) or undistorted_coordinates (direction 1) of the lens of a pinhole descriptor for n
+ * points {x, y} in focal-plane units (pixel * pixel_pitch), on the host, through the functions the kernels run.  A point
+ * whose Brown-Conrady or Photometrix solve fails the reference's 1e-10 test becomes a NaN pair and is counted in *failed
+ * (optional); the call then returns VWGPU_ERR_LOGIC.  out may be points.  A camera that is no pinhole, an unknown lens kind
+ * or direction, a null pointer or n < 0: VWGPU_ERR_ARGUMENT.  Pure host arithmetic, no context. */
+int vwgpu_lens_coordinates(const vwgpu_camera* cam, int direction, const double* points, long long n, double* out, long long* failed);
 
 /* CAHVORModel(C, A, H, V, O, R) and CAHVOREModel(C, A, H, V, O, R, E, T, P) (src/vw/Camera/CAHVOREModel.cc:111-124) into a
  * descriptor; every vector is double[3].  type (T) 1 sets P = 1, 2 sets P = 0, 3 takes P in [0, 1]; any other type or P:

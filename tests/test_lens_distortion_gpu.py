@@ -1,0 +1,326 @@
+"""Pinholes with the FOV, fisheye, Brown-Conrady, adjustable Tsai and Photometrix lenses on the GPU against the CPU
+restatement (tests/refimpl/lens_ref.cc).
+
+Brown-Conrady, adjustable Tsai and Photometrix use only + - * / sqrt fabs (sin(phi) and cos(phi) come from the host): every
+word of every image, mask, count, point, xyz, error and error vector equals the restatement's (same(), NaNs by position).
+
+FOV and fisheye call the device library's atan and tan, which agree with glibc to an ulp or two but not in bits.  Their
+results are held to the bounds test_cahvor_gpu.py derives for CAHVORE, re-derived here for these lenses:
+  points   |q_gpu - q_ref| <= 1e-9 px for |q| <= 1e4.
+           Closed forms (FOV both ways, fisheye distort): the position is conv * p_0 * f + c with conv = rd / ru; two ulps of
+           atan or tan are a relative 4.4e-16 of rd (tan amplifies its argument's error by 1 + tan^2 < 1.02 for the
+           arguments of a frame, rd * k1 < 0.1), so |dq| <= 4.4e-16 * 1e4 = 4.4e-12 px.
+           Fisheye undistort is Newton on f(X) = Y with the numerical Jacobian (f(P + d) - f(P - d)) / 2e-6.  With |f| <=
+           0.1 an ulp of atan is 1.4e-17 in f and enters J amplified by 1 / 2e-6: 1.4e-11 against entries of order 1.  But J
+           only steers the iteration: the fixed point is where f(X) = Y whatever J is.  An error eps_J in J changes a step
+           DX by eps_J |DX|; the last step is below 1e-9, so the returned X moves by 1.4e-20.  What does move X is the
+           rounding of f itself (atan to two ulps, theta_d, the division and the product, in both coordinates: some 16
+           ulps, 2.2e-16): dX = J^-1 df ~ 2.2e-16, times f = 512 px: 1.1e-13 px.  An exit taken one pass apart (|DX|
+           lands on the other side of 1e-9) adds or drops the next step, which for Newton with an inexact Jacobian is at
+           most (eps_J + |f''| |DX| / |J|) |DX| <= (1.4e-11 + 10 * 1e-9) * 1e-9 = 1e-17 for the |f''| <= 10 of these
+           lenses: 5e-15 px.  All of it is four orders below 1e-9.  (On the fixtures every solve leaves on the step;
+           asserted.)
+  images   source <= 128 px wide, values in [0, 1]: |out_gpu - out_ref| <= 1e-4: float(q) may round one float ulp apart
+           (2^-16 below 128), the weights move by that much, the result by at most twice that, plus the rounding of four
+           products.
+  masks, counts   equal, except (the mask only) where the restatement's q lies within 1e-6 of an integer in x or y and
+           floor may pick the neighbouring taps; at most 1 % of an image may be excused (asserted on the restatement).
+  triangulation   |dxyz| <= 64 * 2^-52 * range^2 / baseline with range the largest distance of the restatement's points
+           from camera 1; the error gets the same bound; the convergence angle (acos is the device library's for every
+           lens) gets 64 * 2^-52 * range / baseline.
+The measured maxima are printed (pytest -s) and recorded in profiles/lens_distortion.md."""
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "refimpl"))
+import lens_ref as ref  # noqa: E402
+
+import visionworkbench_amd as vwa  # noqa: E402
+from visionworkbench_amd import camera, stereo  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+LENSES = list(ref.NEW_LENSES)
+SIZES = [(1, 1), (2, 9), (17, 1), (65, 5), (70, 45)]
+EDGES = {"zero": (0, False), "value_valid": (7.5, True), "value_invalid": (-3.25, False)}
+POINT_TOL, IMAGE_TOL = 1e-9, 1e-4
+TURN = (1.5, -1.0)      # degrees: the undistorted partner looks slightly aside
+
+
+def exact(*names):
+    return all(n in ref.EXACT_LENSES or n in (None, "TSAI", "NULL", "CAHV") for n in names)
+
+
+def same(got, want, what=""):
+    """Exact equality of every word; NaNs by position."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype, what
+    if got.dtype.kind != "f":
+        bad = np.argwhere(got != want)
+        assert bad.size == 0, "%s: %d words differ, first at %s: got %r, want %r" % (
+            what, len(bad), tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])])
+        return
+    gn, wn = np.isnan(got), np.isnan(want)
+    assert np.array_equal(gn, wn), "%s: NaNs in different places" % what
+    g, w = got.copy(), want.copy()
+    g[gn], w[wn] = 0, 0
+    bits = {8: np.uint64, 4: np.uint32}[got.dtype.itemsize]
+    bad = np.argwhere(g.view(bits) != w.view(bits))
+    assert bad.size == 0, "%s: %d words differ, first at %s: got %r, want %r" % (
+        what, len(bad), tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])])
+
+
+def close(got, want, tol, what):
+    """|got - want| <= tol, NaNs by position; prints the measured maximum."""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    assert got.shape == want.shape, what
+    gn, wn = np.isnan(got), np.isnan(want)
+    assert np.array_equal(gn, wn), "%s: NaNs in different places" % what
+    worst = float(np.abs(got - want)[~gn].max()) if (~gn).any() else 0.0
+    print("MEASURED %s: max difference %.3g (bound %.3g)" % (what, worst, tol))
+    assert worst <= tol, "%s: max difference %.3g > %.3g" % (what, worst, tol)
+
+
+def check_image(is_exact, got, want, masked, what, edge_value=0.0):
+    """got: image or (image, mask); want: the restatement's dict."""
+    img, mask = got if masked else (got, None)
+    if is_exact:
+        same(img, want["out"], what + " image")
+        if masked:
+            same(mask, want["mask"], what + " mask")
+        return
+    assert abs(edge_value) <= 8      # the edge value enters the taps: the bound is for values in [0, 1] and scales with the range
+    close(img, want["out"], IMAGE_TOL * max(1.0, abs(edge_value)), what + " image")
+    if masked:
+        near = (np.abs(want["q"] - np.round(want["q"])) < 1e-6).any(axis=2) & (want["status"] == 0)
+        assert near.mean() <= 0.01, what
+        bad = (mask != want["mask"]) & ~near
+        assert not bad.any(), "%s mask: %d pixels differ away from integer positions" % (what, bad.sum())
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import torch
+    assert torch.cuda.is_available()
+    c = vwa.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def source():
+    return ref.source_image()
+
+
+@pytest.fixture(scope="module")
+def cams():
+    """lens -> (the fixture pinhole with that lens, the undistorted pinhole at the same centre that looks slightly aside)."""
+    return {n: (ref.small(n), ref.small(None, turn=TURN)) for n in LENSES}
+
+
+def test_fixture_solves_leave_on_the_step():
+    """What the bounds above assume, on the restatement: inside the frame every Newton solve of the fisheye fixture converges."""
+    cam = ref.small("FISHEYE")
+    ys, xs = np.mgrid[0:ref.SH, 0:ref.SW].astype(np.float64)
+    _, how, _ = ref.coordinates(cam, ref.UNDISTORT, np.stack([xs.ravel(), ys.ravel()], 1) * cam.pixel_pitch)
+    assert (how == ref.EXIT_STEP).all()
+
+
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("size", SIZES)
+@pytest.mark.parametrize("lens", LENSES)
+def test_sizes_in_both_roles(ctx, source, cams, lens, size, masked):
+    """Partial workgroups, a single row and column, more than one block in x, several bands; the lens camera as the source
+    (projection through the lens, with the round-trip check) and as the destination (rays through the lens)."""
+    img, mask = source
+    cam, plain = cams[lens]
+    m = mask if masked else None
+    for src, dst, role in ((cam, plain, "src"), (plain, cam, "dst")):
+        want = ref.camera_transform(img, src, dst, size=size, mask=m)
+        assert want["failed"] == 0 and want["rc"] == 0
+        got = camera.camera_transform(img, src, dst, size=size, mask=m, ctx=ctx)
+        check_image(exact(lens), got, want, masked, "%s as %s %dx%d" % ((lens, role) + size))
+
+
+@pytest.mark.parametrize("check", [False, True])
+@pytest.mark.parametrize("edge", sorted(EDGES))
+@pytest.mark.parametrize("lens", LENSES)
+def test_edge_pixels_and_check(ctx, source, lens, edge, check):
+    """A partner turned so that part of the output leaves the source; the source's round-trip check on and off."""
+    img, mask = source
+    cam, plain = ref.small(lens), ref.small(None, turn=(2.5, 1.5))
+    for src, dst, role in ((cam, plain, "src"), (plain, cam, "dst")):
+        want = ref.camera_transform(img, src, dst, size=(37, 29), mask=mask, edge=EDGES[edge], check=check)
+        outside = (want["q"][..., 0] < -1) | (want["q"][..., 1] < -1) | (want["q"][..., 0] > ref.SW) | (want["q"][..., 1] > ref.SH)
+        assert 0.05 < outside.mean() < 0.95 and want["failed"] == 0
+        got = camera.camera_transform(img, src, dst, size=(37, 29), mask=mask, edge=EDGES[edge], check=check, ctx=ctx)
+        check_image(exact(lens), got, want, True, "%s as %s edge %s check %d" % (lens, role, edge, check), edge_value=EDGES[edge][0])
+
+
+@pytest.mark.parametrize("lens", LENSES)
+def test_tiles_and_row_strips_equal_the_whole(ctx, source, cams, lens):
+    """The device against itself: exact for every lens."""
+    img, mask = source
+    cam, plain = cams[lens]
+    for src, dst in ((cam, plain), (plain, cam)):
+        whole, whole_mask = camera.camera_transform(img, src, dst, size=(70, 45), mask=mask, ctx=ctx)
+        for x0, y0, w, h in ((0, 0, 35, 22), (35, 0, 35, 22), (0, 22, 35, 23), (35, 22, 35, 23), (0, 17, 70, 5), (0, 0, 70, 1), (0, 44, 70, 1)):
+            out, om = camera.camera_transform(img, src, dst, size=(w, h), mask=mask, x0=x0, y0=y0, ctx=ctx)
+            same(out, whole[y0:y0 + h, x0:x0 + w], "tile image")
+            same(om, whole_mask[y0:y0 + h, x0:x0 + w], "tile mask")
+
+
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("lens", LENSES)
+def test_host_and_device_entries_agree(ctx, source, cams, lens, masked):
+    import torch
+    img, mask = source
+    cam, plain = cams[lens]
+    m = mask if masked else None
+    for src, dst in ((cam, plain), (plain, cam)):
+        host = camera.camera_transform(img, src, dst, size=(70, 45), mask=m, edge=(2.0, True), ctx=ctx)
+        dev = camera.camera_transform(torch.from_numpy(img).cuda(), src, dst, size=(70, 45),
+                                      mask=None if m is None else torch.from_numpy(m).cuda(), edge=(2.0, True), ctx=ctx)
+        if masked:
+            same(dev[0].cpu().numpy(), host[0], "image")
+            same(dev[1].cpu().numpy(), host[1], "mask")
+        else:
+            same(dev.cpu().numpy(), host, "image")
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 1000])
+@pytest.mark.parametrize("lens", LENSES)
+def test_camera_transform_points(ctx, cams, lens, n):
+    import torch
+    cam, plain = cams[lens]
+    rng = np.random.default_rng(n)
+    pts = np.stack([rng.uniform(2, ref.SW - 3, n), rng.uniform(2, ref.SH - 3, n)], 1)
+    pts[0] = (12.0, 7.0)
+    for src, dst in ((cam, plain), (plain, cam)):
+        t = camera.CameraTransform(src, dst, ctx=ctx)
+        for direction, fn in ((ref.FORWARD, t.forward), (ref.REVERSE, t.reverse)):
+            want, failed, _, rc = ref.transform_points(src, dst, direction, pts)
+            assert (rc, failed) == (0, 0) and np.abs(want).max() <= 1e4
+            what = "%s points %s %d" % (lens, "lens->plain" if src is cam else "plain->lens", direction)
+            got = fn(pts)
+            if exact(lens):
+                same(got, want, what)
+            else:
+                close(got, want, POINT_TOL, what)
+            if n == 65:
+                same(fn(torch.from_numpy(pts).cuda()).cpu().numpy(), got, what + " dev")
+
+
+@pytest.fixture(scope="module")
+def scenes():
+    """pair name -> (disparity, left, right, the restatement's VIEW and MODEL results)."""
+    pairs = {n: (n, n) for n in LENSES}
+    pairs.update({"TSAI+BrownConrady": ("TSAI", "BrownConrady"), "FISHEYE+NULL": ("FISHEYE", None),
+                  "BrownConrady+CAHV": ("BrownConrady", "CAHV"), "CAHV+FISHEYE": ("CAHV", "FISHEYE")})
+    out = {}
+    for name, (a, b) in pairs.items():
+        left, right = ref.stereo_pair(a, b)
+        d = ref.scene_disparity(left, right)
+        out[name] = (d, left, right, ref.stereo_triangulate(d, left, right, ref.VIEW), ref.stereo_triangulate(d, left, right, ref.MODEL),
+                     exact(a, b))
+    return out
+
+
+def _tri_bounds(want, left, right):
+    c0, c1 = np.array(camera.descriptor_of(left).center[:]), np.array(camera.descriptor_of(right).center[:])
+    valid = np.any(want["xyz"] != 0, axis=2)
+    rng = float(np.sqrt(((want["xyz"] - c0) ** 2).sum(axis=2))[valid].max())
+    base = float(np.sqrt(((c1 - c0) ** 2).sum()))
+    return 64 * 2.0 ** -52 * rng * rng / base, 64 * 2.0 ** -52 * rng / base, int(valid.sum())
+
+
+@pytest.mark.parametrize("pair", LENSES + ["TSAI+BrownConrady", "FISHEYE+NULL", "BrownConrady+CAHV", "CAHV+FISHEYE"])
+def test_triangulation(ctx, scenes, pair):
+    import torch
+    d, left, right, view, model, is_exact = scenes[pair]
+    xyz_tol, ang_tol, npoints = _tri_bounds(view, left, right)
+    assert npoints >= 800 and d.shape == (29, 37, 3) and view["stats"][0] == int((d[..., 2] != 0).sum())
+
+    def agree(got, want, tol, what):
+        if is_exact:
+            same(got, want, what)
+        else:
+            close(got, want, tol, what)
+    for with_stats in (False, True):
+        stats = [] if with_stats else None
+        xyz, err, ev = stereo.stereo_triangulate(d, left, right, error=True, error_vector=True, stats=stats, ctx=ctx)
+        agree(xyz, view["xyz"], xyz_tol, pair + " view xyz")
+        agree(err, view["error"], xyz_tol, pair + " view error")
+        agree(ev, view["errvec"], xyz_tol, pair + " view error vector")
+        if with_stats:
+            assert stats[0] == view["stats"][0]
+            agree(np.array(stats[1]), np.array(view["stats"][1]), xyz_tol, pair + " max error")
+            assert abs(stats[2] - view["stats"][2]) <= 1e-12 * view["stats"][2] + stats[0] * (0 if is_exact else xyz_tol)
+        mstats = [] if with_stats else None
+        mxyz, merr = stereo.StereoModel(left, right)(d, stats=mstats, ctx=ctx)
+        agree(mxyz, model["xyz"], xyz_tol, pair + " model xyz")
+        agree(merr, model["error"], xyz_tol, pair + " model error")
+        if with_stats:
+            assert mstats[0] == model["stats"][0]
+    assert np.isfinite(view["xyz"]).all() and (view["error"][np.any(view["xyz"] != 0, axis=2)] > 0).all()
+    txyz = stereo.stereo_triangulate(torch.from_numpy(d).cuda(), left, right, ctx=ctx)
+    same(txyz.cpu().numpy(), stereo.stereo_triangulate(d, left, right, ctx=ctx), "device entry")
+    ang = stereo.StereoModel(left, right).convergence_angle(d, semantics="view", ctx=ctx)
+    close(ang, view["angle"], ang_tol, pair + " convergence angle")
+    assert (ang[d[..., 2] != 0] > 0).all() and (ang[d[..., 2] == 0] == 0).all()
+
+
+@pytest.mark.parametrize("check", [False, True])
+def test_brown_conrady_source_whose_solve_fails(ctx, source, check):
+    """A lens that folds inside the frame: the failed pixels are the edge pixel, counted, equal to the restatement's; the
+    throw belongs to point_to_pixel_no_check, so it is there with the check off too."""
+    import torch
+    img, mask = source
+    src, dst = ref.failing_brown_conrady(), ref.small(None)
+    want = ref.camera_transform(img, src, dst, mask=mask, edge=(0.25, True), check=check)
+    n = want["failed"]
+    assert 0 < n < ref.SW * ref.SH and want["lens"] > 0 and (want["status"] == ref.LS_LENS).sum() == want["lens"]
+    with pytest.raises(vwa.LogicErr, match=r"LensDistortion: Did not converge\. \(%d pixels\)" % n):
+        camera.camera_transform(img, src, dst, mask=mask, edge=(0.25, True), check=check, ctx=ctx)
+    failed = torch.full((1,), -1, dtype=torch.int64, device="cuda")
+    out, om = camera.camera_transform(torch.from_numpy(img).cuda(), src, dst, mask=torch.from_numpy(mask).cuda(), edge=(0.25, True),
+                                      check=check, ctx=ctx, failed=failed)
+    assert int(failed.cpu()[0]) == n
+    same(out.cpu().numpy(), want["out"], "image")
+    same(om.cpu().numpy(), want["mask"], "mask")
+    # the C ABI's host entry: the images are complete, the count is returned, the status is the logic error
+    o, k, cnt = np.empty((ref.SH, ref.SW), np.float32), np.empty((ref.SH, ref.SW), np.uint8), ctypes.c_longlong(-1)
+    rc = ctx._lib.vwgpu_camera_transform(ctx._h, img.ctypes.data, ref.SW, ref.SH, 0, mask.ctypes.data, 0, ctypes.byref(src.descriptor),
+                                         src.matrix.ctypes.data, ctypes.byref(dst.descriptor), dst.matrix.ctypes.data, ref.SW, ref.SH, 0, 0,
+                                         0.25, 1, int(check), o.ctypes.data, 0, k.ctypes.data, 0, ctypes.addressof(cnt))
+    assert rc == -5 and cnt.value == n
+    same(o, want["out"], "host entry image")
+    same(k, want["mask"], "host entry mask")
+    # points: NaN pairs by position, counted
+    ys, xs = np.mgrid[0:ref.SH:3, 0:ref.SW:3].astype(np.float64)
+    pts = np.stack([xs.ravel(), ys.ravel()], 1)
+    wantp, nfail, nlens, rc = ref.transform_points(src, dst, ref.REVERSE, pts, check=check)
+    assert rc == 0 and 0 < nfail < len(pts) and nlens > 0
+    gotp = camera.CameraTransform(src, dst, check=check, ctx=ctx).reverse(torch.from_numpy(pts).cuda()).cpu().numpy()
+    same(gotp, wantp, "NaN pairs")
+    with pytest.raises(vwa.LogicErr, match="LensDistortion: Did not converge"):
+        camera.CameraTransform(src, dst, check=check, ctx=ctx).reverse(pts)
+
+
+def test_cahvor_and_cahvore_beside_a_lens_pinhole_have_no_kernel(ctx, source):
+    import cahvor_ref
+    img, _ = source
+    d = np.zeros((4, 6, 3), np.float32)
+    d[..., 2] = 1
+    for kind in ("cahvor", "cahvore"):
+        raw = cahvor_ref.small(kind)
+        pin = ref.small("BrownConrady", center=raw.C)
+        for src, dst in ((raw, pin), (pin, raw)):
+            with pytest.raises(vwa.NoImplErr, match="no kernel for the pair"):
+                camera.camera_transform(img, src, dst, size=(8, 8), ctx=ctx)
+            with pytest.raises(vwa.NoImplErr, match="no kernel for the pair"):
+                stereo.stereo_triangulate(d, src, dst, ctx=ctx)

@@ -8,7 +8,9 @@ bytes per pixel over that time (4 read + 4 written, 5 + 5 with masks), and the r
 SAME number of bytes timed in the same run, which is the yardstick (no data-sheet number enters).  Cases: pinhole ->
 pinhole with the point-to-pixel check on and off, a Tsai source with the check on (the Newton loop) and off, CAHV -> CAHV,
 the masked form, and a CAHVOR and a CAHVORE source (the reference's test cameras scaled to the frame) into their own
-linearisation, masked and not, with the re-distortion (CAHV -> CAHVOR / CAHVORE) beside them.  VWGPU_LIBRARY selects another build of the library (make -C visionworkbench_amd/csrc ct16: the
+linearisation, masked and not, with the re-distortion (CAHV -> CAHVOR / CAHVORE) beside them, and a pinhole with each of
+the FOV, fisheye, Brown-Conrady, adjustable Tsai and Photometrix lenses as the source with the check on and off and as the
+destination (--no-lenses leaves them out).  VWGPU_LIBRARY selects another build of the library (make -C visionworkbench_amd/csrc ct16: the
 16 x 16 workgroup footprint).
 usage: python tools/time_camera_transform.py [--size 4096] [--repeat 20] [--windows 5]"""
 import argparse
@@ -28,6 +30,7 @@ def main():
     ap.add_argument("--size", type=int, default=4096)
     ap.add_argument("--repeat", type=int, default=20)
     ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--no-lenses", action="store_true", help="only the cases without the any-lens instantiations")
     args = ap.parse_args()
     import torch
     import epipolar_ref as ref
@@ -111,6 +114,19 @@ def main():
         report("%s -> CAHV" % name, gpu(transform(raw, lin, True, False)), 8)
         report("%s -> CAHV, masked" % name, gpu(transform(raw, lin, True, True)), 10)
         report("CAHV -> %s" % name, gpu(transform(lin, raw, True, False)), 8)
+    if args.no_lenses:
+        ctx.close()
+        return
+    # one camera per lens of the any-lens instantiations; Brown-Conrady and Photometrix work in focal-plane units (pixels here)
+    lenses = (("FOV", camera.FovLensDistortion([0.9])), ("fisheye", camera.FisheyeLensDistortion([-0.05, 0.01, -0.003, 0.001])),
+              ("Brown-Conrady", camera.BrownConradyDistortion([-0.6, -0.2, 0.13e-8, -0.52e-16, 0, 0.55e-9, 0, 0.201])),
+              ("adjustable Tsai", camera.AdjustableTsaiLensDistortion([-0.1, 0.02, -0.003, 1e-3, -2e-3, 0.01])),
+              ("Photometrix", camera.PhotometrixLensDistortion([0.6, -0.3, -5e-9, 2e-16, -1e-24, 1e-9, -2e-9, 0, 0])))
+    for name, lens_k in lenses:
+        cam = camera.PinholeModel(ref.CENTER, rot_s, f, f, c, c, distortion=lens_k)
+        report("%s src -> pinhole, check on" % name, gpu(transform(cam, dst, True, False)), 8)
+        report("%s src -> pinhole, check off" % name, gpu(transform(cam, dst, False, False)), 8)
+        report("pinhole -> %s dst, check on" % name, gpu(transform(dst, cam, True, False)), 8)
     ctx.close()
 
 

@@ -7,7 +7,8 @@ calls after a warm-up call, divided by the count; the median of `--windows` such
 bytes per pixel over that time, and the ratio to a device-to-device copy of the SAME number of bytes timed in the same
 run, which is the yardstick (no data-sheet number enters).  Compulsory bytes per pixel: 12 read + 24 xyz (+ 8 error + 24
 error vector).  Cases: the null-distortion pinhole pair with xyz only, with every output, with the statistics; a pair
-with Tsai lenses; a CAHV pair; the universe radius on the point image (24 read + 24 written).
+with Tsai lenses; a CAHV pair; the universe radius on the point image (24 read + 24 written); a pair with each of the FOV,
+fisheye, Brown-Conrady, adjustable Tsai and Photometrix lenses on both cameras (--no-lenses leaves them out).
 usage: python tools/time_triangulate.py [--size 4096] [--repeat 20] [--windows 5]"""
 import argparse
 import ctypes
@@ -26,6 +27,7 @@ def main():
     ap.add_argument("--size", type=int, default=4096)
     ap.add_argument("--repeat", type=int, default=20)
     ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--no-lenses", action="store_true", help="only the cases without the any-lens instantiations")
     args = ap.parse_args()
     import torch
     import triangulate_ref as ref
@@ -103,6 +105,17 @@ def main():
     def universe():
         ctx.check(lib.vwgpu_universe_radius_dev(ctx._h, xyz.data_ptr(), 3, n, n, 0, origin.ctypes.data, 11.0, 13.0, out.data_ptr(), 0, None))
     report("universe_radius, 3 channels", gpu(universe), 48)
+    if args.no_lenses:
+        ctx.close()
+        return
+    # one camera per lens of the any-lens instantiations; Brown-Conrady and Photometrix work in focal-plane units (pixels here)
+    lenses = (("FOV", camera.FovLensDistortion([0.9])), ("fisheye", camera.FisheyeLensDistortion([-0.05, 0.01, -0.003, 0.001])),
+              ("Brown-Conrady", camera.BrownConradyDistortion([-0.6, -0.2, 0.13e-8, -0.52e-16, 0, 0.55e-9, 0, 0.201])),
+              ("adjustable Tsai", camera.AdjustableTsaiLensDistortion([-0.1, 0.02, -0.003, 1e-3, -2e-3, 0.01])),
+              ("Photometrix", camera.PhotometrixLensDistortion([0.6, -0.3, -5e-9, 2e-16, -1e-24, 1e-9, -2e-9, 0, 0])))
+    for name, lens_k in lenses:
+        cam1, cam2 = ref.pinhole_pair(n, n, f=500.0 * n / 70.0, distortion1=lens_k, distortion2=lens_k)
+        report("pinhole pair (%s lenses), xyz" % name, gpu(triangulate(cam1, cam2, False, False)), 36)
     ctx.close()
 
 

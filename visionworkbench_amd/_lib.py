@@ -37,7 +37,7 @@ SYMBOLS = [
     "vwgpu_convergence_angle_dev", "vwgpu_convergence_angle", "vwgpu_universe_radius_dev", "vwgpu_universe_radius",
     "vwgpu_pinhole_camera_matrix", "vwgpu_epipolar_pinhole", "vwgpu_epipolar_cahv",
     "vwgpu_camera_transform_dev", "vwgpu_camera_transform", "vwgpu_camera_transform_points_dev", "vwgpu_camera_transform_points",
-    "vwgpu_cahvor_camera", "vwgpu_cahvore_camera", "vwgpu_linearize_camera",
+    "vwgpu_cahvor_camera", "vwgpu_cahvore_camera", "vwgpu_linearize_camera", "vwgpu_camera_set_lens", "vwgpu_lens_coordinates",
     "vwgpu_disparity_filter_dev", "vwgpu_disparity_filter",
     "vwgpu_disparity_mask_dev", "vwgpu_disparity_mask",
     "vwgpu_subdivide_regions",
@@ -236,6 +236,8 @@ def load():
     lib.vwgpu_cahvor_camera.argtypes = [P, P, P, P, P, P, CP]
     lib.vwgpu_cahvore_camera.argtypes = [P, P, P, P, P, P, P, I, D, CP]
     lib.vwgpu_linearize_camera.argtypes = [CP, I, I, I, I, CP]
+    lib.vwgpu_camera_set_lens.argtypes = [CP, I, P, I]
+    lib.vwgpu_lens_coordinates.argtypes = [CP, I, P, ctypes.c_longlong, P, P]
     ctr = [P, P, I, I, PD, P, PD, CP, P, CP, P, I, I, I, I, F, I, I, P, PD, P, PD, P]
     lib.vwgpu_camera_transform_dev.argtypes = ctr
     lib.vwgpu_camera_transform.argtypes = ctr

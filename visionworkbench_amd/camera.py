@@ -1,6 +1,6 @@
-"""The part of vw::camera that triangulation and epipolar rectification need: PinholeModel with the null or the Tsai lens
-distortion, CAHVModel, CAHVORModel and CAHVOREModel, epipolar(), linearize_camera, resize_epipolar_cameras_to_fit,
-CameraTransform and camera_transform.
+"""The part of vw::camera that triangulation and epipolar rectification need: PinholeModel with the null, Tsai, FOV,
+fisheye, Brown-Conrady, adjustable Tsai or Photometrix lens distortion and its .tsai files, CAHVModel, CAHVORModel and
+CAHVOREModel, epipolar(), linearize_camera, resize_epipolar_cameras_to_fit, CameraTransform and camera_transform.
 
 Each model is a host object that produces the flat camera descriptor of the C ABI (struct vwgpu_camera, include/vwgpu.h)
 and, for a pinhole, the 3 x 4 camera matrix that travels beside it; the rays and projections themselves are computed on
@@ -14,10 +14,33 @@ import numpy as np
 
 from . import _lib
 from ._operands import Operands
-from .core import ArgumentErr, BBox2i, IOErr, LogicErr
+from .core import ArgumentErr, BBox2i, IOErr, LogicErr, NoImplErr
 
 CAMERA_PINHOLE, CAMERA_CAHV, CAMERA_CAHVOR, CAMERA_CAHVORE = 0, 1, 3, 4      # 2 is unassigned and refused (include/vwgpu.h)
 DISTORTION_NULL, DISTORTION_TSAI = 0, 1
+DISTORTION_FOV, DISTORTION_FISHEYE, DISTORTION_BROWN_CONRADY, DISTORTION_ADJUSTABLE_TSAI, DISTORTION_PHOTOMETRIX = 2, 3, 4, 6, 7   # 5 is refused
+
+
+def _g17(v):
+    return "%.17g" % v          # std::setprecision(17): the digits that survive double -> text -> double
+
+
+def _read_fields(lines, names, missing_ok=()):
+    """read_fields_in_vec (src/vw/Camera/LensDistortion.cc:52-92): `name = value` lines in any order, others ignored."""
+    found = {}
+    for line in lines:
+        t = line.replace("=", " ").split()
+        if len(t) >= 2:
+            try:
+                found[t[0]] = float(t[1])
+            except ValueError:
+                pass
+    out = []
+    for n in names:
+        if n not in found and n not in missing_ok:
+            raise IOErr("LensDistortion: Could not read a value for %s." % n)
+        out.append(found.get(n, 0.0))
+    return out
 
 
 def _vec3(v, what):
@@ -27,14 +50,143 @@ def _vec3(v, what):
     return np.ascontiguousarray(a)
 
 
-class TsaiLensDistortion(object):
+class LensDistortion(object):
+    """vw::camera::LensDistortion (src/vw/Camera/LensDistortion.h): the parameters of one lens.  The two coordinate
+    functions take a PinholeModel and a point in focal-plane units (pixel * pixel_pitch) and run, on the host, the
+    functions the kernels run (vwgpu_lens_coordinates)."""
+    KIND, NAME, PARAM_NAMES = None, None, ()
+
+    def _set(self, params):
+        self.params = np.ascontiguousarray(np.array(params, np.float64).reshape(-1))
+        if self.PARAM_NAMES and self.params.size != len(self.PARAM_NAMES):
+            raise IOErr("%s: Incorrect number of parameters was passed in." % type(self).__name__)
+
+    def name(self):
+        return self.NAME
+
+    def distortion_parameters(self):
+        return self.params.copy()
+
+    def _coordinates(self, cam, direction, p):
+        if cam.distortion is not self:
+            raise ArgumentErr("%s: the camera carries another lens" % type(self).__name__)
+        pts = np.ascontiguousarray(np.array(p, np.float64))
+        if pts.ndim < 1 or pts.shape[-1] != 2:
+            raise ArgumentErr("%s: the points must be (..., 2) {x, y}" % type(self).__name__)
+        out = np.empty_like(pts)
+        rc = _lib.load().vwgpu_lens_coordinates(ctypes.byref(cam.descriptor), direction, pts.ctypes.data, pts.size // 2,
+                                                out.ctypes.data, None)
+        if rc == -5:
+            raise LogicErr("LensDistortion: Did not converge.")
+        if rc != 0:
+            raise ArgumentErr("%s: bad arguments" % type(self).__name__)
+        return out
+
+    def distorted_coordinates(self, cam, p):
+        return self._coordinates(cam, 0, p)
+
+    def undistorted_coordinates(self, cam, p):
+        return self._coordinates(cam, 1, p)
+
+    def write(self, f):
+        for n, v in zip(self.PARAM_NAMES, self.params):
+            f.write("%s = %s\n" % (n, _g17(v)))
+
+    @classmethod
+    def read(cls, lines):
+        return cls(_read_fields(lines, cls.PARAM_NAMES))
+
+
+class FovLensDistortion(LensDistortion):
+    """vw::camera::FovLensDistortion (src/vw/Camera/LensDistortion.cc:418-530): the one-parameter wide-angle lens; k1 must
+    be positive (IOErr)."""
+    KIND, NAME, PARAM_NAMES = 2, "FOV", ("k1",)
+
+    def __init__(self, params):
+        self._set(np.atleast_1d(params))
+        if not self.params[0] > 0:
+            raise IOErr("FovLensDistortion: The distortion coefficient must be positive.")
+
+
+class FisheyeLensDistortion(LensDistortion):
+    """vw::camera::FisheyeLensDistortion (src/vw/Camera/LensDistortion.cc:532-673): k1, k2, k3, k4."""
+    KIND, NAME, PARAM_NAMES = 3, "FISHEYE", ("k1", "k2", "k3", "k4")
+
+    def __init__(self, params):
+        self._set(params)
+
+
+class BrownConradyDistortion(LensDistortion):
+    """vw::camera::BrownConradyDistortion (src/vw/Camera/LensDistortion.cc:675-775): BrownConradyDistortion(params) with
+    the eight numbers xp, yp, k1, k2, k3, p1, p2, phi, or BrownConradyDistortion(principal, radial, centering, angle)."""
+    KIND, NAME, PARAM_NAMES = 4, "BrownConrady", ("xp", "yp", "k1", "k2", "k3", "p1", "p2", "phi")
+
+    def __init__(self, params, radial=None, centering=None, angle=None):
+        if radial is not None:
+            params = list(np.atleast_1d(params)) + list(radial) + list(centering) + [angle]
+        if np.size(params) != 8:
+            raise ArgumentErr("BrownConradyDistortion: requires constructor input of size 8.")
+        self._set(params)
+
+    def write(self, f):
+        for n, v in zip(self.PARAM_NAMES, self.params):            # :746-756: two blanks before `=`, but for phi
+            f.write("%s%s= %s\n" % (n, " " if n == "phi" else "  ", _g17(v)))
+
+
+class AdjustableTsaiLensDistortion(LensDistortion):
+    """vw::camera::AdjustableTsaiLensDistortion (src/vw/Camera/LensDistortion.cc:777-917): n - 3 even radial coefficients,
+    two tangential ones and alpha; 4 <= n, and n <= 13 is what the camera descriptor holds."""
+    KIND, NAME = 6, "AdjustableTSAI"
+
+    def __init__(self, params):
+        self._set(params)
+        if self.params.size <= 3:
+            raise ArgumentErr("Requires at least 4 coefficients for distortion. Last 3 are always the distortion coefficients and "
+                              "alpha. All leading elements are even radial distortion coefficients.")
+        if self.params.size > 13:
+            raise NoImplErr("AdjustableTsaiLensDistortion: more than 13 coefficients do not fit the camera descriptor")
+
+    def write(self, f):
+        def vec(v):
+            return "Vector%d(%s)" % (len(v), ",".join(_g17(x) for x in v))
+        f.write("Radial Coeff: %s\nTangential Coeff: %s\nAlpha: %s\n" % (vec(self.params[:-3]), vec(self.params[-3:-1]), _g17(self.params[-1])))
+
+    @classmethod
+    def read(cls, lines):
+        """AdjustableTsaiLensDistortion::read (:889-913): the three-line form."""
+        text = "\n".join(lines)
+        m = re.match(r"\s*Radial\s+Coeff:\s*Vector(\d+)\(([^)]*)\)\s*Tangential\s+Coeff:\s*Vector(\d+)\(([^)]*)\)\s*Alpha:\s*(\S+)", text)
+        if m is None:
+            raise IOErr("AdjustableTsaiLensDistortion::read(): Could not read vector params.")
+        try:
+            radial, tangential = [float(t) for t in m.group(2).split(",")], [float(t) for t in m.group(4).split(",")]
+            alpha = float(m.group(5))
+        except ValueError:
+            raise IOErr("AdjustableTsaiLensDistortion::read(): Could not read vector params.")
+        if len(radial) != int(m.group(1)) or len(tangential) != int(m.group(3)):
+            raise IOErr("AdjustableTsaiLensDistortion::read(): Could not read vector params.")
+        return cls(radial + tangential + [alpha])
+
+
+class PhotometrixLensDistortion(LensDistortion):
+    """vw::camera::PhotometrixLensDistortion (src/vw/Camera/LensDistortion.cc:919-1013): xp, yp, k1, k2, k3, p1, p2, b1, b2
+    (b1 and b2 are not used, as in the reference)."""
+    KIND, NAME, PARAM_NAMES = 7, "Photometrix", ("xp", "yp", "k1", "k2", "k3", "p1", "p2", "b1", "b2")
+
+    def __init__(self, params):
+        self._set(params)
+
+
+class TsaiLensDistortion(LensDistortion):
     """vw::camera::TsaiLensDistortion (src/vw/Camera/LensDistortion.cc:225-400): parameters k1, k2, p1, p2, k3."""
+    KIND, NAME, PARAM_NAMES = 1, "TSAI", ("k1", "k2", "p1", "p2", "k3")
 
     def __init__(self, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
         self.params = np.array([k1, k2, p1, p2, k3], np.float64)
 
-    def distortion_parameters(self):
-        return self.params.copy()
+    @classmethod
+    def read(cls, lines):
+        return cls(*_read_fields(lines, cls.PARAM_NAMES, missing_ok=("k3",)))
 
     def distorted_coordinates(self, cam, p):
         """TsaiLensDistortion::distorted_coordinates (:345-369) of an undistorted pixel (in units of the focal length)."""
@@ -52,8 +204,8 @@ class TsaiLensDistortion(object):
 class PinholeModel(object):
     """vw::camera::PinholeModel(center, rotation, fu, fv, cu, cv, u, v, w, distortion, pixel_pitch)
     (src/vw/Camera/PinholeModel.h): rotation is the camera-to-world matrix, (u, v, w) the image-plane frame (the default
-    +x right, +y down, +z forward).  distortion: None (NullLensDistortion) or a TsaiLensDistortion.  u, v, w that fail the
-    reference's orthonormality asserts raise ArgumentErr."""
+    +x right, +y down, +z forward).  distortion: None (NullLensDistortion) or a LensDistortion (Tsai, FOV, fisheye, Brown-Conrady, adjustable Tsai,
+    Photometrix).  u, v, w that fail the reference's orthonormality asserts raise ArgumentErr."""
 
     def __init__(self, center, rotation, fu, fv, cu, cv, u=(1, 0, 0), v=(0, 1, 0), w=(0, 0, 1), distortion=None, pixel_pitch=1.0):
         self.center = _vec3(center, "PinholeModel: the camera center")
@@ -62,22 +214,28 @@ class PinholeModel(object):
             raise ArgumentErr("PinholeModel: the rotation must be 3 x 3")
         self.fu, self.fv, self.cu, self.cv = float(fu), float(fv), float(cu), float(cv)
         self.u, self.v, self.w = _vec3(u, "PinholeModel: u"), _vec3(v, "PinholeModel: v"), _vec3(w, "PinholeModel: w")
-        if distortion is not None and not isinstance(distortion, TsaiLensDistortion):
-            raise ArgumentErr("PinholeModel: the lens distortion must be None or a TsaiLensDistortion")
+        if distortion is not None and not isinstance(distortion, LensDistortion):
+            raise ArgumentErr("PinholeModel: the lens distortion must be None or a LensDistortion")
         self.distortion = distortion
         self.pixel_pitch = float(pixel_pitch)
         self.descriptor = _lib.Camera()
-        params = distortion.params if distortion is not None else None
+        tsai = isinstance(distortion, TsaiLensDistortion)
+        params = distortion.params if tsai else None
         rc = _lib.load().vwgpu_pinhole_camera(
             self.center.ctypes.data, self.rotation.ctypes.data, self.fu, self.fv, self.cu, self.cv, self.u.ctypes.data,
-            self.v.ctypes.data, self.w.ctypes.data, self.pixel_pitch, DISTORTION_TSAI if distortion is not None else DISTORTION_NULL,
+            self.v.ctypes.data, self.w.ctypes.data, self.pixel_pitch, DISTORTION_TSAI if tsai else DISTORTION_NULL,
             params.ctypes.data if params is not None else None, ctypes.byref(self.descriptor))
         if rc != 0:
             raise ArgumentErr("PinholeModel: u, v, w must be orthonormal")
+        if distortion is not None and not tsai:
+            rc = _lib.load().vwgpu_camera_set_lens(ctypes.byref(self.descriptor), distortion.KIND, distortion.params.ctypes.data,
+                                                   int(distortion.params.size))
+            if rc != 0:
+                raise ArgumentErr("PinholeModel: the parameters of the %s lens are refused" % distortion.name())
         self.matrix = np.empty((3, 4), np.float64)
         rc = _lib.load().vwgpu_pinhole_camera_matrix(
             self.center.ctypes.data, self.rotation.ctypes.data, self.fu, self.fv, self.cu, self.cv, self.u.ctypes.data,
-            self.v.ctypes.data, self.w.ctypes.data, self.pixel_pitch, DISTORTION_TSAI if distortion is not None else DISTORTION_NULL,
+            self.v.ctypes.data, self.w.ctypes.data, self.pixel_pitch, DISTORTION_TSAI if tsai else DISTORTION_NULL,
             params.ctypes.data if params is not None else None, self.matrix.ctypes.data)
         if rc != 0:
             raise ArgumentErr("PinholeModel: u, v, w must be orthonormal")
@@ -102,12 +260,105 @@ class PinholeModel(object):
                       self.pixel_pitch)
 
     def point_to_pixel(self, point):
-        """PinholeModel::point_to_pixel without its round-trip check (src/vw/Camera/PinholeModel.cc:370-413)."""
+        """PinholeModel::point_to_pixel without its round-trip check (src/vw/Camera/PinholeModel.cc:370-413); LogicErr where
+        the lens's distorted_coordinates does not converge."""
         q = self.camera_matrix() @ np.append(_vec3(point, "point_to_pixel: the point"), 1.0)
         pix = q[:2] / q[2]
         if self.distortion is not None:
             pix = self.distortion.distorted_coordinates(self, pix)
         return pix / self.pixel_pitch
+
+    def pixel_to_vector(self, pix):
+        """PinholeModel::pixel_to_vector (src/vw/Camera/PinholeModel.cc:422-430)."""
+        u = np.array(pix, np.float64).reshape(2) * self.pixel_pitch
+        if self.distortion is not None:
+            u = LensDistortion.undistorted_coordinates(self.distortion, self, u)
+        m, x, y = list(self.descriptor.inv_camera_transform), float(u[0]), float(u[1])
+        v = [0.0 + m[3 * i] * x + m[3 * i + 1] * y + m[3 * i + 2] * 1.0 for i in range(3)]       # a dot_prod per row, from zero
+        n = float(np.sqrt(0.0 + v[0] * v[0] + v[1] * v[1] + v[2] * v[2]))
+        return np.array([v[0] / n, v[1] / n, v[2] / n])
+
+    @classmethod
+    def read(cls, path):
+        """PinholeModel::read (src/vw/Camera/PinholeModel.cc:119-304): a .tsai file of any version, with or without the
+        PINHOLE line, the pitch line and the name of the lens (an old file without a name holds Tsai parameters)."""
+        try:
+            with open(path) as f:
+                lines = f.read().split("\n")
+        except OSError as e:
+            raise IOErr("PinholeModel::read_file: Could not open file: %s (%s)" % (path, e))
+        k, version = 0, 1
+        if "VERSION" in lines[0]:
+            m = re.match(r"VERSION_(\d+)", lines[0])
+            version = int(m.group(1)) if m else 1
+            k = 1
+            if version == 4:
+                if len(lines) < 2 or "PINHOLE" not in lines[1]:
+                    raise ArgumentErr("PinholeModel::read_file: Expected PINHOLE type, but got type %s" % (lines[1] if len(lines) > 1 else ""))
+                k = 2
+        elif re.match(r"fu\s*=", lines[0]) is None:
+            raise IOErr("PinholeModel::read_file(): A Pinhole camera file must start either with the VERSION line or the focal "
+                        "length. Got instead:\n%s\n" % lines[0])
+        vals = {}
+        for name, count in (("fu", 1), ("fv", 1), ("cu", 1), ("cv", 1), ("u_direction", 3), ("v_direction", 3), ("w_direction", 3),
+                            ("C", 3), ("R", 9)):
+            t = lines[k].replace("=", " = ").split() if k < len(lines) else []
+            try:
+                if t[:2] != [name, "="] or len(t) < 2 + count:
+                    raise ValueError
+                vals[name] = [float(x) for x in t[2:2 + count]]
+            except ValueError:
+                raise IOErr("PinholeModel::read_file(): Could not read %s" % name)
+            k += 1
+        pitch = 1.0
+        if k < len(lines) and "pitch" in lines[k]:
+            try:
+                pitch = float(lines[k].replace("=", " ").split()[1])
+            except (ValueError, IndexError):
+                raise IOErr("PinholeModel::read_file(): Could not read the pixel pitch")
+            k += 1
+        elif version > 2:
+            raise IOErr("PinholeModel::read_file(): Pitch value required in this file version!")
+        # construct_lens_distortion (:264-304): the first name the line holds, whatever its case, in the reference's order
+        line = lines[k].lower() if k < len(lines) else ""
+        lens = None
+        for name, kind in (("NULL", None), ("BrownConrady", BrownConradyDistortion), ("AdjustableTSAI", AdjustableTsaiLensDistortion),
+                           ("Photometrix", PhotometrixLensDistortion), ("RPC", "RPC"), ("FOV", FovLensDistortion),
+                           ("FISHEYE", FisheyeLensDistortion), ("TSAI", TsaiLensDistortion)):
+            if name.lower() in line:
+                lens = (kind,)
+                break
+        if lens is None:
+            if version > 2:
+                raise IOErr("PinholeModel::read_file(): Distortion name required in this file version!")
+            lens = (TsaiLensDistortion,)
+        else:
+            k += 1
+        if lens[0] == "RPC":
+            raise NoImplErr("PinholeModel::read_file(): the RPC lens distortion is not implemented")
+        distortion = lens[0].read(lines[k:]) if lens[0] is not None else None
+        return cls(vals["C"], np.array(vals["R"]).reshape(3, 3), vals["fu"][0], vals["fv"][0], vals["cu"][0], vals["cv"][0],
+                   vals["u_direction"], vals["v_direction"], vals["w_direction"], distortion, pitch)
+
+    def write(self, path):
+        """PinholeModel::write (src/vw/Camera/PinholeModel.cc:306-347): VERSION_4 with 17 significant digits, into `path` with
+        the extension .tsai; returns the path written."""
+        path = re.sub(r"\.[^./\\]*$", "", str(path)) + ".tsai" if re.search(r"\.[^./\\]*$", str(path)) else str(path) + ".tsai"
+
+        def row(v):
+            return " ".join(_g17(x) for x in np.array(v).reshape(-1))
+        try:
+            with open(path, "w") as f:
+                f.write("VERSION_4\nPINHOLE\n")
+                f.write("fu = %s\nfv = %s\ncu = %s\ncv = %s\n" % tuple(_g17(x) for x in (self.fu, self.fv, self.cu, self.cv)))
+                f.write("u_direction = %s\nv_direction = %s\nw_direction = %s\n" % (row(self.u), row(self.v), row(self.w)))
+                f.write("C = %s\nR = %s\npitch = %s\n" % (row(self.center), row(self.rotation), _g17(self.pixel_pitch)))
+                f.write("%s\n" % (self.distortion.name() if self.distortion is not None else "NULL"))
+                if self.distortion is not None:
+                    self.distortion.write(f)
+        except OSError as e:
+            raise IOErr("PinholeModel::write: Could not open file: %s (%s)" % (path, e))
+        return path
 
 
 class CAHVModel(object):
@@ -514,6 +765,7 @@ def resize_epipolar_cameras_to_fit(cam1, cam2, epi1, epi2, roi1, roi2, ctx=None)
     return new[0], new[1], sizes[0], sizes[1]
 
 
-__all__ = ["PinholeModel", "TsaiLensDistortion", "CAHVModel", "CAHVORModel", "CAHVOREModel", "linearize_camera",
+__all__ = ["PinholeModel", "LensDistortion", "TsaiLensDistortion", "FovLensDistortion", "FisheyeLensDistortion", "BrownConradyDistortion",
+           "AdjustableTsaiLensDistortion", "PhotometrixLensDistortion", "CAHVModel", "CAHVORModel", "CAHVOREModel", "linearize_camera",
            "linearize_camera_transform", "descriptor_of", "matrix_of", "epipolar", "CameraTransform",
            "camera_transform", "compute_transformed_bbox_fast", "resize_epipolar_cameras_to_fit", "BBox2i"]

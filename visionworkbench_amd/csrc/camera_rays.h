@@ -6,16 +6,19 @@
 // triangulate.hip and camera_transform.hip; internal linkage, so every translation unit compiles its own copy.
 #pragma once
 #include <cmath>
+#include <cstddef>
 
 #include "vwgpu_internal.h"
 
 namespace {
 
 // which code a kernel carries for one camera: a pinhole without lens distortion, a pinhole whose distortion kind is read
-// at run time, CAHV, CAHVOR, CAHVORE
-enum { TR_CAM_PINHOLE_NULL = 0, TR_CAM_PINHOLE = 1, TR_CAM_CAHV = 2, TR_CAM_CAHVOR = 3, TR_CAM_CAHVORE = 4 };
-// how a CAHVORE function left: its result, or one of the reference's two throws
-enum { TR_OK = 0, TR_NOT_CONVERGED = 1, TR_THETA_OUT_OF_BOUNDS = 2 };
+// at run time (null or Tsai), CAHV, CAHVOR, CAHVORE, and a pinhole with any of the seven lenses: the code of every pinhole
+// of a pair in which one carries a lens other than null and Tsai
+enum { TR_CAM_PINHOLE_NULL = 0, TR_CAM_PINHOLE = 1, TR_CAM_CAHV = 2, TR_CAM_CAHVOR = 3, TR_CAM_CAHVORE = 4, TR_CAM_PINHOLE_LENS = 5 };
+// how a CAHVORE function or a projection left: its result, one of the reference's two CAHVORE throws, or the throw of
+// LensDistortion::distorted_coordinates
+enum { TR_OK = 0, TR_NOT_CONVERGED = 1, TR_THETA_OUT_OF_BOUNDS = 2, TR_LENS_NOT_CONVERGED = 3 };
 
 struct tr_v3 { double x, y, z; };
 struct tr_v2 { double x, y; };
@@ -32,6 +35,25 @@ __host__ __device__ inline tr_v3 tr_normalize(const tr_v3& a) {
   return tr_v3{a.x / n, a.y / n, a.z / n};
 }
 __host__ __device__ inline tr_v3 tr_load3(const double* p) { return tr_v3{p[0], p[1], p[2]}; }
+
+// the lens words L[0..13] of a pinhole: distortion[0..4], A, H, V are contiguous, and a pinhole uses none of A, H, V
+static_assert(offsetof(vwgpu_camera, distortion) == 144 && offsetof(vwgpu_camera, V) + sizeof(double[3]) == 256, "lens words");
+__host__ __device__ inline const double* tr_lens_words(const vwgpu_camera& c) { return reinterpret_cast<const double*>(&c) + 18; }
+inline bool tr_lens_known(int kind) {
+  return kind == VWGPU_DISTORTION_NULL || kind == VWGPU_DISTORTION_TSAI || kind == VWGPU_DISTORTION_FOV || kind == VWGPU_DISTORTION_FISHEYE ||
+         kind == VWGPU_DISTORTION_BROWN_CONRADY || kind == VWGPU_DISTORTION_ADJUSTABLE_TSAI || kind == VWGPU_DISTORTION_PHOTOMETRIX;
+}
+// a lens kind the kernels know, and for the adjustable Tsai a coefficient count the lens words can hold (it indexes them)
+inline bool tr_lens_valid(const vwgpu_camera& c) {
+  if (!tr_lens_known(c.distortion_kind)) return false;
+  if (c.distortion_kind != VWGPU_DISTORTION_ADJUSTABLE_TSAI) return true;
+  const double n = tr_lens_words(c)[13];
+  return n >= 4 && n <= 13 && n == (double)(int)n;
+}
+// a pinhole whose lens the null / Tsai instantiations do not carry
+inline bool tr_lens_pinhole(const vwgpu_camera& c) {
+  return c.kind == VWGPU_CAMERA_PINHOLE && c.distortion_kind != VWGPU_DISTORTION_NULL && c.distortion_kind != VWGPU_DISTORTION_TSAI;
+}
 
 // the two kinds that are paired only with CAHV (camera transform) or with their own kind (triangulation)
 inline bool tr_new_kind(const vwgpu_camera& c) { return c.kind == VWGPU_CAMERA_CAHVOR || c.kind == VWGPU_CAMERA_CAHVORE; }
@@ -181,7 +203,7 @@ __host__ __device__ inline int tr_cahvore_project(const vwgpu_camera& c, const t
 }
 
 // TsaiDistortionNorm (LensDistortion.cc:260-276)
-__device__ inline tr_v2 tr_tsai_norm(const tr_v2& P, const double* distortion) {
+__host__ __device__ inline tr_v2 tr_tsai_norm(const tr_v2& P, const double* distortion) {
   double x = P.x;
   double y = P.y;
   double k1 = distortion[0];
@@ -197,7 +219,7 @@ __device__ inline tr_v2 tr_tsai_norm(const tr_v2& P, const double* distortion) {
 }
 
 // TsaiDistortionJacobian (LensDistortion.cc:286-324)
-__device__ inline void tr_tsai_jacobian(const tr_v2& P, const double* distortion, double* jacobian) {
+__host__ __device__ inline void tr_tsai_jacobian(const tr_v2& P, const double* distortion, double* jacobian) {
   double x = P.x;
   double y = P.y;
   double k1 = distortion[0];
@@ -221,15 +243,37 @@ __device__ inline void tr_tsai_jacobian(const tr_v2& P, const double* distortion
               + p1 * (dr2dy + 4.0 * y) + 2.0 * p2 * x;
 }
 
+// what NewtonRaphson::solve iterates on: the distortion of a normalised pixel and its Jacobian {J00, J01, J10, J11}
+struct tr_tsai_model {
+  const double* distortion;
+  __host__ __device__ tr_v2 norm(const tr_v2& P) const { return tr_tsai_norm(P, distortion); }
+  __host__ __device__ void jacobian(const tr_v2& P, double* J) const { tr_tsai_jacobian(P, distortion, J); }
+};
+
+// numericalJacobian::operator() (NewtonRaphson.cc:27-47): central differences with step 1e-6, a column per coordinate
+template <class MODEL>
+__host__ __device__ inline void tr_numerical_jacobian(const MODEL& m, const tr_v2& P, double* J) {
+  const double step = 1e-6;
+  const tr_v2 xp = m.norm(tr_v2{P.x + step, P.y + 0.0}), xm = m.norm(tr_v2{P.x - step, P.y - 0.0});
+  const tr_v2 JX{(xp.x - xm.x) / (2 * step), (xp.y - xm.y) / (2 * step)};
+  const tr_v2 yp = m.norm(tr_v2{P.x + 0.0, P.y + step}), ym = m.norm(tr_v2{P.x - 0.0, P.y - step});
+  const tr_v2 JY{(yp.x - ym.x) / (2 * step), (yp.y - ym.y) / (2 * step)};
+  J[0] = JX.x;
+  J[1] = JY.x;
+  J[2] = JX.y;
+  J[3] = JY.y;
+}
+
 // NewtonRaphson::solve (NewtonRaphson.cc:58-119) with guessX = outY = the normalised distorted pixel, tol = 1e-9
-__device__ inline tr_v2 tr_newton_tsai(const tr_v2& outY, const double* distortion) {
+template <class MODEL>
+__host__ __device__ inline tr_v2 tr_newton(const tr_v2& outY, const MODEL& model) {
   tr_v2 X = outY;
   tr_v2 bestX = X;
   double best_err = 1.7976931348623157e308;   // std::numeric_limits<double>::max()
   int count = 1;
   const int maxTries = 20;
   while (count < maxTries) {
-    const tr_v2 FX = tr_tsai_norm(X, distortion);
+    const tr_v2 FX = model.norm(X);
     const tr_v2 F{FX.x - outY.x, FX.y - outY.y};
     const double nF = tr_norm(F);
     if (nF != nF) return bestX;
@@ -238,7 +282,7 @@ __device__ inline tr_v2 tr_newton_tsai(const tr_v2& outY, const double* distorti
       bestX = X;
     }
     double J[4];
-    tr_tsai_jacobian(X, distortion, J);
+    model.jacobian(X, J);
     const double det = J[0] * J[3] - J[1] * J[2];
     if (fabs(det) < 1e-6 || det != det) return bestX;
     tr_v2 DX;
@@ -253,21 +297,150 @@ __device__ inline tr_v2 tr_newton_tsai(const tr_v2& outY, const double* distorti
 }
 
 // TsaiLensDistortion::undistorted_coordinates (LensDistortion.cc:371-400)
-__device__ inline tr_v2 tr_tsai_undistort(const vwgpu_camera& c, const tr_v2& p) {
+__host__ __device__ inline tr_v2 tr_tsai_undistort(const vwgpu_camera& c, const tr_v2& p) {
   if (c.fu < 1e-300 || c.fv < 1e-300) return tr_v2{HUGE_VAL, HUGE_VAL};
   const tr_v2 p0{(p.x - c.cu) / c.fu, (p.y - c.cv) / c.fv};
-  const tr_v2 U = tr_newton_tsai(p0, c.distortion);
+  const tr_v2 U = tr_newton(p0, tr_tsai_model{c.distortion});
   double ux = U.x, uy = U.y;
   ux = ux * c.fu + c.cu;
   uy = uy * c.fv + c.cv;
   return tr_v2{ux, uy};
 }
 
+// FovLensDistortion::undistorted_coordinates (LensDistortion.cc:490-515); L = {k1, 1 / k1, 2 tan(k1 / 2)}
+__host__ __device__ inline tr_v2 tr_fov_undistort(const vwgpu_camera& c, const tr_v2& p) {
+  const double* L = tr_lens_words(c);
+  if (c.fu < 1e-300 || c.fv < 1e-300) return tr_v2{HUGE_VAL, HUGE_VAL};
+  const tr_v2 p0{(p.x - c.cu) / c.fu, (p.y - c.cv) / c.fv};
+  const double rd = tr_norm(p0);
+  const double ru = tan(rd * L[0]) / L[2];
+  double conv = 1.0;
+  if (rd > 1e-8) conv = ru / rd;
+  return tr_v2{conv * p0.x * c.fu + c.cu, conv * p0.y * c.fv + c.cv};
+}
+
+// fishEyeDistortionNorm (LensDistortion.cc:573-598)
+__host__ __device__ inline tr_v2 tr_fisheye_norm(const tr_v2& P, const double* dist) {
+  double k1 = dist[0];
+  double k2 = dist[1];
+  double k3 = dist[2];
+  double k4 = dist[3];
+  double x = P.x;
+  double y = P.y;
+  double r2 = x * x + y * y;
+  double r = sqrt(r2);
+  double theta = atan(r);
+  double theta1 = theta * theta;
+  double theta2 = theta1 * theta1;
+  double theta3 = theta2 * theta1;
+  double theta4 = theta2 * theta2;
+  double theta_d = theta * (1 + k1 * theta1 + k2 * theta2 + k3 * theta3 + k4 * theta4);
+  double scale = 1.0;
+  if (r > 1e-8) scale = theta_d / r;
+  return tr_v2{x * scale, y * scale};
+}
+
+// AdjTsaiDistortionNorm (LensDistortion.cc:799-824): n - 3 radial coefficients, two tangential ones and alpha; n = L[13]
+// is between 4 and 13 (vwgpu_camera_set_lens), so the radial loop makes at most 10 passes
+__host__ __device__ inline tr_v2 tr_adjustable_tsai_norm(const tr_v2& p_0, const double* distortion) {
+  const int n = (int)distortion[13];
+  const double r2 = 0.0 + p_0.x * p_0.x + p_0.y * p_0.y;
+  double r_n = 1, radial = 0;
+  for (int i = 0; i < 10 && i < n - 3; i++) {
+    r_n *= r2;
+    radial += distortion[i] * r_n;
+  }
+  tr_v2 tangent{0.0, 0.0};
+  const tr_v2 swap_coeff{distortion[n - 2], distortion[n - 3]};
+  tangent.x += swap_coeff.x * (r2 + 2 * (p_0.x * p_0.x));
+  tangent.y += swap_coeff.y * (r2 + 2 * (p_0.y * p_0.y));
+  tangent.x += 2 * (p_0.x * p_0.y) * distortion[n - 3];
+  tangent.y += 2 * (p_0.x * p_0.y) * distortion[n - 2];
+  tr_v2 result{p_0.x + tangent.x + radial * p_0.x, p_0.y + tangent.y + radial * p_0.y};
+  result.x += distortion[n - 1] * result.y;
+  result.y += 0.0;
+  return result;
+}
+
+// the two lenses NewtonRaphson::solve inverts with the numerical Jacobian
+struct tr_fisheye_model {
+  const double* L;
+  __host__ __device__ tr_v2 norm(const tr_v2& P) const { return tr_fisheye_norm(P, L); }
+  __host__ __device__ void jacobian(const tr_v2& P, double* J) const { tr_numerical_jacobian(*this, P, J); }
+};
+struct tr_adjustable_tsai_model {
+  const double* L;
+  __host__ __device__ tr_v2 norm(const tr_v2& P) const { return tr_adjustable_tsai_norm(P, L); }
+  __host__ __device__ void jacobian(const tr_v2& P, double* J) const { tr_numerical_jacobian(*this, P, J); }
+};
+
+// FisheyeLensDistortion::undistorted_coordinates (LensDistortion.cc:634-658) and
+// AdjustableTsaiLensDistortion::undistorted_coordinates (:851-880)
+template <class MODEL>
+__host__ __device__ inline tr_v2 tr_numeric_undistort(const vwgpu_camera& c, const tr_v2& p) {
+  if (c.fu < 1e-300 || c.fv < 1e-300) return tr_v2{HUGE_VAL, HUGE_VAL};
+  const tr_v2 p0{(p.x - c.cu) / c.fu, (p.y - c.cv) / c.fv};
+  const tr_v2 U = tr_newton(p0, MODEL{tr_lens_words(c)});
+  return tr_v2{U.x * c.fu + c.cu, U.y * c.fv + c.cv};
+}
+
+// BrownConradyDistortion::undistorted_coordinates (LensDistortion.cc:731-744); L = {xp, yp, k1, k2, k3, p1, p2, phi, sin(phi),
+// cos(phi)}
+__host__ __device__ inline tr_v2 tr_brown_conrady_undistort(const vwgpu_camera& c, const tr_v2& p) {
+  const double* L = tr_lens_words(c);
+  tr_v2 intermediate{p.x - L[0] - c.cu, p.y - L[1] - c.cv};
+  const double r2 = 0.0 + intermediate.x * intermediate.x + intermediate.y * intermediate.y;
+  const double radial = 1 + L[2] * r2 + L[3] * r2 * r2 + L[4] * r2 * r2 * r2;
+  const double tangential = L[5] * r2 + L[6] * r2 * r2;
+  intermediate.x *= radial;
+  intermediate.y *= radial;
+  intermediate.x -= tangential * L[8];
+  intermediate.y += tangential * L[9];
+  return tr_v2{intermediate.x + c.cu, intermediate.y + c.cv};
+}
+
+// PhotometrixLensDistortion::undistorted_coordinates (LensDistortion.cc:961-999); L = {xp, yp, k1, k2, k3, p1, p2, b1, b2},
+// b1 and b2 unused as in the reference
+__host__ __device__ inline tr_v2 tr_photometrix_undistort(const vwgpu_camera& c, const tr_v2& p) {
+  const double* L = tr_lens_words(c);
+  double x_meas = p.x;
+  double y_meas = p.y;
+  double xp = L[0] + c.cu;
+  double yp = L[1] + c.cv;
+  double x = x_meas - xp;
+  double y = y_meas - yp;
+  double x2 = x * x;
+  double y2 = y * y;
+  double r2 = x2 + y2;
+  double K1 = L[2];
+  double K2 = L[3];
+  double K3 = L[4];
+  double P1 = L[5];
+  double P2 = L[6];
+  double drr = K1 * r2 + K2 * r2 * r2 + K3 * r2 * r2 * r2;
+  double x_corr = x_meas + x * drr + P1 * (r2 + 2.0 * x2) + 2.0 * P2 * x * y;
+  double y_corr = y_meas + y * drr + P2 * (r2 + 2.0 * y2) + 2.0 * P1 * x * y;
+  return tr_v2{x_corr, y_corr};
+}
+
+// undistorted_coordinates of a pinhole's lens, whichever it is (the kinds are checked on the host)
+__host__ __device__ inline tr_v2 tr_lens_undistort(const vwgpu_camera& c, const tr_v2& p) {
+  switch (c.distortion_kind) {
+    case VWGPU_DISTORTION_TSAI: return tr_tsai_undistort(c, p);
+    case VWGPU_DISTORTION_FOV: return tr_fov_undistort(c, p);
+    case VWGPU_DISTORTION_FISHEYE: return tr_numeric_undistort<tr_fisheye_model>(c, p);
+    case VWGPU_DISTORTION_BROWN_CONRADY: return tr_brown_conrady_undistort(c, p);
+    case VWGPU_DISTORTION_ADJUSTABLE_TSAI: return tr_numeric_undistort<tr_adjustable_tsai_model>(c, p);
+    case VWGPU_DISTORTION_PHOTOMETRIX: return tr_photometrix_undistort(c, p);
+    default: return p;
+  }
+}
+
 // pixel_to_vector of the camera kinds a kernel carries
 // `flip`: the handedness test of CAHVModel::pixel_to_vector, dot(cross(V, H), A) < 0 — the same for every pixel, so the
 // host evaluates it once (tr_cahv_flips)
 template <int CAM>
-__device__ inline tr_v3 tr_ray(const vwgpu_camera& c, const tr_v2& pix, bool flip) {
+__host__ __device__ inline tr_v3 tr_ray(const vwgpu_camera& c, const tr_v2& pix, bool flip) {
   if (CAM == TR_CAM_CAHV) {
     // CAHVModel::pixel_to_vector (CAHVModel.cc:173-185)
     const tr_v3 A = tr_load3(c.A), H = tr_load3(c.H), V = tr_load3(c.V);
@@ -283,7 +456,8 @@ __device__ inline tr_v3 tr_ray(const vwgpu_camera& c, const tr_v2& pix, bool fli
   }
   // PinholeModel::pixel_to_vector (PinholeModel.cc:422-430)
   tr_v2 u{pix.x * c.pixel_pitch, pix.y * c.pixel_pitch};
-  if (CAM != TR_CAM_PINHOLE_NULL && c.distortion_kind == VWGPU_DISTORTION_TSAI) u = tr_tsai_undistort(c, u);
+  if (CAM == TR_CAM_PINHOLE_LENS) u = tr_lens_undistort(c, u);
+  else if (CAM != TR_CAM_PINHOLE_NULL && c.distortion_kind == VWGPU_DISTORTION_TSAI) u = tr_tsai_undistort(c, u);
   const tr_v3 p{u.x, u.y, 1.0};
   const double* m = c.inv_camera_transform;
   return tr_normalize(tr_v3{tr_dot(tr_load3(m), p), tr_dot(tr_load3(m + 3), p), tr_dot(tr_load3(m + 6), p)});

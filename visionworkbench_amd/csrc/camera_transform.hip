@@ -14,6 +14,10 @@
 // a lens, or a src with a lens whose round-trip check is on, carries the Newton loop.  CAHVOR and CAHVORE
 // (camera_rays.h) are paired with CAHV alone, in either role: eight more image kernels and four more point kernels.
 // linearize_camera (CAHVORModel.cc:460-547, CAHVOREModel.cc:303-381) is host arithmetic over the same model functions.
+// A pair in which a pinhole carries a FOV, fisheye, Brown-Conrady, adjustable Tsai or Photometrix lens takes the any-lens
+// codes for its pinholes (TR_CAM_PINHOLE_LENS, CT_TO_PINHOLE_LENS_*): ten more image kernels and five more point kernels,
+// with distorted_coordinates of every lens (LensDistortion.cc:175-195, :462-488, :612-632, :832-849), which
+// vwgpu_lens_coordinates runs on the host.
 //
 // Everything up to the source position is double in the reference's expression order (-ffp-contract=off); the tap is
 // float, every product and sum rounded on its own.
@@ -35,13 +39,19 @@ constexpr int CT_COUNTERS = 1024;
 // how a kernel projects into a camera (point_to_pixel): a pinhole without the round-trip check (the lens kind is read at
 // run time: distorted_coordinates is closed form), a pinhole without lens with the check, a pinhole whose lens kind is
 // read at run time with the check (the Newton loop), CAHV (has no check), CAHVOR (closed form), CAHVORE (a Newton loop
-// and two ways to throw)
-enum { CT_TO_PINHOLE_NOCHECK = 0, CT_TO_PINHOLE_NULL_CHECK = 1, CT_TO_PINHOLE_CHECK = 2, CT_TO_CAHV = 3, CT_TO_CAHVOR = 4, CT_TO_CAHVORE = 5 };
+// and two ways to throw), and a pinhole with any of the seven lenses without and with the check (TR_CAM_PINHOLE_LENS: the
+// Levenberg-Marquardt loop of the Brown-Conrady and Photometrix lenses, whose failure is a throw with the check off too)
+enum {
+  CT_TO_PINHOLE_NOCHECK = 0, CT_TO_PINHOLE_NULL_CHECK = 1, CT_TO_PINHOLE_CHECK = 2, CT_TO_CAHV = 3, CT_TO_CAHVOR = 4, CT_TO_CAHVORE = 5,
+  CT_TO_PINHOLE_LENS_NOCHECK = 6, CT_TO_PINHOLE_LENS_CHECK = 7
+};
+template <int TO>
+__host__ __device__ constexpr bool ct_to_lens() { return TO == CT_TO_PINHOLE_LENS_NOCHECK || TO == CT_TO_PINHOLE_LENS_CHECK; }
 
 struct ct_mat { double m[12]; };   // m_camera_matrix, row-major 3 x 4
 
 // TsaiLensDistortion::distorted_coordinates (LensDistortion.cc:345-369)
-__device__ inline tr_v2 ct_tsai_distort(const vwgpu_camera& c, const tr_v2& p) {
+__host__ __device__ inline tr_v2 ct_tsai_distort(const vwgpu_camera& c, const tr_v2& p) {
   if (c.fu < 1e-300 || c.fv < 1e-300) return tr_v2{HUGE_VAL, HUGE_VAL};
   const tr_v2 p0{(p.x - c.cu) / c.fu, (p.y - c.cv) / c.fv};
   const tr_v2 d = tr_tsai_norm(p0, c.distortion);
@@ -51,32 +61,146 @@ __device__ inline tr_v2 ct_tsai_distort(const vwgpu_camera& c, const tr_v2& p) {
   return tr_v2{dx, dy};
 }
 
-// point_to_pixel of the camera `c`; false where PinholeModel::point_to_pixel throws PointToPixelErr (PinholeModel.cc:378-394)
+// FovLensDistortion::distorted_coordinates (LensDistortion.cc:462-488); L = {k1, 1 / k1, 2 tan(k1 / 2)}
+__host__ __device__ inline tr_v2 ct_fov_distort(const vwgpu_camera& c, const tr_v2& p) {
+  const double* L = tr_lens_words(c);
+  if (c.fu < 1e-300 || c.fv < 1e-300) return tr_v2{HUGE_VAL, HUGE_VAL};
+  const tr_v2 p0{(p.x - c.cu) / c.fu, (p.y - c.cv) / c.fv};
+  const double ru = tr_norm(p0);
+  const double rd = atan(ru * L[2]) * L[1];
+  double conv = 1.0;
+  if (ru > 1e-8) conv = rd / ru;
+  return tr_v2{conv * p0.x * c.fu + c.cu, conv * p0.y * c.fv + c.cv};
+}
+
+// FisheyeLensDistortion::distorted_coordinates (:612-632) and AdjustableTsaiLensDistortion::distorted_coordinates (:832-849)
+template <class MODEL>
+__host__ __device__ inline tr_v2 ct_norm_distort(const vwgpu_camera& c, const tr_v2& p) {
+  if (c.fu < 1e-300 || c.fv < 1e-300) return tr_v2{HUGE_VAL, HUGE_VAL};
+  const tr_v2 p0{(p.x - c.cu) / c.fu, (p.y - c.cv) / c.fv};
+  const tr_v2 d = MODEL{tr_lens_words(c)}.norm(p0);
+  return tr_v2{d.x * c.fu + c.cu, d.y * c.fv + c.cv};
+}
+
+// DistortOptimizeFunctor (LensDistortion.cc:29-41) for the two lenses that have no distorted_coordinates of their own
+__host__ __device__ inline tr_v2 ct_solver_model(const vwgpu_camera& c, const tr_v2& x) {
+  return c.distortion_kind == VWGPU_DISTORTION_PHOTOMETRIX ? tr_photometrix_undistort(c, x) : tr_brown_conrady_undistort(c, x);
+}
+
+// LensDistortion::distorted_coordinates (LensDistortion.cc:175-195): levenberg_marquardtFixed(model, v, v, status, 1e-16,
+// 1e-16, 100) (Math/LevenbergMarquardt.h:389-561) for two unknowns, with the forward-difference Jacobian of
+// LeastSquaresModelBaseFixed::jacobian (:344-377) and inverse() of Math/Matrix.h:2209-2216, then the 1e-10 test.  At most
+// 100 outer passes of at most 6 inner ones.  false where the reference throws "LensDistortion: Did not converge.", and
+// where det(hessian_lm) > 0.0 does not hold (NaN, overflow), for which the reference leaves for LAPACK.
+__host__ __device__ inline bool ct_solver_distort(const vwgpu_camera& c, const tr_v2& v, tr_v2& solution) {
+  const double abs_tolerance = 1e-16, rel_tolerance = 1e-16;
+  const int max_iterations = 100;
+  bool done = false;
+  const double Rinv = 10;
+  double lambda = 0.1;
+  tr_v2 x_try{0.0, 0.0}, x = v;
+  tr_v2 h = ct_solver_model(c, x);
+  tr_v2 error{v.x - h.x, v.y - h.y};
+  double norm_start = tr_norm(error);
+  if (norm_start < abs_tolerance) done = true;
+  for (int outer_iter = 1; outer_iter <= max_iterations && !done; ++outer_iter) {
+    bool shortCircuit = false;
+    h = ct_solver_model(c, x);
+    error = tr_v2{v.x - h.x, v.y - h.y};
+    norm_start = tr_norm(error);
+    // the Jacobian, J[row][column]
+    const tr_v2 h0 = ct_solver_model(c, x);
+    const double eps0 = 1e-7 + fabs(x.x * 1e-7), eps1 = 1e-7 + fabs(x.y * 1e-7);
+    const tr_v2 h_0 = ct_solver_model(c, tr_v2{x.x + eps0, x.y}), h_1 = ct_solver_model(c, tr_v2{x.x, x.y + eps1});
+    const double J00 = (h_0.x - h0.x) / eps0, J10 = (h_0.y - h0.y) / eps0;
+    const double J01 = (h_1.x - h0.x) / eps1, J11 = (h_1.y - h0.y) / eps1;
+    const double del_J0 = -1.0 * Rinv * (0.0 + J00 * error.x + J10 * error.y);
+    const double del_J1 = -1.0 * Rinv * (0.0 + J01 * error.x + J11 * error.y);
+    const double H00 = Rinv * (0.0 + J00 * J00 + J10 * J10), H01 = Rinv * (0.0 + J00 * J01 + J10 * J11);
+    const double H10 = Rinv * (0.0 + J01 * J00 + J11 * J10), H11 = Rinv * (0.0 + J01 * J01 + J11 * J11);
+    int iterations = 0;
+    double norm_try = norm_start + 1.0;
+    while (norm_try > norm_start && iterations < 6) {
+      double d0 = H00, d3 = H11;
+      const double d1 = H01, d2 = H10;
+      d0 += d0 * lambda + lambda;
+      d3 += d3 * lambda + lambda;
+      const double det = d0 * d3 - d1 * d2;
+      if (!(det > 0.0)) return false;
+      const double i0 = d3 / det, i1 = -d1 / det, i2 = -d2 / det, i3 = d0 / det;
+      const tr_v2 delta_x{0.0 + i0 * del_J0 + i1 * del_J1, 0.0 + i2 * del_J0 + i3 * del_J1};
+      x_try = tr_v2{x.x - delta_x.x, x.y - delta_x.y};
+      const tr_v2 h_try = ct_solver_model(c, x_try);
+      const tr_v2 error_try{v.x - h_try.x, v.y - h_try.y};
+      norm_try = tr_norm(error_try);
+      if (norm_try > norm_start) lambda *= 10;
+      ++iterations;
+      if (iterations > 5) {
+        shortCircuit = true;
+        norm_try = norm_start;
+      }
+    }
+    if (!shortCircuit && ((norm_start - norm_try) / norm_start) < rel_tolerance) done = true;
+    if (norm_try < abs_tolerance) done = true;
+    if (!shortCircuit) x = x_try;
+    norm_start = norm_try;
+    lambda /= 10;
+  }
+  solution = x;
+  const tr_v2 undist = ct_solver_model(c, solution);
+  const double nv = tr_norm(v);
+  const double err = tr_norm(tr_v2{undist.x - v.x, undist.y - v.y}) / (nv > 0.1 ? nv : 0.1);
+  return !(err > 1e-10);
+}
+
+// distorted_coordinates of a pinhole's lens, whichever it is; false where the reference throws
+__host__ __device__ inline bool ct_lens_distort(const vwgpu_camera& c, const tr_v2& p, tr_v2& out) {
+  switch (c.distortion_kind) {
+    case VWGPU_DISTORTION_TSAI: out = ct_tsai_distort(c, p); return true;
+    case VWGPU_DISTORTION_FOV: out = ct_fov_distort(c, p); return true;
+    case VWGPU_DISTORTION_FISHEYE: out = ct_norm_distort<tr_fisheye_model>(c, p); return true;
+    case VWGPU_DISTORTION_ADJUSTABLE_TSAI: out = ct_norm_distort<tr_adjustable_tsai_model>(c, p); return true;
+    case VWGPU_DISTORTION_BROWN_CONRADY:
+    case VWGPU_DISTORTION_PHOTOMETRIX: return ct_solver_distort(c, p, out);
+    default: out = p; return true;
+  }
+}
+
+// point_to_pixel of the camera `c`; TR_NOT_CONVERGED where PinholeModel::point_to_pixel throws PointToPixelErr (PinholeModel.cc:378-394)
+// (PinholeModel.cc:378-394), TR_LENS_NOT_CONVERGED where the lens's distorted_coordinates does
 template <int TO>
-__device__ inline bool ct_point_to_pixel(const vwgpu_camera& c, const ct_mat& M, bool flip, const tr_v3& point, tr_v2& pix) {
+__device__ inline int ct_point_to_pixel(const vwgpu_camera& c, const ct_mat& M, bool flip, const tr_v3& point, tr_v2& pix) {
   if (TO == CT_TO_CAHV) {
     // CAHVModel::point_to_pixel (CAHVModel.cc:167-171)
     const tr_v3 d = tr_sub(point, tr_load3(c.center));
     const double dDot = tr_dot(d, tr_load3(c.A));
     pix = tr_v2{tr_dot(d, tr_load3(c.H)) / dDot, tr_dot(d, tr_load3(c.V)) / dDot};
-    return true;
+    return TR_OK;
   }
   // point_to_pixel_no_check (PinholeModel.cc:351-368)
   const double* m = M.m;
   const double den = m[8] * point.x + m[9] * point.y + m[10] * point.z + m[11];
   tr_v2 pixel{(m[0] * point.x + m[1] * point.y + m[2] * point.z + m[3]) / den,
               (m[4] * point.x + m[5] * point.y + m[6] * point.z + m[7]) / den};
-  if (TO != CT_TO_PINHOLE_NULL_CHECK && c.distortion_kind == VWGPU_DISTORTION_TSAI) pixel = ct_tsai_distort(c, pixel);
+  if (ct_to_lens<TO>()) {
+    tr_v2 distorted;
+    if (!ct_lens_distort(c, pixel, distorted)) return TR_LENS_NOT_CONVERGED;
+    pixel = distorted;
+  } else if (TO != CT_TO_PINHOLE_NULL_CHECK && c.distortion_kind == VWGPU_DISTORTION_TSAI) {
+    pixel = ct_tsai_distort(c, pixel);
+  }
   pix = tr_v2{pixel.x / c.pixel_pitch, pixel.y / c.pixel_pitch};
-  if (TO == CT_TO_PINHOLE_NOCHECK) return true;
+  if (TO == CT_TO_PINHOLE_NOCHECK || TO == CT_TO_PINHOLE_LENS_NOCHECK) return TR_OK;
   // the round trip (:378-394)
   const double ERROR_THRESHOLD = 0.01;
-  const tr_v3 pixel_vector = TO == CT_TO_PINHOLE_NULL_CHECK ? tr_ray<TR_CAM_PINHOLE_NULL>(c, pix, false) : tr_ray<TR_CAM_PINHOLE>(c, pix, false);
+  const tr_v3 pixel_vector = TO == CT_TO_PINHOLE_NULL_CHECK   ? tr_ray<TR_CAM_PINHOLE_NULL>(c, pix, false)
+                             : TO == CT_TO_PINHOLE_LENS_CHECK ? tr_ray<TR_CAM_PINHOLE_LENS>(c, pix, false)
+                                                              : tr_ray<TR_CAM_PINHOLE>(c, pix, false);
   const tr_v3 phys_vector = tr_normalize(tr_sub(point, tr_load3(c.center)));
   double diff = tr_norm(tr_sub(pixel_vector, phys_vector));
   if (diff >= ERROR_THRESHOLD)
     diff = tr_norm(tr_v3{pixel_vector.x + phys_vector.x, pixel_vector.y + phys_vector.y, pixel_vector.z + phys_vector.z});
-  return !(diff >= ERROR_THRESHOLD || diff != diff);
+  return !(diff >= ERROR_THRESHOLD || diff != diff) ? TR_OK : TR_NOT_CONVERGED;
 }
 
 // CameraTransform::reverse / forward (CameraTransform.h:52-74): a pixel of `from` to the pixel of `to` that sees the same
@@ -93,19 +217,20 @@ __device__ inline int ct_transform(const vwgpu_camera& from, bool flip_from, con
     q = tr_cahvor_project(to, point);
     return TR_OK;
   }
-  return ct_point_to_pixel<TO>(to, Mto, false, point, q) ? TR_OK : TR_NOT_CONVERGED;
+  return ct_point_to_pixel<TO>(to, Mto, false, point, q);
 }
-// whether a kernel counts failures: the pinhole's check, or a CAHVORE on either side
+// whether a kernel counts failures: the pinhole's check, a projection through any lens, or a CAHVORE on either side
 template <int FROM, int TO>
 __device__ constexpr bool ct_kernel_counts() {
-  return TO == CT_TO_PINHOLE_NULL_CHECK || TO == CT_TO_PINHOLE_CHECK || TO == CT_TO_CAHVORE || FROM == TR_CAM_CAHVORE;
+  return TO == CT_TO_PINHOLE_NULL_CHECK || TO == CT_TO_PINHOLE_CHECK || TO == CT_TO_CAHVORE || FROM == TR_CAM_CAHVORE || ct_to_lens<TO>();
 }
-// the failures of a workgroup into bank 0 of the counters, those by theta out of bounds into bank 1 as well
+// the failures of a workgroup into bank 0 of the counters, those by theta out of bounds (CAHVORE) or by the lens solver
+// (a pinhole with any lens) into bank 1 as well
 template <int TO>
 __device__ inline void ct_count(unsigned long long* counters, unsigned slot, bool failed, bool theta) {
   const int n = __syncthreads_count(failed);
   if (n != 0 && threadIdx.x == 0 && threadIdx.y == 0) atomicAdd(counters + slot, (unsigned long long)n);
-  if (TO == CT_TO_CAHVORE) {
+  if (TO == CT_TO_CAHVORE || ct_to_lens<TO>()) {
     const int nt = __syncthreads_count(theta);
     if (nt != 0 && threadIdx.x == 0 && threadIdx.y == 0) atomicAdd(counters + CT_COUNTERS + slot, (unsigned long long)nt);
   }
@@ -185,7 +310,7 @@ __global__ __launch_bounds__(CT_THREADS) void ct_image_kernel(ct_args a, vwgpu_c
       }
     } else {
       failed = true;   // PointToPixelErr, PixelToRayErr: the edge pixel, counted
-      theta = status == TR_THETA_OUT_OF_BOUNDS;
+      theta = status == TR_THETA_OUT_OF_BOUNDS || status == TR_LENS_NOT_CONVERGED;
     }
     a.out[(long long)y * a.ostride + x] = res;
     if (MASKED && a.omask) a.omask[(long long)y * a.omstride + x] = valid ? 255 : 0;
@@ -211,7 +336,7 @@ __global__ __launch_bounds__(CT_THREADS) void ct_points_kernel(ct_points_args a,
     const int status = ct_transform<FROM, TO>(from, a.flip_from != 0, to, Mto, p, q);
     if (status != TR_OK) {
       failed = true;   // PointToPixelErr, PixelToRayErr: a NaN pair, counted
-      theta = status == TR_THETA_OUT_OF_BOUNDS;
+      theta = status == TR_THETA_OUT_OF_BOUNDS || status == TR_LENS_NOT_CONVERGED;
       q = tr_v2{__longlong_as_double(0x7ff8000000000000LL), __longlong_as_double(0x7ff8000000000000LL)};
     }
     a.out[2 * i] = q.x;
@@ -251,7 +376,7 @@ int ct_camera_check(vwgpu_ctx* ctx, const char* name, const char* which, const v
   if (!c) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: null %s camera", name, which);
   if (c->kind != VWGPU_CAMERA_PINHOLE && c->kind != VWGPU_CAMERA_CAHV && !tr_new_kind(*c))
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: unknown camera kind %d", name, c->kind);
-  if (c->kind == VWGPU_CAMERA_PINHOLE && c->distortion_kind != VWGPU_DISTORTION_NULL && c->distortion_kind != VWGPU_DISTORTION_TSAI)
+  if (c->kind == VWGPU_CAMERA_PINHOLE && !tr_lens_valid(*c))
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: unknown lens distortion kind %d", name, c->distortion_kind);
   if (c->kind == VWGPU_CAMERA_PINHOLE && !matrix)
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: the %s camera is a pinhole and has no camera matrix", name, which);
@@ -272,19 +397,23 @@ int ct_same_center(vwgpu_ctx* ctx, const vwgpu_camera* src, const vwgpu_camera* 
                     "CameraTransformFunctor: Camera transformation require that the camera center is always the same for both cameras.");
 }
 
-// the code a kernel carries for the camera whose rays it forms / for the camera it projects into
-int ct_from_code(const vwgpu_camera& c) {
+// the code a kernel carries for the camera whose rays it forms / for the camera it projects into.  `lens`: one camera of
+// the pair is a pinhole with a lens other than null and Tsai, and every pinhole of the pair takes the any-lens code.
+int ct_from_code(const vwgpu_camera& c, bool lens) {
   if (tr_new_kind(c)) return c.kind == VWGPU_CAMERA_CAHVOR ? TR_CAM_CAHVOR : TR_CAM_CAHVORE;
+  if (lens && c.kind == VWGPU_CAMERA_PINHOLE) return TR_CAM_PINHOLE_LENS;
   return c.kind == VWGPU_CAMERA_CAHV ? TR_CAM_CAHV : c.distortion_kind == VWGPU_DISTORTION_NULL ? TR_CAM_PINHOLE_NULL : TR_CAM_PINHOLE;
 }
-int ct_to_code(const vwgpu_camera& c, int check) {
+int ct_to_code(const vwgpu_camera& c, int check, bool lens) {
   if (tr_new_kind(c)) return c.kind == VWGPU_CAMERA_CAHVOR ? CT_TO_CAHVOR : CT_TO_CAHVORE;
   if (c.kind == VWGPU_CAMERA_CAHV) return CT_TO_CAHV;
+  if (lens) return check ? CT_TO_PINHOLE_LENS_CHECK : CT_TO_PINHOLE_LENS_NOCHECK;
   if (!check) return CT_TO_PINHOLE_NOCHECK;
   return c.distortion_kind == VWGPU_DISTORTION_NULL ? CT_TO_PINHOLE_NULL_CHECK : CT_TO_PINHOLE_CHECK;
 }
+bool ct_lens_to(int to) { return to == CT_TO_PINHOLE_LENS_NOCHECK || to == CT_TO_PINHOLE_LENS_CHECK; }
 bool ct_counts(int from, int to) {
-  return to == CT_TO_PINHOLE_NULL_CHECK || to == CT_TO_PINHOLE_CHECK || to == CT_TO_CAHVORE || from == TR_CAM_CAHVORE;
+  return to == CT_TO_PINHOLE_NULL_CHECK || to == CT_TO_PINHOLE_CHECK || to == CT_TO_CAHVORE || from == TR_CAM_CAHVORE || ct_lens_to(to);
 }
 
 ct_mat ct_matrix(const double* m) {
@@ -319,6 +448,21 @@ ct_mat ct_matrix(const double* m) {
     else if (TO == CT_TO_CAHVOR) hipLaunchKernelGGL((KERNEL<TR_CAM_CAHV, CT_TO_CAHVOR, FLAG>), (GRID), ct_block, 0, ctx->stream, __VA_ARGS__); \
     else hipLaunchKernelGGL((KERNEL<TR_CAM_CAHV, CT_TO_CAHVORE, FLAG>), (GRID), ct_block, 0, ctx->stream, __VA_ARGS__);                      \
   } while (0)
+// the five pairs in which a pinhole carries the any-lens code: the other camera is such a pinhole or CAHV
+#define CT_LAUNCH_LENS(KERNEL, FROM, TO, FLAG, GRID, ...)                                                                                   \
+  do {                                                                                                                                      \
+    if (FROM == TR_CAM_CAHV) {                                                                                                              \
+      if (TO == CT_TO_PINHOLE_LENS_CHECK) hipLaunchKernelGGL((KERNEL<TR_CAM_CAHV, CT_TO_PINHOLE_LENS_CHECK, FLAG>), (GRID), ct_block, 0, ctx->stream, __VA_ARGS__); \
+      else hipLaunchKernelGGL((KERNEL<TR_CAM_CAHV, CT_TO_PINHOLE_LENS_NOCHECK, FLAG>), (GRID), ct_block, 0, ctx->stream, __VA_ARGS__);       \
+    } else if (TO == CT_TO_PINHOLE_LENS_CHECK) {                                                                                            \
+      hipLaunchKernelGGL((KERNEL<TR_CAM_PINHOLE_LENS, CT_TO_PINHOLE_LENS_CHECK, FLAG>), (GRID), ct_block, 0, ctx->stream, __VA_ARGS__);      \
+    } else if (TO == CT_TO_PINHOLE_LENS_NOCHECK) {                                                                                          \
+      hipLaunchKernelGGL((KERNEL<TR_CAM_PINHOLE_LENS, CT_TO_PINHOLE_LENS_NOCHECK, FLAG>), (GRID), ct_block, 0, ctx->stream, __VA_ARGS__);    \
+    } else {                                                                                                                                \
+      hipLaunchKernelGGL((KERNEL<TR_CAM_PINHOLE_LENS, CT_TO_CAHV, FLAG>), (GRID), ct_block, 0, ctx->stream, __VA_ARGS__);                    \
+    }                                                                                                                                       \
+  } while (0)
+bool ct_lens_pair(int from, int to) { return from == TR_CAM_PINHOLE_LENS || ct_lens_to(to); }
 bool ct_new_pair(int from, int to) { return from == TR_CAM_CAHVOR || from == TR_CAM_CAHVORE || to == CT_TO_CAHVOR || to == CT_TO_CAHVORE; }
 
 // the counters of a call, zeroed; nullptr in *d_counter when the kernel does not count
@@ -334,11 +478,12 @@ int ct_counters(vwgpu_ctx* ctx, bool counts, unsigned long long** d_counter) {
 }
 
 // what a host-pointer call learns: the failures, and how many of them were CAHVORE's theta out of bounds
-struct ct_failures { long long failed, theta; bool cahvore; };
+// (for a pinhole with any lens: how many were the lens solver's)
+struct ct_failures { long long failed, theta; bool cahvore, lens; };
 
 // after the kernel: fold the counters; d_failed (device, optional) receives the count, *h_failed (host, optional) too (synchronises)
 int ct_count_out(vwgpu_ctx* ctx, int from, int to, unsigned long long* d_counter, long long* d_failed, ct_failures* h_failed) {
-  const bool counts = ct_counts(from, to), theta = to == CT_TO_CAHVORE;
+  const bool counts = ct_counts(from, to), theta = to == CT_TO_CAHVORE || ct_lens_to(to);
   if (counts) hipLaunchKernelGGL(ct_count_fold_kernel, dim3(theta ? 2 : 1), dim3(CT_THREADS), 0, ctx->stream, d_counter);
   VWGPU_HIP(ctx, hipGetLastError());
   if (d_failed) VWGPU_HIP(ctx, hipMemcpyAsync(d_failed, d_counter, 8, hipMemcpyDeviceToDevice, ctx->stream));
@@ -347,7 +492,7 @@ int ct_count_out(vwgpu_ctx* ctx, int from, int to, unsigned long long* d_counter
     VWGPU_HIP(ctx, hipMemcpyAsync(&cnt, d_counter, 8, hipMemcpyDeviceToHost, ctx->stream));
     if (theta) VWGPU_HIP(ctx, hipMemcpyAsync(&cnt_theta, d_counter + CT_COUNTERS, 8, hipMemcpyDeviceToHost, ctx->stream));
     VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *h_failed = ct_failures{(long long)cnt, (long long)cnt_theta, to == CT_TO_CAHVORE || from == TR_CAM_CAHVORE};
+    *h_failed = ct_failures{(long long)cnt, (long long)cnt_theta, to == CT_TO_CAHVORE || from == TR_CAM_CAHVORE, ct_lens_to(to)};
   }
   return VWGPU_OK;
 }
@@ -355,6 +500,7 @@ int ct_count_out(vwgpu_ctx* ctx, int from, int to, unsigned long long* d_counter
 // the reference's message for what it would have thrown.  It throws at the first failing pixel in raster order; here the
 // message names non-convergence when any pixel did not converge, and theta otherwise.
 int ct_inaccurate(vwgpu_ctx* ctx, const ct_failures& f) {
+  if (f.lens && f.theta != 0) return vwgpu_fail(ctx, VWGPU_ERR_LOGIC, "LensDistortion: Did not converge. (%lld pixels)", f.failed);
   if (!f.cahvore) return vwgpu_fail(ctx, VWGPU_ERR_LOGIC, "PinholeModel: Projection into pinhole camera is inaccurate. (%lld pixels)", f.failed);
   if (f.theta == f.failed) return vwgpu_fail(ctx, VWGPU_ERR_LOGIC, "CAHVOREModel: Theta out of bounds. (%lld pixels)", f.failed);
   return vwgpu_fail(ctx, VWGPU_ERR_LOGIC, "CAHVOREModel: Did not converge. (%lld pixels)", f.failed);
@@ -396,7 +542,8 @@ int ct_image_check(vwgpu_ctx* ctx, ct_image_call& c) {
 
 // all pointers of `c` are device pointers here
 int ct_image_run(vwgpu_ctx* ctx, const ct_image_call& c, long long* d_failed, ct_failures* h_failed) {
-  const int from = ct_from_code(*c.dst_cam), to = ct_to_code(*c.src_cam, c.check);
+  const bool lens = tr_lens_pinhole(*c.dst_cam) || tr_lens_pinhole(*c.src_cam);
+  const int from = ct_from_code(*c.dst_cam, lens), to = ct_to_code(*c.src_cam, c.check, lens);
   unsigned long long* d_counter = nullptr;
   const bool want = d_failed || h_failed;
   if (ct_counts(from, to) || want) {
@@ -409,7 +556,10 @@ int ct_image_run(vwgpu_ctx* ctx, const ct_image_call& c, long long* d_failed, ct
   const bool masked = c.smask || c.omask;
   {
     vwgpu_prof_scope ps(ctx, "camera_transform");
-    if (ct_new_pair(from, to)) {
+    if (ct_lens_pair(from, to)) {
+      if (masked) CT_LAUNCH_LENS(ct_image_kernel, from, to, true, ct_grid(c.w, c.h), a, *c.dst_cam, *c.src_cam, M);
+      else CT_LAUNCH_LENS(ct_image_kernel, from, to, false, ct_grid(c.w, c.h), a, *c.dst_cam, *c.src_cam, M);
+    } else if (ct_new_pair(from, to)) {
       if (masked) CT_LAUNCH_NEW(ct_image_kernel, from, to, true, ct_grid(c.w, c.h), a, *c.dst_cam, *c.src_cam, M);
       else CT_LAUNCH_NEW(ct_image_kernel, from, to, false, ct_grid(c.w, c.h), a, *c.dst_cam, *c.src_cam, M);
     } else if (masked) {
@@ -443,7 +593,8 @@ int ct_points_run(vwgpu_ctx* ctx, const vwgpu_camera* src, const double* src_mat
   const bool fwd = direction == VWGPU_CAMERA_TRANSFORM_FORWARD;
   const vwgpu_camera& cfrom = fwd ? *src : *dst;
   const vwgpu_camera& cto = fwd ? *dst : *src;
-  const int from = ct_from_code(cfrom), to = ct_to_code(cto, check);
+  const bool lens = tr_lens_pinhole(cfrom) || tr_lens_pinhole(cto);
+  const int from = ct_from_code(cfrom, lens), to = ct_to_code(cto, check, lens);
   unsigned long long* d_counter = nullptr;
   const bool want = d_failed || h_failed;
   if (ct_counts(from, to) || want) {
@@ -455,7 +606,8 @@ int ct_points_run(vwgpu_ctx* ctx, const vwgpu_camera* src, const double* src_mat
   const dim3 grid((unsigned)((n + CT_THREADS - 1) / CT_THREADS));
   {
     vwgpu_prof_scope ps(ctx, "camera_transform_points");
-    if (ct_new_pair(from, to)) CT_LAUNCH_NEW(ct_points_kernel, from, to, false, grid, a, cfrom, cto, M);
+    if (ct_lens_pair(from, to)) CT_LAUNCH_LENS(ct_points_kernel, from, to, false, grid, a, cfrom, cto, M);
+    else if (ct_new_pair(from, to)) CT_LAUNCH_NEW(ct_points_kernel, from, to, false, grid, a, cfrom, cto, M);
     else CT_LAUNCH_FROM(ct_points_kernel, from, to, false, grid, a, cfrom, cto, M);
     VWGPU_HIP(ctx, hipGetLastError());
   }
@@ -593,6 +745,66 @@ int vwgpu_pinhole_camera_matrix(const double* center, const double* rotation, do
       out[i * 4 + j] = s;
     }
   return VWGPU_OK;
+}
+
+int vwgpu_camera_set_lens(vwgpu_camera* cam, int distortion_kind, const double* params, int n) {
+  if (!cam || cam->kind != VWGPU_CAMERA_PINHOLE || !tr_lens_known(distortion_kind) || n < 0 || (n > 0 && !params)) return VWGPU_ERR_ARGUMENT;
+  bool n_ok = false;
+  switch (distortion_kind) {
+    case VWGPU_DISTORTION_NULL: n_ok = n == 0; break;
+    case VWGPU_DISTORTION_TSAI: n_ok = n == 4 || n == 5; break;
+    case VWGPU_DISTORTION_FOV: n_ok = n == 1; break;
+    case VWGPU_DISTORTION_FISHEYE: n_ok = n == 4; break;
+    case VWGPU_DISTORTION_BROWN_CONRADY: n_ok = n == 8; break;
+    case VWGPU_DISTORTION_ADJUSTABLE_TSAI: n_ok = n >= 4 && n <= 13; break;
+    default: n_ok = n == 9; break;   // Photometrix
+  }
+  if (!n_ok) return VWGPU_ERR_ARGUMENT;
+  double L[14] = {0};
+  for (int k = 0; k < n; ++k) {
+    if (!std::isfinite(params[k])) return VWGPU_ERR_ARGUMENT;
+    L[k] = params[k];
+  }
+  if (distortion_kind == VWGPU_DISTORTION_FOV) {
+    // FovLensDistortion::set_distortion_parameters (LensDistortion.cc:441-455)
+    if (L[0] <= 0) return VWGPU_ERR_ARGUMENT;
+    L[1] = 1 / L[0];
+    L[2] = 2 * tan(L[0] / 2);
+  } else if (distortion_kind == VWGPU_DISTORTION_BROWN_CONRADY) {
+    L[8] = sin(L[7]);
+    L[9] = cos(L[7]);
+  } else if (distortion_kind == VWGPU_DISTORTION_ADJUSTABLE_TSAI) {
+    L[13] = (double)n;
+  }
+  cam->distortion_kind = distortion_kind;
+  std::memcpy(cam->distortion, L, 5 * sizeof(double));
+  std::memcpy(cam->A, L + 5, 3 * sizeof(double));
+  std::memcpy(cam->H, L + 8, 3 * sizeof(double));
+  std::memcpy(cam->V, L + 11, 3 * sizeof(double));
+  return VWGPU_OK;
+}
+
+int vwgpu_lens_coordinates(const vwgpu_camera* cam, int direction, const double* points, long long n, double* out, long long* failed) {
+  if (failed) *failed = 0;
+  if (!cam || cam->kind != VWGPU_CAMERA_PINHOLE || !tr_lens_valid(*cam) || (direction != 0 && direction != 1) || n < 0 ||
+      (n > 0 && (!points || !out)))
+    return VWGPU_ERR_ARGUMENT;
+  const vwgpu_camera c = *cam;
+  long long count = 0;
+  for (long long i = 0; i < n; ++i) {
+    const tr_v2 p{points[2 * i], points[2 * i + 1]};
+    tr_v2 q;
+    if (direction == 1) {
+      q = tr_lens_undistort(c, p);
+    } else if (!ct_lens_distort(c, p, q)) {
+      q = tr_v2{std::nan(""), std::nan("")};
+      ++count;
+    }
+    out[2 * i] = q.x;
+    out[2 * i + 1] = q.y;
+  }
+  if (failed) *failed = count;
+  return count != 0 ? VWGPU_ERR_LOGIC : VWGPU_OK;
 }
 
 int vwgpu_epipolar_pinhole(const double* center0, const double* rotation0, const double* focal0, const double* offset0, double pitch0,

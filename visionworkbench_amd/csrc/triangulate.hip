@@ -12,7 +12,9 @@
 // through scalar loads.  A lane reads the 12 bytes of its pixel and writes 24 contiguous bytes of xyz, so a wavefront's
 // stores cover 1536 contiguous bytes.  The null-distortion pinhole pair, the other pinhole pairs and the three pairs
 // with a CAHV camera are separate instantiations: the common case carries no Newton loop.  Two CAHVOR and two CAHVORE
-// cameras (camera_rays.h) are one instantiation each; a CAHVORE ray that does not converge gives the zero point.
+// cameras (camera_rays.h) are one instantiation each; a CAHVORE ray that does not converge gives the zero point.  Pairs
+// in which a pinhole carries one of the five other lenses (camera_rays.h) are three more: every pinhole of such a pair
+// takes the any-lens code.
 //
 // Everything is double in the reference's expression order; the Makefile's -ffp-contract=off keeps products and sums
 // apart, and fp64 division and square root are correctly rounded on the device.  Sums written `0.0 + ...` are the
@@ -334,17 +336,19 @@ int tr_camera_check(vwgpu_ctx* ctx, const char* name, const vwgpu_camera* c) {
   if (!c) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: null camera", name);
   if (c->kind != VWGPU_CAMERA_PINHOLE && c->kind != VWGPU_CAMERA_CAHV && !tr_new_kind(*c))
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: unknown camera kind %d", name, c->kind);
-  if (c->kind == VWGPU_CAMERA_PINHOLE && c->distortion_kind != VWGPU_DISTORTION_NULL && c->distortion_kind != VWGPU_DISTORTION_TSAI)
+  if (c->kind == VWGPU_CAMERA_PINHOLE && !tr_lens_valid(*c))
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: unknown lens distortion kind %d", name, c->distortion_kind);
   return VWGPU_OK;
 }
 
 // the instantiation for a camera pair, as 3 * (code of cam1) + (code of cam2): (0, 0) for two pinholes without lens
 // distortion, (1, 1) for other pinhole pairs, the three pairs with a CAHV camera, (3, 3) for two CAHVOR and (4, 4) for
-// two CAHVORE cameras (tr_check refuses every other pair with one of those)
+// two CAHVORE cameras (tr_check refuses every other pair with one of those).  Where a pinhole carries a lens other than
+// null and Tsai every pinhole of the pair takes the any-lens code: (5, 5), (5, 2) and (2, 5).
 int tr_cams_of(const vwgpu_camera& c1, const vwgpu_camera& c2) {
   if (tr_new_kind(c1)) return c1.kind == VWGPU_CAMERA_CAHVOR ? 3 * TR_CAM_CAHVOR + TR_CAM_CAHVOR : 3 * TR_CAM_CAHVORE + TR_CAM_CAHVORE;
   const bool cahv1 = c1.kind == VWGPU_CAMERA_CAHV, cahv2 = c2.kind == VWGPU_CAMERA_CAHV;
+  if (tr_lens_pinhole(c1) || tr_lens_pinhole(c2)) return 3 * (cahv1 ? TR_CAM_CAHV : TR_CAM_PINHOLE_LENS) + (cahv2 ? TR_CAM_CAHV : TR_CAM_PINHOLE_LENS);
   if (!cahv1 && !cahv2 && c1.distortion_kind == VWGPU_DISTORTION_NULL && c2.distortion_kind == VWGPU_DISTORTION_NULL) return 0;
   return 3 * (cahv1 ? TR_CAM_CAHV : TR_CAM_PINHOLE) + (cahv2 ? TR_CAM_CAHV : TR_CAM_PINHOLE);
 }
@@ -422,6 +426,9 @@ tr_args tr_make_args(int type, const void* d_disp, int w, int h, ptrdiff_t dstri
       case 7: TR_LAUNCH_ONE(KERNEL, TR_CAM_CAHV, TR_CAM_PINHOLE, GRID, __VA_ARGS__); break;                        \
       case 12: TR_LAUNCH_ONE(KERNEL, TR_CAM_CAHVOR, TR_CAM_CAHVOR, GRID, __VA_ARGS__); break;                      \
       case 16: TR_LAUNCH_ONE(KERNEL, TR_CAM_CAHVORE, TR_CAM_CAHVORE, GRID, __VA_ARGS__); break;                    \
+      case 20: TR_LAUNCH_ONE(KERNEL, TR_CAM_PINHOLE_LENS, TR_CAM_PINHOLE_LENS, GRID, __VA_ARGS__); break;          \
+      case 17: TR_LAUNCH_ONE(KERNEL, TR_CAM_PINHOLE_LENS, TR_CAM_CAHV, GRID, __VA_ARGS__); break;                  \
+      case 11: TR_LAUNCH_ONE(KERNEL, TR_CAM_CAHV, TR_CAM_PINHOLE_LENS, GRID, __VA_ARGS__); break;                  \
       default: TR_LAUNCH_ONE(KERNEL, TR_CAM_CAHV, TR_CAM_CAHV, GRID, __VA_ARGS__); break;                          \
     }                                                                                                              \
     VWGPU_HIP(ctx, hipGetLastError());                                                                             \

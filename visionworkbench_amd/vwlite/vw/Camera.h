@@ -1,5 +1,6 @@
-// vw/Camera.h — the part of vw::camera that triangulation and epipolar rectification need: PinholeModel with the null or
-// the Tsai lens distortion (src/vw/Camera/PinholeModel.{h,cc}, LensDistortion.{h,cc}), CAHVModel
+// vw/Camera.h — the part of vw::camera that triangulation and epipolar rectification need: PinholeModel with the null, Tsai,
+// FOV, fisheye, Brown-Conrady, adjustable Tsai or Photometrix lens distortion (src/vw/Camera/PinholeModel.{h,cc},
+// LensDistortion.{h,cc}; the lens arithmetic is the engine's, vwgpu_lens_coordinates), CAHVModel
 // (src/vw/Camera/CAHVModel.{h,cc}) and epipolar() for both, CAHVORModel and CAHVOREModel (src/vw/Camera/CAHVORModel.{h,cc},
 // CAHVOREModel.{h,cc}) and linearize_camera() for those.  Each model carries the flat camera descriptor of the C ABI
 // (struct vwgpu_camera, include/vwgpu.h) and, for a pinhole, the 3 x 4 camera matrix beside it, which is what the engine's
@@ -12,6 +13,7 @@
 #include <limits>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "Core.h"
 #include "Math.h"
@@ -50,14 +52,45 @@ protected:
   vwgpu_camera m_desc;
 };
 
-/// TsaiLensDistortion (LensDistortion.cc:225-400): parameters k1, k2, p1, p2, k3.
-class TsaiLensDistortion {
-  double m_p[5];
+/// What the lens solvers throw (src/vw/Camera/CameraModel.h).
+VWLITE_EXCEPTION(PixelToRayErr, Exception);
+VWLITE_EXCEPTION(PointToPixelErr, Exception);
+
+class PinholeModel;
+
+/// LensDistortion (LensDistortion.h): the name and the parameters of a lens (the reference's Vector<double> of any length is
+/// a std::vector<double> here).  The two coordinate functions take a point in
+/// focal-plane units (pixel * pixel_pitch) and run the functions of the engine's kernels on the host
+/// (vwgpu_lens_coordinates) on the descriptor of `cam`, which must carry this lens.
+class LensDistortion {
+protected:
+  std::vector<double> m_distortion;
+  LensDistortion(const double* p, size_t n) : m_distortion(p, p + n) {}
+  explicit LensDistortion(std::vector<double> const& v) : m_distortion(v) {}
 public:
-  TsaiLensDistortion(double k1, double k2, double p1, double p2, double k3 = 0) { m_p[0] = k1; m_p[1] = k2; m_p[2] = p1; m_p[3] = p2; m_p[4] = k3; }
-  const double* distortion_parameters() const { return m_p; }
+  virtual ~LensDistortion() {}
+  virtual std::string name() const = 0;
+  virtual int kind() const = 0;   ///< vwgpu_distortion_kind
+  virtual LensDistortion* copy() const = 0;
+  std::vector<double> distortion_parameters() const { return m_distortion; }
+  const double* parameter_data() const { return m_distortion.data(); }
+  int parameter_count() const { return (int)m_distortion.size(); }
+  inline Vector2 distorted_coordinates(PinholeModel const& cam, Vector2 const& p) const;
+  inline Vector2 undistorted_coordinates(PinholeModel const& cam, Vector2 const& p) const;
+};
+
+/// TsaiLensDistortion (LensDistortion.cc:225-400): parameters k1, k2, p1, p2, k3.
+class TsaiLensDistortion : public LensDistortion {
+  static std::vector<double> five(double k1, double k2, double p1, double p2, double k3) { return std::vector<double>{k1, k2, p1, p2, k3}; }
+public:
+  TsaiLensDistortion(double k1, double k2, double p1, double p2, double k3 = 0) : LensDistortion(five(k1, k2, p1, p2, k3).data(), 5) {}
+  std::string name() const { return "TSAI"; }
+  int kind() const { return VWGPU_DISTORTION_TSAI; }
+  LensDistortion* copy() const { return new TsaiLensDistortion(*this); }
+  const double* distortion_parameters() const { return m_distortion.data(); }
   /// TsaiDistortionNorm (:260-276)
   Vector2 distort_norm(Vector2 const& P) const {
+    const double* m_p = m_distortion.data();
     const double x = P[0], y = P[1], k1 = m_p[0], k2 = m_p[1], p1 = m_p[2], p2 = m_p[3], k3 = m_p[4];
     const double r2 = x * x + y * y;
     const double rdist = 1.0 + k1 * r2 + k2 * r2 * r2 + k3 * r2 * r2 * r2;
@@ -65,22 +98,87 @@ public:
   }
 };
 
+/// FovLensDistortion (LensDistortion.cc:418-530): k1 > 0, or IOErr.
+class FovLensDistortion : public LensDistortion {
+public:
+  explicit FovLensDistortion(std::vector<double> const& params) : LensDistortion(params) {
+    VW_ASSERT(params.size() == 1, IOErr() << "FovLensDistortion: Incorrect number of parameters was passed in.");
+    VW_ASSERT(params[0] > 0, IOErr() << "FovLensDistortion: The distortion coefficient must be positive.\n");
+  }
+  std::string name() const { return "FOV"; }
+  int kind() const { return VWGPU_DISTORTION_FOV; }
+  LensDistortion* copy() const { return new FovLensDistortion(*this); }
+};
+
+/// FisheyeLensDistortion (LensDistortion.cc:532-673): k1, k2, k3, k4.
+class FisheyeLensDistortion : public LensDistortion {
+public:
+  explicit FisheyeLensDistortion(std::vector<double> const& params) : LensDistortion(params) {
+    VW_ASSERT(params.size() == 4, IOErr() << "FisheyeLensDistortion: Incorrect number of parameters was passed in.");
+  }
+  std::string name() const { return "FISHEYE"; }
+  int kind() const { return VWGPU_DISTORTION_FISHEYE; }
+  LensDistortion* copy() const { return new FisheyeLensDistortion(*this); }
+};
+
+/// BrownConradyDistortion (LensDistortion.cc:675-775): xp, yp, k1, k2, k3, p1, p2, phi, or the four groups.
+class BrownConradyDistortion : public LensDistortion {
+  static std::vector<double> join(Vector2 const& principal, Vector3 const& radial, Vector2 const& centering, double angle) {
+    return std::vector<double>{principal[0], principal[1], radial[0], radial[1], radial[2], centering[0], centering[1], angle};
+  }
+public:
+  explicit BrownConradyDistortion(std::vector<double> const& params) : LensDistortion(params) {
+    VW_ASSERT(params.size() == 8, ArgumentErr() << "BrownConradyDistortion: requires constructor input of size 8.");
+  }
+  BrownConradyDistortion(Vector2 const& principal, Vector3 const& radial, Vector2 const& centering, double const& angle)
+      : LensDistortion(join(principal, radial, centering, angle)) {}
+  std::string name() const { return "BrownConrady"; }
+  int kind() const { return VWGPU_DISTORTION_BROWN_CONRADY; }
+  LensDistortion* copy() const { return new BrownConradyDistortion(*this); }
+};
+
+/// AdjustableTsaiLensDistortion (LensDistortion.cc:777-917): n - 3 radial coefficients, two tangential ones and alpha; the
+/// camera descriptor holds up to 13.
+class AdjustableTsaiLensDistortion : public LensDistortion {
+public:
+  explicit AdjustableTsaiLensDistortion(std::vector<double> params) : LensDistortion(params) {
+    VW_ASSERT(params.size() > 3, ArgumentErr() << "Requires at least 4 coefficients for distortion. Last 3 are always the distortion coefficients and alpha. All leading elements are even radial distortion coefficients.");
+    VW_ASSERT(params.size() <= 13, NoImplErr() << "AdjustableTsaiLensDistortion: more than 13 coefficients do not fit the camera descriptor.");
+  }
+  std::string name() const { return "AdjustableTSAI"; }
+  int kind() const { return VWGPU_DISTORTION_ADJUSTABLE_TSAI; }
+  LensDistortion* copy() const { return new AdjustableTsaiLensDistortion(*this); }
+};
+
+/// PhotometrixLensDistortion (LensDistortion.cc:919-1013): xp, yp, k1, k2, k3, p1, p2, b1, b2.
+class PhotometrixLensDistortion : public LensDistortion {
+public:
+  explicit PhotometrixLensDistortion(std::vector<double> const& params) : LensDistortion(params) {
+    VW_ASSERT(params.size() == 9, IOErr() << "PhotometrixLensDistortion: Incorrect number of parameters was passed in.");
+  }
+  std::string name() const { return "Photometrix"; }
+  int kind() const { return VWGPU_DISTORTION_PHOTOMETRIX; }
+  LensDistortion* copy() const { return new PhotometrixLensDistortion(*this); }
+};
+
 /// PinholeModel(center, rotation, fu, fv, cu, cv[, u, v, w][, distortion][, pixel_pitch]) (PinholeModel.h).
 class PinholeModel : public CameraModel {
   Vector3 m_center;
   Matrix3x3 m_rotation;
   Vector3 m_u, m_v, m_w;
-  std::shared_ptr<TsaiLensDistortion> m_distortion;   // null: NullLensDistortion
+  std::shared_ptr<LensDistortion> m_distortion;   // null: NullLensDistortion
   double m_matrix[12];
   bool m_check = true;
   void rebuild() {
     const double c[3] = {m_center[0], m_center[1], m_center[2]}, u[3] = {m_u[0], m_u[1], m_u[2]}, v[3] = {m_v[0], m_v[1], m_v[2]},
                  w[3] = {m_w[0], m_w[1], m_w[2]};
     const double fu = m_desc.fu, fv = m_desc.fv, cu = m_desc.cu, cv = m_desc.cv, pitch = m_desc.pixel_pitch;
-    const int rc = vwgpu_pinhole_camera(c, m_rotation.data(), fu, fv, cu, cv, u, v, w, pitch,
-                                        m_distortion ? VWGPU_DISTORTION_TSAI : VWGPU_DISTORTION_NULL,
-                                        m_distortion ? m_distortion->distortion_parameters() : NULL, &m_desc);
+    const int rc = vwgpu_pinhole_camera(c, m_rotation.data(), fu, fv, cu, cv, u, v, w, pitch, VWGPU_DISTORTION_NULL, NULL, &m_desc);
     VW_ASSERT(rc == VWGPU_OK, ArgumentErr() << "PinholeModel: the coordinate frame u, v, w must be orthonormal.");
+    if (m_distortion) {
+      const int lens_rc = vwgpu_camera_set_lens(&m_desc, m_distortion->kind(), m_distortion->parameter_data(), m_distortion->parameter_count());
+      VW_ASSERT(lens_rc == VWGPU_OK, ArgumentErr() << "PinholeModel: the parameters of the " << m_distortion->name() << " lens are refused.");
+    }
     vwgpu_pinhole_camera_matrix(c, m_rotation.data(), fu, fv, cu, cv, u, v, w, pitch, VWGPU_DISTORTION_NULL, NULL, m_matrix);
   }
   static Matrix3x3 identity() { Matrix3x3 r; r.set_identity(); return r; }
@@ -88,14 +186,14 @@ public:
   PinholeModel() : PinholeModel(Vector3(0, 0, 0), identity(), 1, 1, 0, 0) {}
   PinholeModel(Vector3 const& center, Matrix3x3 const& rotation, double fu, double fv, double cu, double cv,
                Vector3 const& u = Vector3(1, 0, 0), Vector3 const& v = Vector3(0, 1, 0), Vector3 const& w = Vector3(0, 0, 1),
-               TsaiLensDistortion const* distortion = NULL, double pixel_pitch = 1.0)
+               LensDistortion const* distortion = NULL, double pixel_pitch = 1.0)
       : m_center(center), m_rotation(rotation), m_u(u), m_v(v), m_w(w) {
-    if (distortion) m_distortion.reset(new TsaiLensDistortion(*distortion));
+    if (distortion) m_distortion.reset(distortion->copy());
     m_desc.fu = fu; m_desc.fv = fv; m_desc.cu = cu; m_desc.cv = cv; m_desc.pixel_pitch = pixel_pitch;
     rebuild();
   }
   PinholeModel(Vector3 const& center, Matrix3x3 const& rotation, double fu, double fv, double cu, double cv,
-               TsaiLensDistortion const* distortion, double pixel_pitch = 1.0)
+               LensDistortion const* distortion, double pixel_pitch = 1.0)
       : PinholeModel(center, rotation, fu, fv, cu, cv, Vector3(1, 0, 0), Vector3(0, 1, 0), Vector3(0, 0, 1), distortion, pixel_pitch) {}
 
   Vector3 camera_center(Vector2 const& = Vector2()) const { return m_center; }
@@ -108,11 +206,13 @@ public:
   void set_do_point_to_pixel_check(bool value) { m_check = value; }
   bool do_point_to_pixel_check() const { return m_check; }
 
-  /// PinholeModel::pixel_to_vector (PinholeModel.cc:422-430); a Tsai lens is undone by the engine's restated solver on the
-  /// device only, so this host method serves undistorted pinholes (NoImplErr otherwise)
+  LensDistortion const* lens_distortion() const { return m_distortion.get(); }
+
+  /// PinholeModel::pixel_to_vector (PinholeModel.cc:422-430); the lens is undone by the engine's functions on the host
   Vector3 pixel_to_vector(Vector2 const& pix) const {
-    VW_ASSERT(!m_distortion, NoImplErr() << "PinholeModel::pixel_to_vector: lens distortion is undone on the device only.");
-    const Vector3 p(pix[0] * m_desc.pixel_pitch, pix[1] * m_desc.pixel_pitch, 1);
+    Vector2 u(pix[0] * m_desc.pixel_pitch, pix[1] * m_desc.pixel_pitch);
+    if (m_distortion) u = m_distortion->undistorted_coordinates(*this, u);
+    const Vector3 p(u[0], u[1], 1);
     const double* m = m_desc.inv_camera_transform;
     return detail::normalize3(Vector3(detail::dot3(m, p), detail::dot3(m + 3, p), detail::dot3(m + 6, p)));
   }
@@ -130,10 +230,29 @@ public:
       }
     }
     Vector2 pix(q[0] / q[2], q[1] / q[2]);   // normalised; the intrinsics follow
-    if (m_distortion) pix = m_distortion->distort_norm(pix);
+    if (m_distortion && m_distortion->kind() != VWGPU_DISTORTION_TSAI) {
+      // distorted_coordinates of the undistorted position in focal-plane units; PointToPixelErr where it does not converge
+      const Vector2 d = m_distortion->distorted_coordinates(*this, Vector2(pix[0] * m_desc.fu + m_desc.cu, pix[1] * m_desc.fv + m_desc.cv));
+      return Vector2(d[0] / m_desc.pixel_pitch, d[1] / m_desc.pixel_pitch);
+    }
+    if (m_distortion) pix = static_cast<TsaiLensDistortion const*>(m_distortion.get())->distort_norm(pix);
     return Vector2((pix[0] * m_desc.fu + m_desc.cu) / m_desc.pixel_pitch, (pix[1] * m_desc.fv + m_desc.cv) / m_desc.pixel_pitch);
   }
 };
+
+namespace detail {
+inline Vector2 lens_coordinates(PinholeModel const& cam, LensDistortion const* lens, int direction, Vector2 const& p) {
+  VW_ASSERT(cam.lens_distortion() && cam.lens_distortion()->kind() == lens->kind(), ArgumentErr() << "LensDistortion: the camera carries another lens.");
+  const double in[2] = {p[0], p[1]};
+  double out[2];
+  const int rc = vwgpu_lens_coordinates(&cam.descriptor(), direction, in, 1, out, NULL);
+  if (rc == VWGPU_ERR_LOGIC) vw_throw(PointToPixelErr() << "LensDistortion: Did not converge.\n");
+  VW_ASSERT(rc == VWGPU_OK, ArgumentErr() << "LensDistortion: bad arguments.");
+  return Vector2(out[0], out[1]);
+}
+}  // namespace detail
+inline Vector2 LensDistortion::distorted_coordinates(PinholeModel const& cam, Vector2 const& p) const { return detail::lens_coordinates(cam, this, 0, p); }
+inline Vector2 LensDistortion::undistorted_coordinates(PinholeModel const& cam, Vector2 const& p) const { return detail::lens_coordinates(cam, this, 1, p); }
 
 /// CAHVModel(C, A, H, V) (CAHVModel.h).
 class CAHVModel : public CameraModel {
@@ -163,10 +282,6 @@ public:
   }
   Vector3 camera_center(Vector2 const& = Vector2()) const { return C; }
 };
-
-/// What the CAHVORE model throws (src/vw/Camera/CameraModel.h).
-VWLITE_EXCEPTION(PixelToRayErr, Exception);
-VWLITE_EXCEPTION(PointToPixelErr, Exception);
 
 /// CAHVORModel(C, A, H, V, O, R) (CAHVORModel.h): CAHV with radial distortion about the axis O.  The single-pixel functions
 /// are host code in the reference's expressions (CAHVORModel.cc:297-348, :431-448); images and arrays of points go through

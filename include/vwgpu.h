@@ -778,10 +778,11 @@ int vwgpu_intersect_mask_and_data(vwgpu_ctx* ctx, int type, const void* data, pt
  * O, R, E and P live in storage only a pinhole uses:
  *   inv_camera_transform[0..2] = O, [3..5] = R, [6..8] = E (CAHVORE);  distortion[0] = P (CAHVORE).
  * Callers do not write these by hand: vwgpu_cahvor_camera and vwgpu_cahvore_camera fill a descriptor.
- * Pairs that have a kernel: vwgpu_camera_transform* with one CAHVOR or CAHVORE camera and one CAHV camera, in either role;
- * triangulation and the convergence angle with two CAHVOR or two CAHVORE cameras.  Every other pair with a CAHVOR or
- * CAHVORE camera (with a pinhole, CAHVOR with CAHVORE, two of them in a camera transform, one of them beside another kind
- * in triangulation) is VWGPU_ERR_NOIMPL with a message that names the pair, before any device work. */
+ * Which pairs have a kernel — the rule: pinholes (with any lens) and CAHV cameras go with one another in every entry point;
+ * a CAHVOR or CAHVORE camera goes with a CAHV camera alone in vwgpu_camera_transform*, in either role, and with a camera
+ * of its own kind alone in triangulation and the convergence angle.  Every other pair is VWGPU_ERR_NOIMPL with a message
+ * that names the pair, before any device work.  (The engine keeps one table of instantiated pairs per entry-point family,
+ * and a pair without a row is refused.) */
 typedef enum vwgpu_camera_kind {
   VWGPU_CAMERA_PINHOLE = 0, VWGPU_CAMERA_CAHV = 1, VWGPU_CAMERA_CAHVOR = 3, VWGPU_CAMERA_CAHVORE = 4
 } vwgpu_camera_kind;

@@ -207,6 +207,8 @@ def camera_pairs():
         "pinhole_cahv": (sp, tri.cahv_of(dp)),
         "cahv_pinhole": (tri.cahv_of(sp), dp),
         "tsai_cahv": (src_pinhole(MILD_TSAI), tri.cahv_of(dp)),
+        "tsai_tsai": (src_pinhole(MILD_TSAI), dst_pinhole(MILD_TSAI)),
+        "cahv_tsai": (tri.cahv_of(sp), dst_pinhole(MILD_TSAI)),
     }
 
 

@@ -415,6 +415,70 @@ def test_refusals(ctx, source, linear):
         camera.CameraTransform(moved, cahvore, ctx=ctx).forward(np.zeros((3, 2)))
 
 
+# Which ordered pairs have a kernel, written from the rule of include/vwgpu.h (struct vwgpu_camera): every pair of pinholes
+# (with any lens) and CAHV cameras has one; a CAHVOR or CAHVORE camera goes with a CAHV camera alone in a camera transform,
+# in either role, and with one of its own kind alone in triangulation and the convergence angle.  Rows: the first camera
+# (src, cam1); columns: the second (dst, cam2), in the order of PAIR_KINDS.
+PAIR_KINDS = ["pinhole", "tsai", "fisheye", "brown_conrady", "cahv", "cahvor", "cahvore"]
+PAIR_NAMES = {"pinhole": "Pinhole", "tsai": "Pinhole", "fisheye": "Pinhole", "brown_conrady": "Pinhole", "cahv": "CAHV", "cahvor": "CAHVOR",
+              "cahvore": "CAHVORE"}
+TRANSFORM_HAS_KERNEL = {
+    "pinhole":       "YYYYYNN",
+    "tsai":          "YYYYYNN",
+    "fisheye":       "YYYYYNN",
+    "brown_conrady": "YYYYYNN",
+    "cahv":          "YYYYYYY",
+    "cahvor":        "NNNNYNN",
+    "cahvore":       "NNNNYNN",
+}
+TRIANGULATE_HAS_KERNEL = {
+    "pinhole":       "YYYYYNN",
+    "tsai":          "YYYYYNN",
+    "fisheye":       "YYYYYNN",
+    "brown_conrady": "YYYYYNN",
+    "cahv":          "YYYYYNN",
+    "cahvor":        "NNNNNYN",
+    "cahvore":       "NNNNNNY",
+}
+
+
+def test_which_pairs_have_a_kernel(ctx, source):
+    """Every ordered pair of seven descriptors through camera_transform, CameraTransform (both directions), stereo_triangulate
+    and convergence_angle: a result of the right shape, or NoImplErr that names the pair.  The operands are tensors: such a
+    call never synchronises, so a pixel that fails a check cannot turn an accepted pair into a LogicErr."""
+    import torch
+    import lens_ref
+    C = ref.small("cahvor").C
+    cams = {"pinhole": lens_ref.small(None, center=C), "tsai": lens_ref.small("TSAI", center=C), "fisheye": lens_ref.small("FISHEYE", center=C),
+            "brown_conrady": lens_ref.small("BrownConrady", center=C), "cahv": lens_ref.cahv(center=C), "cahvor": ref.small("cahvor"),
+            "cahvore": ref.small("cahvore", C=C)}
+    assert sorted(cams) == sorted(PAIR_KINDS)
+    img = torch.from_numpy(source[0]).cuda()
+    pts = torch.from_numpy(np.stack([np.linspace(2, 50, 65), np.linspace(3, 40, 65)], 1)).cuda()
+    d = np.zeros((29, 37, 3), np.float32)
+    d[..., 0], d[..., 2] = -2.0, 1
+    d = torch.from_numpy(d).cuda()
+
+    def expect(has_kernel, shape, first, second, fn):
+        if has_kernel:
+            assert tuple(fn().shape) == shape, (first, second)
+            return
+        with pytest.raises(vwa.NoImplErr, match="no kernel for the pair") as e:
+            fn()
+        assert PAIR_NAMES[first] in str(e.value) and PAIR_NAMES[second] in str(e.value), str(e.value)
+    for first in PAIR_KINDS:
+        for k, second in enumerate(PAIR_KINDS):
+            a, b = cams[first], cams[second]
+            has = TRANSFORM_HAS_KERNEL[first][k] == "Y"
+            expect(has, (29, 37), first, second, lambda: camera.camera_transform(img, a, b, size=(37, 29), ctx=ctx))
+            expect(has, (65, 2), first, second, lambda: camera.CameraTransform(a, b, ctx=ctx).forward(pts))
+            expect(has, (65, 2), first, second, lambda: camera.CameraTransform(a, b, ctx=ctx).reverse(pts))
+            has = TRIANGULATE_HAS_KERNEL[first][k] == "Y"
+            expect(has, (29, 37, 3), first, second, lambda: stereo.stereo_triangulate(d, a, b, ctx=ctx))
+            expect(has, (29, 37), first, second, lambda: stereo.StereoModel(a, b).convergence_angle(d, ctx=ctx))
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("kind", KINDS)
 def test_epipolar_transformed_images_end_to_end(ctx, source, kind):
     """Two scaled models with a baseline: linearize_camera per frame, epipolar() on the two CAHV results and one

@@ -244,19 +244,22 @@ POINT_PAIRS = ["pinhole_pinhole", "turned_pitch", "tsai_src", "tsai_dst", "cahv_
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 1000])
 def test_camera_transform_points(ctx, n):
+    """At n = 65 every pair of ref.camera_pairs() in both directions with the check on and off: every point kernel of the
+    null / Tsai pinholes and CAHV (the rows of ct_pairs in camera_transform.hip) against the restatement."""
     import torch
     rng = np.random.default_rng(n)
     pts = np.stack([rng.uniform(-5, 66, n), rng.uniform(-5, 52, n)], 1)
     pts[0] = (12.0, 7.0)
-    for pair in POINT_PAIRS:
+    for pair in (sorted(ref.camera_pairs()) if n == 65 else POINT_PAIRS):
         src, dst = ref.camera_pairs()[pair]
-        t = camera.CameraTransform(src, dst, ctx=ctx)
-        for direction, fn in ((ref.FORWARD, t.forward), (ref.REVERSE, t.reverse)):
-            want, failed, rc = ref.transform_points(src, dst, direction, pts)
-            assert (rc, failed) == (0, 0)
-            same(fn(pts), want, "%s %d" % (pair, direction))
-            if n == 65:
-                same(fn(torch.from_numpy(pts).cuda()).cpu().numpy(), want, "%s %d dev" % (pair, direction))
+        for check_on in ((True, False) if n == 65 else (True,)):
+            t = camera.CameraTransform(src, dst, check=check_on, ctx=ctx)
+            for direction, fn in ((ref.FORWARD, t.forward), (ref.REVERSE, t.reverse)):
+                want, failed, rc = ref.transform_points(src, dst, direction, pts, check=check_on)
+                assert (rc, failed) == (0, 0)
+                same(fn(pts), want, "%s %d check %d" % (pair, direction, check_on))
+                if n == 65:
+                    same(fn(torch.from_numpy(pts).cuda()).cpu().numpy(), want, "%s %d check %d dev" % (pair, direction, check_on))
     # the strong lens: NaN pairs where the check fails; LogicErr from the host entry, the NaNs from the device entry
     src, dst = ref.strong_tsai_pair()
     grid = np.stack(np.meshgrid(np.arange(0.0, 70.0, 3.0), np.arange(0.0, 45.0, 4.0)), -1).reshape(-1, 2)[:max(n, 2)]

@@ -55,6 +55,13 @@ def exact(*names):
     return all(n in ref.EXACT_LENSES or n in (None, "TSAI", "NULL", "CAHV") for n in names)
 
 
+def cahv_like(pin):
+    """The CAHV camera that sees what the undistorted pinhole `pin` sees (in pixels: the pitch divided out)."""
+    r, k = pin.rotation, 1.0 / pin.pixel_pitch
+    a = r[:, 2]
+    return camera.CAHVModel(pin.center, a, pin.fu * k * r[:, 0] + pin.cu * k * a, pin.fv * k * r[:, 1] + pin.cv * k * a)
+
+
 def same(got, want, what=""):
     """Exact equality of every word; NaNs by position."""
     got, want = np.asarray(got), np.asarray(want)
@@ -150,15 +157,21 @@ def test_sizes_in_both_roles(ctx, source, cams, lens, size, masked):
 @pytest.mark.parametrize("edge", sorted(EDGES))
 @pytest.mark.parametrize("lens", LENSES)
 def test_edge_pixels_and_check(ctx, source, lens, edge, check):
-    """A partner turned so that part of the output leaves the source; the source's round-trip check on and off."""
+    """A partner, an undistorted pinhole or its CAHV form, turned so that part of the output leaves the source; the source's
+    round-trip check on and off, with and without masks: every image kernel of the any-lens rows of ct_pairs
+    (camera_transform.hip)."""
     img, mask = source
-    cam, plain = ref.small(lens), ref.small(None, turn=(2.5, 1.5))
-    for src, dst, role in ((cam, plain, "src"), (plain, cam, "dst")):
-        want = ref.camera_transform(img, src, dst, size=(37, 29), mask=mask, edge=EDGES[edge], check=check)
-        outside = (want["q"][..., 0] < -1) | (want["q"][..., 1] < -1) | (want["q"][..., 0] > ref.SW) | (want["q"][..., 1] > ref.SH)
-        assert 0.05 < outside.mean() < 0.95 and want["failed"] == 0
-        got = camera.camera_transform(img, src, dst, size=(37, 29), mask=mask, edge=EDGES[edge], check=check, ctx=ctx)
-        check_image(exact(lens), got, want, True, "%s as %s edge %s check %d" % (lens, role, edge, check), edge_value=EDGES[edge][0])
+    cam, pinhole = ref.small(lens), ref.small(None, turn=(2.5, 1.5))
+    for partner, plain in (("pinhole", pinhole), ("cahv", cahv_like(pinhole))):
+        for src, dst, role in ((cam, plain, "src"), (plain, cam, "dst")):
+            for masked in (True, False):
+                m = mask if masked else None
+                want = ref.camera_transform(img, src, dst, size=(37, 29), mask=m, edge=EDGES[edge], check=check)
+                outside = (want["q"][..., 0] < -1) | (want["q"][..., 1] < -1) | (want["q"][..., 0] > ref.SW) | (want["q"][..., 1] > ref.SH)
+                assert 0.05 < outside.mean() < 0.95 and want["failed"] == 0
+                got = camera.camera_transform(img, src, dst, size=(37, 29), mask=m, edge=EDGES[edge], check=check, ctx=ctx)
+                check_image(exact(lens), got, want, masked, "%s as %s of %s edge %s check %d" % (lens, role, partner, edge, check),
+                            edge_value=EDGES[edge][0])
 
 
 @pytest.mark.parametrize("lens", LENSES)
@@ -200,19 +213,22 @@ def test_camera_transform_points(ctx, cams, lens, n):
     rng = np.random.default_rng(n)
     pts = np.stack([rng.uniform(2, ref.SW - 3, n), rng.uniform(2, ref.SH - 3, n)], 1)
     pts[0] = (12.0, 7.0)
-    for src, dst in ((cam, plain), (plain, cam)):
-        t = camera.CameraTransform(src, dst, ctx=ctx)
-        for direction, fn in ((ref.FORWARD, t.forward), (ref.REVERSE, t.reverse)):
-            want, failed, _, rc = ref.transform_points(src, dst, direction, pts)
-            assert (rc, failed) == (0, 0) and np.abs(want).max() <= 1e4
-            what = "%s points %s %d" % (lens, "lens->plain" if src is cam else "plain->lens", direction)
-            got = fn(pts)
-            if exact(lens):
-                same(got, want, what)
-            else:
-                close(got, want, POINT_TOL, what)
-            if n == 65:
-                same(fn(torch.from_numpy(pts).cuda()).cpu().numpy(), got, what + " dev")
+    # at n = 65 a CAHV partner and the check off as well: every point kernel of the any-lens rows of ct_pairs
+    for partner, check in (((plain, True), (plain, False), (cahv_like(plain), True), (cahv_like(plain), False)) if n == 65 else ((plain, True),)):
+        for src, dst in ((cam, partner), (partner, cam)):
+            t = camera.CameraTransform(src, dst, check=check, ctx=ctx)
+            for direction, fn in ((ref.FORWARD, t.forward), (ref.REVERSE, t.reverse)):
+                want, failed, _, rc = ref.transform_points(src, dst, direction, pts, check=check)
+                assert (rc, failed) == (0, 0) and np.abs(want).max() <= 1e4
+                what = "%s points %s %s %d check %d" % (lens, "lens->" if src is cam else "->lens", "plain" if partner is plain else "cahv",
+                                                        direction, check)
+                got = fn(pts)
+                if exact(lens):
+                    same(got, want, what)
+                else:
+                    close(got, want, POINT_TOL, what)
+                if n == 65:
+                    same(fn(torch.from_numpy(pts).cuda()).cpu().numpy(), got, what + " dev")
 
 
 @pytest.fixture(scope="module")

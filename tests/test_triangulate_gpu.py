@@ -108,6 +108,7 @@ def test_camera_kinds_and_semantics(ctx, pair, semantics, dtype):
     if semantics == "view":
         xyz, err, vec = stereo.stereo_triangulate(d, c1, c2, error=True, error_vector=True, stats=st, ctx=ctx)
         check_all(xyz, err, vec, st, want, pair)
+        same(stereo.stereo_triangulate(d, c1, c2, ctx=ctx), want["xyz"], pair + " xyz only")      # the kernel without statistics
     else:
         xyz, err = stereo.StereoModel(c1, c2)(d, stats=st, ctx=ctx)
         same(xyz, want["xyz"], pair + " xyz")
@@ -124,6 +125,7 @@ def test_tsai_pair(ctx, semantics):
     st = []
     xyz, err, vec = stereo._triangulate("test", d, c1, c2, 0, 0, 0.0, semantics, None, True, True, st, ctx)
     check_all(xyz, err, vec, st, want, "tsai " + semantics)
+    same(stereo._triangulate("test", d, c1, c2, 0, 0, 0.0, semantics, None, False, False, None, ctx)[0], want["xyz"], "tsai xyz only")
 
 
 def test_semantics_differ(ctx, main):
@@ -264,7 +266,7 @@ def test_tiles_equal_whole_map(ctx, main, semantics):
 CONVERGENCE_ANGLE_MEASURED = 5.55e-17
 
 
-@pytest.mark.parametrize("pair", ["pinhole", "tsai", "cahv_pinhole"])
+@pytest.mark.parametrize("pair", ["pinhole", "tsai", "cahv_pinhole", "pinhole_cahv", "cahv_flipped", "cahv_plain"])
 def test_convergence_angle(ctx, pair):
     import torch
     if pair == "tsai":

@@ -1,9 +1,12 @@
-// camera_rays.h — the part of vw::camera the kernels share: the small fp64 vector helpers in the reference's expression
-// order and pixel_to_vector of PinholeModel with the null and the Tsai lens (src/vw/Camera/PinholeModel.cc:422-434,
-// src/vw/Camera/LensDistortion.cc:260-400 over src/vw/Math/NewtonRaphson.cc:58-119) and of CAHVModel
-// (src/vw/Camera/CAHVModel.cc:173-189), and both directions of CAHVORModel (src/vw/Camera/CAHVORModel.cc:297-348, :431-448)
-// and CAHVOREModel (src/vw/Camera/CAHVOREModel.cc:167-301), which the host's linearize_camera runs as well.  Used by
-// triangulate.hip and camera_transform.hip; internal linkage, so every translation unit compiles its own copy.
+// camera_rays.h — the camera models, both directions, and what the two camera engines share.  The small fp64 vector
+// helpers in the reference's expression order; pixel_to_vector of PinholeModel (src/vw/Camera/PinholeModel.cc:422-434)
+// and of CAHVModel (src/vw/Camera/CAHVModel.cc:173-189); undistorted_coordinates and distorted_coordinates of the seven
+// lenses (src/vw/Camera/LensDistortion.cc, over src/vw/Math/NewtonRaphson.cc:58-119 and
+// src/vw/Math/LevenbergMarquardt.h:389-561); both directions of CAHVORModel (src/vw/Camera/CAHVORModel.cc:297-348,
+// :431-448) and CAHVOREModel (src/vw/Camera/CAHVOREModel.cc:167-301).  Then what the host side of both engines shares: the
+// camera check, the code a kernel carries for a camera, the handedness test of the CAHV family and the grid of row bands.
+// Used by triangulate.hip and camera_transform.hip, and by camera_host.hip, which runs the model functions on the host;
+// internal linkage, so every translation unit compiles its own copy.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -436,9 +439,125 @@ __host__ __device__ inline tr_v2 tr_lens_undistort(const vwgpu_camera& c, const 
   }
 }
 
+// TsaiLensDistortion::distorted_coordinates (LensDistortion.cc:345-369)
+__host__ __device__ inline tr_v2 tr_tsai_distort(const vwgpu_camera& c, const tr_v2& p) {
+  if (c.fu < 1e-300 || c.fv < 1e-300) return tr_v2{HUGE_VAL, HUGE_VAL};
+  const tr_v2 p0{(p.x - c.cu) / c.fu, (p.y - c.cv) / c.fv};
+  const tr_v2 d = tr_tsai_norm(p0, c.distortion);
+  double dx = d.x, dy = d.y;
+  dx = dx * c.fu + c.cu;
+  dy = dy * c.fv + c.cv;
+  return tr_v2{dx, dy};
+}
+
+// FovLensDistortion::distorted_coordinates (LensDistortion.cc:462-488); L = {k1, 1 / k1, 2 tan(k1 / 2)}
+__host__ __device__ inline tr_v2 tr_fov_distort(const vwgpu_camera& c, const tr_v2& p) {
+  const double* L = tr_lens_words(c);
+  if (c.fu < 1e-300 || c.fv < 1e-300) return tr_v2{HUGE_VAL, HUGE_VAL};
+  const tr_v2 p0{(p.x - c.cu) / c.fu, (p.y - c.cv) / c.fv};
+  const double ru = tr_norm(p0);
+  const double rd = atan(ru * L[2]) * L[1];
+  double conv = 1.0;
+  if (ru > 1e-8) conv = rd / ru;
+  return tr_v2{conv * p0.x * c.fu + c.cu, conv * p0.y * c.fv + c.cv};
+}
+
+// FisheyeLensDistortion::distorted_coordinates (:612-632) and AdjustableTsaiLensDistortion::distorted_coordinates (:832-849)
+template <class MODEL>
+__host__ __device__ inline tr_v2 tr_norm_distort(const vwgpu_camera& c, const tr_v2& p) {
+  if (c.fu < 1e-300 || c.fv < 1e-300) return tr_v2{HUGE_VAL, HUGE_VAL};
+  const tr_v2 p0{(p.x - c.cu) / c.fu, (p.y - c.cv) / c.fv};
+  const tr_v2 d = MODEL{tr_lens_words(c)}.norm(p0);
+  return tr_v2{d.x * c.fu + c.cu, d.y * c.fv + c.cv};
+}
+
+// DistortOptimizeFunctor (LensDistortion.cc:29-41) for the two lenses that have no distorted_coordinates of their own
+__host__ __device__ inline tr_v2 tr_solver_model(const vwgpu_camera& c, const tr_v2& x) {
+  return c.distortion_kind == VWGPU_DISTORTION_PHOTOMETRIX ? tr_photometrix_undistort(c, x) : tr_brown_conrady_undistort(c, x);
+}
+
+// LensDistortion::distorted_coordinates (LensDistortion.cc:175-195): levenberg_marquardtFixed(model, v, v, status, 1e-16,
+// 1e-16, 100) (Math/LevenbergMarquardt.h:389-561) for two unknowns, with the forward-difference Jacobian of
+// LeastSquaresModelBaseFixed::jacobian (:344-377) and inverse() of Math/Matrix.h:2209-2216, then the 1e-10 test.  At most
+// 100 outer passes of at most 6 inner ones.  false where the reference throws "LensDistortion: Did not converge.", and
+// where det(hessian_lm) > 0.0 does not hold (NaN, overflow), for which the reference leaves for LAPACK.
+__host__ __device__ inline bool tr_solver_distort(const vwgpu_camera& c, const tr_v2& v, tr_v2& solution) {
+  const double abs_tolerance = 1e-16, rel_tolerance = 1e-16;
+  const int max_iterations = 100;
+  bool done = false;
+  const double Rinv = 10;
+  double lambda = 0.1;
+  tr_v2 x_try{0.0, 0.0}, x = v;
+  tr_v2 h = tr_solver_model(c, x);
+  tr_v2 error{v.x - h.x, v.y - h.y};
+  double norm_start = tr_norm(error);
+  if (norm_start < abs_tolerance) done = true;
+  for (int outer_iter = 1; outer_iter <= max_iterations && !done; ++outer_iter) {
+    bool shortCircuit = false;
+    h = tr_solver_model(c, x);
+    error = tr_v2{v.x - h.x, v.y - h.y};
+    norm_start = tr_norm(error);
+    // the Jacobian, J[row][column]
+    const tr_v2 h0 = tr_solver_model(c, x);
+    const double eps0 = 1e-7 + fabs(x.x * 1e-7), eps1 = 1e-7 + fabs(x.y * 1e-7);
+    const tr_v2 h_0 = tr_solver_model(c, tr_v2{x.x + eps0, x.y}), h_1 = tr_solver_model(c, tr_v2{x.x, x.y + eps1});
+    const double J00 = (h_0.x - h0.x) / eps0, J10 = (h_0.y - h0.y) / eps0;
+    const double J01 = (h_1.x - h0.x) / eps1, J11 = (h_1.y - h0.y) / eps1;
+    const double del_J0 = -1.0 * Rinv * (0.0 + J00 * error.x + J10 * error.y);
+    const double del_J1 = -1.0 * Rinv * (0.0 + J01 * error.x + J11 * error.y);
+    const double H00 = Rinv * (0.0 + J00 * J00 + J10 * J10), H01 = Rinv * (0.0 + J00 * J01 + J10 * J11);
+    const double H10 = Rinv * (0.0 + J01 * J00 + J11 * J10), H11 = Rinv * (0.0 + J01 * J01 + J11 * J11);
+    int iterations = 0;
+    double norm_try = norm_start + 1.0;
+    while (norm_try > norm_start && iterations < 6) {
+      double d0 = H00, d3 = H11;
+      const double d1 = H01, d2 = H10;
+      d0 += d0 * lambda + lambda;
+      d3 += d3 * lambda + lambda;
+      const double det = d0 * d3 - d1 * d2;
+      if (!(det > 0.0)) return false;
+      const double i0 = d3 / det, i1 = -d1 / det, i2 = -d2 / det, i3 = d0 / det;
+      const tr_v2 delta_x{0.0 + i0 * del_J0 + i1 * del_J1, 0.0 + i2 * del_J0 + i3 * del_J1};
+      x_try = tr_v2{x.x - delta_x.x, x.y - delta_x.y};
+      const tr_v2 h_try = tr_solver_model(c, x_try);
+      const tr_v2 error_try{v.x - h_try.x, v.y - h_try.y};
+      norm_try = tr_norm(error_try);
+      if (norm_try > norm_start) lambda *= 10;
+      ++iterations;
+      if (iterations > 5) {
+        shortCircuit = true;
+        norm_try = norm_start;
+      }
+    }
+    if (!shortCircuit && ((norm_start - norm_try) / norm_start) < rel_tolerance) done = true;
+    if (norm_try < abs_tolerance) done = true;
+    if (!shortCircuit) x = x_try;
+    norm_start = norm_try;
+    lambda /= 10;
+  }
+  solution = x;
+  const tr_v2 undist = tr_solver_model(c, solution);
+  const double nv = tr_norm(v);
+  const double err = tr_norm(tr_v2{undist.x - v.x, undist.y - v.y}) / (nv > 0.1 ? nv : 0.1);
+  return !(err > 1e-10);
+}
+
+// distorted_coordinates of a pinhole's lens, whichever it is; false where the reference throws
+__host__ __device__ inline bool tr_lens_distort(const vwgpu_camera& c, const tr_v2& p, tr_v2& out) {
+  switch (c.distortion_kind) {
+    case VWGPU_DISTORTION_TSAI: out = tr_tsai_distort(c, p); return true;
+    case VWGPU_DISTORTION_FOV: out = tr_fov_distort(c, p); return true;
+    case VWGPU_DISTORTION_FISHEYE: out = tr_norm_distort<tr_fisheye_model>(c, p); return true;
+    case VWGPU_DISTORTION_ADJUSTABLE_TSAI: out = tr_norm_distort<tr_adjustable_tsai_model>(c, p); return true;
+    case VWGPU_DISTORTION_BROWN_CONRADY:
+    case VWGPU_DISTORTION_PHOTOMETRIX: return tr_solver_distort(c, p, out);
+    default: out = p; return true;
+  }
+}
+
 // pixel_to_vector of the camera kinds a kernel carries
 // `flip`: the handedness test of CAHVModel::pixel_to_vector, dot(cross(V, H), A) < 0 — the same for every pixel, so the
-// host evaluates it once (tr_cahv_flips)
+// host evaluates it once (tr_cahv_flip)
 template <int CAM>
 __host__ __device__ inline tr_v3 tr_ray(const vwgpu_camera& c, const tr_v2& pix, bool flip) {
   if (CAM == TR_CAM_CAHV) {
@@ -473,6 +592,46 @@ __device__ inline int tr_ray_status(const vwgpu_camera& c, const tr_v2& pix, boo
   }
   vec = tr_ray<CAM>(c, pix, flip);
   return TR_OK;
+}
+
+// ---- what the host side of both engines shares -------------------------------------------------------------------------
+
+inline int tr_cahv_flip(const vwgpu_camera& c) {   // CAHVORModel.cc:306 is the same test
+  return (c.kind == VWGPU_CAMERA_CAHV || c.kind == VWGPU_CAMERA_CAHVOR) && tr_dot(tr_cross(tr_load3(c.V), tr_load3(c.H)), tr_load3(c.A)) < 0.0;   // CAHVModel.cc:182
+}
+
+// a camera of a kind and with a lens the kernels know; `which` ("source", "destination") names it in the null message, or is null
+inline int tr_camera_check(vwgpu_ctx* ctx, const char* name, const char* which, const vwgpu_camera* c) {
+  if (!c) return which ? vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: null %s camera", name, which) : vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: null camera", name);
+  if (c->kind != VWGPU_CAMERA_PINHOLE && c->kind != VWGPU_CAMERA_CAHV && !tr_new_kind(*c))
+    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: unknown camera kind %d", name, c->kind);
+  if (c->kind == VWGPU_CAMERA_PINHOLE && !tr_lens_valid(*c))
+    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: unknown lens distortion kind %d", name, c->distortion_kind);
+  return VWGPU_OK;
+}
+
+// the code a kernel carries for the camera whose rays it forms.  `lens_pair`: one camera of the pair is a pinhole with a
+// lens other than null and Tsai, and every pinhole of the pair takes the any-lens code.
+inline int tr_camera_code(const vwgpu_camera& c, bool lens_pair) {
+  if (tr_new_kind(c)) return c.kind == VWGPU_CAMERA_CAHVOR ? TR_CAM_CAHVOR : TR_CAM_CAHVORE;
+  if (lens_pair && c.kind == VWGPU_CAMERA_PINHOLE) return TR_CAM_PINHOLE_LENS;
+  return c.kind == VWGPU_CAMERA_CAHV ? TR_CAM_CAHV : c.distortion_kind == VWGPU_DISTORTION_NULL ? TR_CAM_PINHOLE_NULL : TR_CAM_PINHOLE;
+}
+
+// Every band of BY rows has a workgroup of BX x BY lanes of its own, numbered through grid y and then z: a row loop would
+// keep both cameras and every argument live across its iterations, in more scalar registers than there are.
+template <int BX, int BY>
+inline dim3 tr_band_grid(int w, int h) {
+  const long long bands = ((long long)h + BY - 1) / BY, gy = bands < 65535 ? bands : 65535;
+  return dim3((unsigned)((w + BX - 1) / BX), (unsigned)gy, (unsigned)((bands + gy - 1) / gy));
+}
+template <int BX, int BY>
+__device__ inline bool tr_band_position(int w, int h, int& x, int& y, long long& band) {
+  x = blockIdx.x * BX + threadIdx.x;
+  band = (long long)blockIdx.z * gridDim.y + blockIdx.y;
+  const long long row = band * BY + threadIdx.y;
+  y = (int)row;
+  return x < w && row < h;
 }
 
 }  // namespace

@@ -10,11 +10,10 @@
 // One lane per pixel, blocks of 64 x 4, every band of four rows a workgroup of its own, no neighbourhood and no LDS (the
 // statistics variant keeps one partial per wavefront there).  The cameras arrive by value: they are uniform and are read
 // through scalar loads.  A lane reads the 12 bytes of its pixel and writes 24 contiguous bytes of xyz, so a wavefront's
-// stores cover 1536 contiguous bytes.  The null-distortion pinhole pair, the other pinhole pairs and the three pairs
-// with a CAHV camera are separate instantiations: the common case carries no Newton loop.  Two CAHVOR and two CAHVORE
-// cameras (camera_rays.h) are one instantiation each; a CAHVORE ray that does not converge gives the zero point.  Pairs
-// in which a pinhole carries one of the five other lenses (camera_rays.h) are three more: every pinhole of such a pair
-// takes the any-lens code.
+// stores cover 1536 contiguous bytes.  The kernels are instantiated per pair of camera codes (camera_rays.h), so that
+// the common case, two pinholes without lens distortion, carries no Newton loop; the table tr_pairs lists the pairs
+// that exist, and a pair without a row is refused.  A CAHVORE ray that does not converge gives the zero point.
+// vwgpu_pinhole_camera, pure host arithmetic, is in camera_host.hip.
 //
 // Everything is double in the reference's expression order; the Makefile's -ffp-contract=off keeps products and sums
 // apart, and fp64 division and square root are correctly rounded on the device.  Sums written `0.0 + ...` are the
@@ -197,22 +196,12 @@ __device__ inline void tr_pixel(const tr_args& a, const vwgpu_camera& cam1, cons
   }
 }
 
-// Every band of 4 rows has a workgroup of its own, numbered through grid y and then z: a row loop would keep both cameras
-// and every argument live across its iterations, in more scalar registers than there are.
-__device__ inline bool tr_position(int w, int h, int& x, int& y, long long& band) {
-  x = blockIdx.x * TR_BX + threadIdx.x;
-  band = (long long)blockIdx.z * gridDim.y + blockIdx.y;
-  const long long row = band * TR_BY + threadIdx.y;
-  y = (int)row;
-  return x < w && row < h;
-}
-
 template <int CAM1, int CAM2>
 __global__ __launch_bounds__(TR_THREADS) void tr_triangulate_kernel(tr_args a, vwgpu_camera cam1, vwgpu_camera cam2) {
   int x, y;
   long long band;
   tr_acc acc{0, 0.0, 0.0};
-  if (tr_position(a.w, a.h, x, y, band)) tr_pixel<CAM1, CAM2, false>(a, cam1, cam2, x, y, acc);
+  if (tr_band_position<TR_BX, TR_BY>(a.w, a.h, x, y, band)) tr_pixel<CAM1, CAM2, false>(a, cam1, cam2, x, y, acc);
 }
 
 // the statistics variant: one partial per workgroup
@@ -222,7 +211,7 @@ __global__ __launch_bounds__(TR_THREADS) void tr_triangulate_stats_kernel(tr_arg
   int x, y;
   long long band;
   tr_acc acc{0, 0.0, 0.0};
-  if (tr_position(a.w, a.h, x, y, band)) tr_pixel<CAM1, CAM2, true>(a, cam1, cam2, x, y, acc);
+  if (tr_band_position<TR_BX, TR_BY>(a.w, a.h, x, y, band)) tr_pixel<CAM1, CAM2, true>(a, cam1, cam2, x, y, acc);
   tr_acc_block_reduce(acc, lds, threadIdx.y * TR_BX + threadIdx.x, TR_THREADS);
   if (threadIdx.x == 0 && threadIdx.y == 0) {
     vwgpu_triangulate_stats* s = a.partial + (band * gridDim.x + blockIdx.x);
@@ -256,7 +245,7 @@ template <int CAM1, int CAM2>
 __global__ __launch_bounds__(TR_THREADS) void tr_angle_kernel(tr_args a, vwgpu_camera cam1, vwgpu_camera cam2) {
   int x, y;
   long long band;
-  if (!tr_position(a.w, a.h, x, y, band)) return;
+  if (!tr_band_position<TR_BX, TR_BY>(a.w, a.h, x, y, band)) return;
   uint32_t da, db;
   double ang = 0.0;
   if (tr_load_disp(a, x, y, da, db)) {
@@ -288,7 +277,7 @@ __global__ __launch_bounds__(TR_THREADS) void tr_universe_kernel(tr_universe_arg
   int x, y;
   long long band;
   bool rejected = false;
-  if (tr_position(a.w, a.h, x, y, band)) {
+  if (tr_band_position<TR_BX, TR_BY>(a.w, a.h, x, y, band)) {
     const double* p = a.in + ((long long)y * a.istride + x) * CH;
     double v[CH];
 #pragma unroll
@@ -323,34 +312,48 @@ __global__ __launch_bounds__(TR_THREADS) void tr_universe_fold_kernel(unsigned l
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
 const dim3 tr_block(TR_BX, TR_BY);
-dim3 tr_grid(int w, int h) {
-  const long long bands = ((long long)h + TR_BY - 1) / TR_BY, gy = bands < 65535 ? bands : 65535;
-  return dim3((unsigned)((w + TR_BX - 1) / TR_BX), (unsigned)gy, (unsigned)((bands + gy - 1) / gy));
-}
+dim3 tr_grid(int w, int h) { return tr_band_grid<TR_BX, TR_BY>(w, h); }
 
 int tr_elem_words(int layout) {
   return layout == VWGPU_DISPARITY_LAYOUT_DXDYV ? 3 : layout == VWGPU_DISPARITY_LAYOUT_D ? 1 : 2;
 }
 
-int tr_camera_check(vwgpu_ctx* ctx, const char* name, const vwgpu_camera* c) {
-  if (!c) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: null camera", name);
-  if (c->kind != VWGPU_CAMERA_PINHOLE && c->kind != VWGPU_CAMERA_CAHV && !tr_new_kind(*c))
-    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: unknown camera kind %d", name, c->kind);
-  if (c->kind == VWGPU_CAMERA_PINHOLE && !tr_lens_valid(*c))
-    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: unknown lens distortion kind %d", name, c->distortion_kind);
-  return VWGPU_OK;
-}
+// The camera pairs that have kernels, one row each: the codes of the two cameras and the three kernels instantiated for
+// them.  Two pinholes without lens distortion, the other null / Tsai pinhole pairs, the three pairs with a CAHV camera,
+// two CAHVOR and two CAHVORE cameras, and the three pairs in which a pinhole carries the any-lens code.  A pair without
+// a row has no kernel (tr_check).
+using tr_kernel = void (*)(tr_args, vwgpu_camera, vwgpu_camera);
+struct tr_pair {
+  int cam1, cam2;
+  tr_kernel triangulate, triangulate_stats, angle;
+};
+#define TR_ROW(C1, C2) {C1, C2, tr_triangulate_kernel<C1, C2>, tr_triangulate_stats_kernel<C1, C2>, tr_angle_kernel<C1, C2>}
+const tr_pair tr_pairs[] = {
+  TR_ROW(TR_CAM_PINHOLE_NULL, TR_CAM_PINHOLE_NULL),
+  TR_ROW(TR_CAM_PINHOLE, TR_CAM_PINHOLE),
+  TR_ROW(TR_CAM_PINHOLE, TR_CAM_CAHV),
+  TR_ROW(TR_CAM_CAHV, TR_CAM_PINHOLE),
+  TR_ROW(TR_CAM_CAHV, TR_CAM_CAHV),
+  TR_ROW(TR_CAM_CAHVOR, TR_CAM_CAHVOR),
+  TR_ROW(TR_CAM_CAHVORE, TR_CAM_CAHVORE),
+  TR_ROW(TR_CAM_PINHOLE_LENS, TR_CAM_PINHOLE_LENS),
+  TR_ROW(TR_CAM_PINHOLE_LENS, TR_CAM_CAHV),
+  TR_ROW(TR_CAM_CAHV, TR_CAM_PINHOLE_LENS),
+};
+#undef TR_ROW
 
-// the instantiation for a camera pair, as 3 * (code of cam1) + (code of cam2): (0, 0) for two pinholes without lens
-// distortion, (1, 1) for other pinhole pairs, the three pairs with a CAHV camera, (3, 3) for two CAHVOR and (4, 4) for
-// two CAHVORE cameras (tr_check refuses every other pair with one of those).  Where a pinhole carries a lens other than
-// null and Tsai every pinhole of the pair takes the any-lens code: (5, 5), (5, 2) and (2, 5).
-int tr_cams_of(const vwgpu_camera& c1, const vwgpu_camera& c2) {
-  if (tr_new_kind(c1)) return c1.kind == VWGPU_CAMERA_CAHVOR ? 3 * TR_CAM_CAHVOR + TR_CAM_CAHVOR : 3 * TR_CAM_CAHVORE + TR_CAM_CAHVORE;
-  const bool cahv1 = c1.kind == VWGPU_CAMERA_CAHV, cahv2 = c2.kind == VWGPU_CAMERA_CAHV;
-  if (tr_lens_pinhole(c1) || tr_lens_pinhole(c2)) return 3 * (cahv1 ? TR_CAM_CAHV : TR_CAM_PINHOLE_LENS) + (cahv2 ? TR_CAM_CAHV : TR_CAM_PINHOLE_LENS);
-  if (!cahv1 && !cahv2 && c1.distortion_kind == VWGPU_DISTORTION_NULL && c2.distortion_kind == VWGPU_DISTORTION_NULL) return 0;
-  return 3 * (cahv1 ? TR_CAM_CAHV : TR_CAM_PINHOLE) + (cahv2 ? TR_CAM_CAHV : TR_CAM_PINHOLE);
+// the row of a camera pair, or nullptr.  The codes are those of tr_camera_code, but a pinhole takes the no-lens code only
+// when both cameras are pinholes without lens distortion: the common case carries no Newton loop.
+const tr_pair* tr_cams_of(const vwgpu_camera& c1, const vwgpu_camera& c2) {
+  const bool lens = tr_lens_pinhole(c1) || tr_lens_pinhole(c2);
+  int k1 = tr_camera_code(c1, lens), k2 = tr_camera_code(c2, lens);
+  if (k1 != k2) {
+    if (k1 == TR_CAM_PINHOLE_NULL) k1 = TR_CAM_PINHOLE;
+    if (k2 == TR_CAM_PINHOLE_NULL) k2 = TR_CAM_PINHOLE;
+  }
+  for (const tr_pair& row : tr_pairs)
+    if (row.cam1 == k1 && row.cam2 == k2) return &row;
+  return nullptr;
 }
 
 // the checks the triangulation and the convergence angle share; strides of 0 become the packed ones
@@ -364,10 +367,10 @@ int tr_check(vwgpu_ctx* ctx, const char* name, int type, const void* disp, int w
   const int sem = semantics & ~TR_LAYOUT_MASK;
   if (semantics < 0 || (sem != VWGPU_TRIANGULATE_VIEW && sem != VWGPU_TRIANGULATE_MODEL))
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "%s: semantics %d is neither view nor model, with a disparity layout", name, semantics);
-  int rc = tr_camera_check(ctx, name, cam1);
+  int rc = tr_camera_check(ctx, name, nullptr, cam1);
   if (rc) return rc;
-  if ((rc = tr_camera_check(ctx, name, cam2))) return rc;
-  if ((tr_new_kind(*cam1) || tr_new_kind(*cam2)) && cam1->kind != cam2->kind)
+  if ((rc = tr_camera_check(ctx, name, nullptr, cam2))) return rc;
+  if (!tr_cams_of(*cam1, *cam2))
     return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "%s: no kernel for the pair %s + %s: a CAHVOR or CAHVORE camera goes with one of its own kind", name,
                       tr_kind_name(*cam1), tr_kind_name(*cam2));
   if (dstride == 0) dstride = w;
@@ -398,10 +401,6 @@ int triangulate_check(vwgpu_ctx* ctx, int type, const void* disp, int w, int h, 
   return tr_out_stride(ctx, name, errvec, vstride, w);
 }
 
-int tr_cahv_flip(const vwgpu_camera& c) {   // CAHVORModel.cc:306 is the same test
-  return (c.kind == VWGPU_CAMERA_CAHV || c.kind == VWGPU_CAMERA_CAHVOR) && tr_dot(tr_cross(tr_load3(c.V), tr_load3(c.H)), tr_load3(c.A)) < 0.0;   // CAHVModel.cc:182
-}
-
 tr_args tr_make_args(int type, const void* d_disp, int w, int h, ptrdiff_t dstride, int x0, int y0, int semantics, const vwgpu_camera& cam1,
                      const vwgpu_camera& cam2) {
   tr_args a{};
@@ -415,35 +414,17 @@ tr_args tr_make_args(int type, const void* d_disp, int w, int h, ptrdiff_t dstri
   return a;
 }
 
-#define TR_LAUNCH_ONE(KERNEL, C1, C2, GRID, ...) \
-  hipLaunchKernelGGL((KERNEL<C1, C2>), (GRID), tr_block, 0, ctx->stream, __VA_ARGS__)
-#define TR_LAUNCH(KERNEL, CAMS, GRID, ...)                                                                         \
-  do {                                                                                                             \
-    switch (CAMS) {                                                                                                \
-      case 0: TR_LAUNCH_ONE(KERNEL, TR_CAM_PINHOLE_NULL, TR_CAM_PINHOLE_NULL, GRID, __VA_ARGS__); break;           \
-      case 4: TR_LAUNCH_ONE(KERNEL, TR_CAM_PINHOLE, TR_CAM_PINHOLE, GRID, __VA_ARGS__); break;                     \
-      case 5: TR_LAUNCH_ONE(KERNEL, TR_CAM_PINHOLE, TR_CAM_CAHV, GRID, __VA_ARGS__); break;                        \
-      case 7: TR_LAUNCH_ONE(KERNEL, TR_CAM_CAHV, TR_CAM_PINHOLE, GRID, __VA_ARGS__); break;                        \
-      case 12: TR_LAUNCH_ONE(KERNEL, TR_CAM_CAHVOR, TR_CAM_CAHVOR, GRID, __VA_ARGS__); break;                      \
-      case 16: TR_LAUNCH_ONE(KERNEL, TR_CAM_CAHVORE, TR_CAM_CAHVORE, GRID, __VA_ARGS__); break;                    \
-      case 20: TR_LAUNCH_ONE(KERNEL, TR_CAM_PINHOLE_LENS, TR_CAM_PINHOLE_LENS, GRID, __VA_ARGS__); break;          \
-      case 17: TR_LAUNCH_ONE(KERNEL, TR_CAM_PINHOLE_LENS, TR_CAM_CAHV, GRID, __VA_ARGS__); break;                  \
-      case 11: TR_LAUNCH_ONE(KERNEL, TR_CAM_CAHV, TR_CAM_PINHOLE_LENS, GRID, __VA_ARGS__); break;                  \
-      default: TR_LAUNCH_ONE(KERNEL, TR_CAM_CAHV, TR_CAM_CAHV, GRID, __VA_ARGS__); break;                          \
-    }                                                                                                              \
-    VWGPU_HIP(ctx, hipGetLastError());                                                                             \
-  } while (0)
-
 int triangulate_run(vwgpu_ctx* ctx, int type, const void* d_disp, int w, int h, ptrdiff_t dstride, int x0, int y0,
                     const vwgpu_camera* cam1, const vwgpu_camera* cam2, double angle_tol, int semantics, double* d_xyz, ptrdiff_t xstride,
                     double* d_error, ptrdiff_t estride, double* d_errvec, ptrdiff_t vstride, vwgpu_triangulate_stats* d_stats) {
   tr_args a = tr_make_args(type, d_disp, w, h, dstride, x0, y0, semantics, *cam1, *cam2);
   a.tol = angle_tol > 0 ? angle_tol : 1e-4;   // StereoModel.cc:81-83
   a.xyz = d_xyz; a.xstride = xstride; a.error = d_error; a.estride = estride; a.errvec = d_errvec; a.vstride = vstride;
-  const int cams = tr_cams_of(*cam1, *cam2);
+  const tr_pair* pair = tr_cams_of(*cam1, *cam2);
   vwgpu_prof_scope ps(ctx, "stereo_triangulate");
   if (!d_stats) {
-    TR_LAUNCH(tr_triangulate_kernel, cams, tr_grid(w, h), a, *cam1, *cam2);
+    hipLaunchKernelGGL(pair->triangulate, tr_grid(w, h), tr_block, 0, ctx->stream, a, *cam1, *cam2);
+    VWGPU_HIP(ctx, hipGetLastError());
     return VWGPU_OK;
   }
   const dim3 grid = tr_grid(w, h);
@@ -452,7 +433,8 @@ int triangulate_run(vwgpu_ctx* ctx, int type, const void* d_disp, int w, int h, 
   int rc = vwgpu_arena_reserve(ctx, &ctx->scratch, (size_t)(npartial + nfold) * sizeof(vwgpu_triangulate_stats));
   if (rc) return rc;
   a.partial = static_cast<vwgpu_triangulate_stats*>(ctx->scratch.base);
-  TR_LAUNCH(tr_triangulate_stats_kernel, cams, grid, a, *cam1, *cam2);
+  hipLaunchKernelGGL(pair->triangulate_stats, grid, tr_block, 0, ctx->stream, a, *cam1, *cam2);
+  VWGPU_HIP(ctx, hipGetLastError());
   if (nfold > 1) {
     vwgpu_triangulate_stats* second = a.partial + npartial;
     hipLaunchKernelGGL(tr_stats_fold_kernel, dim3((unsigned)nfold), dim3(TR_THREADS), 0, ctx->stream, a.partial, npartial, TR_FOLD_CHUNK, second);
@@ -477,9 +459,10 @@ int angle_run(vwgpu_ctx* ctx, int type, const void* d_disp, int w, int h, ptrdif
               const vwgpu_camera* cam2, int semantics, double* d_out, ptrdiff_t ostride) {
   tr_args a = tr_make_args(type, d_disp, w, h, dstride, x0, y0, semantics, *cam1, *cam2);
   a.error = d_out; a.estride = ostride;
-  const int cams = tr_cams_of(*cam1, *cam2);
+  const tr_pair* pair = tr_cams_of(*cam1, *cam2);
   vwgpu_prof_scope ps(ctx, "convergence_angle");
-  TR_LAUNCH(tr_angle_kernel, cams, tr_grid(w, h), a, *cam1, *cam2);
+  hipLaunchKernelGGL(pair->angle, tr_grid(w, h), tr_block, 0, ctx->stream, a, *cam1, *cam2);
+  VWGPU_HIP(ctx, hipGetLastError());
   return VWGPU_OK;
 }
 
@@ -527,56 +510,11 @@ int universe_run(vwgpu_ctx* ctx, const double* d_points, int channels, int w, in
   return VWGPU_OK;
 }
 
-// 3 x 3 helpers of vwgpu_pinhole_camera (row-major)
-void tr_mat_mul(const double* a, const double* b, double* out) {
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      double s = 0.0;
-      for (int k = 0; k < 3; ++k) s += a[i * 3 + k] * b[k * 3 + j];
-      out[i * 3 + j] = s;
-    }
-}
-void tr_mat_inverse(const double* m, double* out) {
-  const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
-  const double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
-  out[0] = c00 / det; out[1] = (m[2] * m[7] - m[1] * m[8]) / det; out[2] = (m[1] * m[5] - m[2] * m[4]) / det;
-  out[3] = c01 / det; out[4] = (m[0] * m[8] - m[2] * m[6]) / det; out[5] = (m[2] * m[3] - m[0] * m[5]) / det;
-  out[6] = c02 / det; out[7] = (m[1] * m[6] - m[0] * m[7]) / det; out[8] = (m[0] * m[4] - m[1] * m[3]) / det;
-}
-
 }  // namespace
 
 // ---- extern "C" entry points (include/vwgpu.h) -------------------------------------------------------------------------
 
 extern "C" {
-
-int vwgpu_pinhole_camera(const double* center, const double* rotation, double fu, double fv, double cu, double cv, const double* u_dir,
-                         const double* v_dir, const double* w_dir, double pixel_pitch, int distortion_kind, const double* distortion,
-                         vwgpu_camera* out) {
-  if (!center || !rotation || !u_dir || !v_dir || !w_dir || !out) return VWGPU_ERR_ARGUMENT;
-  if (distortion_kind != VWGPU_DISTORTION_NULL && distortion_kind != VWGPU_DISTORTION_TSAI) return VWGPU_ERR_ARGUMENT;
-  if (distortion_kind == VWGPU_DISTORTION_TSAI && !distortion) return VWGPU_ERR_ARGUMENT;
-  // the asserts of rebuild_camera_matrix (PinholeModel.cc:586-591)
-  const tr_v3 u = tr_load3(u_dir), v = tr_load3(v_dir), w = tr_load3(w_dir);
-  if (!(tr_dot(u, v) == 0) || !(tr_dot(u, w) == 0) || !(tr_dot(v, w) == 0)) return VWGPU_ERR_ARGUMENT;
-  if (!(fabs(tr_norm(u) - 1) < 0.001) || !(fabs(tr_norm(v) - 1) < 0.001) || !(fabs(tr_norm(w) - 1) < 0.001)) return VWGPU_ERR_ARGUMENT;
-  std::memset(out, 0, sizeof(*out));
-  out->kind = VWGPU_CAMERA_PINHOLE;
-  out->distortion_kind = distortion_kind;
-  std::memcpy(out->center, center, sizeof(out->center));
-  out->pixel_pitch = pixel_pitch;
-  out->fu = fu; out->fv = fv; out->cu = cu; out->cv = cv;
-  if (distortion) std::memcpy(out->distortion, distortion, sizeof(out->distortion));
-  const double uvw[9] = {u.x, u.y, u.z, v.x, v.y, v.z, w.x, w.y, w.z};
-  const double rt[9] = {rotation[0], rotation[3], rotation[6], rotation[1], rotation[4], rotation[7], rotation[2], rotation[5], rotation[8]};
-  const double k[9] = {fu, 0, cu, 0, fv, cv, 0, 0, 1};
-  double ext[9], ext_inv[9], k_inv[9];
-  tr_mat_mul(uvw, rt, ext);
-  tr_mat_inverse(ext, ext_inv);
-  tr_mat_inverse(k, k_inv);
-  tr_mat_mul(ext_inv, k_inv, out->inv_camera_transform);   // :604
-  return VWGPU_OK;
-}
 
 int vwgpu_stereo_triangulate_dev(vwgpu_ctx* ctx, int type, const void* d_disp, int w, int h, ptrdiff_t dstride, int x0, int y0,
                                  const vwgpu_camera* cam1, const vwgpu_camera* cam2, double angle_tol, int semantics, double* d_xyz,

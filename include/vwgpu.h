@@ -1015,6 +1015,115 @@ int vwgpu_camera_transform_points(vwgpu_ctx* ctx, const vwgpu_camera* src_camera
                                   const vwgpu_camera* dst_camera, const double* dst_matrix, int direction, int check, const double* points,
                                   long long n, double* out, long long* failed);
 
+/* ---- vw::transform: closed-form 2-D maps, interpolations, edge extensions ------------------------------ */
+
+/* The map functors of src/vw/Math/Transform.h:231-443 as plain descriptors, in fp64 and in the reference's expression
+ * order, with only + - * /:
+ *   IDENTITY    p                                                                     (IdentityTransform, :231-237)
+ *   TRANSLATE   forward p + (fwd[0], fwd[1]); reverse p - (rev[0], rev[1])            (TranslateTransform, :281-287)
+ *   RESAMPLE    forward p * (fwd[0], fwd[1]); reverse p / (rev[0], rev[1]): a division, no reciprocal
+ *                                                                                     (ResampleTransform, :256-262)
+ *   AFFINE      forward (fwd[0] x + fwd[1] y + fwd[4], fwd[2] x + fwd[3] y + fwd[5]); reverse px = x - rev[4],
+ *               py = y - rev[5], (rev[0] px + rev[1] py, rev[2] px + rev[3] py): fwd holds the matrix, rev its inverse,
+ *               both the offset (AffineTransform, :329-339; LinearTransform is the offset 0, RotateTransform the words
+ *               of vwgpu_transform_rotate)
+ *   HOMOGRAPHY  w = m[6] x + m[7] y + m[8] first, then ((m[0] x + m[1] y + m[2]) / w, (m[3] x + m[4] y + m[5]) / w)
+ *               with m = fwd (H, row-major) for forward and m = rev (its inverse) for reverse
+ *                                                                                     (HomographyTransform, :377-387)
+ * A caller may fill the struct by hand (a homography known by its inverse alone: rev, and fwd unused by images).
+ * reserved is 0; vwgpu_transform_invert leaves 1 there, which makes forward and reverse change places
+ * (InverseTransform, :394-411).  Words a kind does not name are ignored. */
+typedef enum vwgpu_transform_kind {
+  VWGPU_TRANSFORM_IDENTITY = 0, VWGPU_TRANSFORM_TRANSLATE = 1, VWGPU_TRANSFORM_RESAMPLE = 2, VWGPU_TRANSFORM_AFFINE = 3,
+  VWGPU_TRANSFORM_HOMOGRAPHY = 4
+} vwgpu_transform_kind;
+/* NearestPixelInterpolation, BilinearInterpolation, BicubicInterpolation (src/vw/Image/Interpolation.h:75-225) */
+typedef enum vwgpu_transform_interp {
+  VWGPU_TRANSFORM_INTERP_NEAREST = 0, VWGPU_TRANSFORM_INTERP_BILINEAR = 1, VWGPU_TRANSFORM_INTERP_BICUBIC = 2
+} vwgpu_transform_interp;
+/* Zero, Value, Constant, Periodic, Cylindrical, Reflect and LinearEdgeExtension (src/vw/Image/EdgeExtension.tcc:47-272).
+ * An enum of its own: vwgpu_edge keeps its two values. */
+typedef enum vwgpu_transform_edge {
+  VWGPU_TRANSFORM_EDGE_ZERO = 0, VWGPU_TRANSFORM_EDGE_VALUE = 1, VWGPU_TRANSFORM_EDGE_CONSTANT = 2, VWGPU_TRANSFORM_EDGE_PERIODIC = 3,
+  VWGPU_TRANSFORM_EDGE_CYLINDRICAL = 4, VWGPU_TRANSFORM_EDGE_REFLECT = 5, VWGPU_TRANSFORM_EDGE_LINEAR = 6
+} vwgpu_transform_edge;
+typedef enum vwgpu_transform_direction { VWGPU_TRANSFORM_FORWARD = 0, VWGPU_TRANSFORM_REVERSE = 1 } vwgpu_transform_direction;
+typedef struct vwgpu_transform {
+  int kind;       /* vwgpu_transform_kind */
+  int reserved;   /* 0; 1 after vwgpu_transform_invert */
+  double fwd[9];
+  double rev[9];
+} vwgpu_transform;
+/* How vwgpu_transform_image samples: the interpolation and the edge extension of interpolate(v, interp, edge)
+ * (src/vw/Image/Interpolation.h:228-310), and the switch of transform_nodata (src/vw/Image/Transform.h:401-437, :606-618). */
+typedef struct vwgpu_transform_params {
+  int interp;           /* vwgpu_transform_interp */
+  int edge;             /* vwgpu_transform_edge */
+  float edge_value;     /* the pixel of ValueEdgeExtension (other kinds ignore it) ... */
+  int edge_valid;       /* ... and its validity in a masked call */
+  int nodata;           /* nonzero: TransformViewNoData */
+  float nodata_value;   /* the nodata pixel ... */
+  int nodata_valid;     /* ... and its validity in a masked call */
+} vwgpu_transform_params;
+
+/* The descriptor of one map (src/vw/Math/Transform.h:231-389).  params, n:  IDENTITY none, 0;  TRANSLATE {tx, ty};
+ * RESAMPLE {fx, fy};  AFFINE {a, b, c, d, x, y} (the matrix row-major, then the offset);  HOMOGRAPHY row-major H[9].
+ * The inverse matrix is the plain adjugate over the determinant (the bits of the reference's inverse() are not pinned).
+ * A determinant that is 0 or not finite, a parameter that is not finite, a resample factor of 0, a wrong n, an unknown
+ * kind or a null pointer: VWGPU_ERR_ARGUMENT, out unchanged.  Pure host arithmetic, no context. */
+int vwgpu_transform_make(int kind, const double* params, int n, vwgpu_transform* out);
+/* RotateTransform(theta, (cx, cy)) (src/vw/Math/Transform.h:351-362): the affine map with the matrix (c, -s, s, c) of
+ * cos and sin on the host and the offset translate - rotate * translate.  Pure host arithmetic, no context. */
+int vwgpu_transform_rotate(double theta, double cx, double cy, vwgpu_transform* out);
+/* InverseTransform (src/vw/Math/Transform.h:394-411): forward and reverse change places.  out may be in. */
+int vwgpu_transform_invert(const vwgpu_transform* in, vwgpu_transform* out);
+/* forward or reverse of a chain of 1 to 4 maps on count points (x, y double pairs) with the functions the kernel runs.
+ * The chain is compose(steps[0], compose(steps[1], ...)) (src/vw/Math/Transform.h:429-443): reverse applies the steps'
+ * reverse in array order, forward their forward from the last to the first.  out == points is allowed.  A null pointer,
+ * n_steps outside 1..4, a kind or direction out of range, count < 0: VWGPU_ERR_ARGUMENT.  Pure host arithmetic, no context. */
+int vwgpu_transform_points(const vwgpu_transform* steps, int n_steps, int direction, const double* points, long long count, double* out);
+
+/* Replaces rasterising transform(image, tx, w, h, edge, interp) and transform_nodata(...) (src/vw/Image/Transform.h:335-387,
+ * :401-437, :485-618) for a float image with an optional validity mask (PixelMask<float>), and with them resample, resize,
+ * translate and rotate (:624-843).
+ *   src          sw x sh floats; src_mask optional uint8 of the same size (0 = invalid); strides in elements, 0 = packed
+ *   steps        HOST array of n_steps (1..4) maps, the chain of vwgpu_transform_points
+ *   params       HOST vwgpu_transform_params
+ *   w, h         output size; x0, y0 the image coordinates of output pixel (0, 0): a tile equals that region of the whole call
+ *   out          w x h floats; out_mask uint8 (255 valid, 0 invalid), present exactly when src_mask is
+ * Output pixel p = (x0 + x, y0 + y): TransformView::operator() (:362-365), q = reverse(p) in double, then the
+ * interpolation of the edge-extended source at q (src/vw/Image/Interpolation.h:75-225):
+ *   NEAREST   the pixel at (_round(q.x), _round(q.y)), _round(v) = int32(v - 0.5) for v < 0 and int32(v + 0.5) otherwise
+ *             (src/vw/Math/Functions.h:48-51)
+ *   BILINEAR  exactly as vwgpu_disparity_warp computes it: the pixel itself at an integer position, otherwise four taps
+ *             weighted in float, every product and sum rounded on its own (:83-105)
+ *   BICUBIC   the pixel itself at an integer position; otherwise the weights s0..s3, t0..t3 in double from
+ *             normx = q.x - floor q.x, four row sums of four double * float products from left to right over the taps
+ *             (x-1, y-1) .. (x+2, y+2), t0 row0 + t1 row1 + t2 row2 + t3 row3 in that order, * 0.25, one conversion to
+ *             float (:143-184)
+ * Taps outside the source come from the edge extension (src/vw/Image/EdgeExtension.tcc:47-272), each kind with the
+ * reference's integer index arithmetic, LINEAR with its float extrapolation in the reference's expression order.
+ * With a mask the value is formed from the tap values whatever their validity and is valid only if every tap used is
+ * (src/vw/Image/PixelMask.h:321-345, :424-433): 1 tap at an integer position and for NEAREST, else 4 or 16; a ZERO tap
+ * outside is {0, invalid}, a VALUE tap {edge_value, edge_valid}.
+ * params->nodata (TransformViewNoData, :430-437): with b = 1 for NEAREST and BILINEAR and 2 for BICUBIC the output is
+ * {nodata_value, nodata_valid} where q.x < b - 1 || q.x >= sw - b || q.y < b - 1 || q.y >= sh - b, compared in double; a
+ * NaN passes none of them and is interpolated.
+ * A coordinate of q that is NaN or beyond +-2^30 has an undefined int32 conversion in the reference: 0 here, and
+ * {0, invalid} with a mask, for every edge kind.
+ * VWGPU_ERR_ARGUMENT before any device work: null src / out / steps / params, sizes <= 0, a stride below the width,
+ * n_steps outside 1..4, a kind, interp or edge out of range, one mask without the other, out or out_mask aliasing an
+ * input or each other, a NaN edge_value (with VALUE) or nodata_value (with nodata) that is marked valid, REFLECT on a
+ * source with a side of 1 (a % 0 in the reference) or above 2^30, LINEAR on a side below 2 (it reads outside the
+ * image).  LINEAR with a mask is VWGPU_ERR_NOIMPL; every other edge works masked.  No atomics, no counters, and the _dev
+ * entry does not synchronise. */
+int vwgpu_transform_image_dev(vwgpu_ctx* ctx, const float* d_src, int sw, int sh, ptrdiff_t sstride, const uint8_t* d_src_mask,
+                              ptrdiff_t mstride, const vwgpu_transform* steps, int n_steps, const vwgpu_transform_params* params, int w,
+                              int h, int x0, int y0, float* d_out, ptrdiff_t ostride, uint8_t* d_out_mask, ptrdiff_t omstride);
+int vwgpu_transform_image(vwgpu_ctx* ctx, const float* src, int sw, int sh, ptrdiff_t sstride, const uint8_t* src_mask, ptrdiff_t mstride,
+                          const vwgpu_transform* steps, int n_steps, const vwgpu_transform_params* params, int w, int h, int x0, int y0,
+                          float* out, ptrdiff_t ostride, uint8_t* out_mask, ptrdiff_t omstride);
+
 /* ---- disparity clean-up filters and the zone scheduler ------------------------------------------------- */
 
 /* Replaces rasterising vw::stereo::rm_outliers_using_thresh (cleanup == 0) or

@@ -1,0 +1,15 @@
+# transform_view: the C++ surface of vw::transform (vwlite vw/Transform.h) on libvwgpu.so, as a stand-alone program
+# (test infrastructure only); make -f transform_view.mk.
+CXX ?= g++
+ROOT := ../..
+LIBDIR := $(ROOT)/visionworkbench_amd/lib
+CXXFLAGS ?= -O1 -std=c++17 -Wall -ffp-contract=off
+VWLITE := $(ROOT)/visionworkbench_amd/vwlite
+
+all: transform_view
+
+transform_view: transform_view.cc $(wildcard $(VWLITE)/vw/*.h) $(ROOT)/include/vwgpu.h
+	$(CXX) $(CXXFLAGS) -I$(ROOT)/include -I$(VWLITE) -o $@ transform_view.cc -L$(LIBDIR) -lvwgpu -Wl,-rpath,$(abspath $(LIBDIR)) -Wl,-rpath,/opt/rocm/lib -pthread
+
+clean:
+	rm -f transform_view

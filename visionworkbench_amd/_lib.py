@@ -38,6 +38,8 @@ SYMBOLS = [
     "vwgpu_pinhole_camera_matrix", "vwgpu_epipolar_pinhole", "vwgpu_epipolar_cahv",
     "vwgpu_camera_transform_dev", "vwgpu_camera_transform", "vwgpu_camera_transform_points_dev", "vwgpu_camera_transform_points",
     "vwgpu_cahvor_camera", "vwgpu_cahvore_camera", "vwgpu_linearize_camera", "vwgpu_camera_set_lens", "vwgpu_lens_coordinates",
+    "vwgpu_transform_make", "vwgpu_transform_rotate", "vwgpu_transform_invert", "vwgpu_transform_points",
+    "vwgpu_transform_image_dev", "vwgpu_transform_image",
     "vwgpu_disparity_filter_dev", "vwgpu_disparity_filter",
     "vwgpu_disparity_mask_dev", "vwgpu_disparity_mask",
     "vwgpu_subdivide_regions",
@@ -66,6 +68,17 @@ class Camera(ctypes.Structure):
         ("fu", ctypes.c_double), ("fv", ctypes.c_double), ("cu", ctypes.c_double), ("cv", ctypes.c_double),
         ("distortion", ctypes.c_double * 5), ("A", ctypes.c_double * 3), ("H", ctypes.c_double * 3), ("V", ctypes.c_double * 3),
     ]
+
+
+class Transform(ctypes.Structure):
+    """struct vwgpu_transform (include/vwgpu.h)."""
+    _fields_ = [("kind", ctypes.c_int), ("reserved", ctypes.c_int), ("fwd", ctypes.c_double * 9), ("rev", ctypes.c_double * 9)]
+
+
+class TransformParams(ctypes.Structure):
+    """struct vwgpu_transform_params (include/vwgpu.h)."""
+    _fields_ = [("interp", ctypes.c_int), ("edge", ctypes.c_int), ("edge_value", ctypes.c_float), ("edge_valid", ctypes.c_int),
+                ("nodata", ctypes.c_int), ("nodata_value", ctypes.c_float), ("nodata_valid", ctypes.c_int)]
 
 
 class TriangulateStats(ctypes.Structure):
@@ -244,6 +257,14 @@ def load():
     ctp = [P, CP, P, CP, P, I, I, P, ctypes.c_longlong, P, P]
     lib.vwgpu_camera_transform_points_dev.argtypes = ctp
     lib.vwgpu_camera_transform_points.argtypes = ctp
+    TP = ctypes.POINTER(Transform)
+    lib.vwgpu_transform_make.argtypes = [I, P, I, TP]
+    lib.vwgpu_transform_rotate.argtypes = [D, D, D, TP]
+    lib.vwgpu_transform_invert.argtypes = [TP, TP]
+    lib.vwgpu_transform_points.argtypes = [P, I, I, P, ctypes.c_longlong, P]
+    tfi = [P, P, I, I, PD, P, PD, P, I, ctypes.POINTER(TransformParams), I, I, I, I, P, PD, P, PD]
+    lib.vwgpu_transform_image_dev.argtypes = tfi
+    lib.vwgpu_transform_image.argtypes = tfi
     df = [P, P, I, I, I, I, D, D, I, P]
     lib.vwgpu_disparity_filter_dev.argtypes = df
     lib.vwgpu_disparity_filter.argtypes = df

@@ -1124,6 +1124,102 @@ int vwgpu_transform_image(vwgpu_ctx* ctx, const float* src, int sw, int sh, ptrd
                           const vwgpu_transform* steps, int n_steps, const vwgpu_transform_params* params, int w, int h, int x0, int y0,
                           float* out, ptrdiff_t ostride, uint8_t* out_mask, ptrdiff_t omstride);
 
+/* ---- vw::ip matching and the RANSAC alignment of vw::math ------------------------------------------------ */
+
+typedef enum vwgpu_ip_metric { VWGPU_IP_METRIC_L2 = 0, VWGPU_IP_METRIC_HAMMING = 1 } vwgpu_ip_metric;
+typedef enum vwgpu_ip_mode { VWGPU_IP_MODE_SIMPLE = 0, VWGPU_IP_MODE_KNN = 1 } vwgpu_ip_mode;
+typedef enum vwgpu_ip_constraint {
+  VWGPU_IP_CONSTRAINT_NONE = 0, VWGPU_IP_CONSTRAINT_SCALE_ORIENTATION = 1, VWGPU_IP_CONSTRAINT_POSITION = 2
+} vwgpu_ip_constraint;
+typedef struct vwgpu_ip_match_params {
+  int metric;          /* vwgpu_ip_metric */
+  int mode;            /* vwgpu_ip_mode */
+  double threshold;    /* m_threshold */
+  int constraint;      /* vwgpu_ip_constraint; read in KNN mode only (InterestPointMatcherSimple never calls its constraint) */
+  int bidirectional;   /* KNN: the constraint is checked both ways (src/vw/InterestPoint/Matcher.h:262-276) */
+  double bounds[4];    /* scale_ratio_min, scale_ratio_max, ori_diff_min, ori_diff_max | min_x, max_x, min_y, max_y */
+} vwgpu_ip_match_params;
+
+/* The number of list-2 candidates one workgroup searches for n2 candidates in all; the partial results of the chunks are
+ * merged by a second kernel.  Tests place their scenes at its multiples. */
+int vwgpu_ip_match_chunk(int n2);
+
+/* Replaces InterestPointMatcherSimple (VWGPU_IP_MODE_SIMPLE, src/vw/InterestPoint/Matcher.h:435-508) and the index-list
+ * call of InterestPointMatcher (VWGPU_IP_MODE_KNN, :282-386), the latter with an exact two-nearest search where the
+ * reference asks FLANN.
+ *   desc1, desc2   n1 x k and n2 x k descriptors: float for L2, uint8 for HAMMING; stride1 / stride2 elements between rows
+ *                  (0 = k), so a matrix may be a column slice of a wider one.  k is 1 .. 512.
+ *   pol1, pol2     uint8 polarity per point, both or neither; neither means all equal.  SIMPLE skips a candidate whose
+ *                  byte differs from the query's; KNN does not read them.
+ *   attr1, attr2   float[n][4] = x, y, scale, orientation; needed in KNN mode with a constraint other than NONE
+ *   params         HOST vwgpu_ip_match_params
+ *   index          int32[n1]: the matched row of list 2, or -1
+ *   dist           optional float[n1][2]: the smallest and the second smallest distance, +inf where there is none
+ *   stats          optional HOST long long[2] = {matched, queries}; asking for it makes the _dev entry synchronise
+ * Distances.  L2 (L2NormMetric, Matcher.cc:34-44): one float accumulator, dist += (a[k] - b[k]) * (a[k] - b[k]) for
+ * k = 0 .. K-1 in that order, each operation rounded to float, no contraction.  HAMMING (HammingMetric, :47-102): the bit
+ * count of the XOR of the bytes, as a float (exact).
+ * SIMPLE: first_pick is the smallest and second_pick the second smallest distance of the multiset over the candidates
+ * of equal polarity (a duplicate of the minimum is the second), the index the lowest j that attains the minimum; a
+ * missing pick is 1e100; no match when first_pick > threshold * second_pick, in double.  KNN: no polarity test; fewer
+ * than two candidates means no match; otherwise the constraint (ScaleOrientationConstraint, PositionConstraint,
+ * Matcher.cc:119-147: float quotient and differences compared in double, the orientation difference wrapped by 2 pi
+ * once) is checked with the nearest candidate as baseline_ip and the query as test_ip, with `bidirectional` also the
+ * other way round, and the match is accepted when (double)dist0 < threshold * (double)dist1.  Ties go to the lowest
+ * index.  A distance that is NaN or +inf is never picked, in either mode.
+ * Deviation: where the KNN constraint fails the reference pushes nothing, so that its index list comes out short and
+ * later entries shift; here the entry of that point is -1.
+ * VWGPU_ERR_ARGUMENT before any device work: a null desc1 / desc2 / params / index, n1 / n2 / k < 1, a stride below k,
+ * an unknown metric, mode or constraint, a NaN threshold, one polarity list without the other, a constraint in KNN
+ * mode without attr1 and attr2, index or dist equal to an input or to each other.  k > 512: VWGPU_ERR_NOIMPL. */
+int vwgpu_ip_match_dev(vwgpu_ctx* ctx, const void* d_desc1, int n1, ptrdiff_t stride1, const void* d_desc2, int n2, ptrdiff_t stride2,
+                       int k, const uint8_t* d_pol1, const uint8_t* d_pol2, const float* d_attr1, const float* d_attr2,
+                       const vwgpu_ip_match_params* params, int32_t* d_index, float* d_dist, long long* stats);
+int vwgpu_ip_match(vwgpu_ctx* ctx, const void* desc1, int n1, ptrdiff_t stride1, const void* desc2, int n2, ptrdiff_t stride2, int k,
+                   const uint8_t* pol1, const uint8_t* pol2, const float* attr1, const float* attr2,
+                   const vwgpu_ip_match_params* params, int32_t* index, float* dist, long long* stats);
+
+/* The entries below run on the host and take no context.  Each clears, and on failure sets, a detail text kept per
+ * calling thread: vwgpu_host_last_error() returns it ("" after a success). */
+const char* vwgpu_host_last_error(void);
+
+/* remove_duplicates (src/vw/InterestPoint/Matcher.cc:152-195) of n matched pairs: xy1, xy2 float[n][2].  Walking from
+ * the last pair to the first, a pair is kept only if neither its list-1 (x, y) nor its list-2 (x, y) was kept before (a
+ * skipped pair blocks nothing).  keep: uint8[n], 1 = kept; the kept pairs in input order are the result.  n >= 0. */
+int vwgpu_ip_remove_duplicates(const float* xy1, const float* xy2, long long n, uint8_t* keep, long long* n_kept);
+
+typedef enum vwgpu_fit_kind { VWGPU_FIT_SIMILARITY = 0, VWGPU_FIT_AFFINE = 1, VWGPU_FIT_HOMOGRAPHY = 2 } vwgpu_fit_kind;
+
+/* SimilarityFittingFunctor, AffineFittingFunctor, HomographyFittingFunctor (src/vw/Math/Geometry.h:50-351): the row-major
+ * 3 x 3 matrix H that takes p1 to p2, both double[n][2]; n >= 3, 3, 4.
+ *   SIMILARITY  literally :305-347: the scale is the ratio of the mean distances to the centroids, the rotation
+ *               transpose(VT) * transpose(U) of the SVD of the 2 x 2 cross-covariance sum (p1 - m1)(p2 - m2)^T, with no
+ *               determinant fix (a reflection comes out as one), the translation m2 - scale * R * m1
+ *   AFFINE      the least-squares problem of :222-270 (normal equations on centred points)
+ *   HOMOGRAPHY  n == 4: the normalised DLT divided by H(2,2) (:136-147).  n > 4: the minimum of
+ *               sum |p2 - proj(H p1)|^2 over the first eight entries with H(2,2) = 1, by damped Gauss-Newton from `seed`
+ *               (double[9]), or from the DLT of the first four pairs when seed is null (:149-190)
+ * The reference calls LAPACK and its own Levenberg-Marquardt; results agree to rounding and conditioning, not bit for bit.
+ * VWGPU_ERR_ARGUMENT: null pointers, too few pairs, an unknown kind, coordinates that are not finite; VWGPU_ERR_LOGIC: a
+ * degenerate configuration (all points equal, four points with three in a line). */
+int vwgpu_fit_transform(int kind, const double* p1, const double* p2, long long n, const double* seed, double* H);
+
+/* RandomSampleConsensus<FitT, HomogeneousL2NormErrorMetric<2>> (src/vw/Math/RANSAC.h:77-100, :212-330).
+ *   samples       int32[iterations][m], m = 3 for SIMILARITY and AFFINE, 4 for HOMOGRAPHY: the rows to fit in every
+ *                 iteration.  The reference draws them with an unseeded rand() (:139-155); here the caller does.
+ *   inlier_flags  optional uint8[n]: inlier_indices of the returned H;  num_inliers optional: their count
+ * Per iteration: fit the sampled rows, take the inliers by error < inlier_threshold, skip with fewer than min_inliers,
+ * refit on the inliers with the first fit as seed, take the mean inlier error; the lowest mean wins, the earliest
+ * iteration on a tie (the reference's OpenMP order is unspecified).  An iteration whose fit is degenerate is skipped.
+ * reduce_if_no_fit: up to ten attempts with min_inliers = int(min_inliers / 1.5), stopping below 2 (:212-243).
+ * Deviation: the same table serves every attempt, where the reference draws afresh.
+ * VWGPU_ERR_ARGUMENT: null pointers, n < m, iterations < 1, min_inliers < m, a NaN threshold, a row of `samples` with a
+ * repeated or out-of-range index.  VWGPU_ERR_LOGIC with the text "RANSAC was unable to find a fit that matched the
+ * supplied data." when no attempt finds a model. */
+int vwgpu_ransac(int kind, const double* p1, const double* p2, long long n, const int32_t* samples, int iterations,
+                 double inlier_threshold, int min_inliers, int reduce_if_no_fit, double* H, uint8_t* inlier_flags,
+                 long long* num_inliers);
+
 /* ---- disparity clean-up filters and the zone scheduler ------------------------------------------------- */
 
 /* Replaces rasterising vw::stereo::rm_outliers_using_thresh (cleanup == 0) or

@@ -40,6 +40,7 @@ SYMBOLS = [
     "vwgpu_cahvor_camera", "vwgpu_cahvore_camera", "vwgpu_linearize_camera", "vwgpu_camera_set_lens", "vwgpu_lens_coordinates",
     "vwgpu_transform_make", "vwgpu_transform_rotate", "vwgpu_transform_invert", "vwgpu_transform_points",
     "vwgpu_transform_image_dev", "vwgpu_transform_image",
+    "vwgpu_ip_match_chunk", "vwgpu_ip_match_dev", "vwgpu_ip_match", "vwgpu_host_last_error", "vwgpu_ip_remove_duplicates", "vwgpu_fit_transform", "vwgpu_ransac",
     "vwgpu_disparity_filter_dev", "vwgpu_disparity_filter",
     "vwgpu_disparity_mask_dev", "vwgpu_disparity_mask",
     "vwgpu_subdivide_regions",
@@ -79,6 +80,12 @@ class TransformParams(ctypes.Structure):
     """struct vwgpu_transform_params (include/vwgpu.h)."""
     _fields_ = [("interp", ctypes.c_int), ("edge", ctypes.c_int), ("edge_value", ctypes.c_float), ("edge_valid", ctypes.c_int),
                 ("nodata", ctypes.c_int), ("nodata_value", ctypes.c_float), ("nodata_valid", ctypes.c_int)]
+
+
+class IpMatchParams(ctypes.Structure):
+    """struct vwgpu_ip_match_params (include/vwgpu.h)."""
+    _fields_ = [("metric", ctypes.c_int), ("mode", ctypes.c_int), ("threshold", ctypes.c_double), ("constraint", ctypes.c_int),
+                ("bidirectional", ctypes.c_int), ("bounds", ctypes.c_double * 4)]
 
 
 class TriangulateStats(ctypes.Structure):
@@ -265,6 +272,15 @@ def load():
     tfi = [P, P, I, I, PD, P, PD, P, I, ctypes.POINTER(TransformParams), I, I, I, I, P, PD, P, PD]
     lib.vwgpu_transform_image_dev.argtypes = tfi
     lib.vwgpu_transform_image.argtypes = tfi
+    lib.vwgpu_ip_match_chunk.argtypes = [I]
+    ipm = [P, P, I, PD, P, I, PD, I, P, P, P, P, ctypes.POINTER(IpMatchParams), P, P, P]
+    lib.vwgpu_ip_match_dev.argtypes = ipm
+    lib.vwgpu_ip_match.argtypes = ipm
+    lib.vwgpu_host_last_error.argtypes = []
+    lib.vwgpu_host_last_error.restype = ctypes.c_char_p
+    lib.vwgpu_ip_remove_duplicates.argtypes = [P, P, ctypes.c_longlong, P, P]
+    lib.vwgpu_fit_transform.argtypes = [I, P, P, ctypes.c_longlong, P, P]
+    lib.vwgpu_ransac.argtypes = [I, P, P, ctypes.c_longlong, P, I, D, I, I, P, P, P]
     df = [P, P, I, I, I, I, D, D, I, P]
     lib.vwgpu_disparity_filter_dev.argtypes = df
     lib.vwgpu_disparity_filter.argtypes = df

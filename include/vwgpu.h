@@ -37,7 +37,8 @@ extern "C" {
  *     of version 2 changed, but observable behaviour did (VWGPU_PATH_CERTIFIED where a version-2 host saw VWGPU_PATH_EXACT_ORDER), and hosts
  *     compare versions for EQUALITY: a host built against version 2 refuses this library and is rebuilt against this header.
  *     Round 6 added option values only (VWGPU_OPT_SGM_PATH_MODE, VWGPU_OPT_SAD_GROUPS = 3): same version.
- *     VWGPU_OPT_SAD_LAYOUT, VWGPU_OPT_SAD_LAST_LAUNCH, VWGPU_OPT_SAD_ROUND_SLOTS (options 20, 21, 22) likewise.
+ *     VWGPU_OPT_SAD_LAYOUT, VWGPU_OPT_SAD_LAST_LAUNCH, VWGPU_OPT_SAD_ROUND_SLOTS (options 20, 21, 22) likewise, and
+ *     VWGPU_OPT_IP_SCRATCH_MB (23) with the interest-point entries.
  * A host checks vwgpu_abi_version() == VWGPU_ABI_VERSION once after loading the library (vw::engine does, vw/Engine.h). */
 #define VWGPU_ABI_VERSION 3
 
@@ -52,7 +53,8 @@ typedef enum vwgpu_status {
   VWGPU_ERR_NOIMPL = -2,
   VWGPU_ERR_HIP = -3,
   VWGPU_ERR_NOMEM = -4,
-  VWGPU_ERR_LOGIC = -5
+  VWGPU_ERR_LOGIC = -5,
+  VWGPU_ERR_CAPACITY = -6   /* an output segment is too small; the call's counts say how large it must be */
 } vwgpu_status;
 
 /* vw::stereo::CostFunctionType, src/vw/Stereo/CostFunctions.h:143-149 (same numeric values). */
@@ -137,6 +139,8 @@ const char* vwgpu_last_error(const vwgpu_ctx* ctx);
  *       small grids reach the round logic of the kernels a large image runs.  Timing only; same results.  For tests and tools.
  *   VWGPU_OPT_EXACT_SCRATCH_MB scratch budget of the exact-order path in MiB (16 .. 65536, default 4096): column-sum volumes
  *       beyond it are swept in row bands / zone groups / disparity groups.
+ *   VWGPU_OPT_IP_SCRATCH_MB    scratch budget of vwgpu_ip_detect in MiB (1 .. 65536, default 1024): the tiles of a call are taken in
+ *       batches whose integral images, interest planes and candidate lists fit it (at least one tile per batch).  Same results.
  *   VWGPU_OPT_TRACE            bit 0: host-side timeline of a pyramid tile on stderr, bit 1: the zone shapes of a level, bit 2: certification
  *       statistics of every tile (one host round trip per tile; VWGPU_OPT_CERT_PERMILLE reads the running total).
  *   VWGPU_OPT_CERTIFY          pyramid levels whose box sums could round (prefiltered imagery, float imagery, deep levels under SSD / NCC): 1
@@ -181,7 +185,8 @@ typedef enum vwgpu_option {
   VWGPU_OPT_TRACE = 5, VWGPU_OPT_SGM_SWEEP = 6, /* 7: removed in ABI 2 */ VWGPU_OPT_MGM_SWEEP = 8, VWGPU_OPT_EXACT_SPLIT = 9,
   /* 10: removed in ABI 2 */ VWGPU_OPT_HOST_RING_KB = 11, VWGPU_OPT_HOST_RING_WRAPS = 12, VWGPU_OPT_CERTIFY = 13,
   VWGPU_OPT_CERT_PERMILLE = 14, VWGPU_OPT_ZONE_SXC = 15, VWGPU_OPT_CERT_F32 = 16, VWGPU_OPT_CERT_F64_PERMILLE = 17, VWGPU_OPT_ZONE_TILE16 = 18,
-  VWGPU_OPT_SGM_PATH_MODE = 19, VWGPU_OPT_SAD_LAYOUT = 20, VWGPU_OPT_SAD_LAST_LAUNCH = 21, VWGPU_OPT_SAD_ROUND_SLOTS = 22
+  VWGPU_OPT_SGM_PATH_MODE = 19, VWGPU_OPT_SAD_LAYOUT = 20, VWGPU_OPT_SAD_LAST_LAUNCH = 21, VWGPU_OPT_SAD_ROUND_SLOTS = 22,
+  VWGPU_OPT_IP_SCRATCH_MB = 23
 } vwgpu_option;
 int vwgpu_set_option(vwgpu_ctx* ctx, int option, int value);
 int vwgpu_get_option(const vwgpu_ctx* ctx, int option, int* value);
@@ -1219,6 +1224,89 @@ int vwgpu_fit_transform(int kind, const double* p1, const double* p2, long long 
 int vwgpu_ransac(int kind, const double* p1, const double* p2, long long n, const int32_t* samples, int iterations,
                  double inlier_threshold, int min_inliers, int reduce_if_no_fit, double* H, uint8_t* inlier_flags,
                  long long* num_inliers);
+
+/* ---- vw::ip detection: IntegralImage, the OBALoG detectors and their orientation --------------------------- */
+
+/* Replaces IntegralImage(source) (src/vw/InterestPoint/IntegralImage.h:43-91): out is (w + 1) x (h + 1) floats with row 0
+ * and column 0 zero and out(x + 1, y + 1) = ((src(x, y) + out(x, y + 1)) + out(x + 1, y)) - out(x, y), every operation
+ * rounded to float in that order: the reference's words, not those of a prefix sum.  Strides in elements (0 = dense).
+ * VWGPU_ERR_ARGUMENT: null pointers, an empty image, a stride below the width, out == src. */
+int vwgpu_integral_image_dev(vwgpu_ctx* ctx, const float* d_src, int w, int h, ptrdiff_t sstride, float* d_out, ptrdiff_t ostride);
+int vwgpu_integral_image(vwgpu_ctx* ctx, const float* src, int w, int h, ptrdiff_t sstride, float* out, ptrdiff_t ostride);
+
+typedef enum vwgpu_ip_detector { VWGPU_IP_DETECTOR_IAGD = 0, VWGPU_IP_DETECTOR_OBALOG = 1 } vwgpu_ip_detector;
+typedef struct vwgpu_ip_detect_params {
+  int detector;        /* vwgpu_ip_detector: IntegralAutoGainDetector | IntegralInterestPointDetector */
+  int scales;          /* m_scales, 1 .. 8; fewer than 3 give no points */
+  double threshold;    /* OBALoGInterestOperator's m_threshold; IAGD constructs its operator with 0 */
+  int max_points;      /* m_max_points; <= 0: no limit */
+  int reserved;        /* 0 */
+} vwgpu_ip_detect_params;
+/* The fields of vw::ip::InterestPoint that a detector sets, as arrays (polarity, octave and scale_lvl stay 0). */
+typedef struct vwgpu_ip_points {
+  float *x, *y;
+  int32_t *ix, *iy;
+  float *orientation, *scale, *interest;
+} vwgpu_ip_points;
+
+/* Replaces IntegralAutoGainDetector::process_image and IntegralInterestPointDetector::process_image
+ * (src/vw/InterestPoint/IntegralDetector.cc:150-245, :264-370) on every tile of detect_interest_points
+ * (DetectorBase.h:225-236, :267-296): a tile is an independent crop with its own integral image, and its points are
+ * shifted by its origin.
+ *   tiles            HOST int[n_tiles][4] = x, y, w, h inside the image
+ *   params           HOST vwgpu_ip_detect_params
+ *   desired_num_ip   optional HOST int[n_tiles]; an entry > 0 overrides max_points for its tile
+ *   out              HOST struct of seven arrays of n_tiles x capacity elements (device arrays for _dev): tile i's points
+ *                    are the first stats[3 i + 2] elements of its segment, which begins at i * capacity
+ *   stats            HOST int[n_tiles][3] = {extrema, points that passed the threshold and Harris, points written}
+ * Order: scale ascending, then rows, then columns; where the reference sorts (OBALoG whenever the limit is positive, IAGD
+ * when the limit is positive and below the count) by interest descending with ties in that order, then cut at the limit.
+ * OBALoG records a point one pixel right and down of its extremum and tests and orients it there, as the reference does.
+ * A tile with more points than `capacity`: VWGPU_ERR_CAPACITY; no tile's points are then to be used, and every stats row
+ * is valid, so a second call can be sized.  Both entries synchronise the stream (the counts decide the later launches).
+ * VWGPU_ERR_ARGUMENT before any device work: null pointers, sizes < 1, a tile that leaves the image, an unknown detector,
+ * a NaN threshold.  scales > 8: VWGPU_ERR_NOIMPL (the reference's rows 8 and 9 are placeholders that read outside). */
+int vwgpu_ip_detect_dev(vwgpu_ctx* ctx, const float* d_img, int w, int h, ptrdiff_t stride, const int* tiles, int n_tiles,
+                        const vwgpu_ip_detect_params* params, const int* desired_num_ip, int capacity, const vwgpu_ip_points* d_out,
+                        int* stats);
+int vwgpu_ip_detect(vwgpu_ctx* ctx, const float* img, int w, int h, ptrdiff_t stride, const int* tiles, int n_tiles,
+                    const vwgpu_ip_detect_params* params, const int* desired_num_ip, int capacity, const vwgpu_ip_points* out, int* stats);
+
+/* Replaces AssignOrientation (IntegralDetector.cc:37-104) for n points {ix, iy, scale} of an integral image of iw x ih
+ * floats: 113 Haar responses on the bilinear view of the integral with constant extension, sorted into 13 slices by an
+ * atan2f that is the same on the host and the device, the orientation that of the strongest slice. */
+int vwgpu_ip_orientation_dev(vwgpu_ctx* ctx, const float* d_integral, int iw, int ih, ptrdiff_t istride, int n, const int32_t* d_ix,
+                             const int32_t* d_iy, const float* d_scale, float* d_orientation);
+int vwgpu_ip_orientation(vwgpu_ctx* ctx, const float* integral, int iw, int ih, ptrdiff_t istride, int n, const int32_t* ix, const int32_t* iy,
+                         const float* scale, float* orientation);
+
+typedef enum vwgpu_ip_descriptor { VWGPU_IP_DESCRIPTOR_SGRAD = 0, VWGPU_IP_DESCRIPTOR_SGRAD2 = 1 } vwgpu_ip_descriptor;
+
+/* Replaces SGradDescriptorGenerator (src/vw/InterestPoint/Descriptor.h:120-132, :214-255, :416-471; 180 floats) and
+ * SGrad2DescriptorGenerator (IntegralDescriptor.h:76-179; 128 floats) run on one crop of the image, which is what
+ * InterestPointDescriptionTask does per tile (Descriptor.h:259-301).
+ *   crop          HOST int[4] = x, y, w, h; it may leave the image and is rasterised with zero extension.  The crop is part
+ *                 of the result: SGrad extends the crop with zeros, SGrad2 integrates the crop.
+ *   x, y, scale, orientation   n points in IMAGE coordinates; they are re-based to the crop as floats
+ *   desc          n rows of 180 or 128 floats, dstride elements apart (0 = dense), so that it feeds vwgpu_ip_match_dev
+ * SGRAD: the 42 x 42 support through the affine map of 1 / scale and cos, sin(-orientation) in double and the bilinear tap
+ * with zero extension, its own integral image in IntegralImage's order, 5 scales x 3 x 3 cells x 4 quadrant differences, the
+ * float sum of squares in order, the reciprocal of its correctly rounded root (0 when that is no normal number).
+ * SGRAD2: the integral image of the crop, bilinear with constant extension, 16 boxes x 9 positions x 2 Haar responses
+ * rotated in double, each histogram word a double sum rounded to float at every step, two norm_2 normalisations with the
+ * clamp at 0.2 between them.  cos and sin are the device library's: with an orientation other than 0 the words agree with a
+ * host run to rounding, not bit for bit.
+ * VWGPU_ERR_ARGUMENT before any device work: null pointers, n < 0, an empty image or crop, an unknown kind, a stride
+ * below the row.  A crop of more than 2^28 pixels: VWGPU_ERR_NOIMPL. */
+int vwgpu_ip_describe_dev(vwgpu_ctx* ctx, const float* d_img, int w, int h, ptrdiff_t stride, const int* crop, int n, const float* d_x,
+                          const float* d_y, const float* d_scale, const float* d_orientation, int kind, float* d_desc, ptrdiff_t dstride);
+int vwgpu_ip_describe(vwgpu_ctx* ctx, const float* img, int w, int h, ptrdiff_t stride, const int* crop, int n, const float* x, const float* y,
+                      const float* scale, const float* orientation, int kind, float* desc, ptrdiff_t dstride);
+
+/* The cull of the two detectors on the host, with the comparison the device uses: n candidates in natural order with
+ * their interests, the limit (desired_num_ip if positive, else max_points).  order: int32[n], the indices kept, in output
+ * order; n_out their count.  No context. */
+int vwgpu_ip_cull_order(int detector, int limit, int n, const float* interest, int32_t* order, int* n_out);
 
 /* ---- disparity clean-up filters and the zone scheduler ------------------------------------------------- */
 

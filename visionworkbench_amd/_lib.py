@@ -41,6 +41,8 @@ SYMBOLS = [
     "vwgpu_transform_make", "vwgpu_transform_rotate", "vwgpu_transform_invert", "vwgpu_transform_points",
     "vwgpu_transform_image_dev", "vwgpu_transform_image",
     "vwgpu_ip_match_chunk", "vwgpu_ip_match_dev", "vwgpu_ip_match", "vwgpu_host_last_error", "vwgpu_ip_remove_duplicates", "vwgpu_fit_transform", "vwgpu_ransac",
+    "vwgpu_integral_image_dev", "vwgpu_integral_image", "vwgpu_ip_detect_dev", "vwgpu_ip_detect", "vwgpu_ip_orientation_dev", "vwgpu_ip_orientation",
+    "vwgpu_ip_describe_dev", "vwgpu_ip_describe", "vwgpu_ip_cull_order",
     "vwgpu_disparity_filter_dev", "vwgpu_disparity_filter",
     "vwgpu_disparity_mask_dev", "vwgpu_disparity_mask",
     "vwgpu_subdivide_regions",
@@ -86,6 +88,17 @@ class IpMatchParams(ctypes.Structure):
     """struct vwgpu_ip_match_params (include/vwgpu.h)."""
     _fields_ = [("metric", ctypes.c_int), ("mode", ctypes.c_int), ("threshold", ctypes.c_double), ("constraint", ctypes.c_int),
                 ("bidirectional", ctypes.c_int), ("bounds", ctypes.c_double * 4)]
+
+
+class IpDetectParams(ctypes.Structure):
+    """struct vwgpu_ip_detect_params (include/vwgpu.h)."""
+    _fields_ = [("detector", ctypes.c_int), ("scales", ctypes.c_int), ("threshold", ctypes.c_double), ("max_points", ctypes.c_int),
+                ("reserved", ctypes.c_int)]
+
+
+class IpPoints(ctypes.Structure):
+    """struct vwgpu_ip_points (include/vwgpu.h)."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("x", "y", "ix", "iy", "orientation", "scale", "interest")]
 
 
 class TriangulateStats(ctypes.Structure):
@@ -281,6 +294,19 @@ def load():
     lib.vwgpu_ip_remove_duplicates.argtypes = [P, P, ctypes.c_longlong, P, P]
     lib.vwgpu_fit_transform.argtypes = [I, P, P, ctypes.c_longlong, P, P]
     lib.vwgpu_ransac.argtypes = [I, P, P, ctypes.c_longlong, P, I, D, I, I, P, P, P]
+    itg = [P, P, I, I, PD, P, PD]
+    lib.vwgpu_integral_image_dev.argtypes = itg
+    lib.vwgpu_integral_image.argtypes = itg
+    ipd = [P, P, I, I, PD, P, I, ctypes.POINTER(IpDetectParams), P, I, ctypes.POINTER(IpPoints), P]
+    lib.vwgpu_ip_detect_dev.argtypes = ipd
+    lib.vwgpu_ip_detect.argtypes = ipd
+    ipo = [P, P, I, I, PD, I, P, P, P, P]
+    lib.vwgpu_ip_orientation_dev.argtypes = ipo
+    lib.vwgpu_ip_orientation.argtypes = ipo
+    ips = [P, P, I, I, PD, P, I, P, P, P, P, I, P, PD]
+    lib.vwgpu_ip_describe_dev.argtypes = ips
+    lib.vwgpu_ip_describe.argtypes = ips
+    lib.vwgpu_ip_cull_order.argtypes = [I, I, I, P, P, IP]
     df = [P, P, I, I, I, I, D, D, I, P]
     lib.vwgpu_disparity_filter_dev.argtypes = df
     lib.vwgpu_disparity_filter.argtypes = df

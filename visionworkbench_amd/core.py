@@ -26,6 +26,10 @@ class LogicErr(VWException):
     """vw::LogicErr"""
 
 
+class CapacityErr(LogicErr):
+    """VWGPU_ERR_CAPACITY: an output segment of the call was too small; its counts say how large it must be."""
+
+
 class IOErr(VWException):
     """vw::IOErr"""
 
@@ -48,6 +52,7 @@ OPT_DEFER_EXACTNESS, OPT_DEVICE_COUNT, OPT_SAD_GROUPS, OPT_EXACT_SCRATCH_MB, OPT
 OPT_MGM_SWEEP, OPT_EXACT_SPLIT, OPT_HOST_RING_KB, OPT_HOST_RING_WRAPS, OPT_CERTIFY, OPT_CERT_PERMILLE, OPT_ZONE_SXC = 8, 9, 11, 12, 13, 14, 15      # vwgpu_option
 OPT_CERT_F32, OPT_CERT_F64_PERMILLE, OPT_ZONE_TILE16, OPT_SGM_PATH_MODE, OPT_SAD_LAYOUT, OPT_SAD_LAST_LAUNCH = 16, 17, 18, 19, 20, 21
 OPT_SAD_ROUND_SLOTS = 22
+OPT_IP_SCRATCH_MB = 23
 VALID_I32 = 0x7FFFFFFF
 
 
@@ -86,7 +91,7 @@ def bounding_box(img):
     return BBox2i(0, 0, img.shape[1], img.shape[0])
 
 
-_STATUS_EXC = {-1: ArgumentErr, -2: NoImplErr, -3: LogicErr, -4: LogicErr, -5: LogicErr}
+_STATUS_EXC = {-1: ArgumentErr, -2: NoImplErr, -3: LogicErr, -4: LogicErr, -5: LogicErr, -6: CapacityErr}
 
 
 class Context:

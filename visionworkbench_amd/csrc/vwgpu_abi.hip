@@ -180,6 +180,7 @@ const char* vwgpu_strerror(int status) {
     case VWGPU_ERR_HIP: return "HIP runtime error";
     case VWGPU_ERR_NOMEM: return "out of device memory";
     case VWGPU_ERR_LOGIC: return "internal logic error";
+    case VWGPU_ERR_CAPACITY: return "an output segment is too small";
     default: return "unknown status";
   }
 }
@@ -292,6 +293,7 @@ static const struct { int id; int vwgpu_ctx::* field; int lo, hi; bool settable;
   {VWGPU_OPT_SAD_LAST_LAUNCH, &vwgpu_ctx::sad_last_launch, 0, 0, false},
   {VWGPU_OPT_SAD_ROUND_SLOTS, &vwgpu_ctx::sad_round_slots, 0, 1 << 20, true},
   {VWGPU_OPT_EXACT_SCRATCH_MB, &vwgpu_ctx::exact_scratch_mb, 16, 65536, true},
+  {VWGPU_OPT_IP_SCRATCH_MB, &vwgpu_ctx::ip_scratch_mb, 1, 65536, true},
   {VWGPU_OPT_TRACE, &vwgpu_ctx::trace, 0, 7, true},
   {VWGPU_OPT_CERTIFY, &vwgpu_ctx::certify, 0, 1, true},
   {VWGPU_OPT_CERT_F32, &vwgpu_ctx::cert_f32, 0, 1, true},

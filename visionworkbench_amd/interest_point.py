@@ -1,10 +1,12 @@
 """vw::ip matching and the RANSAC alignment of vw::math on the GPU: InterestPointMatcherSimple and InterestPointMatcher
 (src/vw/InterestPoint/Matcher.h) as an exact search, remove_duplicates, the fitting functors of src/vw/Math/Geometry.h,
 RandomSampleConsensus (src/vw/Math/RANSAC.h), the binary .vwip / .match files of src/vw/InterestPoint/MatcherIO.cc and the
-alignment step of tools/correlate.cc:147-166.
+alignment step of tools/correlate.cc:147-166; and what tools/ipfind.cc runs without OpenCV: IntegralImage, the OBALoG detectors
+IntegralAutoGainDetector and IntegralInterestPointDetector (src/vw/InterestPoint/IntegralDetector.h) over the tiles of
+detect_interest_points, and the SGrad / SGrad2 descriptors over the crops of describe_interest_points.
 
 Descriptors are (N, K) arrays: numpy in -> numpy out, CUDA tensors in -> CUDA tensors out on the current torch stream.  The
-fits, RANSAC and remove_duplicates run on the host.
+fits, RANSAC and remove_duplicates run on the host; so do the tile loops, the cull rule and the crops of the detectors.
 """
 import ctypes
 import os
@@ -14,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from ._operands import Operands, is_tensor, new_stats, put_stats
-from .core import ArgumentErr, IOErr, LogicErr, NoImplErr
+from .core import ArgumentErr, CapacityErr, IOErr, LogicErr, NoImplErr
 from .stereo import HomographyTransform
 
 METRICS = {"L2": 0, "HAMMING": 1}
@@ -392,7 +394,266 @@ def align_homography(matches, iterations=100, inlier_threshold=30, min_inliers=N
     return HomographyTransform(H)
 
 
-__all__ = ["InterestPoints", "match", "matched_pairs", "remove_duplicates", "remove_duplicates_mask", "NullConstraint",
+# ---- detection and description (src/vw/InterestPoint/IntegralDetector.h, DetectorBase.h, Descriptor.h, tools/ipfind.cc) --------
+
+DETECTORS = {"iagd": 0, "obalog": 1}
+DESCRIPTORS = {"sgrad": 0, "sgrad2": 1}
+IP_DEFAULT_SCALES = 8
+MAX_SCALES = 8
+TILE_SIZE = 1024
+IDEAL_OBALOG_THRESHOLD = np.float32(.07)      # tools/ipfind.cc:71
+
+
+def _image2d(ops, image, what):
+    img = ops.image(image, np.float32, rows=True)
+    if img.ndim != 2 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ArgumentErr("%s: a float32 image (rows, cols) with at least one pixel" % what)
+    return img
+
+
+def integral_image(image, ctx=None):
+    """IntegralImage(image) (IntegralImage.h:43-91): float32 (rows + 1, cols + 1), row 0 and column 0 zero, every word
+    ((src + left) + up) - upleft in float, in that order, which is not what a cumulative sum gives."""
+    ops = Operands("integral_image", image, ctx)
+    img = _image2d(ops, image, "integral_image")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    out = ops.empty((h + 1, w + 1), np.float32)
+    ops.call("integral_image", ops.ptr(img), w, h, ops.row_stride(img), ops.ptr(out), w + 1)
+    return out
+
+
+def assign_orientation(integral, ix, iy, scale, ctx=None):
+    """AssignOrientation (IntegralDetector.cc:37-104) for points {ix, iy, scale} of an integral image (integral_image(image), or a
+    view of a wider one): float32 orientations, on the side of `integral`."""
+    ops = Operands("assign_orientation", integral, ctx)
+    integ = ops.image(integral, np.float32, rows=True)
+    if integ.ndim != 2 or integ.shape[0] < 2 or integ.shape[1] < 2:
+        raise ArgumentErr("assign_orientation: an integral image of at least 2 x 2")
+    px, py = np.ascontiguousarray(ix, np.int32).reshape(-1), np.ascontiguousarray(iy, np.int32).reshape(-1)
+    ps = np.ascontiguousarray(scale, np.float32).reshape(-1)
+    if not px.size == py.size == ps.size:
+        raise ArgumentErr("assign_orientation: ix, iy and scale must have one length")
+    out = ops.zeros((px.size,), np.float32)
+    if px.size == 0:
+        return out
+    side = [_side(ops, v) for v in (px, py, ps)]      # kept alive over the call: a tensor freed at once hands its block to the next one
+    ops.call("ip_orientation", ops.ptr(integ), int(integ.shape[1]), int(integ.shape[0]), ops.row_stride(integ), px.size, ops.ptr(side[0]),
+             ops.ptr(side[1]), ops.ptr(side[2]), ops.ptr(out))
+    return out
+
+
+class OBALoGInterestOperator(object):
+    """OBALoGInterestOperator(threshold = 0.05) (IntegralInterestOperator.h:67-159)."""
+
+    def __init__(self, threshold=0.05):
+        self.threshold = float(threshold)
+
+
+def detection_tiles(width, height, desired_num_ip=0, tile_size=TILE_SIZE):
+    """The tiles of detect_interest_points: subdivide_bbox of the image at tile_size (AlgorithmFunctions.cc:28-80) as rows
+    (x, y, w, h), and the number of points asked of each (DetectorBase.h:276-290): 0 when desired_num_ip is not positive,
+    else ceil(area / tile_size^2 * desired_num_ip) kept within [1, desired_num_ip]."""
+    width, height, n = int(width), int(height), int(desired_num_ip)
+    rects, counts = [], []
+    for y in range(0, height, tile_size):
+        for x in range(0, width, tile_size):
+            w, h = min(tile_size, width - x), min(tile_size, height - y)
+            rects.append((x, y, w, h))
+            num = 0
+            if n > 0:
+                num = int(np.ceil(float(w * h) / float(tile_size * tile_size) * float(n)))
+                num = min(max(num, 1), n)
+            counts.append(num)
+    return rects, counts
+
+
+def cull_order(detector, interest, limit):
+    """The indices that the detector's cull keeps of candidates given in natural order (scale, row, column), in output
+    order (IntegralDetector.cc:227-237, :354-367): OBALoG sorts by interest descending whenever limit > 0, IAGD only when
+    0 < limit < count; the sort is stable; then the list is cut at limit."""
+    v = np.ascontiguousarray(interest, np.float32).reshape(-1)
+    order = np.empty(v.size, np.int32)
+    n = ctypes.c_int(0)
+    _host_check(_lib.load().vwgpu_ip_cull_order(_code(DETECTORS, detector, "detector"), int(limit), v.size, v.ctypes.data, order.ctypes.data,
+                                                ctypes.byref(n)))
+    return order[:n.value].copy()
+
+
+class _IntegralDetector(object):
+    kind = None
+
+    def _run(self, image, rects, desired, ctx=None, stats=None, capacity=None):
+        """One vwgpu_ip_detect call over `rects`; the call is repeated with the capacity its counts ask for when a tile
+        has more points than the first guess.  capacity: the segment size to use, without a second call: CapacityErr is
+        raised when it is too small, with stats filled."""
+        ops = Operands("detect", image, ctx)
+        img = _image2d(ops, image, "detect")
+        if not 1 <= self.scales <= MAX_SCALES:
+            raise (NoImplErr if self.scales > MAX_SCALES else ArgumentErr)(
+                "detect: %d scales; 1 .. %d are implemented (the reference's rows 8 and 9 are placeholders)" % (self.scales, MAX_SCALES))
+        n = len(rects)
+        tiles = np.ascontiguousarray(rects, np.int32).reshape(n, 4)
+        want = np.ascontiguousarray(desired, np.int32).reshape(n)
+        limits = np.where(want > 0, want, self.max_points)
+        fixed = capacity is not None
+        if not fixed:
+            capacity = int(limits.max()) if int(limits.min()) > 0 else 4096
+        params = _lib.IpDetectParams(self.kind, int(self.scales), float(self.threshold), int(self.max_points), 0)
+        st = (ctypes.c_int * (3 * n))()
+        while True:
+            out = {name: ops.empty((n, capacity), dtype) for name, dtype in _FIELDS[:7]}
+            pts = _lib.IpPoints(*[ops.ptr(out[name]) for name in ("x", "y", "ix", "iy", "orientation", "scale", "interest")])
+            try:
+                ops.call("ip_detect", ops.ptr(img), int(img.shape[1]), int(img.shape[0]), ops.row_stride(img), tiles.ctypes.data, n,
+                         ctypes.byref(params), want.ctypes.data, capacity, ctypes.byref(pts), st)
+                break
+            except CapacityErr:
+                if fixed:
+                    if stats is not None:
+                        stats[:] = np.asarray(st, np.int32).reshape(n, 3).tolist()
+                    raise
+                capacity = max(st[2::3])
+        counts = np.asarray(st, np.int32).reshape(n, 3)
+        if stats is not None:
+            stats[:] = counts.tolist()
+        fields = {}
+        for name, _ in _FIELDS[:7]:
+            a = out[name].cpu().numpy() if ops.tensor else out[name]
+            fields[name] = np.concatenate([a[i, :counts[i, 2]] for i in range(n)]) if n else a.reshape(-1)
+        total = int(counts[:, 2].sum())
+        x, y = fields.pop("x"), fields.pop("y")
+        return InterestPoints(x, y, ops.zeros((total, 0), np.float32), **fields)
+
+    def process_image(self, image, desired_num_ip=0, ctx=None, stats=None, capacity=None):
+        """process_image(image, desired_num_ip) (IntegralDetector.cc:150-245, :264-370): the image as one tile."""
+        h, w = image.shape
+        return self._run(image, [(0, 0, int(w), int(h))], [int(desired_num_ip)], ctx, stats, capacity)
+
+
+class IntegralInterestPointDetector(_IntegralDetector):
+    """IntegralInterestPointDetector (IntegralDetector.h:40-70), "obalog": OBALoG with a fixed threshold, the list sorted by
+    interest whenever a limit is set, every point given the SURF-style orientation.  As in the reference a point lies one
+    pixel right and down of its extremum."""
+    kind = DETECTORS["obalog"]
+
+    def __init__(self, interest=None, scales=IP_DEFAULT_SCALES, max_points=1000):
+        self.interest = OBALoGInterestOperator() if interest is None else interest
+        self.threshold, self.scales, self.max_points = self.interest.threshold, int(scales), int(max_points)
+
+
+class IntegralAutoGainDetector(_IntegralDetector):
+    """IntegralAutoGainDetector(max_points = 200, scales = 8) (IntegralDetector.h:76-97), "iagd": the threshold is 0.1 % of
+    each interest plane's range; orientation stays 0."""
+    kind = DETECTORS["iagd"]
+
+    def __init__(self, max_points=200, scales=IP_DEFAULT_SCALES):
+        self.threshold, self.scales, self.max_points = 0.0, int(scales), int(max_points)
+
+
+def detect_interest_points(image, detector, desired_num_ip=0, ctx=None, stats=None):
+    """detect_interest_points(view, detector, desired_num_ip) (DetectorBase.h:302-328): every 1024 x 1024 tile is an
+    independent crop; the points are shifted by the tile's origin and appended in tile order.  All tiles go through one
+    library call.  stats: an optional list that receives {extrema, passed, written} per tile."""
+    h, w = image.shape
+    rects, counts = detection_tiles(w, h, desired_num_ip)
+    return detector._run(image, rects, counts, ctx, stats)
+
+
+class SGradDescriptorGenerator(object):
+    """SGradDescriptorGenerator (Descriptor.h:120-132): 180 floats from a 42 x 42 support."""
+    kind, support_size, descriptor_size = DESCRIPTORS["sgrad"], 42, 180
+
+    def __call__(self, image, ip, crop=None, ctx=None):
+        """The generator run on `crop` = (x, y, w, h) of the image (the whole image by default), as operator()(image, points)
+        does on the image it is given: returns ip with its descriptors set."""
+        ops = Operands("describe", image, ctx)
+        img = _image2d(ops, image, "describe")
+        h, w = int(img.shape[0]), int(img.shape[1])
+        rect = np.ascontiguousarray((0, 0, w, h) if crop is None else crop, np.int32).reshape(4)
+        n = len(ip)
+        desc = ops.zeros((n, self.descriptor_size), np.float32)
+        side = [_side(ops, np.ascontiguousarray(v, np.float32)) for v in (ip.x, ip.y, ip.scale, ip.orientation)]
+        if n:
+            ops.call("ip_describe", ops.ptr(img), w, h, ops.row_stride(img), rect.ctypes.data, n, ops.ptr(side[0]), ops.ptr(side[1]),
+                     ops.ptr(side[2]), ops.ptr(side[3]), self.kind, ops.ptr(desc), self.descriptor_size)
+        return InterestPoints(ip.x, ip.y, desc, **{name: getattr(ip, name) for name, _ in _FIELDS[2:] if getattr(ip, name) is not None})
+
+
+class SGrad2DescriptorGenerator(SGradDescriptorGenerator):
+    """SGrad2DescriptorGenerator (IntegralDescriptor.h:76-179): 128 floats from the integral image of what it is given."""
+    kind, support_size, descriptor_size = DESCRIPTORS["sgrad2"], 41, 128
+
+
+def description_crop(ip, support_size):
+    """The crop InterestPointDescriptionTask rasterises for the points of one tile (Descriptor.h:261-277): the union of
+    reverse_bbox (Math/Transform.h:176-205) of every point's support square under its affine map, expanded by 1, as
+    (x, y, w, h).  It may leave the image."""
+    import math
+    half = np.float32(support_size - 1) / np.float32(2.0)
+    lo, hi = [None, None], [None, None]
+    for x, y, scale, ori in zip(ip.x, ip.y, ip.scale, ip.orientation):
+        scaling = np.float32(1.0) / np.float32(scale)
+        c, s = math.cos(float(-np.float32(ori))), math.sin(float(-np.float32(ori)))
+        sc, x, y = float(scaling), float(x), float(y)
+        a, b, cc, d = sc * c, -sc * s, sc * s, sc * c
+        mx, my = sc * (s * y - c * x) + float(half), -sc * (s * x + c * y) + float(half)
+        det = a * d - b * cc
+        ai, bi, ci, di = d / det, -b / det, -cc / det, a / det
+        pts = []
+        for px, py in ((0, 0), (support_size - 1, 0), (0, support_size - 1), (support_size - 1, support_size - 1)):
+            qx, qy = px - mx, py - my
+            pts.append((ai * qx + bi * qy, ci * qx + di * qy))
+        bmin = [min(p[k] for p in pts) for k in (0, 1)]
+        bmax = [max(p[k] for p in pts) for k in (0, 1)]
+        for k in (0, 1):      # grow_bbox_to_int (BBox.tcc:368-389), then the union
+            a0, a1 = int(math.floor(bmin[k])), int(math.floor(bmax[k])) + 1
+            lo[k] = a0 if lo[k] is None else min(lo[k], a0)
+            hi[k] = a1 if hi[k] is None else max(hi[k], a1)
+    if lo[0] is None:
+        return (0, 0, 0, 0)
+    return (lo[0] - 1, lo[1] - 1, hi[0] - lo[0] + 2, hi[1] - lo[1] + 2)
+
+
+def describe_interest_points(image, generator, ip, ctx=None):
+    """describe_interest_points(view, descriptor, list) (Descriptor.h:324-354): the points are grouped by the 1024 x 1024 tile
+    that holds them (by their truncated x, y), each group is described on its own crop (description_crop), which for SGrad2
+    is part of the result.  Deviation: the reference reorders the list with std::partition; the caller's order is kept."""
+    h, w = image.shape
+    n = len(ip)
+    tx, ty = ip.x.astype(np.int32), ip.y.astype(np.int32)      # Vector2i(ip.x, ip.y)
+    if n and not ((tx >= 0) & (ty >= 0) & (tx < w) & (ty < h)).all():
+        raise ArgumentErr("describe_interest_points: a point lies outside the image")
+    ops = Operands("describe", image, ctx)
+    desc = ops.zeros((n, generator.descriptor_size), np.float32)
+    tile_id = (ty // TILE_SIZE) * ((int(w) + TILE_SIZE - 1) // TILE_SIZE) + tx // TILE_SIZE
+    for t in np.unique(tile_id):
+        index = np.flatnonzero(tile_id == t)
+        part = ip.take(index)
+        d = generator(image, part, description_crop(part, generator.support_size), ctx).descriptor
+        if ops.tensor:
+            import torch
+            desc[torch.as_tensor(index, device=ops.device)] = d
+        else:
+            desc[index] = d
+    return InterestPoints(ip.x, ip.y, desc, **{name: getattr(ip, name) for name, _ in _FIELDS[2:] if getattr(ip, name) is not None})
+
+
+def ipfind(image, detector="iagd", descriptor="sgrad", ip_per_tile=250, gain=1, ctx=None):
+    """What tools/ipfind.cc does to one float image without OpenCV (:328-339, :395-400): detect with "iagd" (the default) or
+    "obalog", whose threshold is IDEAL_OBALOG_THRESHOLD / gain, ip_per_tile points per 1024 x 1024 tile, then describe with
+    "sgrad" or "sgrad2".  The result goes to match() and write_binary_ip_file()."""
+    if _code(DETECTORS, detector, "detector") == DETECTORS["obalog"]:
+        det = IntegralInterestPointDetector(OBALoGInterestOperator(float(IDEAL_OBALOG_THRESHOLD / np.float32(gain))), max_points=ip_per_tile)
+    else:
+        det = IntegralAutoGainDetector(ip_per_tile)
+    gen = SGrad2DescriptorGenerator() if _code(DESCRIPTORS, descriptor, "descriptor") == DESCRIPTORS["sgrad2"] else SGradDescriptorGenerator()
+    return describe_interest_points(image, gen, detect_interest_points(image, det, ip_per_tile, ctx), ctx)
+
+
+__all__ = ["integral_image", "assign_orientation", "OBALoGInterestOperator", "IntegralInterestPointDetector", "IntegralAutoGainDetector", "detect_interest_points",
+           "detection_tiles", "cull_order", "SGradDescriptorGenerator", "SGrad2DescriptorGenerator", "description_crop",
+           "describe_interest_points", "ipfind",
+           "InterestPoints", "match", "matched_pairs", "remove_duplicates", "remove_duplicates_mask", "NullConstraint",
            "ScaleOrientationConstraint", "PositionConstraint", "fit_similarity", "fit_affine", "fit_homography", "ransac", "ransac_samples",
            "iplist_to_vectorlist", "read_binary_ip_file", "write_binary_ip_file", "read_binary_match_file", "write_binary_match_file",
            "align_homography", "chunk_size", "HomographyTransform"]

@@ -7,8 +7,10 @@
 //   vw::math  HomographyFittingFunctor, AffineFittingFunctor, SimilarityFittingFunctor (src/vw/Math/Geometry.h),
 //             InterestPointErrorMetric, RandomSampleConsensus (src/vw/Math/RANSAC.h)
 // The matchers search exactly where the reference's InterestPointMatcher asks FLANN (its flann_method argument is accepted
-// and ignored); where its constraint fails the entry of the index list is size_t(-1) instead of missing.  Detectors and
-// descriptors are not part of vwlite.
+// and ignored); where its constraint fails the entry of the index list is size_t(-1) instead of missing.
+//   vw::ip    also what tools/ipfind.cc runs without OpenCV (:328-339, :395-400): IntegralImage, OBALoGInterestOperator,
+//             IntegralInterestPointDetector, IntegralAutoGainDetector, detect_interest_points, SGradDescriptorGenerator,
+//             SGrad2DescriptorGenerator, describe_interest_points (further down)
 #ifndef VWLITE_INTERESTPOINT_H
 #define VWLITE_INTERESTPOINT_H
 
@@ -21,10 +23,12 @@
 #include <iterator>
 #include <limits>
 #include <list>
+#include <map>
 #include <string>
 #include <vector>
 
 #include "Engine.h"
+#include "Image.h"
 #include "Math.h"
 
 namespace vw {
@@ -340,6 +344,239 @@ inline void write_match_file(std::string match_file, std::vector<InterestPoint> 
                              bool matches_as_txt = false) {
   if (matches_as_txt) vw_throw(NoImplErr() << "write_match_file: text match files are not implemented");
   write_binary_match_file(match_file, ip1, ip2);
+}
+
+// ---- detection and description: what tools/ipfind.cc runs without OpenCV --------------------------------------------------
+// IntegralImage (IntegralImage.h:43-91), OBALoGInterestOperator (IntegralInterestOperator.h:67-159), IntegralInterestPointDetector
+// and IntegralAutoGainDetector (IntegralDetector.h:40-97), detect_interest_points (DetectorBase.h:302-328),
+// SGradDescriptorGenerator (Descriptor.h:120-132), SGrad2DescriptorGenerator (IntegralDescriptor.h:76-179),
+// describe_interest_points (Descriptor.h:324-354).  The tile loops, the per-tile counts and the crops are host logic here; the
+// pixels go through vwgpu_ip_detect and vwgpu_ip_describe.  describe_interest_points keeps the list's order where the
+// reference's std::partition reorders it.
+
+namespace detail {
+inline float gray_of(float v) { return v; }
+template <class T> float gray_of(PixelGray<T> const& p) { return float(p.v()); }
+template <class T> float gray_of(T const& v) { return float(v); }
+/// the view as dense floats (the detectors and generators take float pixels: pixel_cast<float> in ipfind.cc)
+template <class ViewT>
+ImageView<float> float_image(ImageViewBase<ViewT> const& view) {
+  ImageView<float> img(view.impl().cols(), view.impl().rows());
+  for (int32 r = 0; r < img.rows(); ++r)
+    for (int32 c = 0; c < img.cols(); ++c) img(c, r) = gray_of(view.impl()(c, r));
+  return img;
+}
+inline ImageView<float> float_image(ImageView<float> const& view) { return view; }
+
+const int IP_TILE_SIZE = 1024;      // vw_settings().default_tile_size(), never below 1024 (DetectorBase.h:308-310)
+
+/// One vwgpu_ip_detect call over `tiles` (rows x, y, w, h); repeated with the capacity its counts ask for when a segment is too small.
+inline InterestPointList detect_tiles(ImageView<float> const& img, vwgpu_ip_detect_params const& P, std::vector<int> const& tiles,
+                                      std::vector<int> const& desired) {
+  const int n = (int)desired.size();
+  InterestPointList out;
+  if (!n || img.cols() < 1 || img.rows() < 1) return out;
+  int capacity = 0;
+  for (int i = 0; i < n; ++i) {
+    const int limit = desired[i] > 0 ? desired[i] : P.max_points;
+    if (limit <= 0) { capacity = 4096; break; }
+    capacity = std::max(capacity, limit);
+  }
+  std::vector<int> stats(3 * (size_t)n);
+  vwgpu_ctx* ctx = engine::thread_context();
+  for (;;) {
+    const size_t words = (size_t)n * capacity;
+    std::vector<float> x(words), y(words), ori(words), scale(words), interest(words);
+    std::vector<int32> ix(words), iy(words);
+    vwgpu_ip_points pts = {x.data(), y.data(), ix.data(), iy.data(), ori.data(), scale.data(), interest.data()};
+    const int rc = vwgpu_ip_detect(ctx, img.data(), img.cols(), img.rows(), img.cols(), tiles.data(), n, &P, desired.data(), capacity, &pts,
+                                   stats.data());
+    if (rc == VWGPU_ERR_CAPACITY) {
+      for (int i = 0; i < n; ++i) capacity = std::max(capacity, stats[3 * i + 2]);
+      continue;
+    }
+    engine::check(ctx, rc);
+    for (int i = 0; i < n; ++i)
+      for (int k = 0; k < stats[3 * i + 2]; ++k) {
+        const size_t at = (size_t)i * capacity + k;
+        InterestPoint p(x[at], y[at], scale[at], interest[at], ori[at]);
+        p.ix = ix[at]; p.iy = iy[at];
+        out.push_back(p);
+      }
+    return out;
+  }
+}
+inline InterestPointList detect_whole(ImageView<float> const& img, vwgpu_ip_detect_params const& P, int desired_num_ip) {
+  const int tile[4] = {0, 0, img.cols(), img.rows()};
+  return detect_tiles(img, P, std::vector<int>(tile, tile + 4), std::vector<int>(1, desired_num_ip));
+}
+}  // namespace detail
+
+/// IntegralImage(source): (cols + 1) x (rows + 1) floats in the reference's summation order.
+template <class ViewT>
+ImageView<float> IntegralImage(ImageViewBase<ViewT> const& source) {
+  const ImageView<float> img = detail::float_image(source.impl());
+  ImageView<float> integral(img.cols() + 1, img.rows() + 1);
+  if (img.cols() < 1 || img.rows() < 1) return integral;
+  vwgpu_ctx* ctx = engine::thread_context();
+  engine::check(ctx, vwgpu_integral_image(ctx, img.data(), img.cols(), img.rows(), img.cols(), integral.data(), integral.cols()));
+  return integral;
+}
+
+class OBALoGInterestOperator {
+  double m_threshold;
+public:
+  OBALoGInterestOperator(double threshold = 0.05) : m_threshold(threshold) {}
+  double threshold() const { return m_threshold; }
+};
+
+/// "obalog": a fixed threshold, the list sorted by interest whenever a limit is set, every point oriented; as in the reference a
+/// point lies one pixel right and down of its extremum.
+class IntegralInterestPointDetector {
+  OBALoGInterestOperator m_interest;
+  int m_scales, m_max_points;
+public:
+  static const int IP_DEFAULT_SCALES = 8;
+  IntegralInterestPointDetector(int max_points = 1000, int num_scales = IP_DEFAULT_SCALES)
+      : m_interest(OBALoGInterestOperator()), m_scales(num_scales), m_max_points(max_points) {}
+  IntegralInterestPointDetector(OBALoGInterestOperator const& interest, int max_points = 1000)
+      : m_interest(interest), m_scales(IP_DEFAULT_SCALES), m_max_points(max_points) {}
+  IntegralInterestPointDetector(OBALoGInterestOperator const& interest, int scales, int max_points)
+      : m_interest(interest), m_scales(scales), m_max_points(max_points) {}
+  vwgpu_ip_detect_params params() const {
+    vwgpu_ip_detect_params P = {VWGPU_IP_DETECTOR_OBALOG, m_scales, m_interest.threshold(), m_max_points, 0};
+    return P;
+  }
+  template <class ViewT>
+  InterestPointList process_image(ImageViewBase<ViewT> const& image, int desired_num_ip = 0) const {
+    return detail::detect_whole(detail::float_image(image.impl()), params(), desired_num_ip);
+  }
+};
+
+/// "iagd": the threshold is 0.1 % of each interest plane's range; no orientation.
+class IntegralAutoGainDetector {
+  int m_scales, m_max_points;
+public:
+  static const int IP_DEFAULT_SCALES = 8;
+  IntegralAutoGainDetector(size_t max_points = 200, size_t scales = IP_DEFAULT_SCALES) : m_scales((int)scales), m_max_points((int)max_points) {}
+  vwgpu_ip_detect_params params() const {
+    vwgpu_ip_detect_params P = {VWGPU_IP_DETECTOR_IAGD, m_scales, 0.0, m_max_points, 0};
+    return P;
+  }
+  template <class ViewT>
+  InterestPointList process_image(ImageViewBase<ViewT> const& image, int desired_num_ip = 0) const {
+    return detail::detect_whole(detail::float_image(image.impl()), params(), desired_num_ip);
+  }
+};
+
+/// Every 1024 x 1024 tile is an independent crop; the points are shifted by the tile's origin and appended in tile order; a
+/// tile is asked for ceil(area / 1024^2 * desired_num_ip) points, kept within [1, desired_num_ip].  One library call.
+template <class ViewT, class DetectorT>
+InterestPointList detect_interest_points(ImageViewBase<ViewT> const& view, DetectorT& detector, int desired_num_ip = 0) {
+  const ImageView<float> img = detail::float_image(view.impl());
+  const int tile_size = detail::IP_TILE_SIZE;
+  std::vector<int> tiles, desired;
+  for (int y = 0; y < img.rows(); y += tile_size)
+    for (int x = 0; x < img.cols(); x += tile_size) {
+      const int w = std::min(tile_size, img.cols() - x), h = std::min(tile_size, img.rows() - y);
+      const int t[4] = {x, y, w, h};
+      tiles.insert(tiles.end(), t, t + 4);
+      int num_ip = 0;
+      if (desired_num_ip > 0) {
+        const double expected_area = (double)tile_size * tile_size, area = (double)w * h;
+        num_ip = (int)std::ceil(area / expected_area * static_cast<double>(desired_num_ip));
+        if (num_ip < 1) num_ip = 1;
+        if (num_ip > desired_num_ip) num_ip = desired_num_ip;
+      }
+      desired.push_back(num_ip);
+    }
+  return detail::detect_tiles(img, detector.params(), tiles, desired);
+}
+
+namespace detail {
+/// The crop InterestPointDescriptionTask rasterises (Descriptor.h:261-277): the union of reverse_bbox of every point's support
+/// square under its affine map, expanded by 1.  It may leave the image.
+inline void description_crop(std::vector<InterestPoint*> const& pts, int support_size, int* crop) {
+  const float half_size = ((float)(support_size - 1)) / 2.0f;
+  bool first = true;
+  int lo[2] = {0, 0}, hi[2] = {0, 0};
+  for (const InterestPoint* it : pts) {
+    const float scaling = 1.0f / it->scale;
+    const double c = std::cos((double)(-it->orientation)), s = std::sin((double)(-it->orientation));
+    const double sc = scaling, x = it->x, y = it->y;
+    const double ma = sc * c, mb = -sc * s, mc = sc * s, md = sc * c;
+    const double mx = sc * (s * y - c * x) + (double)half_size, my = -sc * (s * x + c * y) + (double)half_size;
+    const double det = ma * md - mb * mc;
+    const double ai = md / det, bi = -mb / det, ci = -mc / det, di = ma / det;
+    double bmin[2] = {0, 0}, bmax[2] = {0, 0};
+    const int corner[4][2] = {{0, 0}, {support_size - 1, 0}, {0, support_size - 1}, {support_size - 1, support_size - 1}};
+    for (int k = 0; k < 4; ++k) {
+      const double qx = corner[k][0] - mx, qy = corner[k][1] - my;
+      const double r[2] = {ai * qx + bi * qy, ci * qx + di * qy};
+      for (int d = 0; d < 2; ++d) {
+        if (k == 0 || r[d] < bmin[d]) bmin[d] = r[d];
+        if (k == 0 || r[d] > bmax[d]) bmax[d] = r[d];
+      }
+    }
+    for (int d = 0; d < 2; ++d) {      // grow_bbox_to_int (BBox.tcc:368-389), then the union
+      const int a0 = (int)std::floor(bmin[d]), a1 = (int)std::floor(bmax[d]) + 1;
+      if (first || a0 < lo[d]) lo[d] = a0;
+      if (first || a1 > hi[d]) hi[d] = a1;
+    }
+    first = false;
+  }
+  crop[0] = lo[0] - 1; crop[1] = lo[1] - 1; crop[2] = hi[0] - lo[0] + 2; crop[3] = hi[1] - lo[1] + 2;
+}
+inline void describe_on_crop(ImageView<float> const& img, const int* crop, std::vector<InterestPoint*> const& pts, int kind, int k) {
+  const int n = (int)pts.size();
+  if (!n) return;
+  std::vector<float> x(n), y(n), scale(n), ori(n), desc((size_t)n * k);
+  for (int i = 0; i < n; ++i) { x[i] = pts[i]->x; y[i] = pts[i]->y; scale[i] = pts[i]->scale; ori[i] = pts[i]->orientation; }
+  vwgpu_ctx* ctx = engine::thread_context();
+  engine::check(ctx, vwgpu_ip_describe(ctx, img.data(), img.cols(), img.rows(), img.cols(), crop, n, x.data(), y.data(), scale.data(),
+                                       ori.data(), kind, desc.data(), k));
+  for (int i = 0; i < n; ++i) {
+    pts[i]->descriptor.set_size(k);
+    std::copy(desc.begin() + (size_t)i * k, desc.begin() + (size_t)(i + 1) * k, pts[i]->descriptor.begin());
+  }
+}
+template <int KIND, int SUPPORT, int SIZE>
+struct DescriptorGenerator {
+  static const int vwgpu_descriptor = KIND;
+  int support_size() { return SUPPORT; }
+  int descriptor_size() { return SIZE; }
+  /// The generator on the image it is given: operator()(image, points).
+  template <class ViewT>
+  void operator()(ImageViewBase<ViewT> const& image, InterestPointList& points) {
+    const ImageView<float> img = float_image(image.impl());
+    std::vector<InterestPoint*> pts;
+    for (InterestPoint& p : points) pts.push_back(&p);
+    const int crop[4] = {0, 0, img.cols(), img.rows()};
+    describe_on_crop(img, crop, pts, KIND, SIZE);
+  }
+};
+}  // namespace detail
+
+struct SGradDescriptorGenerator : detail::DescriptorGenerator<VWGPU_IP_DESCRIPTOR_SGRAD, 42, 180> {};
+struct SGrad2DescriptorGenerator : detail::DescriptorGenerator<VWGPU_IP_DESCRIPTOR_SGRAD2, 41, 128> {};
+
+/// The points are grouped by the 1024 x 1024 tile that holds them (their truncated x, y); every group is described on its own
+/// crop.  A point outside the image belongs to no tile: ArgumentErr (the reference leaves it undescribed).
+template <class ViewT, class DescriptorT>
+void describe_interest_points(ImageViewBase<ViewT> const& view, DescriptorT& descriptor, InterestPointList& list) {
+  const ImageView<float> img = detail::float_image(view.impl());
+  const int tile_size = detail::IP_TILE_SIZE, across = (img.cols() + tile_size - 1) / tile_size;
+  std::map<int, std::vector<InterestPoint*>> groups;
+  for (InterestPoint& p : list) {
+    const int tx = int32(p.x), ty = int32(p.y);
+    VW_ASSERT(tx >= 0 && ty >= 0 && tx < img.cols() && ty < img.rows(), ArgumentErr() << "describe_interest_points: a point lies outside the image");
+    groups[(ty / tile_size) * across + tx / tile_size].push_back(&p);
+  }
+  for (auto& g : groups) {
+    int crop[4];
+    detail::description_crop(g.second, descriptor.support_size(), crop);
+    detail::describe_on_crop(img, crop, g.second, DescriptorT::vwgpu_descriptor, descriptor.descriptor_size());
+  }
 }
 
 }  // namespace ip

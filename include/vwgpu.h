@@ -38,7 +38,7 @@ extern "C" {
  *     compare versions for EQUALITY: a host built against version 2 refuses this library and is rebuilt against this header.
  *     Round 6 added option values only (VWGPU_OPT_SGM_PATH_MODE, VWGPU_OPT_SAD_GROUPS = 3): same version.
  *     VWGPU_OPT_SAD_LAYOUT, VWGPU_OPT_SAD_LAST_LAUNCH, VWGPU_OPT_SAD_ROUND_SLOTS (options 20, 21, 22) likewise, and
- *     VWGPU_OPT_IP_SCRATCH_MB (23) with the interest-point entries.
+ *     VWGPU_OPT_IP_SCRATCH_MB (23) with the interest-point entries, VWGPU_OPT_SGM_LAST_FORM (24, read only) likewise.
  * A host checks vwgpu_abi_version() == VWGPU_ABI_VERSION once after loading the library (vw::engine does, vw/Engine.h). */
 #define VWGPU_ABI_VERSION 3
 
@@ -170,6 +170,22 @@ const char* vwgpu_last_error(const vwgpu_ctx* ctx);
  *       kernel forms the census costs itself from the census rasters (up to 129 disparities; no u8 cost volume; measured slower).
  *       Ragged boxes (a previous level's disparities given): bit 4 / bit 7 = four / two scan lines per wavefront whatever the level's boxes
  *       (path_multi_kernel; default: chosen per level from the share of small boxes), bit 6 = always one line per wavefront.
+ *   VWGPU_OPT_SGM_LAST_FORM    (read only) the form the context's last calc_disparity_sgm call took (0 = none yet, or that call failed; a pyramid's SGM
+ *       levels count, the last one stays).  Every form returns the same result; tests assert this word so that a wrong route fails.
+ *       bits 0-3   aggregation: 1 = ring per direction (path_ring_kernel), 2 = register per direction (path_uniform_reg_kernel), 3 = fused
+ *                  sweeps, 4 = MGM sweeps, 5 = MGM fronts, register form, 6 = MGM fronts, ragged form, 7 = all-direction uniform 2-D
+ *                  (path_uniform_kernel), 8 / 9 = multi-line with four / two scan lines per wavefront (path_multi_kernel), 10 = in-place
+ *                  (path_inplace_kernel), 11 = three-phase (path_kernel); 0 with bit 20
+ *       bits 4-8   width of a launch: forms 1 / 2 = scan lines per workgroup of the last direction launched, 3 / 4 = rows / lines per
+ *                  workgroup, 5 = disparity pairs per lane, 6 = pixels per workgroup, 7 = disparities per lane, 8 / 9 = 4 / 2,
+ *                  10 = its R (64 R disparities at most), 11 = 0
+ *       bit 9      forms 7 - 11: the eight directions went in one launch (0 = eight launches)
+ *       bits 10-12 form 1: log2 of the consecutive workgroups given to one XCD
+ *       bits 13-15 costs: 0 = none (census costs formed in the ring), 1 = cost_row, 2 = cost_uniform16, 3 = ragged census (cost_kernel),
+ *                  4 = block row, 5 = block generic
+ *       bits 16-17 winners: 0 = the general kernel only, 1 = wta_uniform first, 2 = taken in the last direction
+ *       bits 18-19 memory conservation level at which the loop stopped (0 .. 3)
+ *       bit 20     no level fitted the memory limit: the all-invalid result, nothing else ran
  *   VWGPU_OPT_EXACT_SPLIT      pass 2 of the exact-order matchers: 0 = chosen by the width of a zone (the recurrence alone + a parallel
  *       selection for zones of 1024 pixels and more (whole rasters), the tiled form — row sums transposed through LDS — for narrower
  *       ones), 1 = always the split form, 2 = always the fused form (selection across the disparity lanes inside the chain), 3 = always
@@ -186,7 +202,7 @@ typedef enum vwgpu_option {
   /* 10: removed in ABI 2 */ VWGPU_OPT_HOST_RING_KB = 11, VWGPU_OPT_HOST_RING_WRAPS = 12, VWGPU_OPT_CERTIFY = 13,
   VWGPU_OPT_CERT_PERMILLE = 14, VWGPU_OPT_ZONE_SXC = 15, VWGPU_OPT_CERT_F32 = 16, VWGPU_OPT_CERT_F64_PERMILLE = 17, VWGPU_OPT_ZONE_TILE16 = 18,
   VWGPU_OPT_SGM_PATH_MODE = 19, VWGPU_OPT_SAD_LAYOUT = 20, VWGPU_OPT_SAD_LAST_LAUNCH = 21, VWGPU_OPT_SAD_ROUND_SLOTS = 22,
-  VWGPU_OPT_IP_SCRATCH_MB = 23
+  VWGPU_OPT_IP_SCRATCH_MB = 23, VWGPU_OPT_SGM_LAST_FORM = 24
 } vwgpu_option;
 int vwgpu_set_option(vwgpu_ctx* ctx, int option, int value);
 int vwgpu_get_option(const vwgpu_ctx* ctx, int option, int* value);

@@ -53,6 +53,7 @@ OPT_MGM_SWEEP, OPT_EXACT_SPLIT, OPT_HOST_RING_KB, OPT_HOST_RING_WRAPS, OPT_CERTI
 OPT_CERT_F32, OPT_CERT_F64_PERMILLE, OPT_ZONE_TILE16, OPT_SGM_PATH_MODE, OPT_SAD_LAYOUT, OPT_SAD_LAST_LAUNCH = 16, 17, 18, 19, 20, 21
 OPT_SAD_ROUND_SLOTS = 22
 OPT_IP_SCRATCH_MB = 23
+OPT_SGM_LAST_FORM = 24
 VALID_I32 = 0x7FFFFFFF
 
 

@@ -336,8 +336,6 @@ cost_kernel(const uint64_t* __restrict__ lc, int lcw, const uint64_t* __restrict
 // Uniform layout (every pixel searches the full range, vectors `stride` apart, stride a multiple of 16): one thread per 16
 // consecutive disparities — 16 census words of the right image in flight, one 16-byte store (4 disparities and a dword store per
 // thread ran at 0.7 TB/s: 0.79 ms for the 541 MB of a 2048^2 x 129 volume).
-// ONE_ROW: num_dy == 1, the disparity index is the column offset.
-template <bool ONE_ROW>
 __global__ void cost_uniform16_kernel(const uint64_t* __restrict__ lc, int lcw, const uint64_t* __restrict__ rc, int rcw,
                                       int ocols, int orows, int num_dx, int num_disp, int stride, int off_c, int off_r,
                                       uint32_t* __restrict__ cost32) {
@@ -352,7 +350,7 @@ __global__ void cost_uniform16_kernel(const uint64_t* __restrict__ lc, int lcw, 
   for (int e = 0; e < 16; ++e) {
     const int i = 16 * w + e;
     const int ii = i < num_disp ? i : 0;                  // dead slots read disparity 0 and are zeroed below
-    const int qy = ONE_ROW ? 0 : ii / num_dx, qx = ii - qy * num_dx;
+    const int qy = ii / num_dx, qx = ii - qy * num_dx;
     rv[e] = rc[(size_t)(br + qy) * rcw + bc + qx];
   }
   uint32_t v[4] = {0u, 0u, 0u, 0u};
@@ -1268,11 +1266,10 @@ path_multi_kernel(SgmGeom g, DirSet D, int lines, int spread,
 //  * ONE wavefront per scan line (no workgroup barrier on the serial path; the lines of a direction are the parallelism),
 //    EPT = ceil(num_disp / 64) disparities per lane; the vector is updated IN PLACE: a step reads all its neighbours into
 //    registers before it writes (LDS executes a wave's accesses in order), so every LDS address is fixed for the whole line;
-//  * ONE_D (num_dy == 1, the +-N x 1 searches): the clamped 2-D adjacency collapses to {left, right, self};
 //  * the line is processed in chunks of K pixels: cost (u8) and accumulator (u16) vectors, stored with a stride of `stride`
 //    elements (multiple of 16) per pixel, are bulk-loaded into LDS 16 bytes per lane (many loads in flight while other lines of the
 //    CU compute), the K serial steps touch LDS only, and the K updated accumulator vectors are written back as dwords.
-template <int EPT, bool ONE_D>
+template <int EPT>
 __global__ void __launch_bounds__(64)
 path_uniform_kernel(SgmGeom g, DirSet D, int K, int stride,
                     const uint8_t* __restrict__ left, int lw, int min_col, int min_row,
@@ -1297,7 +1294,7 @@ path_uniform_kernel(SgmGeom g, DirSet D, int K, int stride,
     p2tab[q] = (uint16_t)v;
   }
   // LDS addresses of the centre and its neighbours, fixed for the whole line; dead lanes of the last slot read slot 0
-  constexpr int NN = ONE_D ? 3 : 9;
+  constexpr int NN = 9;
   const uint16_t* nptr[EPT][NN];
   bool live[EPT];
 #pragma unroll
@@ -1310,10 +1307,8 @@ path_uniform_kernel(SgmGeom g, DirSet D, int K, int stride,
     const int yl = (qy - 1 < 0 ? qy : qy - 1) * g.num_dx, ym = (qy + 1 > g.max_dy - g.min_dy ? qy : qy + 1) * g.num_dx, yc = qy * g.num_dx;
     nptr[e][0] = buf + yc + qx;
     nptr[e][1] = buf + yc + xl; nptr[e][2] = buf + yc + xm;
-    if (!ONE_D) {
-      nptr[e][3] = buf + yl + qx; nptr[e][4] = buf + ym + qx;
-      nptr[e][5] = buf + yl + xl; nptr[e][6] = buf + yl + xm; nptr[e][7] = buf + ym + xl; nptr[e][8] = buf + ym + xm;
-    }
+    nptr[e][3] = buf + yl + qx; nptr[e][4] = buf + ym + qx;
+    nptr[e][5] = buf + yl + xl; nptr[e][6] = buf + yl + xm; nptr[e][7] = buf + ym + xl; nptr[e][8] = buf + ym + xm;
   }
   // 16-byte quanta per pixel vector (stride is a multiple of 16 elements), exact division j / q for j < 2^16 by a
   // multiply-high with ceil(2^32 / q), and the extra global offset per chunk pixel
@@ -1354,7 +1349,6 @@ path_uniform_kernel(SgmGeom g, DirSet D, int K, int stride,
 #pragma unroll
           for (int q = 2; q < NN; ++q) m = min(m, (unsigned)*nptr[e][q]);
           const unsigned ctr = *nptr[e][0];
-          if (ONE_D) m = min(m, ctr);                           // the clamped vertical neighbours are the centre itself
           unsigned v = adds16(m, p1);
           v = min(v, min(ctr, dJ));
           v = adds16(v, live[e] ? (unsigned)cc[tid + e * 64] : 0u);
@@ -1458,9 +1452,7 @@ __device__ __forceinline__ void wave_shl1_keep(unsigned& dst, unsigned src) {
 // stop advancing at the last pixel of the line — with conditional loads the compiler falls back to s_waitcnt vmcnt(0) in front
 // of every chunk, i.e. no prefetch at all (measured: 770 clk per step).
 enum { ACC_ATOMIC = 1, ACC_STORE = 2, ACC_NONE = 3, ACC_RMW = 4, ACC_RMW_WTA = 5 };
-#ifndef VWGPU_PATH_KC
-#define VWGPU_PATH_KC 8
-#endif
+constexpr int PATH_KC = 8;     // steps per prefetched chunk (the host sizes the guard zones by it)
 // CenArgs: the two census rasters at output pixel (0, 0), disparity 0 (path_ring_kernel<.., CEN> forms the Hamming costs itself).
 struct CenArgs {
   const uint64_t* lcen; const uint64_t* rcen;
@@ -1470,13 +1462,13 @@ struct CenArgs {
 // pixels' vectors share (a 272-byte vector straddles three) are fetched by ONE compute unit / XCD instead of two.
 // (Round 6 also built this kernel with the census costs formed in registers — 32 bytes of census words per lane and step, fetched a
 // chunk ahead: 320 registers, one wave per SIMD, 9.6 ms against 5.4 — and removed it; profiles/r06_sgm_traffic.md.)
-template <int EPT, int ACC, int KC, int WPB>
+template <int EPT, int ACC, int WPB>
 __global__ void __launch_bounds__(64 * WPB)
 path_uniform_reg_kernel(SgmGeom g, DirSet D, int stride, const uint8_t* __restrict__ left, int lw, int min_col, int min_row,
                         const uint8_t* __restrict__ cost, uint16_t* __restrict__ accum, unsigned p1, unsigned p2,
                         int32_t* __restrict__ disp = nullptr, uint8_t* __restrict__ todo = nullptr, int* __restrict__ any_todo = nullptr) {
   constexpr bool RMW = (ACC == ACC_RMW || ACC == ACC_RMW_WTA);
-  constexpr int NW = CostWords<EPT>::N;
+  constexpr int NW = CostWords<EPT>::N, KC = PATH_KC;
   const int num_disp = g.num_dx;                                                     // num_dy == 1
   const int npairs = (num_disp + 1) / 2;
   const int tid = threadIdx.x & 63;
@@ -2097,18 +2089,9 @@ struct SweepParams {
   uint16_t* out1;
   unsigned* sync;                    // [0] ticket counter
   unsigned long long* bnd;           // boundary rows: [sweep][block][pixel][3 vectors + minima] of (word, epoch)
-#ifdef VWGPU_SWEEP_DEBUG
-  int dbg;                           // tools build only (timing experiments, wrong results): 1 no boundary stores, 2 feeder trusts every word, 4 rows do not wait, 8 no sum stores
-#endif
 };
 
 typedef __attribute__((address_space(3))) unsigned lds_uint;
-#ifdef VWGPU_SWEEP_DEBUG
-__device__ unsigned long long sweep_trace[2 * 2048 * 8];          // tools build: [sweep][block][event] timestamps (s_memrealtime, 100 MHz)
-#define SWEEP_STAMP(ev) do { if (tid == 0 && blk < 2048) sweep_trace[((size_t)pass * 2048 + blk) * 8 + (ev)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define SWEEP_STAMP(ev) do {} while (0)
-#endif
 
 __device__ __forceinline__ unsigned long long ld_coherent(const unsigned long long* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2141,9 +2124,6 @@ template <int N> struct __attribute__((packed, aligned(4))) SweepWords { unsigne
 template <int SLOT, int NWORDS>
 __device__ __forceinline__ void sweep_feeder(const unsigned long long* __restrict__ src, int W, lds_uint* ring, volatile lds_uint* done, int NW,
                                              unsigned epoch, int tid
-#ifdef VWGPU_SWEEP_DEBUG
-                                             , int dbg, int pass, int blk
-#endif
                                              ) {
   constexpr int FRING = SWEEP_FRING, PER = (NWORDS + 63) / 64;
   constexpr int FB = PER <= 4 ? SWEEP_FB : SWEEP_FB / 2;            // entries requested at once: 32 / 28 loads in flight per lane
@@ -2154,9 +2134,6 @@ __device__ __forceinline__ void sweep_feeder(const unsigned long long* __restric
     const int B = min(FB, W - e);
     const int needc = e + B - FRING + 2;                           // row wave 0 must be done with the slots about to be overwritten
     while ((int)cons < needc) {
-#ifdef VWGPU_SWEEP_DEBUG
-      if (dbg & 4) break;
-#endif
       cons = done[0];
       if ((int)cons < needc) __builtin_amdgcn_s_sleep(2);
     }
@@ -2173,9 +2150,6 @@ __device__ __forceinline__ void sweep_feeder(const unsigned long long* __restric
       bool ok = true;
 #pragma unroll
       for (int q = 0; q < PER; ++q) ok = ok && (unsigned)(wd[b][q] >> 32) == epoch;
-#ifdef VWGPU_SWEEP_DEBUG
-      if (dbg & 2) ok = true;
-#endif
       if (__all(ok) && b < B && k == b) k = b + 1;
     }
 #pragma unroll
@@ -2188,9 +2162,6 @@ __device__ __forceinline__ void sweep_feeder(const unsigned long long* __restric
       }
     }
     if (k) {
-#ifdef VWGPU_SWEEP_DEBUG
-      if (e == 0 && tid == 0 && blk < 2048) sweep_trace[((size_t)pass * 2048 + blk) * 8 + 4] = __builtin_amdgcn_s_memrealtime();
-#endif
       asm volatile("" ::: "memory");                               // LDS executes a wave's accesses in order: data, then the counter
       done[NW] = (unsigned)(e + k);
       e += k;
@@ -2198,9 +2169,6 @@ __device__ __forceinline__ void sweep_feeder(const unsigned long long* __restric
       __builtin_amdgcn_s_sleep(8);
     }
   }
-#ifdef VWGPU_SWEEP_DEBUG
-  if (tid == 0 && blk < 2048) sweep_trace[((size_t)pass * 2048 + blk) * 8 + 5] = __builtin_amdgcn_s_memrealtime();
-#endif
 }
 
 template <int Q>
@@ -2228,9 +2196,6 @@ sweep_uniform_kernel(SweepParams A) {
 
   if (wv == NW) {                                                  // ---- feeder: boundary row of the previous block -> LDS ring of row wave 0
     if (blk > 0) sweep_feeder<SLOT, NWORDS>(A.bnd + ((size_t)(pass * A.nblk + blk - 1) * W) * ENT, W, rings + NW * RING * SLOT, done, NW, epoch, tid
-#ifdef VWGPU_SWEEP_DEBUG
-                                            , A.dbg, pass, blk
-#endif
                                             );
     return;
   }
@@ -2320,9 +2285,6 @@ sweep_uniform_kernel(SweepParams A) {
     unsigned o[Q];
 #pragma unroll
     for (int e = 0; e < Q; ++e) o[e] = as_u32(as_us2(sa[e]) + as_us2(sb[e]));
-#ifdef VWGPU_SWEEP_DEBUG
-    if (A.dbg & 8) {} else
-#endif
     if (st_full) {
       SweepWords<Q> w;
 #pragma unroll
@@ -2356,9 +2318,6 @@ sweep_uniform_kernel(SweepParams A) {
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         avail = (unsigned)__builtin_amdgcn_readfirstlane((int)got);
-#ifdef VWGPU_SWEEP_DEBUG
-        if (A.dbg & 4) break;
-#endif
         if (avail >= (unsigned)need) break;
         __builtin_amdgcn_s_sleep(1);
       }
@@ -2413,9 +2372,6 @@ sweep_uniform_kernel(SweepParams A) {
     if (mode == 1) {                                               // to the row below, through this wave's LDS ring
       const int needc = xx - RING + 2;
       while ((int)cavail < needc) {
-#ifdef VWGPU_SWEEP_DEBUG
-        if (A.dbg & 4) break;
-#endif
         cavail = done[wv + 1];
         if ((int)cavail < needc) __builtin_amdgcn_s_sleep(1);
       }
@@ -2426,9 +2382,6 @@ sweep_uniform_kernel(SweepParams A) {
         if (j == 0) slot[moff] = nm;
       }
     } else if (mode == 2
-#ifdef VWGPU_SWEEP_DEBUG
-               && !(A.dbg & 1)
-#endif
                ) {                                                 // to the next block, through HBM: every word with this launch's epoch
       unsigned long long* ent = bdst + (size_t)xx * ENT;
       const unsigned long long tag = (unsigned long long)epoch << 32;
@@ -2470,11 +2423,8 @@ sweep_uniform_kernel(SweepParams A) {
     // pinned in this order: the waits of the loop count the loads issued AFTER the one a step needs, on every path into the loop
     __builtin_amdgcn_sched_barrier(0);
   }
-  if (wv == 0) SWEEP_STAMP(0);
-  if (mode != 1) SWEEP_STAMP(2);
   for (int x0 = 0; x0 < W; x0 += KC) {
     if ((x0 & 15) == 0) refresh(x0);
-    if (x0 == KC) { if (wv == 0) SWEEP_STAMP(6); if (mode != 1) SWEEP_STAMP(7); }
 #pragma unroll
     for (int k = 0; k < KC; ++k) {
       if (x0 + k < W) step(cq[k], x0 + k);
@@ -2484,8 +2434,6 @@ sweep_uniform_kernel(SweepParams A) {
   sum_issue();                                                     // the row's last pixel
   sum_mid();
   sum_finish();
-  if (wv == 0) SWEEP_STAMP(1);
-  if (mode != 1) SWEEP_STAMP(3);
 }
 
 
@@ -2553,9 +2501,6 @@ mgm_sweep_kernel(MgmSweepParams A) {
   unsigned long long* bnd = A.bnd + A.bnd_off[sweep] * ENT;
   if (wv == NW) {
     if (blk > 0) sweep_feeder<SLOT, NWORDS>(bnd + (size_t)(blk - 1) * U * ENT, U, rings + NW * RING * SLOT, done, NW, epoch, tid
-#ifdef VWGPU_SWEEP_DEBUG
-                                            , 0, 0, 4096
-#endif
                                             );
     return;
   }
@@ -3141,6 +3086,7 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
                    const uint8_t* lmask, int lmw, int lmh, const uint8_t* rmask, int rmw, int rmh,
                    const int32_t* prev, int pw, int ph, int32_t* out_disp, float* out_sub, size_t out_cap_pixels, int* ow, int* oh) {
   hipStream_t st = ctx->stream;
+  ctx->sgm_last_form = 0;                              // VWGPU_OPT_SGM_LAST_FORM: set when the call has queued all its work
   const int kernel = P->kernel_size;
   const int hk = (kernel - 1) / 2;
   SgmGeom g;
@@ -3169,7 +3115,7 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
   // fixed-size part of the arena
   const int lcw = lw - 2 * hk, lch = lh - 2 * hk, rcw = rw - 2 * hk, rch = rh - 2 * hk;
   // (guard zones around the census rasters: the register-resident path kernel requests census words up to 2 KC steps past a line's end)
-  const size_t cen_guard = (size_t)2 * VWGPU_PATH_KC * ((size_t)std::max(lcw, rcw) + 1) + 64;
+  const size_t cen_guard = (size_t)2 * PATH_KC * ((size_t)std::max(lcw, rcw) + 1) + 64;
   const size_t fixed = (size_t)lw * lh + (size_t)rw * rh + 8 * ((size_t)lcw * lch + (size_t)rcw * rch + 3 * cen_guard) + npix * (16 + 8 + 1) +
                        (size_t)g.orows * (24 + 8 + 8) + (1 << 16);
   int rc = vwgpu_arena_reserve(ctx, &ctx->sgm, fixed);
@@ -3221,6 +3167,7 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
   std::vector<unsigned long long> h_rows((size_t)3 * g.orows);
   unsigned long long main_buf = 0, n_total = 0, small16 = 0, small32 = 0, cells16 = 0;
   bool ok = false;
+  int f_level = 3, f_agg = 0, f_width = 0, f_together = 0, f_cluster = 0, f_cost = 0, f_wta = 0;      // VWGPU_OPT_SGM_LAST_FORM
   const int threads = P->num_threads > 0 ? P->num_threads : 1;
   for (int level = 0; level <= 3; ++level) {
     if (prev) {
@@ -3251,11 +3198,12 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
       small_buf = 4 * vert + 4 * horiz;
     }
     const double total = (double)n * (3.0 / MB) + (double)small_buf * (2.0 / MB);
-    if (!(total > (double)P->memory_limit_mb)) { ok = true; break; }
+    if (!(total > (double)P->memory_limit_mb)) { ok = true; f_level = level; break; }
   }
   if (!ok) {   // "Unable to compute valid search ranges for SGM input": an all-invalid disparity (SGM.cc:2428-2434)
     VWGPU_HIP(ctx, hipMemsetAsync(out_disp, 0, npix * 12, st));
     if (out_sub) VWGPU_HIP(ctx, hipMemsetAsync(out_sub, 0, npix * 12, st));
+    ctx->sgm_last_form = 1 << 20 | f_level << 18;
     return VWGPU_OK;
   }
   // every pixel searches the whole range: no masks, no previous level (bounds_kernel then wrote the full box everywhere)
@@ -3274,7 +3222,7 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
   // the two ragged buffers (separate arena: reserving may reallocate, the fixed part above must stay put)
   // The register-resident path kernel fetches two chunks of steps ahead without looking at the end of its line: up to 16 steps
   // past either end, i.e. 16 rows + 16 pixels before / behind a volume.  Guard zones keep those (unused) reads inside the arena.
-  const size_t guard = uniform ? vwgpu_align_up((size_t)2 * VWGPU_PATH_KC * ((size_t)g.ocols + 1) * ustride * 2, 256) : 0;
+  const size_t guard = uniform ? vwgpu_align_up((size_t)2 * PATH_KC * ((size_t)g.ocols + 1) * ustride * 2, 256) : 0;
   // MGM keeps the values of the directions in flight in volumes of their own (mgm_front_kernel): all eight, unless that takes
   // more than 24 GB (then four, two or one at a time: more launches, same result)
   const size_t vol_bytes = vwgpu_align_up((size_t)main_buf * 2, 256);
@@ -3311,7 +3259,7 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
   const int cen_oc = min_col - hk, cen_or = min_row - hk;
   const bool cen_ok = dir_paths && !block_cost && cen_oc >= 0 && cen_or >= 0 && cen_oc + g.ocols <= lcw && cen_or + g.orows <= std::min(lch, rch) &&
                       cen_oc + g.ocols - 1 + (int)num_disp <= rcw;
-  const bool ring_paths = dir_paths && !(ctx->sgm_path_mode & 32) && ustride <= 160;            // path_ring_kernel
+  const bool ring_paths = dir_paths && !sweep_nw && !(ctx->sgm_path_mode & 32) && ustride <= 160;            // path_ring_kernel (the sweeps, when chosen, run instead)
   const bool ring_cen = ring_paths && cen_ok && num_disp <= 129 && (ctx->sgm_path_mode & 2048) && (ctx->sgm_path_mode & 15) < 8;   // ... forming the census costs itself (opt-in: measured slower)
   if (ring_cen) {
   } else if (block_cost) {
@@ -3321,6 +3269,7 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
     for (unsigned n = 0; count > 1 && n <= 255u * count; ++n)         // (a single-pixel kernel returns the plain difference, SGM.cc:1658-1662)
       if ((unsigned)(((unsigned long long)n * magic) >> 32) != n / count) return vwgpu_fail(ctx, VWGPU_ERR_LOGIC, "calc_disparity_sgm: division constant");
     const bool fast = uniform && g.num_dy == 1 && (kernel == 3 || kernel == 5 || kernel == 7 || kernel == 9 || kernel == 11);
+    f_cost = fast ? 4 : 5;
     if (fast) {
       const int nw = (kernel + 3) / 4, rlw = block_row_dwords((int)num_disp, nw);
       const size_t lds = ((size_t)kernel * 4 * rlw + 4 * rlw + (size_t)kernel * (rlw + 1)) * sizeof(unsigned);
@@ -3337,6 +3286,7 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
     }
   } else {
     vwgpu_prof_scope ps(ctx, "sgm_cost");
+    f_cost = !uniform ? 3 : g.num_dy == 1 ? 1 : 2;
     if (uniform)
     {
       if (g.num_dy == 1) {
@@ -3347,7 +3297,7 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
       } else {
         const int qd = ustride / 16;                        // 16-disparity groups per pixel (2-D searches: stride % 16 == 0, 1 .. 32 groups)
         const dim3 blk(qd, std::max(1, 256 / qd)), grd((g.ocols + blk.y - 1) / blk.y, g.orows);
-        hipLaunchKernelGGL(cost_uniform16_kernel<false>, grd, blk, 0, st, lc, lcw, rcen, rcw, g.ocols, g.orows, g.num_dx, (int)num_disp, ustride,
+        hipLaunchKernelGGL(cost_uniform16_kernel, grd, blk, 0, st, lc, lcw, rcen, rcw, g.ocols, g.orows, g.num_dx, (int)num_disp, ustride,
                            min_col - hk, min_row - hk, reinterpret_cast<uint32_t*>(cost));
       }
     }
@@ -3384,6 +3334,7 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
     if (mgm_nw) {
       // the eight passes as four concurrent sweeps (mgm_sweep_kernel), then one pass adds the volumes to the sums
       vwgpu_prof_scope ps(ctx, "sgm_mgm_paths");
+      f_agg = 4; f_width = mgm_nw;
       MgmSweepParams MA;
       MA.g = g; MA.stride = ustride; MA.lw = lw; MA.lh = lh; MA.min_col = min_col; MA.min_row = min_row; MA.nw = mgm_nw;
       const size_t slot_dwords = (size_t)2 * 16 * mgm_q + 4;
@@ -3431,6 +3382,7 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
       int pe = (int)(((num_disp + 1) / 2 + 63) / 64);
       if (pe == 3) pe = 4;
       const bool reg_fronts = uniform && one_d && pe <= 4;
+      f_agg = reg_fronts ? 5 : 6; f_width = reg_fronts ? pe : (4 * lds <= 48 * 1024 ? 4 : 1);
       const size_t words = (vol_bytes + 15) / 16;
       for (int first = 0; first < 8; first += per) {
         MgmDirs M;
@@ -3463,6 +3415,7 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
       // two concurrent raster sweeps, four directions each: the sums are written once per sweep (sweep_uniform_kernel)
       vwgpu_prof_scope ps(ctx, "sgm_paths");
       const int nblk = (g.orows + sweep_nw - 1) / sweep_nw;
+      f_agg = 3; f_width = sweep_nw;
       const size_t slot_dwords = (size_t)3 * 16 * sweep_q + 4;
       const size_t bnd_bytes = (size_t)2 * nblk * g.ocols * slot_dwords * 8 + 256;
       if (ctx->sgm_bnd.cap < bnd_bytes || ctx->sgm_epoch == 0xffffffffu) {       // fresh memory (or the epochs are used up): no word may carry a future epoch
@@ -3475,9 +3428,6 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
       SA.g = g; SA.stride = ustride; SA.lw = lw; SA.min_col = min_col; SA.min_row = min_row; SA.nblk = nblk; SA.nw = sweep_nw;
       SA.p1 = (unsigned)p1; SA.p2 = (unsigned)p2; SA.epoch = ++ctx->sgm_epoch;
       SA.left = l8; SA.cost = cost; SA.out0 = accum; SA.out1 = accum2;
-#ifdef VWGPU_SWEEP_DEBUG
-      SA.dbg = getenv("VWGPU_SWEEP_DBG") ? atoi(getenv("VWGPU_SWEEP_DBG")) : 0;
-#endif
       SA.sync = reinterpret_cast<unsigned*>(static_cast<char*>(ctx->sgm_bnd.base));
       SA.bnd = reinterpret_cast<unsigned long long*>(static_cast<char*>(ctx->sgm_bnd.base) + 256);
       VWGPU_HIP(ctx, hipMemsetAsync(SA.sync, 0, 256, st));
@@ -3490,19 +3440,6 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
         case 5: VWGPU_SWEEP(5); break; case 6: VWGPU_SWEEP(6); break; default: VWGPU_SWEEP(8); break;
       }
 #undef VWGPU_SWEEP
-#ifdef VWGPU_SWEEP_DEBUG
-      if (getenv("VWGPU_SWEEP_TRACE")) {
-        std::vector<unsigned long long> tr((size_t)2 * 2048 * 8);
-        VWGPU_HIP(ctx, hipStreamSynchronize(st));
-        VWGPU_HIP(ctx, hipMemcpyFromSymbol(tr.data(), HIP_SYMBOL(sweep_trace), tr.size() * 8));
-        unsigned long long t0 = ~0ull;
-        for (int b = 0; b < nblk; ++b) for (int q = 0; q < 2; ++q) if (tr[((size_t)q * 2048 + b) * 8]) t0 = std::min(t0, tr[((size_t)q * 2048 + b) * 8]);
-        for (int b = 0; b < std::min(nblk, 2048); b += std::max(1, nblk / 24))
-          fprintf(stderr, "blk %4d fwd: w0 start %8.2f step8 %8.2f end %8.2f | last row start %8.2f step8 %8.2f end %8.2f | feeder first %8.2f last %8.2f us\n", b,
-                  (tr[b * 8 + 0] - t0) * 0.01, (tr[b * 8 + 6] - t0) * 0.01, (tr[b * 8 + 1] - t0) * 0.01, (tr[b * 8 + 2] - t0) * 0.01, (tr[b * 8 + 7] - t0) * 0.01,
-                  (tr[b * 8 + 3] - t0) * 0.01, (tr[b * 8 + 4] - t0) * 0.01, (tr[b * 8 + 5] - t0) * 0.01);
-      }
-#endif
     } else if (dir_paths) {
       // One direction per launch: every pixel lies on exactly one line of a launch, so the path costs are accumulated with plain
       // loads and stores, and the first direction stores (no memset).  (Tried: bands of rows with the directions pipelined over
@@ -3547,19 +3484,21 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
 #define VWGPU_RING2(E, A) do { if (rwpb == 8) VWGPU_RING5(E, A, 3, 8, false); else if (ring_cen) VWGPU_RING5(E, A, 4, 4, true); else VWGPU_RING5(E, A, 4, 4, false); } while (0)
 #define VWGPU_RING(E) do { if (acc == ACC_STORE) VWGPU_RING2(E, ACC_STORE); else if (acc == ACC_RMW_WTA) VWGPU_RING2(E, ACC_RMW_WTA); else VWGPU_RING2(E, ACC_RMW); } while (0)
           if (pe == 1) VWGPU_RING(1); else VWGPU_RING(2);
+          f_agg = 1; f_width = rwpb; f_cluster = (ctx->sgm_path_mode >> 8) & 7;
 #undef VWGPU_RING
 #undef VWGPU_RING2
 #undef VWGPU_RING5
           if (acc == ACC_RMW_WTA) wta_done = true;
           continue;
         }
-#define VWGPU_PATH_DIR3(E, A, WP) hipLaunchKernelGGL((path_uniform_reg_kernel<E, A, VWGPU_PATH_KC, WP>), dim3((nlines + WP - 1) / WP), dim3(64 * WP), 0, st, \
+#define VWGPU_PATH_DIR3(E, A, WP) hipLaunchKernelGGL((path_uniform_reg_kernel<E, A, WP>), dim3((nlines + WP - 1) / WP), dim3(64 * WP), 0, st, \
                                  g, S, ustride, l8, lw, min_col, min_row, cost, accum, (unsigned)p1, (unsigned)p2, out_disp, full_search, wta_flag)
 #define VWGPU_PATH_DIR2(E, A) do { if (wpb >= 4) VWGPU_PATH_DIR3(E, A, 4); else VWGPU_PATH_DIR3(E, A, 1); } while (0)
 #define VWGPU_PATH_DIR(E) do { if (acc == ACC_STORE) VWGPU_PATH_DIR2(E, ACC_STORE); else if (acc == ACC_RMW_WTA) VWGPU_PATH_DIR2(E, ACC_RMW_WTA); \
                                else VWGPU_PATH_DIR2(E, ACC_RMW); } while (0)
         switch (pe) { case 1: VWGPU_PATH_DIR(1); break; case 2: VWGPU_PATH_DIR(2); break; default: VWGPU_PATH_DIR(4); break; }
         if (acc == ACC_RMW_WTA) wta_done = true;
+        f_agg = 2; f_width = wpb >= 4 ? 4 : 1;
 #undef VWGPU_PATH_DIR
 #undef VWGPU_PATH_DIR2
 #undef VWGPU_PATH_DIR3
@@ -3579,10 +3518,12 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
       D.line0[D.n] = lines;
       if (lines <= 0) continue;
       vwgpu_prof_scope ps(ctx, together ? "sgm_paths" : "sgm_path");
+      f_together = together ? 1 : 0;
       if (uniform) {
         // (2-D searches only: one search row is served by path_uniform_reg_kernel above)
-#define VWGPU_PATH_U(E) hipLaunchKernelGGL((path_uniform_kernel<E, false>), dim3(lines), dim3(64), ulds, st, g, D, K, ustride, \
+#define VWGPU_PATH_U(E) hipLaunchKernelGGL((path_uniform_kernel<E>), dim3(lines), dim3(64), ulds, st, g, D, K, ustride, \
                                l8, lw, min_col, min_row, cost, accum, (unsigned)p1, (unsigned)p2)
+        f_agg = 7; f_width = ept >= 8 ? 8 : ept;
         switch (ept) {
           case 1: VWGPU_PATH_U(1); break; case 2: VWGPU_PATH_U(2); break; case 3: VWGPU_PATH_U(3); break; case 4: VWGPU_PATH_U(4); break;
           case 5: VWGPU_PATH_U(5); break; case 6: VWGPU_PATH_U(6); break; case 7: VWGPU_PATH_U(7); break; default: VWGPU_PATH_U(8); break;
@@ -3602,18 +3543,20 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
         const int pm = ctx->sgm_path_mode;
         const bool multi_ok = num_disp <= 4096 && !(pm & 64);           // (five full-range vectors of u16 in LDS; the cell index shares a register with the value)
         const bool large = lines >= 6000;                               // (a 512^2 level; below, the launch is short of wavefronts either way: no gain measured)
-        if (multi_ok && ((pm & 16) || (!(pm & 128) && large && small16 * 5 >= npix * 4 && (n_total - cells16) * 100 <= n_total * 15))) VWGPU_PATH_MULTI(16);
-        else if (multi_ok && ((pm & 128) || (large && small32 * 5 >= npix * 4))) VWGPU_PATH_MULTI(32);
+        if (multi_ok && ((pm & 16) || (!(pm & 128) && large && small16 * 5 >= npix * 4 && (n_total - cells16) * 100 <= n_total * 15))) { f_agg = 8; f_width = 4; VWGPU_PATH_MULTI(16); }
+        else if (multi_ok && ((pm & 128) || (large && small32 * 5 >= npix * 4))) { f_agg = 9; f_width = 2; VWGPU_PATH_MULTI(32); }
         else
 #undef VWGPU_PATH_MULTI
-        if (num_disp <= 64) VWGPU_PATH_IP(1);
-        else if (num_disp <= 128) VWGPU_PATH_IP(2);
-        else if (num_disp <= 256) VWGPU_PATH_IP(4);
-        else if (num_disp <= 512) VWGPU_PATH_IP(8);
-        else if (num_disp <= 1024) VWGPU_PATH_IP(16);
-        else                                        // very large 2-D searches: the three-phase kernel, any size
+        if (num_disp <= 64) { f_agg = 10; f_width = 1; VWGPU_PATH_IP(1); }
+        else if (num_disp <= 128) { f_agg = 10; f_width = 2; VWGPU_PATH_IP(2); }
+        else if (num_disp <= 256) { f_agg = 10; f_width = 4; VWGPU_PATH_IP(4); }
+        else if (num_disp <= 512) { f_agg = 10; f_width = 8; VWGPU_PATH_IP(8); }
+        else if (num_disp <= 1024) { f_agg = 10; f_width = 16; VWGPU_PATH_IP(16); }
+        else {                                      // very large 2-D searches: the three-phase kernel, any size
+          f_agg = 11;
           hipLaunchKernelGGL(path_kernel, dim3(lines), dim3(64), lds, st, g, D, l8, lw, min_col, min_row, bounds, starts, cost, accum,
                              (unsigned)p1, (unsigned)p2);
+        }
 #undef VWGPU_PATH_IP
       }
     }
@@ -3624,13 +3567,13 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
     const uint8_t* todo = nullptr;
     const int* any_todo = nullptr;
     if (wta_done) {                                         // the last direction took the unique minima; ties go to the general kernel
-      todo = full_search; any_todo = wta_flag;
+      todo = full_search; any_todo = wta_flag; f_wta = 2;
     } else if (uniform && g.num_dy == 1 && num_disp <= 256) {      // unique minima straight from the packed vectors; ties go to the general kernel
       int* flag = reinterpret_cast<int*>(mm + 6);
       VWGPU_HIP(ctx, hipMemsetAsync(flag, 0, sizeof(int), st));
       hipLaunchKernelGGL(wta_uniform_kernel, dim3((unsigned)((npix + 4 * WTAU_PPW - 1) / (4 * WTAU_PPW))), dim3(256), 0, st, npix, (int)num_disp, ustride,
                          g.min_dx, g.min_dy, accum, accum2, out_disp, full_search, flag);
-      todo = full_search; any_todo = flag;
+      todo = full_search; any_todo = flag; f_wta = 1;
     }
     hipLaunchKernelGGL(wta_kernel, dim3((unsigned)((npix + 4 * WTA_PPW - 1) / (4 * WTA_PPW))), dim3(256), lds, st, bounds, starts, npix, (int)num_disp, accum, out_disp,
                        todo, any_todo);
@@ -3640,5 +3583,6 @@ int vwgpu_sgm_impl(vwgpu_ctx* ctx, const vwgpu_sgm_params* P, const float* left,
     hipLaunchKernelGGL(subpixel_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, P->subpixel_mode, bounds, starts, npix, accum, accum2, out_disp, out_sub);
   }
   VWGPU_HIP(ctx, hipGetLastError());
+  ctx->sgm_last_form = f_agg | f_width << 4 | f_together << 9 | f_cluster << 10 | f_cost << 13 | f_wta << 16 | f_level << 18;
   return VWGPU_OK;
 }

@@ -302,6 +302,7 @@ static const struct { int id; int vwgpu_ctx::* field; int lo, hi; bool settable;
   {VWGPU_OPT_SGM_SWEEP, &vwgpu_ctx::sgm_sweep, 0, 15, true},
   {VWGPU_OPT_MGM_SWEEP, &vwgpu_ctx::mgm_sweep, 0, 15, true},
   {VWGPU_OPT_SGM_PATH_MODE, &vwgpu_ctx::sgm_path_mode, 0, 4095, true},
+  {VWGPU_OPT_SGM_LAST_FORM, &vwgpu_ctx::sgm_last_form, 0, 0, false},
   {VWGPU_OPT_EXACT_SPLIT, &vwgpu_ctx::exact_split, 0, 3, true},
   {VWGPU_OPT_HOST_RING_KB, &vwgpu_ctx::host_ring_kb, 16, 1 << 20, true},
 };

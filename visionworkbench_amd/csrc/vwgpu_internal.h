@@ -79,6 +79,7 @@ struct vwgpu_ctx {
   int sad_round_slots = 0;    // VWGPU_OPT_SAD_ROUND_SLOTS
   int exact_scratch_mb = 4096;// VWGPU_OPT_EXACT_SCRATCH_MB
   int ip_scratch_mb = 1024;   // VWGPU_OPT_IP_SCRATCH_MB
+  int sgm_last_form = 0;      // VWGPU_OPT_SGM_LAST_FORM
   int exact_split = 0;        // VWGPU_OPT_EXACT_SPLIT: 0 by the longest chain, 1 always the split pass 2, 2 always the fused one
   int trace = 0;              // VWGPU_OPT_TRACE
   int certify = 1;            // VWGPU_OPT_CERTIFY

@@ -132,7 +132,8 @@ const char* vwgpu_last_error(const vwgpu_ctx* ctx);
  *   VWGPU_OPT_SAD_LAYOUT       LDS word-group array of the packed-u8 SAD matcher: 0 (default) = entry-major wherever it fits the LDS budget
  *       (row offsets are immediates; its rows are padded, so the widest searches keep the row-major array), 1 = always row-major.  Same results.
  *   VWGPU_OPT_SAD_LAST_LAUNCH  (read only) what the launcher chose for the context's last packed-u8 SAD launch (0 = none yet): bits 0-7 = tile
- *       rows, bits 8-11 = tile columns / 256, bits 12-15 = wave groups per tile, bit 16 = entry-major word groups.  For tests and tools.
+ *       rows, bits 8-11 = tile columns / 256, bits 12-15 = wave groups per tile, bit 16 = entry-major word groups, bit 17 = the kernel
+ *       with streaming output stores (one-group grids of two rounds or more).  For tests and tools.
  *   VWGPU_OPT_SAD_ROUND_SLOTS  workgroup slots the packed-u8 SAD launcher assumes when it marks the first and the last round of dispatch of a
  *       one-group grid (the first-round hand-off and the end balance engage on grids of at least two rounds): 0 (default) = from the
  *       device's CU count, n (1 .. 1048576) = n slots — the launcher then plans, tile choice included, for a device of n / 2 CUs, so that

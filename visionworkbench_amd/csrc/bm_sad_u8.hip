@@ -165,7 +165,8 @@ __host__ __device__ constexpr size_t ent_words(int nr, int ne, int ew, int gr, i
 // EM = entry-major word groups ([entry][row][EW], rows padded to an odd count): a row of a step is an immediate offset from the lane's
 //      entry.  EM = false is the row-major array ([row][entry][EW], row pitch in a register): the launcher takes it only for searches
 //      so wide that the padded array would not fit the LDS budget.
-template <int KX, int KY, int TY, int GR, int WV = 0, bool EM = true>
+// STREAM = the epilogue's output stores carry the non-temporal hint (one-group kernels on grids of two rounds or more: see the epilogue).
+template <int KX, int KY, int TY, int GR, int WV = 0, bool EM = true, bool STREAM = false>
 __global__ void __launch_bounds__((GR * (Cfg<KX, KY, TY, WV>::THREADS)), (GR > 1 ? 1 : (TY <= 8 && KX <= 8 ? 3 : 2)))
 bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
                  const float* __restrict__ R, ptrdiff_t rs, int rcw, int rch,
@@ -174,6 +175,7 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
                  int gxt, int ntiles, int last_round, int first_round, int stagger_ticks) {
   typedef Cfg<KX, KY, TY, WV> C;
   constexpr bool SPLIT = GR > 1;
+  static_assert(!(STREAM && SPLIT), "streaming output stores: one-group kernels only");
   constexpr int NW = C::NW, EW = C::EW, NR = C::NR;
   // rows per entry column.  Odd: consecutive lanes read consecutive entries, and an even column stride would put lanes l and l + 16
   // (EW = 2: a 64-bit read is served in halves of 32 lanes over 64 banks) or l and l + 8 (EW = 4) on the same banks.
@@ -525,6 +527,13 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
   // A lane owns 4 pixels = 12 consecutive dwords, so direct stores would be 48-byte strided (measured: 80 us of the
   // 400 on the 4096^2 case).  Each wave transposes its 256-pixel row (768 dwords) through LDS and writes it as
   // three fully coalesced 1 KiB stores.
+  // STREAM: the stores carry the non-temporal hint.  The output is never read again, and stored with the default policy it pushes out of the
+  // caches the input rows that the workgroups of the next round stage while this one stores: on the 4096^2 grid (two rounds) the hint is
+  // worth 5-6 us of the launch. On a one-round grid every workgroup stores at the end of the launch, nothing is staged after it, and the
+  // hint only slows the burst (1/4 strip + 2.7 us, 1/2 strip + 1.3 us), so the launcher takes the STREAM kernels for grids of two rounds or
+  // more only.  The validity sweep's rare zero stores below stay plain: they must land after these.  Pieces cut at the 128-byte lines of
+  // the absolute address (a head of single dwords, 16-byte aligned lane stores gathered from LDS, a tail) were measured and are not
+  // used: WRITE_SIZE did not move and the launch got 2-3 us longer (profiles/sad_output_stores.md).
   {
     const int wv = ltid >> 6, lane = ltid & 63;
     u32* ob = ent + (size_t)(grp * (PT / 64) + wv) * 768;
@@ -534,6 +543,11 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
     // di / sx for di < 2^16 as a multiply-high by ceil(2^32 / sx) (exact: di * (magic * sx - 2^32) < 2^32); sx == 1 apart
     const u32 sx_magic = sx > 1 ? (u32)(0xffffffffu / (u32)sx) + 1u : 0u;
     struct __attribute__((packed, aligned(4))) U4 { u32 x, y, z, w; };
+    typedef u32 V4 __attribute__((ext_vector_type(4), aligned(4)));     // the same 16 bytes as a type the non-temporal builtin takes
+    auto put = [&](u32 v, int32_t* p) __attribute__((always_inline)) {
+      if constexpr (STREAM) __builtin_nontemporal_store((int32_t)v, p);
+      else *p = (int32_t)v;
+    };
 #pragma unroll
     for (int y = 0; y < TY; ++y) {
       const int oy = y0 + y;
@@ -559,12 +573,17 @@ bm_sad_u8_kernel(const float* __restrict__ L, ptrdiff_t ls, int lw, int lh,
         const int idx = k * 256 + lane * 4;
         const uint4 t = *reinterpret_cast<const uint4*>(ob + idx);
         if (idx + 3 < nd) {
-          U4 u; u.x = t.x; u.y = t.y; u.z = t.z; u.w = t.w;
-          *reinterpret_cast<U4*>(orow + idx) = u;
+          if constexpr (STREAM) {
+            const V4 u = {t.x, t.y, t.z, t.w};
+            __builtin_nontemporal_store(u, reinterpret_cast<V4*>(orow + idx));   // (the pointer type spelled out: a deduced one drops the alignment)
+          } else {
+            U4 u; u.x = t.x; u.y = t.y; u.z = t.z; u.w = t.w;
+            *reinterpret_cast<U4*>(orow + idx) = u;
+          }
         } else {
-          if (idx < nd) orow[idx] = (int32_t)t.x;
-          if (idx + 1 < nd) orow[idx + 1] = (int32_t)t.y;
-          if (idx + 2 < nd) orow[idx + 2] = (int32_t)t.z;
+          if (idx < nd) put(t.x, orow + idx);
+          if (idx + 1 < nd) put(t.y, orow + idx + 1);
+          if (idx + 2 < nd) put(t.z, orow + idx + 2);
         }
       }
     }
@@ -605,12 +624,13 @@ struct Launch {
   KernelFn fn;
   KernelFn split_fn;         // the two-wave-group matcher for small grids (nullptr: not instantiated for this size)
   KernelFn fn_rm, split_fn_rm;   // the same two with the row-major entry array (searches too wide for the padded entry-major one)
+  KernelFn fn_nt, fn_nt_rm;      // `fn` / `fn_rm` with streaming output stores: grids of two rounds or more
 };
 
 // the kernel, instantiated only where kLaunch can reach it
-template <bool ON, int KX, int KY, int TY, int GR, int WV, bool EM>
+template <bool ON, int KX, int KY, int TY, int GR, int WV, bool EM, bool STREAM = false>
 constexpr KernelFn kernel_if() {
-  if constexpr (ON) return bm_sad_u8_kernel<KX, KY, TY, GR, WV, EM>;
+  if constexpr (ON) return bm_sad_u8_kernel<KX, KY, TY, GR, WV, EM, STREAM>;
   else return nullptr;
 }
 
@@ -621,7 +641,9 @@ constexpr Launch make_launch() {
                 kernel_if<WV == 0, KX, KY, TY, 1, WV, true>(),                   // (the narrow tile exists as the four-group matcher only)
                 kernel_if<WITH_SPLIT, KX, KY, TY, (WV ? 4 : 2), WV, true>(),
                 kernel_if<WV == 0, KX, KY, TY, 1, WV, false>(),
-                kernel_if<WITH_SPLIT, KX, KY, TY, (WV ? 4 : 2), WV, false>()};
+                kernel_if<WITH_SPLIT, KX, KY, TY, (WV ? 4 : 2), WV, false>(),
+                kernel_if<WV == 0, KX, KY, TY, 1, WV, true, true>(),
+                kernel_if<WV == 0, KX, KY, TY, 1, WV, false, true>()};
 }
 
 // Instantiated kernel sizes.  Others fall back to the generic path.
@@ -726,8 +748,6 @@ int launch(vwgpu_ctx* ctx, const vwgpu_bm_args& a, int** d_flag) {
   // may exceed the constant by those 64 bytes, as it always could: a split workgroup has its CU to itself)
   const bool em = ctx->sad_layout == 0 && lds_bytes(*l, sx, groups, true) + ctr_bytes <= kMaxLds;
   const size_t shmem = lds_bytes(*l, sx, groups, em) + ctr_bytes;
-  ctx->sad_last_launch = l->ty | (l->twb / 256) << 8 | groups << 12 | (em ? 1 : 0) << 16;      // VWGPU_OPT_SAD_LAST_LAUNCH
-  const KernelFn main_fn = em ? (split ? l->split_fn : l->fn) : (split ? l->split_fn_rm : l->fn_rm);
   const unsigned grid1 = (unsigned)((gx * gy + 7) / 8 * 8);   // one tile per workgroup, see the XCD note in the kernel
   // the end balance of the one-group matcher (see the kernel): workgroups are dispatched in index order, and the last `slots` of a grid
   // of two rounds or more are its last round; INT_MAX turns it off (one round: the slots start together, nothing to balance)
@@ -735,6 +755,9 @@ int launch(vwgpu_ctx* ctx, const vwgpu_bm_args& a, int** d_flag) {
   const int slots = ctx->sad_round_slots > 0 ? ctx->sad_round_slots : ctx->num_cu * resident;
   const bool rounds = !split && (int)grid1 >= 2 * slots;
   const int last_round = rounds ? (int)grid1 - slots : INT_MAX;
+  // a grid of two rounds or more stores while later workgroups stage: the kernels with streaming output stores (see the epilogue)
+  const KernelFn main_fn = em ? (split ? l->split_fn : rounds ? l->fn_nt : l->fn) : (split ? l->split_fn_rm : rounds ? l->fn_nt_rm : l->fn_rm);
+  ctx->sad_last_launch = l->ty | (l->twb / 256) << 8 | groups << 12 | (em ? 1 : 0) << 16 | (rounds ? 1 : 0) << 17;   // VWGPU_OPT_SAD_LAST_LAUNCH
   // the first-round hand-off (see the kernel): the first `slots` workgroups, two to a CU
   const int first_round = (rounds && resident == 2) ? slots : 0;
   vwgpu_flag_pair f;

@@ -39,6 +39,7 @@ extern "C" {
  *     Round 6 added option values only (VWGPU_OPT_SGM_PATH_MODE, VWGPU_OPT_SAD_GROUPS = 3): same version.
  *     VWGPU_OPT_SAD_LAYOUT, VWGPU_OPT_SAD_LAST_LAUNCH, VWGPU_OPT_SAD_ROUND_SLOTS (options 20, 21, 22) likewise, and
  *     VWGPU_OPT_IP_SCRATCH_MB (23) with the interest-point entries, VWGPU_OPT_SGM_LAST_FORM (24, read only) likewise.
+ *     The hole-filling entries (vwgpu_grassfire .. vwgpu_fill_nodata_with_avg) and VWGPU_OPT_INPAINT_OVERLAP (25) are additions: same version.
  * A host checks vwgpu_abi_version() == VWGPU_ABI_VERSION once after loading the library (vw::engine does, vw/Engine.h). */
 #define VWGPU_ABI_VERSION 3
 
@@ -196,14 +197,16 @@ const char* vwgpu_last_error(const vwgpu_ctx* ctx);
  *   VWGPU_OPT_HOST_RING_KB     size in KiB (16 .. 1048576, default 16384) of the pinned host ring through which zone / work-item tables
  *       reach the device; pieces larger than a quarter of it are copied from pageable memory and waited for.  A small ring makes the
  *       library wait for the device more often, nothing else (tests use it to wrap the ring on small rasters).
- *   VWGPU_OPT_HOST_RING_WRAPS  (read only) how often the ring cursor has changed halves so far. */
+ *   VWGPU_OPT_HOST_RING_WRAPS  (read only) how often the ring cursor has changed halves so far.
+ *   VWGPU_OPT_INPAINT_OVERLAP  the sweeps of vwgpu_inpaint / vwgpu_fill_holes_grass: 1 (default) = consecutive sweeps over a blob overlap
+ *       in time, 0 = a sweep starts when the previous one has ended.  Same words in both forms. */
 typedef enum vwgpu_option {
   VWGPU_OPT_DEFER_EXACTNESS = 1, VWGPU_OPT_DEVICE_COUNT = 2, VWGPU_OPT_SAD_GROUPS = 3, VWGPU_OPT_EXACT_SCRATCH_MB = 4,
   VWGPU_OPT_TRACE = 5, VWGPU_OPT_SGM_SWEEP = 6, /* 7: removed in ABI 2 */ VWGPU_OPT_MGM_SWEEP = 8, VWGPU_OPT_EXACT_SPLIT = 9,
   /* 10: removed in ABI 2 */ VWGPU_OPT_HOST_RING_KB = 11, VWGPU_OPT_HOST_RING_WRAPS = 12, VWGPU_OPT_CERTIFY = 13,
   VWGPU_OPT_CERT_PERMILLE = 14, VWGPU_OPT_ZONE_SXC = 15, VWGPU_OPT_CERT_F32 = 16, VWGPU_OPT_CERT_F64_PERMILLE = 17, VWGPU_OPT_ZONE_TILE16 = 18,
   VWGPU_OPT_SGM_PATH_MODE = 19, VWGPU_OPT_SAD_LAYOUT = 20, VWGPU_OPT_SAD_LAST_LAUNCH = 21, VWGPU_OPT_SAD_ROUND_SLOTS = 22,
-  VWGPU_OPT_IP_SCRATCH_MB = 23, VWGPU_OPT_SGM_LAST_FORM = 24
+  VWGPU_OPT_IP_SCRATCH_MB = 23, VWGPU_OPT_SGM_LAST_FORM = 24, VWGPU_OPT_INPAINT_OVERLAP = 25
 } vwgpu_option;
 int vwgpu_set_option(vwgpu_ctx* ctx, int option, int value);
 int vwgpu_get_option(const vwgpu_ctx* ctx, int option, int* value);
@@ -770,6 +773,103 @@ int vwgpu_intersect_mask_and_data_dev(vwgpu_ctx* ctx, int type, const void* d_da
                                       ptrdiff_t mstride, int w, int h, void* d_out, ptrdiff_t ostride);
 int vwgpu_intersect_mask_and_data(vwgpu_ctx* ctx, int type, const void* data, ptrdiff_t dstride, const void* mask, ptrdiff_t mstride,
                                   int w, int h, void* out, ptrdiff_t ostride);
+
+/* ---- Image/Grassfire.h, BlobIndex.h, ErodeView.h, InpaintView.h: filling the holes of a masked image ---------- */
+/* (tests/refimpl/hole_fill_ref.cc.)  Strides are in pixels, 0 = packed.  Masked pixels:
+ *   VWGPU_PIXEL_MASK_U8        one uint8, non-zero = valid
+ *   VWGPU_PIXEL_MASKED_F32     PixelMask<float> as float {value, valid != 0}
+ *   VWGPU_PIXEL_DISPARITY_I32  PixelMask<Vector2i> as int32 {dx, dy, valid != 0}
+ *   VWGPU_PIXEL_DISPARITY_F32  PixelMask<Vector2f> as float {dx, dy, valid != 0}
+ * An image holds at most 2^31 - 1 pixels. */
+typedef enum vwgpu_pixel_kind {
+  VWGPU_PIXEL_MASK_U8 = 0, VWGPU_PIXEL_MASKED_F32 = 1, VWGPU_PIXEL_DISPARITY_I32 = 2, VWGPU_PIXEL_DISPARITY_F32 = 3
+} vwgpu_pixel_kind;
+typedef enum vwgpu_grassfire_type { VWGPU_GRASSFIRE_U8 = 0, VWGPU_GRASSFIRE_I32 = 1, VWGPU_GRASSFIRE_F32 = 2 } vwgpu_grassfire_type;
+/* InpaintTask leaves a blob alone when its bounding box grown by one has min < 0 or max >= cols / rows with an EXCLUSIVE max
+ * (src/vw/Image/InpaintView.h:76-80): a blob touching column 0 or row 0 is skipped, and so is one whose last column is >= cols - 2 or
+ * whose last row is >= rows - 2, although a hole with one valid column to its right has its whole ring inside the image.
+ *   VWGPU_HOLE_EDGE_REFERENCE  that rule as written (what the reference gives when it rasterises the whole image as one tile).
+ *   VWGPU_HOLE_EDGE_FIXED      exactly the blobs that touch the image border are skipped; any tiling of the reference then gives
+ *                              these pixels wherever its tile's crop does not cut the rule short. */
+typedef enum vwgpu_hole_edge_semantics { VWGPU_HOLE_EDGE_REFERENCE = 0, VWGPU_HOLE_EDGE_FIXED = 1 } vwgpu_hole_edge_semantics;
+/* The largest hole_fill_len / max_len: a blob's bounding box grown by one lives in the LDS of one workgroup. */
+#define VWGPU_HOLE_FILL_MAX_LEN 64
+
+/* Replaces vw::grassfire(src, dst, ignore_borders) (src/vw/Image/Grassfire.h:79-228) with an int32 output: the Manhattan distance
+ * to the nearest pixel with src == 0 (a NaN is non-zero, -0.0f is zero).  ignore_borders == 0: everything outside the image counts
+ * as zero; otherwise it does not and the result is capped at cols + rows.  cols <= 1 or rows <= 1 gives zeros (:86).
+ * src_type: a vwgpu_grassfire_type.  out must not overlap src. */
+int vwgpu_grassfire_dev(vwgpu_ctx* ctx, int src_type, const void* d_src, int w, int h, ptrdiff_t sstride, int ignore_borders,
+                        int32_t* d_out, ptrdiff_t ostride);
+int vwgpu_grassfire(vwgpu_ctx* ctx, int src_type, const void* src, int w, int h, ptrdiff_t sstride, int ignore_borders, int32_t* out,
+                    ptrdiff_t ostride);
+
+/* Replaces BlobIndexThreaded(src, max_area, tile_size) with the whole image as ONE tile, followed by wipe_big_blobs(wipe_size)
+ * when wipe_size > 0 (src/vw/Image/BlobIndex.h:113-306, :385-477): the 8-connected components of the valid pixels (invert != 0: of
+ * the invalid ones, invert_mask), in the reference's order (the k-th blob is the one whose first pixel in raster order comes
+ * k-th); max_area > 0 drops blobs of more than max_area pixels (:445-453), wipe_size > 0 those whose bounding box is wider or
+ * taller than wipe_size (:457-477).  *count (host, required) receives the number of blobs kept.
+ *   labels (optional, int32 w x h): the 1-based number of the kept blob a pixel belongs to, else 0.  NOT what blob_index() of the
+ *       reference returns: that image keeps the provisional labels of the raster pass (:267-304).
+ *   table (optional, table_cap rows of 5 int32): {min.x, min.y, max.x, max.y, size} per kept blob, the box half-open.  With more
+ *       blobs than table_cap the call returns VWGPU_ERR_CAPACITY, *count says how many rows it takes, the table is not written.
+ * The _dev form takes labels and table on the device and waits for the device (count).  Multi-tile consolidate() and its
+ * tile-dependent blob order are not reproduced. */
+int vwgpu_blob_index_dev(vwgpu_ctx* ctx, int kind, const void* d_img, int w, int h, ptrdiff_t istride, int invert, int max_area,
+                         int wipe_size, int32_t* d_labels, ptrdiff_t lstride, int32_t* d_table, int table_cap, int* count);
+int vwgpu_blob_index(vwgpu_ctx* ctx, int kind, const void* img, int w, int h, ptrdiff_t istride, int invert, int max_area, int wipe_size,
+                     int32_t* labels, ptrdiff_t lstride, int32_t* table, int table_cap, int* count);
+
+/* Replaces vw::get_blob_sizes(image, expand, limit) (src/vw/Image/BlobIndex.h:507-615) with the image as one tile: every valid
+ * pixel receives min(size of its blob, limit), every invalid pixel 0 (uint32 w x h). */
+int vwgpu_blob_sizes_dev(vwgpu_ctx* ctx, int kind, const void* d_img, int w, int h, ptrdiff_t istride, uint32_t limit, uint32_t* d_out,
+                         ptrdiff_t ostride);
+int vwgpu_blob_sizes(vwgpu_ctx* ctx, int kind, const void* img, int w, int h, ptrdiff_t istride, uint32_t limit, uint32_t* out,
+                     ptrdiff_t ostride);
+
+/* Replaces applyErodeView(src, BlobIndexThreaded(src, max_area, ..)) (src/vw/Image/ErodeView.h:199-221) on any pixel kind: every
+ * pixel of a blob of VALID pixels with at most max_area pixels becomes the default pixel (every word 0, invalid), everything else
+ * is copied; max_area < 1 copies.  For int32 disparities this is vwgpu_disparity_blob_filter.  out may be the input. */
+int vwgpu_erode_blobs_dev(vwgpu_ctx* ctx, int kind, const void* d_img, int w, int h, ptrdiff_t istride, int max_area, void* d_out,
+                          ptrdiff_t ostride);
+int vwgpu_erode_blobs(vwgpu_ctx* ctx, int kind, const void* img, int w, int h, ptrdiff_t istride, int max_area, void* out, ptrdiff_t ostride);
+
+/* Replaces rasterising vw::inpaint(src, bindex, use_grassfire, default_inpaint_val) (src/vw/Image/InpaintView.h:44-237) in one
+ * call over the whole image, for VWGPU_PIXEL_MASKED_F32 and VWGPU_PIXEL_DISPARITY_F32.  The blob selection {labels, table, count}
+ * is what vwgpu_blob_index returned, kept on the device for the _dev form.  Every blob is filled independently from the unpatched
+ * input; a blob skipped by the edge rule (vwgpu_hole_edge_semantics) or wider or taller than max_len (<= VWGPU_HOLE_FILL_MAX_LEN;
+ * as wipe_big_blobs(max_len) would have removed it) is left as it is.
+ *   use_grassfire != 0: 10 * max_distance^2 in-place sweeps over the blob's pixels in the order (grassfire distance, column, row);
+ *       a pixel becomes the weighted sum of its eight neighbours (.176765 diagonal, .073235 side; UL U UR L R DL D DR), each term
+ *       added in double and rounded to the float accumulator (:120-138), and valid.  The stored values of the invalid pixels are
+ *       the initial guess.  Word for word the serial result.
+ *   use_grassfire == 0: the blob's pixels become default_pixel (host; 2 or 3 floats, validity last; NULL = zeros) as given.
+ * out may be the input: a blob reads only itself and its ring of valid pixels. */
+int vwgpu_inpaint_dev(vwgpu_ctx* ctx, int kind, const void* d_img, int w, int h, ptrdiff_t istride, const int32_t* d_labels, ptrdiff_t lstride,
+                      const int32_t* d_table, int count, int use_grassfire, const float* default_pixel, int semantics, int max_len,
+                      void* d_out, ptrdiff_t ostride);
+int vwgpu_inpaint(vwgpu_ctx* ctx, int kind, const void* img, int w, int h, ptrdiff_t istride, const int32_t* labels, ptrdiff_t lstride,
+                  const int32_t* table, int count, int use_grassfire, const float* default_pixel, int semantics, int max_len, void* out,
+                  ptrdiff_t ostride);
+
+/* Replaces rasterising vw::fill_holes_grass(img, hole_fill_len) (src/vw/Image/InpaintView.h:239-311) in one call over the whole
+ * image: the blobs of the INVALID pixels, wipe_big_blobs(hole_fill_len) (which implies the area limit hole_fill_len^2), inpaint
+ * with grassfire.  0 <= hole_fill_len <= VWGPU_HOLE_FILL_MAX_LEN, else VWGPU_ERR_ARGUMENT before any device work.  The result
+ * does not depend on a tiling except through the edge rule, which the reference applies to its tile's crop.  Float kinds only.
+ * out may be the input.  Waits for the device (the number of blobs). */
+int vwgpu_fill_holes_grass_dev(vwgpu_ctx* ctx, int kind, const void* d_img, int w, int h, ptrdiff_t istride, int hole_fill_len, int semantics,
+                               void* d_out, ptrdiff_t ostride);
+int vwgpu_fill_holes_grass(vwgpu_ctx* ctx, int kind, const void* img, int w, int h, ptrdiff_t istride, int hole_fill_len, int semantics,
+                           void* out, ptrdiff_t ostride);
+
+/* Replaces rasterising vw::fill_nodata_with_avg(img, kernel_size) (src/vw/Image/InpaintView.h:317-387) on PixelMask<float>
+ * {value, valid}: an invalid pixel becomes the float sum of the valid pixels of its kernel_size x kernel_size window clipped to
+ * the image (column outer, row inner) divided by their count, and valid; it is unchanged without any.  kernel_size is odd and
+ * > 0.  out must not be the input. */
+int vwgpu_fill_nodata_with_avg_dev(vwgpu_ctx* ctx, const float* d_img, int w, int h, ptrdiff_t istride, int kernel_size, float* d_out,
+                                   ptrdiff_t ostride);
+int vwgpu_fill_nodata_with_avg(vwgpu_ctx* ctx, const float* img, int w, int h, ptrdiff_t istride, int kernel_size, float* out,
+                               ptrdiff_t ostride);
 
 /* ---- Stereo/StereoModel.{h,cc} and Stereo/StereoView.h: triangulation and the universe radius ---------- */
 

@@ -1,0 +1,14 @@
+# hole_fill_view: a vwlite program over libvwgpu.so (test infrastructure only); make -f hole_fill_view.mk.
+CXX ?= g++
+ROOT := ../..
+LIBDIR := $(abspath $(ROOT)/visionworkbench_amd/lib)
+ROCM_LIB ?= /opt/rocm/lib
+CXXFLAGS ?= -O1 -std=c++17 -Wall -ffp-contract=off
+
+all: hole_fill_view
+
+hole_fill_view: hole_fill_view.cc $(ROOT)/visionworkbench_amd/vwlite/vw/Image.h $(ROOT)/visionworkbench_amd/vwlite/vw/FileIO.h $(ROOT)/include/vwgpu.h
+	$(CXX) $(CXXFLAGS) -I$(ROOT)/include -I$(ROOT)/visionworkbench_amd/vwlite -o $@ hole_fill_view.cc -L$(LIBDIR) -lvwgpu -Wl,-rpath,$(LIBDIR) -Wl,-rpath,$(ROCM_LIB) -pthread
+
+clean:
+	rm -f hole_fill_view

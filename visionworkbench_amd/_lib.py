@@ -33,6 +33,9 @@ SYMBOLS = [
     "vwgpu_disparity_subsample_dev", "vwgpu_disparity_subsample", "vwgpu_disparity_upsample_dev", "vwgpu_disparity_upsample",
     "vwgpu_disparity_warp_dev", "vwgpu_disparity_warp", "vwgpu_missing_pixel_image_dev", "vwgpu_missing_pixel_image",
     "vwgpu_intersect_mask_and_data_dev", "vwgpu_intersect_mask_and_data",
+    "vwgpu_grassfire_dev", "vwgpu_grassfire", "vwgpu_blob_index_dev", "vwgpu_blob_index", "vwgpu_blob_sizes_dev", "vwgpu_blob_sizes",
+    "vwgpu_erode_blobs_dev", "vwgpu_erode_blobs", "vwgpu_inpaint_dev", "vwgpu_inpaint",
+    "vwgpu_fill_holes_grass_dev", "vwgpu_fill_holes_grass", "vwgpu_fill_nodata_with_avg_dev", "vwgpu_fill_nodata_with_avg",
     "vwgpu_pinhole_camera", "vwgpu_stereo_triangulate_dev", "vwgpu_stereo_triangulate",
     "vwgpu_convergence_angle_dev", "vwgpu_convergence_angle", "vwgpu_universe_radius_dev", "vwgpu_universe_radius",
     "vwgpu_pinhole_camera_matrix", "vwgpu_epipolar_pinhole", "vwgpu_epipolar_cahv",
@@ -252,6 +255,27 @@ def load():
     imd = [P, I, P, PD, P, PD, I, I, P, PD]
     lib.vwgpu_intersect_mask_and_data_dev.argtypes = imd
     lib.vwgpu_intersect_mask_and_data.argtypes = imd
+    gfr = [P, I, P, I, I, PD, I, P, PD]
+    lib.vwgpu_grassfire_dev.argtypes = gfr
+    lib.vwgpu_grassfire.argtypes = gfr
+    bix = [P, I, P, I, I, PD, I, I, I, P, PD, P, I, ctypes.POINTER(ctypes.c_int)]
+    lib.vwgpu_blob_index_dev.argtypes = bix
+    lib.vwgpu_blob_index.argtypes = bix
+    bsz = [P, I, P, I, I, PD, ctypes.c_uint32, P, PD]
+    lib.vwgpu_blob_sizes_dev.argtypes = bsz
+    lib.vwgpu_blob_sizes.argtypes = bsz
+    ero = [P, I, P, I, I, PD, I, P, PD]
+    lib.vwgpu_erode_blobs_dev.argtypes = ero
+    lib.vwgpu_erode_blobs.argtypes = ero
+    inp = [P, I, P, I, I, PD, P, PD, P, I, I, P, I, I, P, PD]
+    lib.vwgpu_inpaint_dev.argtypes = inp
+    lib.vwgpu_inpaint.argtypes = inp
+    fhg = [P, I, P, I, I, PD, I, I, P, PD]
+    lib.vwgpu_fill_holes_grass_dev.argtypes = fhg
+    lib.vwgpu_fill_holes_grass.argtypes = fhg
+    fna = [P, P, I, I, PD, I, P, PD]
+    lib.vwgpu_fill_nodata_with_avg_dev.argtypes = fna
+    lib.vwgpu_fill_nodata_with_avg.argtypes = fna
     CP = ctypes.POINTER(Camera)
     lib.vwgpu_pinhole_camera.argtypes = [P, P, D, D, D, D, P, P, P, D, I, P, CP]
     tri = [P, I, P, I, I, PD, I, I, CP, CP, D, I, P, PD, P, PD, P, PD, P]

@@ -54,6 +54,7 @@ OPT_CERT_F32, OPT_CERT_F64_PERMILLE, OPT_ZONE_TILE16, OPT_SGM_PATH_MODE, OPT_SAD
 OPT_SAD_ROUND_SLOTS = 22
 OPT_IP_SCRATCH_MB = 23
 OPT_SGM_LAST_FORM = 24
+OPT_INPAINT_OVERLAP = 25
 VALID_I32 = 0x7FFFFFFF
 
 

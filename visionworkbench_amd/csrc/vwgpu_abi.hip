@@ -206,7 +206,7 @@ int vwgpu_create(vwgpu_ctx** out, int device) {
 static size_t free_arenas(vwgpu_ctx* ctx) {
   size_t freed = ctx->graveyard_bytes;
   vwgpu_arena* all[] = {&ctx->scratch, &ctx->flags, &ctx->filt, &ctx->misc, &ctx->pyr, &ctx->ztab, &ctx->zrl, &ctx->zext, &ctx->sgm,
-                        &ctx->sgm_main, &ctx->sgm_bnd, &ctx->xvol, &ctx->xtab, &ctx->xcarry, &ctx->staging};
+                        &ctx->sgm_main, &ctx->sgm_bnd, &ctx->xvol, &ctx->xtab, &ctx->xcarry, &ctx->staging, &ctx->hole, &ctx->hole_tab};
   for (vwgpu_arena* a : all) {
     if (a->base) { (void)hipFree(a->base); freed += a->cap; }
     a->base = nullptr; a->cap = 0;
@@ -305,6 +305,7 @@ static const struct { int id; int vwgpu_ctx::* field; int lo, hi; bool settable;
   {VWGPU_OPT_SGM_LAST_FORM, &vwgpu_ctx::sgm_last_form, 0, 0, false},
   {VWGPU_OPT_EXACT_SPLIT, &vwgpu_ctx::exact_split, 0, 3, true},
   {VWGPU_OPT_HOST_RING_KB, &vwgpu_ctx::host_ring_kb, 16, 1 << 20, true},
+  {VWGPU_OPT_INPAINT_OVERLAP, &vwgpu_ctx::inpaint_overlap, 0, 1, true},
 };
 
 int vwgpu_set_option(vwgpu_ctx* ctx, int option, int value) {

@@ -87,6 +87,9 @@ struct vwgpu_ctx {
   int cert_f32 = 1;           // VWGPU_OPT_CERT_F32: the certified pass runs its fp32 tier first (bm_zones.hip)
   int zone_sxc = 0;           // VWGPU_OPT_ZONE_SXC: 0 = 16 dx per right patch, else at most this many
   unsigned long long cert_px[3] = {0, 0, 0};   // with VWGPU_OPT_TRACE bit 2: pixels in certified tiles / in flagged tiles / in tiles the fp32 tier passed on to float64, so far
+  vwgpu_arena hole;      // hole filling (hole_fill.hip): union-find parents, roots and scan partials of one labelling
+  vwgpu_arena hole_tab;  // hole filling: per-blob statistics, the kept-blob numbering, the internal label image and table of fill_holes_grass
+  int inpaint_overlap = 1;    // VWGPU_OPT_INPAINT_OVERLAP
   int num_cu = 256;
   void* host_pool = nullptr;  // helper threads for the per-tile host work of tile groups (pyramid.hip), created on first use
 };

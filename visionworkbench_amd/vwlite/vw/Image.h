@@ -9,9 +9,18 @@
 //   virtual calls (src/vw/Image/ImageViewRef.h:189-267).
 // Layouts are the reference's: ImageView is row-major contiguous and zero-initialised (ImageView.h:209-239),
 // PixelMask<Vector2i> is {int32,int32,int32 valid in {0,INT32_MAX}} (src/vw/Image/PixelMask.h:48-120).
+//
+// Hole filling on the engine (include/vwgpu.h), with the reference's signatures, eager like every
+// other engine wrapper:
+//   grassfire                                      src/vw/Image/Grassfire.h:43-55
+//   BlobIndexThreaded (constructor, num_blobs, blob_bbox, wipe_big_blobs), get_blob_sizes, invert_mask
+//                                                  src/vw/Image/BlobIndex.h:385-500, :507-615
+//   applyErodeView                                 src/vw/Image/ErodeView.h:157-162
+//   inpaint, fill_holes_grass, fill_nodata_with_avg   src/vw/Image/InpaintView.h:231-237, :307-311, :381-387
 #ifndef VWLITE_IMAGE_H
 #define VWLITE_IMAGE_H
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <exception>
@@ -22,6 +31,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "Engine.h"
 #include "Math.h"
 
 namespace vw {
@@ -343,6 +353,168 @@ template <class ViewT> ImageView<typename ViewT::pixel_type> copy(ImageViewBase<
   ImageView<typename ViewT::pixel_type> o(v.impl().cols(), v.impl().rows());
   v.impl().rasterize(o, BBox2i(0, 0, o.cols(), o.rows()));
   return o;
+}
+
+// ---- hole filling on the engine ------------------------------------------------------------------------------
+namespace detail {
+template <class PixelT> struct masked_kind;      // the vwgpu_pixel_kind of a pixel type the engine takes as it is stored
+template <> struct masked_kind<uint8> { static const int value = VWGPU_PIXEL_MASK_U8; };
+template <> struct masked_kind<PixelMask<float>> { static const int value = VWGPU_PIXEL_MASKED_F32; };
+template <> struct masked_kind<PixelMask<Vector2i>> { static const int value = VWGPU_PIXEL_DISPARITY_I32; };
+template <> struct masked_kind<PixelMask<Vector2f>> { static const int value = VWGPU_PIXEL_DISPARITY_F32; };
+static_assert(sizeof(PixelMask<float>) == 8, "PixelMask<float> is {value, valid}");
+template <class T> struct grassfire_type;
+template <> struct grassfire_type<uint8> { static const int value = VWGPU_GRASSFIRE_U8; };
+template <> struct grassfire_type<int32> { static const int value = VWGPU_GRASSFIRE_I32; };
+template <> struct grassfire_type<float> { static const int value = VWGPU_GRASSFIRE_F32; };
+template <> struct grassfire_type<PixelGray<float>> { static const int value = VWGPU_GRASSFIRE_F32; };
+}  // namespace detail
+
+/// grassfire(src, dst, ignore_borders) (Grassfire.h:43-45).
+template <class SourceT, class OutputT>
+void grassfire(ImageViewBase<SourceT> const& src, ImageView<OutputT>& dst, bool ignore_borders = false) {
+  ImageView<typename SourceT::pixel_type> in = src.impl();
+  dst.set_size(in.cols(), in.rows());
+  if (in.cols() == 0 || in.rows() == 0) return;
+  ImageView<int32> d(in.cols(), in.rows());
+  vwgpu_ctx* ctx = engine::thread_context();
+  engine::check(ctx, vwgpu_grassfire(ctx, detail::grassfire_type<typename SourceT::pixel_type>::value, in.data(), in.cols(), in.rows(), 0,
+                                     ignore_borders ? 1 : 0, d.data(), 0));
+  for (int32 r = 0; r < d.rows(); ++r)
+    for (int32 c = 0; c < d.cols(); ++c) dst(c, r) = OutputT(d(c, r));
+}
+/// Without a destination: a new ImageView<int32> (Grassfire.h:48-55).
+template <class SourceT>
+ImageView<int32> grassfire(ImageViewBase<SourceT> const& src, bool ignore_borders = false) {
+  ImageView<int32> result;
+  grassfire(src, result, ignore_borders);
+  return result;
+}
+
+/// invert_mask(view): valid pixels become invalid and invalid ones valid (PixelMask.h); values are kept.
+template <class ViewT>
+ImageView<typename ViewT::pixel_type> invert_mask(ImageViewBase<ViewT> const& view) {
+  ImageView<typename ViewT::pixel_type> in = view.impl(), out(in.cols(), in.rows());
+  for (int32 r = 0; r < in.rows(); ++r)
+    for (int32 c = 0; c < in.cols(); ++c) {
+      out(c, r) = in(c, r);
+      if (is_valid(in(c, r))) out(c, r).invalidate(); else out(c, r).validate();
+    }
+  return out;
+}
+
+/// BlobIndexThreaded (BlobIndex.h:385-500) over the whole image as one tile: the 8-connected blobs of the valid pixels in the
+/// reference's order.  tile_size and num_threads are accepted and ignored (the blob order of several tiles is not reproduced).
+class BlobIndexThreaded {
+  ImageView<uint8> m_mask;
+  int32 m_max_area;
+  std::vector<BBox2i> m_blob_bbox;
+  ImageView<int32> m_labels;
+  std::vector<int32> m_table;
+  void index(int wipe) {
+    m_labels.set_size(m_mask.cols(), m_mask.rows());
+    m_table.clear();
+    m_blob_bbox.clear();
+    if (m_mask.cols() == 0 || m_mask.rows() == 0) return;
+    vwgpu_ctx* ctx = engine::thread_context();
+    int count = 0;
+    engine::check(ctx, vwgpu_blob_index(ctx, VWGPU_PIXEL_MASK_U8, m_mask.data(), m_mask.cols(), m_mask.rows(), 0, 0, m_max_area, wipe, nullptr, 0,
+                                        nullptr, 0, &count));
+    m_table.resize((size_t)5 * std::max(count, 1));
+    engine::check(ctx, vwgpu_blob_index(ctx, VWGPU_PIXEL_MASK_U8, m_mask.data(), m_mask.cols(), m_mask.rows(), 0, 0, m_max_area, wipe,
+                                        m_labels.data(), 0, m_table.data(), count, &count));
+    m_table.resize((size_t)5 * count);
+    for (int k = 0; k < count; ++k)
+      m_blob_bbox.push_back(BBox2i(m_table[5 * k], m_table[5 * k + 1], m_table[5 * k + 2] - m_table[5 * k], m_table[5 * k + 3] - m_table[5 * k + 1]));
+  }
+public:
+  template <class SourceT>
+  BlobIndexThreaded(ImageViewBase<SourceT> const& src, int32 const& max_area = 0, int32 const& /*tile_size*/ = 0, int32 const& /*num_threads*/ = 0)
+      : m_max_area(max_area) {
+    ImageView<typename SourceT::pixel_type> in = src.impl();
+    m_mask.set_size(in.cols(), in.rows());
+    for (int32 r = 0; r < in.rows(); ++r)
+      for (int32 c = 0; c < in.cols(); ++c) m_mask(c, r) = is_valid(in(c, r)) ? 255 : 0;
+    index(0);
+  }
+  /// Wipe blobs whose bounding box is wider or taller than max_size (BlobIndex.h:457-477).
+  void wipe_big_blobs(int max_size) {
+    if (max_size > 0) { index(max_size); return; }
+    m_table.clear();
+    m_blob_bbox.clear();
+    fill(m_labels, 0);
+  }
+  uint32 num_blobs() const { return (uint32)m_blob_bbox.size(); }
+  BBox2i const& blob_bbox(uint32 const& index) const { return m_blob_bbox[index]; }
+  int32 blob_size(uint32 const& index) const { return m_table[5 * (size_t)index + 4]; }
+  // the engine's form of the selection: 1-based blob numbers per pixel, {min.x, min.y, max.x, max.y, size} per blob
+  ImageView<int32> const& labels() const { return m_labels; }
+  std::vector<int32> const& table() const { return m_table; }
+};
+
+/// get_blob_sizes(image, expand_size, size_limit) (BlobIndex.h:611-615) with the image as one tile.
+template <class ImageT>
+ImageView<uint32> get_blob_sizes(ImageViewBase<ImageT> const& image, int /*expand_size*/, uint32 size_limit) {
+  ImageView<typename ImageT::pixel_type> in = image.impl();
+  ImageView<uint32> out(in.cols(), in.rows());
+  if (in.cols() == 0 || in.rows() == 0) return out;
+  vwgpu_ctx* ctx = engine::thread_context();
+  engine::check(ctx, vwgpu_blob_sizes(ctx, detail::masked_kind<typename ImageT::pixel_type>::value, in.data(), in.cols(), in.rows(), 0, size_limit,
+                                      out.data(), 0));
+  return out;
+}
+
+/// applyErodeView(src, bindex) (ErodeView.h:157-162, :199-221): a pixel inside a listed blob becomes the default pixel.
+template <class SourceT>
+ImageView<typename SourceT::pixel_type> applyErodeView(ImageViewBase<SourceT> const& src, BlobIndexThreaded const& bindex) {
+  typedef typename SourceT::pixel_type pixel_type;
+  ImageView<pixel_type> in = src.impl(), out(in.cols(), in.rows());
+  VW_ASSERT(in.cols() == bindex.labels().cols() && in.rows() == bindex.labels().rows(), ArgumentErr() << "applyErodeView: the blob index belongs to another image.");
+  for (int32 r = 0; r < in.rows(); ++r)
+    for (int32 c = 0; c < in.cols(); ++c) out(c, r) = bindex.labels()(c, r) ? pixel_type() : in(c, r);
+  return out;
+}
+
+/// inpaint(src, bindex, use_grassfire, default_inpaint_val) (InpaintView.h:231-237), rasterised over the whole image.
+template <class SourceT>
+ImageView<typename SourceT::pixel_type> inpaint(ImageViewBase<SourceT> const& src, BlobIndexThreaded const& bindex, bool use_grassfire,
+                                                typename SourceT::pixel_type default_inpaint_val) {
+  typedef typename SourceT::pixel_type pixel_type;
+  ImageView<pixel_type> in = src.impl(), out(in.cols(), in.rows());
+  if (in.cols() == 0 || in.rows() == 0) return out;
+  VW_ASSERT(in.cols() == bindex.labels().cols() && in.rows() == bindex.labels().rows(), ArgumentErr() << "inpaint: the blob index belongs to another image.");
+  for (uint32 k = 0; k < bindex.num_blobs(); ++k)
+    VW_ASSERT(bindex.blob_bbox(k).width() <= VWGPU_HOLE_FILL_MAX_LEN && bindex.blob_bbox(k).height() <= VWGPU_HOLE_FILL_MAX_LEN,
+              NoImplErr() << "inpaint: a blob wider or taller than " << VWGPU_HOLE_FILL_MAX_LEN << " pixels.");
+  vwgpu_ctx* ctx = engine::thread_context();
+  engine::check(ctx, vwgpu_inpaint(ctx, detail::masked_kind<pixel_type>::value, in.data(), in.cols(), in.rows(), 0, bindex.labels().data(), 0,
+                                   bindex.table().data(), (int)bindex.num_blobs(), use_grassfire ? 1 : 0,
+                                   reinterpret_cast<const float*>(&default_inpaint_val), VWGPU_HOLE_EDGE_REFERENCE, VWGPU_HOLE_FILL_MAX_LEN,
+                                   out.data(), 0));
+  return out;
+}
+
+/// fill_holes_grass(img, hole_fill_len) (InpaintView.h:307-311), rasterised in one call over the whole image.
+template <class ImageT>
+ImageView<typename ImageT::pixel_type> fill_holes_grass(ImageViewBase<ImageT> const& img, int hole_fill_len) {
+  ImageView<typename ImageT::pixel_type> in = img.impl(), out(in.cols(), in.rows());
+  if (in.cols() == 0 || in.rows() == 0) return out;
+  vwgpu_ctx* ctx = engine::thread_context();
+  engine::check(ctx, vwgpu_fill_holes_grass(ctx, detail::masked_kind<typename ImageT::pixel_type>::value, in.data(), in.cols(), in.rows(), 0,
+                                            hole_fill_len, VWGPU_HOLE_EDGE_REFERENCE, out.data(), 0));
+  return out;
+}
+
+/// fill_nodata_with_avg(img, kernel_size) (InpaintView.h:381-387) on PixelMask<float>.
+template <class ImgT>
+ImageView<PixelMask<float>> fill_nodata_with_avg(ImageViewBase<ImgT> const& img, int kernel_size) {
+  VW_ASSERT((kernel_size % 2 == 1) && (kernel_size > 0), ArgumentErr() << "Expecting odd and positive kernel size.");
+  ImageView<PixelMask<float>> in = img.impl(), out(in.cols(), in.rows());
+  if (in.cols() == 0 || in.rows() == 0) return out;
+  vwgpu_ctx* ctx = engine::thread_context();
+  engine::check(ctx, vwgpu_fill_nodata_with_avg(ctx, reinterpret_cast<const float*>(in.data()), in.cols(), in.rows(), 0, kernel_size,
+                                                reinterpret_cast<float*>(out.data()), 0));
+  return out;
 }
 
 }  // namespace vw

@@ -40,6 +40,7 @@ extern "C" {
  *     VWGPU_OPT_SAD_LAYOUT, VWGPU_OPT_SAD_LAST_LAUNCH, VWGPU_OPT_SAD_ROUND_SLOTS (options 20, 21, 22) likewise, and
  *     VWGPU_OPT_IP_SCRATCH_MB (23) with the interest-point entries, VWGPU_OPT_SGM_LAST_FORM (24, read only) likewise.
  *     The hole-filling entries (vwgpu_grassfire .. vwgpu_fill_nodata_with_avg) and VWGPU_OPT_INPAINT_OVERLAP (25) are additions: same version.
+ *     The vwgpu_composite entries (Mosaic/ImageComposite.h) are additions: same version.
  * A host checks vwgpu_abi_version() == VWGPU_ABI_VERSION once after loading the library (vw::engine does, vw/Engine.h). */
 #define VWGPU_ABI_VERSION 3
 
@@ -870,6 +871,56 @@ int vwgpu_fill_nodata_with_avg_dev(vwgpu_ctx* ctx, const float* d_img, int w, in
                                    ptrdiff_t ostride);
 int vwgpu_fill_nodata_with_avg(vwgpu_ctx* ctx, const float* img, int w, int h, ptrdiff_t istride, int kernel_size, float* out,
                                ptrdiff_t ostride);
+
+/* ---- Mosaic/ImageComposite.h: multi-band blending of positioned images ---------- */
+/* (tests/refimpl/mosaic_ref.cc.)  vw::mosaic::ImageComposite<PixelT> for float pixels with premultiplied
+ * alpha, interleaved, alpha last: channels = 2 is PixelGrayA<float>, 4 is PixelRGBA<float>; draft mode also takes channels = 1
+ * (no alpha: a later image overwrites).  Finite values only.  Every image lives on the device: insert copies it, so the caller's
+ * buffer is free when the call returns (_dev: once the work queued on the context's stream has run).  Strides are in pixels,
+ * 0 = packed.  Boxes are {min.x, min.y, max.x, max.y}, max exclusive.  A composite belongs to the device of the context that
+ * created it, takes a context of that device in every call, and is destroyed before that device's last context.
+ *
+ * Not here: the reference's cache and its mask.N.png files (the masks stay on the device as exactly 0.0f and 1.0f),
+ * set_reuse_masks, sparse_check, integer pixels.  blend_patch adds the images in insertion order, which is the reference's order
+ * with a cold cache.
+ *
+ * Limits: at most VWGPU_COMPOSITE_MAX_IMAGES images, image sides up to VWGPU_COMPOSITE_MAX_DIM, view sides up to twice that,
+ * VWGPU_COMPOSITE_MAX_BYTES device bytes per composite (sources, pyramids and scratch): VWGPU_ERR_NOIMPL above.
+ * VWGPU_ERR_ARGUMENT before any device work: null pointers, an empty image, a stride below the width, channels other than 1, 2, 4
+ * or other than the first image's, insert after prepare, prepare twice or without an image, a total box that does not contain
+ * every image (the reference's / 2 and % 2 would act on negative numbers), generate_patch before prepare or with a patch that
+ * leaves the view, blending 1-channel images, blending after a prepare() in draft mode (it made no masks). */
+#define VWGPU_COMPOSITE_MAX_IMAGES 64
+#define VWGPU_COMPOSITE_MAX_DIM 65536
+#define VWGPU_COMPOSITE_MAX_BYTES (1ull << 34)
+typedef struct vwgpu_composite vwgpu_composite;
+/* ImageComposite() (:246-247) and its destructor. */
+int vwgpu_composite_create(vwgpu_ctx* ctx, vwgpu_composite** out);
+void vwgpu_composite_destroy(vwgpu_composite* c);
+/* insert(image, x, y) (:411-431): the view and data boxes grow, mindim shrinks. */
+int vwgpu_composite_insert_dev(vwgpu_ctx* ctx, vwgpu_composite* c, const float* d_img, int w, int h, ptrdiff_t stride, int channels, int x, int y);
+int vwgpu_composite_insert(vwgpu_ctx* ctx, vwgpu_composite* c, const float* img, int w, int h, ptrdiff_t stride, int channels, int x, int y);
+/* set_draft_mode / set_fill_holes (:261-263).  fill_holes may change after prepare: the next patch builds the pyramids again. */
+int vwgpu_composite_set_draft_mode(vwgpu_ctx* ctx, vwgpu_composite* c, int draft_mode);
+int vwgpu_composite_set_fill_holes(vwgpu_ctx* ctx, vwgpu_composite* c, int fill_holes);
+/* prepare() / prepare(total_bbox) (:434-455): total_bbox is a HOST box or NULL.  The boxes move to the view's origin,
+ * levels = max(1, (int)floorf(logf(mindim / 2.0f) / logf(2.0f)) - 1); outside draft mode generate_masks (:331-369) runs, on the
+ * float grassfire of every alpha plane, and so does PyramidGenerator::generate (:373-408) for every image, which the reference
+ * defers to the first patch. */
+int vwgpu_composite_prepare(vwgpu_ctx* ctx, vwgpu_composite* c, const int* total_bbox);
+/* cols(), rows() (:267-268), the level count (0 before prepare), and bbox() (which = 0: the data box, moved by prepare) /
+ * source_data_bbox() (which = 1: the view box, which keeps its place) (:271-272). */
+int vwgpu_composite_cols(const vwgpu_composite* c);
+int vwgpu_composite_rows(const vwgpu_composite* c);
+int vwgpu_composite_levels(const vwgpu_composite* c);
+int vwgpu_composite_bbox(const vwgpu_composite* c, int which, int* box);
+/* The level-0 mask of image `index` (what the reference writes to mask.N.png, :362-365) into HOST floats of the image's size:
+ * 1 where the image's grassfire distance is positive and beats every other image's, the later image winning a tie. */
+int vwgpu_composite_mask(vwgpu_ctx* ctx, vwgpu_composite* c, int index, float* out, ptrdiff_t ostride);
+/* generate_patch(BBox2i(x0, y0, w, h)) (:255-258): blend_patch (:468-567) or, in draft mode, draft_patch (:573-590), into
+ * w x h pixels.  operator()(x, y) (:274-279) is the 1 x 1 patch. */
+int vwgpu_composite_generate_patch_dev(vwgpu_ctx* ctx, vwgpu_composite* c, int x0, int y0, int w, int h, float* d_out, ptrdiff_t ostride);
+int vwgpu_composite_generate_patch(vwgpu_ctx* ctx, vwgpu_composite* c, int x0, int y0, int w, int h, float* out, ptrdiff_t ostride);
 
 /* ---- Stereo/StereoModel.{h,cc} and Stereo/StereoView.h: triangulation and the universe radius ---------- */
 

@@ -12,7 +12,7 @@ __all__ = ["core", "synth", "stereo", "camera", "Context", "BBox2i", "CostFuncti
 
 
 def __getattr__(name):
-    if name in ("stereo", "camera", "transform", "interest_point", "image"):
+    if name in ("stereo", "camera", "transform", "interest_point", "image", "mosaic"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -36,6 +36,10 @@ SYMBOLS = [
     "vwgpu_grassfire_dev", "vwgpu_grassfire", "vwgpu_blob_index_dev", "vwgpu_blob_index", "vwgpu_blob_sizes_dev", "vwgpu_blob_sizes",
     "vwgpu_erode_blobs_dev", "vwgpu_erode_blobs", "vwgpu_inpaint_dev", "vwgpu_inpaint",
     "vwgpu_fill_holes_grass_dev", "vwgpu_fill_holes_grass", "vwgpu_fill_nodata_with_avg_dev", "vwgpu_fill_nodata_with_avg",
+    "vwgpu_composite_create", "vwgpu_composite_destroy", "vwgpu_composite_insert_dev", "vwgpu_composite_insert",
+    "vwgpu_composite_set_draft_mode", "vwgpu_composite_set_fill_holes", "vwgpu_composite_prepare", "vwgpu_composite_cols",
+    "vwgpu_composite_rows", "vwgpu_composite_levels", "vwgpu_composite_bbox", "vwgpu_composite_mask",
+    "vwgpu_composite_generate_patch_dev", "vwgpu_composite_generate_patch",
     "vwgpu_pinhole_camera", "vwgpu_stereo_triangulate_dev", "vwgpu_stereo_triangulate",
     "vwgpu_convergence_angle_dev", "vwgpu_convergence_angle", "vwgpu_universe_radius_dev", "vwgpu_universe_radius",
     "vwgpu_pinhole_camera_matrix", "vwgpu_epipolar_pinhole", "vwgpu_epipolar_cahv",
@@ -276,6 +280,23 @@ def load():
     fna = [P, P, I, I, PD, I, P, PD]
     lib.vwgpu_fill_nodata_with_avg_dev.argtypes = fna
     lib.vwgpu_fill_nodata_with_avg.argtypes = fna
+    lib.vwgpu_composite_create.argtypes = [P, ctypes.POINTER(P)]
+    lib.vwgpu_composite_destroy.argtypes = [P]
+    lib.vwgpu_composite_destroy.restype = None
+    cin = [P, P, P, I, I, PD, I, I, I]
+    lib.vwgpu_composite_insert_dev.argtypes = cin
+    lib.vwgpu_composite_insert.argtypes = cin
+    lib.vwgpu_composite_set_draft_mode.argtypes = [P, P, I]
+    lib.vwgpu_composite_set_fill_holes.argtypes = [P, P, I]
+    lib.vwgpu_composite_prepare.argtypes = [P, P, ctypes.POINTER(ctypes.c_int)]
+    lib.vwgpu_composite_cols.argtypes = [P]
+    lib.vwgpu_composite_rows.argtypes = [P]
+    lib.vwgpu_composite_levels.argtypes = [P]
+    lib.vwgpu_composite_bbox.argtypes = [P, I, ctypes.POINTER(ctypes.c_int)]
+    lib.vwgpu_composite_mask.argtypes = [P, P, I, P, PD]
+    cgp = [P, P, I, I, I, I, P, PD]
+    lib.vwgpu_composite_generate_patch_dev.argtypes = cgp
+    lib.vwgpu_composite_generate_patch.argtypes = cgp
     CP = ctypes.POINTER(Camera)
     lib.vwgpu_pinhole_camera.argtypes = [P, P, D, D, D, D, P, P, P, D, I, P, CP]
     tri = [P, I, P, I, I, PD, I, I, CP, CP, D, I, P, PD, P, PD, P, PD, P]

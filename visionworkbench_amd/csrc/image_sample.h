@@ -149,6 +149,18 @@ IS_HD is_row4 is_load_row4(const float* p) {
   return r;
 }
 
+// BilinearInterpolationImpl (:94-105) on its four taps; mosaic.hip runs it per channel of an interleaved pixel
+IS_HD float is_bilinear_mix(float t00, float t10, float t01, float t11, float normx, float normy) {
+  const float norm1mx = 1.0f - normx, norm1my = 1.0f - normy;
+  float res = t00 * norm1mx;
+  res += t10 * normx;
+  res *= norm1my;
+  float row = t01 * norm1mx;
+  row += t11 * normx;
+  res += row * normy;
+  return res;
+}
+
 // ---- the interpolations ------------------------------------------------------------------------------------------------
 // The value of the interpolation at (qx, qy); `valid` is set: false where a tap that was used is invalid.  A coordinate
 // that is NaN or beyond +-2^30 has an undefined int32 conversion in the reference: 0 and invalid here.  Every pixel
@@ -174,7 +186,6 @@ IS_HD float is_sample(const is_src& s, double qx, double qy, bool& valid) {
   if (INTERP == VWGPU_TRANSFORM_INTERP_BILINEAR) {
     // BilinearInterpolationImpl (:94-105)
     const float normx = (float)qx - (float)xi, normy = (float)qy - (float)yi;
-    const float norm1mx = 1.0f - normx, norm1my = 1.0f - normy;
     float t00, t10, t01, t11;
     if (is_inside(s, xi, yi, xi + 1, yi + 1)) {
       t00 = is_at<MASKED>(s, xi, yi, valid);
@@ -187,13 +198,7 @@ IS_HD float is_sample(const is_src& s, double qx, double qy, bool& valid) {
       t01 = is_tap<MASKED>(s, xi, yi + 1, valid);
       t11 = is_tap<MASKED>(s, xi + 1, yi + 1, valid);
     }
-    float res = t00 * norm1mx;
-    res += t10 * normx;
-    res *= norm1my;
-    float row = t01 * norm1mx;
-    row += t11 * normx;
-    res += row * normy;
-    return res;
+    return is_bilinear_mix(t00, t10, t01, t11, normx, normy);
   }
   // BicubicInterpolationImpl (:153-184)
   const double normx = qx - xi, normy = qy - yi;

@@ -78,6 +78,46 @@ def test_batch_with_masks_and_dead_tiles(ctx, oracle):
     _check(ctx, left, right, lm, rm, 2, float(np.float32(1.4)), (-10, -1, 11, 2), (7, 7), 2, boxes, oracle=oracle)
 
 
+def _mean_sum_bits(img, mask, x0, y0, w, h):
+    """hi + 1 + lg(n + 1) - lo over the pixels the nodata mean of a tile adds up (every second row and column of the edge-extended crop at
+    (x0, y0), where the mask is set): the bits a partial sum can need — above 53 the partial sums may round and the mean is formed serially."""
+    ys = np.clip(np.arange(y0, y0 + h, 2), 0, img.shape[0] - 1)
+    xs = np.clip(np.arange(x0, x0 + w, 2), 0, img.shape[1] - 1)
+    v = img[np.ix_(ys, xs)][mask[np.ix_(ys, xs)] != 0]
+    n = v.size
+    u = v[v != 0].view(np.uint32).astype(np.int64)
+    e, m = (u >> 23) & 0xff, (u & 0x7fffff) | 0x800000
+    assert ((e > 0) & (e < 255)).all()                                # normal numbers only
+    low = (m & -m).astype(np.float64)                                 # lowest set bit of the 24-bit significand
+    lo = int((e - 150 + np.log2(low).astype(np.int64)).min())
+    hi = int((e - 127).max())
+    lgn = 0
+    while (1 << lgn) < n + 1:
+        lgn += 1
+    return hi + 1 + lgn - lo
+
+
+@pytest.mark.parametrize("kind", ["sum_above_53_bits", "nan_under_valid_mask"])
+def test_batch_nodata_mean_serial_fallback(ctx, oracle, kind):
+    """The nodata mean in the reference's serial order (masked_mean_serial_kernel), single tile and group: a 2^30 pixel among multiples of
+    2^-12 makes the partial sums of the first tile's crop need more than 53 bits; a NaN under a valid mask is the other trigger.  The
+    second tile of the group does not see that pixel and keeps the tree sum: one group, both forms."""
+    left, right = _scene(4242, H=200, W=300)
+    lm = np.full(left.shape, 255, np.uint8); rm = np.full(right.shape, 255, np.uint8)
+    lm[10:30, 60:80] = 0                                              # a hole in the first tile, filled with the mean
+    if kind == "sum_above_53_bits":
+        left = (left * np.float32(2.0 ** -12)).astype(np.float32)
+        left[50, 40] = np.float32(2.0 ** 30)
+        bits = _mean_sum_bits(left, lm, -12, -12, 96 + 24, 96 + 24)   # the first tile's crop: the tile grown by half_kernel * 2^levels = 3 * 4
+        print("bits of the first tile's partial sums:", bits)
+        assert bits > 53
+        assert _mean_sum_bits(left, lm, 96 - 12, -12, 96 + 24, 96 + 24) <= 53
+    else:
+        left[50, 40] = np.nan
+    boxes = [BBox2i(0, 0, 96, 96), BBox2i(96, 0, 96, 96)]
+    _check(ctx, left, right, lm, rm, 0, 0.0, (-8, -1, 9, 2), (7, 7), 0, boxes, oracle=oracle, max_pyramid_levels=2, filter_half_kernel=3, consistency_threshold=2.0)
+
+
 @pytest.mark.parametrize("kw", [dict(filter_half_kernel=0), dict(consistency_threshold=-1.0), dict(max_pyramid_levels=0), dict(max_pyramid_levels=5, filter_half_kernel=5),
                                 dict(blob_filter_area=20), dict(corr_timeout=5, seconds_per_op=1e-12), dict(algorithm=1)])
 def test_batch_options_and_fallbacks(ctx, kw):

@@ -18,12 +18,10 @@
 // the reference's own summation order (bm_exact.hip); the class of every level is measured on the device.
 // VW_CORRELATION_MGM runs every level with use_mgm, _FINAL_MGM only level 0 (:365-366).  collar_size is applied by the caller
 // (PyramidCorrelationView::rasterize, CorrelationView.h:123-133: a larger tile is rasterised and cropped).
-#include <atomic>
+// The rules that are arithmetic on sizes, boxes and zone lists are in pyramid_plan.h (no HIP, tested on its own); the clean-up, blob and
+// mask kernels in pyramid_filters.hip; the helper threads of a tile group in host_pool.hip.
 #include <chrono>
 #include <climits>
-#include <condition_variable>
-#include <mutex>
-#include <thread>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -33,6 +31,7 @@
 #include <vector>
 
 #include "vwgpu_internal.h"
+#include "pyramid_plan.h"
 #include "zones.h"
 
 namespace {
@@ -163,169 +162,6 @@ __global__ void add_offset_kernel(int32_t* __restrict__ d, ptrdiff_t stride_px, 
   p[0] += ax; p[1] += ay;
 }
 
-// RmOutliersUsingThreshFunc (src/vw/Stereo/DisparityMap.h:357-385) evaluated over the output domain
-// [ox0, ox0+ow) x [oy0, oy0+oh) of the constant-edge-extended input.  A 32 x 8 output tile and its (2 hh + 1) x (2 hv + 1)
-// neighbourhood rim are staged in LDS once (the direct version read 121 x 12 B per pixel through the L1: 0.3 ms per 1024^2 level).
-// `fabs((double)(a - b)) <= pthr` on int32 differences is the unsigned compare |a - b| <= floor(pthr) (thr; `never` for a
-// negative or NaN threshold); the match ratio is compared in float64 as the reference does.
-// Packed form: when every valid disparity of the tile is below 2^13 in magnitude and thr < 2^13 (always, in a pyramid) the tile is
-// ALSO staged as one dword per pixel — (dx + 2^14) | (dy + 2^14) << 16, 0xffffffff for an invalid pixel — and a neighbour is one LDS
-// read and four instructions: t = n + (thr - c) per half (v_pk_add_u16: |n - c| <= thr  <=>  t <= 2 thr as unsigned 16-bit values —
-// a negative n - c + thr wraps to more than 2^15, and the invalid code gives 65535 - (c + 2^14) + thr, between 2^15 and 2^16: it
-// never passes), max with 2 thr per half, compare with the splat, add the carry.  The three-array form took
-// ten instructions and three LDS reads per neighbour: 160 us of an 870 us SAD tile went into this filter.
-// HH > 0: hh == hv == HH known at compile time (the loops unroll: the small levels of a pyramid are latency bound here).
-template <int HH>
-__global__ void __launch_bounds__(256)
-rm_outliers_kernel(const int32_t* __restrict__ src, int w, int h, int hh, int hv, unsigned thr, int never, double rthr,
-                   int32_t* __restrict__ dst, int ow, int oh, int ox0, int oy0, size_t src_tile = 0, size_t dst_tile = 0) {
-  extern __shared__ int32_t rm_sm[];
-  src += blockIdx.z * src_tile; dst += blockIdx.z * dst_tile;     // tile groups: blockIdx.z = the tile, its images at a fixed stride (ints)
-  if (HH > 0) { hh = HH; hv = HH; }
-  const int tw = 32 + 2 * hh, th = 8 + 2 * hv, tn = tw * th;
-  int32_t* sx = rm_sm;
-  int32_t* sy = rm_sm + tn;
-  unsigned* pk = reinterpret_cast<unsigned*>(rm_sm + 2 * tn);
-  uint8_t* sv = reinterpret_cast<uint8_t*>(rm_sm + 3 * tn);
-  const int tid = threadIdx.y * 32 + threadIdx.x;
-  const int bx = blockIdx.x * 32 + ox0 - hh, by = blockIdx.y * 8 + oy0 - hv;      // source coordinates of the tile's corner
-  bool big = thr >= 8192u;
-  // (three pixels per thread and batch: their nine loads are requested together — the plain loop waited for every pixel's three words)
-  for (int i0 = tid; i0 < tn; i0 += 3 * 256) {
-    int32_t d0[3], d1[3], d2[3];
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const int i = i0 + b * 256;
-      const int ty = i / tw, tx = i - ty * tw;
-      int x = bx + tx, y = by + ty;
-      x = x < 0 ? 0 : (x >= w ? w - 1 : x);
-      y = y < 0 ? 0 : (y >= h ? h - 1 : y);
-      const int32_t* c = src + ((size_t)y * w + x) * 3;
-      const bool in = i < tn;
-      d0[b] = in ? c[0] : 0; d1[b] = in ? c[1] : 0; d2[b] = in ? c[2] : 0;
-    }
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const int i = i0 + b * 256;
-      if (i >= tn) break;
-      const bool v = d2[b] != 0;
-      sx[i] = d0[b]; sy[i] = d1[b]; sv[i] = v;
-      if (v) big = big || d0[b] <= -8192 || d0[b] >= 8192 || d1[b] <= -8192 || d1[b] >= 8192;
-      pk[i] = v ? ((unsigned)(d0[b] + 16384) & 0xffffu) | ((unsigned)(d1[b] + 16384) << 16) : 0xffffffffu;
-    }
-  }
-  const bool wide = __syncthreads_or(big ? 1 : 0) != 0;         // (also the barrier behind the staging)
-  const int ox = blockIdx.x * 32 + threadIdx.x, oy = blockIdx.y * 8 + threadIdx.y;
-  if (ox >= ow || oy >= oh) return;
-  const int ci = (threadIdx.y + hv) * tw + threadIdx.x + hh;
-  int32_t r0 = sx[ci], r1 = sy[ci], r2 = 0;
-  if (sv[ci]) {
-    // the valid flag is written back as the source has it
-    const int x = min(max(ox + ox0, 0), w - 1), y = min(max(oy + oy0, 0), h - 1);
-    r2 = src[((size_t)y * w + x) * 3 + 2];
-    int matched = 0;
-    if (!never && !wide) {
-      typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
-      const unsigned cb = ((thr - (unsigned)(r0 + 16384)) & 0xffffu) | ((thr - (unsigned)(r1 + 16384)) << 16);      // thr - c per half (mod 2^16)
-      const unsigned lim = (2u * thr) | ((2u * thr) << 16);
-      auto one = [&](unsigned n) __attribute__((always_inline)) {
-        const us2_t t = __builtin_bit_cast(us2_t, n) + __builtin_bit_cast(us2_t, cb);
-        const us2_t m = __builtin_elementwise_max(t, __builtin_bit_cast(us2_t, lim));
-        matched += __builtin_bit_cast(unsigned, m) == lim ? 1 : 0;
-      };
-      if (HH > 0) {
-#pragma unroll
-        for (int yk = 0; yk <= 2 * HH; ++yk) {
-          const unsigned* row = pk + (threadIdx.y + yk) * tw + threadIdx.x;
-#pragma unroll
-          for (int xk = 0; xk <= 2 * HH; ++xk) one(row[xk]);
-        }
-      } else {
-        for (int yk = 0; yk <= 2 * hv; ++yk) {
-          const unsigned* row = pk + (threadIdx.y + yk) * tw + threadIdx.x;
-          for (int xk = 0; xk <= 2 * hh; ++xk) one(row[xk]);
-        }
-      }
-    } else if (!never) {
-      for (int yk = 0; yk <= 2 * hv; ++yk) {
-        const int row = (threadIdx.y + yk) * tw + threadIdx.x;
-        for (int xk = 0; xk <= 2 * hh; ++xk) {
-          const int i = row + xk;
-          const int d0 = r0 - sx[i], d1 = r1 - sy[i];                         // int32 wrap-around, as the reference's subtraction
-          const unsigned a0 = d0 < 0 ? 0u - (unsigned)d0 : (unsigned)d0, a1 = d1 < 0 ? 0u - (unsigned)d1 : (unsigned)d1;
-          matched += (sv[i] && a0 <= thr && a1 <= thr) ? 1 : 0;
-        }
-      }
-    }
-    const int total = (2 * hh + 1) * (2 * hv + 1);
-    if (((double)matched / (double)total) < rthr) { r0 = r1 = r2 = 0; }
-  }
-  int32_t* o = dst + ((size_t)oy * ow + ox) * 3;
-  o[0] = r0; o[1] = r1; o[2] = r2;
-}
-
-// The same filter without the LDS tile, for neighbourhoods too large for it (64 KB).
-__global__ void rm_outliers_direct_kernel(const int32_t* __restrict__ src, int w, int h, int hh, int hv, double pthr, double rthr,
-                                   int32_t* __restrict__ dst, int ow, int oh, int ox0, int oy0) {
-  const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y * blockDim.y + threadIdx.y;
-  if (ox >= ow || oy >= oh) return;
-  auto at = [&](int x, int y) -> const int32_t* {
-    x = x < 0 ? 0 : (x >= w ? w - 1 : x);
-    y = y < 0 ? 0 : (y >= h ? h - 1 : y);
-    return src + ((size_t)y * w + x) * 3;
-  };
-  const int x = ox + ox0, y = oy + oy0;
-  const int32_t* c = at(x, y);
-  int32_t r0 = c[0], r1 = c[1], r2 = c[2];
-  if (r2) {
-    int matched = 0, total = 0;
-    for (int yk = -hv; yk <= hv; ++yk)
-      for (int xk = -hh; xk <= hh; ++xk) {
-        const int32_t* n = at(x + xk, y + yk);
-        if (n[2] && fabs((double)(r0 - n[0])) <= pthr && fabs((double)(r1 - n[1])) <= pthr) matched++;
-        total++;
-      }
-    if (((double)matched / (double)total) < rthr) { r0 = r1 = r2 = 0; }
-  }
-  int32_t* o = dst + ((size_t)oy * ow + ox) * 3;
-  o[0] = r0; o[1] = r1; o[2] = r2;
-}
-
-// second pass of disparity_cleanup_using_thresh: functor (1,1,3.0,0.20) over the inner VIEW, which is given here on
-// the domain padded by one pixel (DisparityMap.h:427-441).
-__global__ void cleanup_outer_kernel(const int32_t* __restrict__ inner, int w, int h, int32_t* __restrict__ dst) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-  if (x >= w || y >= h) return;
-  const int pw = w + 2;
-  const int32_t* c = inner + ((size_t)(y + 1) * pw + (x + 1)) * 3;
-  int32_t r0 = c[0], r1 = c[1], r2 = c[2];
-  if (r2) {
-    int matched = 0;
-    for (int yk = -1; yk <= 1; ++yk)
-      for (int xk = -1; xk <= 1; ++xk) {
-        const int32_t* n = inner + ((size_t)(y + 1 + yk) * pw + (x + 1 + xk)) * 3;
-        if (n[2] && fabs((double)(r0 - n[0])) <= 3.0 && fabs((double)(r1 - n[1])) <= 3.0) matched++;
-      }
-    if (((double)matched / 9.0) < 0.20) { r0 = r1 = r2 = 0; }
-  }
-  int32_t* o = dst + ((size_t)y * w + x) * 3;
-  o[0] = r0; o[1] = r1; o[2] = r2;
-}
-
-// DisparityMaskView::operator() (DisparityMap.h:132-155), in place.
-__global__ void disparity_mask_kernel(int32_t* __restrict__ d, int w, int h, const uint8_t* __restrict__ m1,
-                                      const uint8_t* __restrict__ m2, int m2w, int m2h) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y;
-  if (i >= w || j >= h) return;
-  int32_t* p = d + ((size_t)j * w + i) * 3;
-  bool keep = m1[(size_t)j * w + i] != 0 && p[2] != 0;
-  if (keep) {
-    const int x = i + p[0], y = j + p[1];
-    keep = !(x < 0 || x >= m2w || y < 0 || y >= m2h || m2[(size_t)y * m2w + x] == 0);
-  }
-  if (!keep) { p[0] = 0; p[1] = 0; p[2] = 0; }
-}
-
 // disparity_mask_kernel + finish_kernel in one pass, for the last level of a block-matching tile when nothing else reads the masked image
 __global__ void finish_masked_kernel(const int32_t* __restrict__ d, int w, int h, const uint8_t* __restrict__ m1, const uint8_t* __restrict__ m2,
                                      int m2w, int m2h, int ax, int ay, float* __restrict__ out, ptrdiff_t ostride_px) {
@@ -350,58 +186,6 @@ __global__ void finish_kernel(const int32_t* __restrict__ d, int w, int h, int a
   const int32_t* p = d + ((size_t)y * w + x) * 3;
   float* o = out + ((ptrdiff_t)y * ostride_px + x) * 3;
   o[0] = (float)(p[0] + ax); o[1] = (float)(p[1] + ay); o[2] = p[2] ? 1.0f : 0.0f;
-}
-
-// ---- blob filter (disparity_blob_filter, CorrelationView.cc:242-271): 8-connected components of the valid pixels by a
-// lock-free union-find (roots = smallest pixel index), component sizes by atomics, components of <= area pixels erased.
-__device__ __forceinline__ int cc_find(int* L, int x) {
-  int p = L[x];
-  while (p != x) { const int g = L[p]; L[x] = g; x = p; p = g; }     // path halving; racy writes only ever shorten paths
-  return x;
-}
-__device__ __forceinline__ void cc_unite(int* L, int a, int b) {
-  while (true) {
-    a = cc_find(L, a); b = cc_find(L, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }                     // hang the larger root under the smaller one
-    const int old = atomicMin(&L[a], b);
-    if (old == a) return;
-    a = old;
-  }
-}
-__global__ void cc_init_kernel(const int32_t* __restrict__ d, int n, int* __restrict__ label, int* __restrict__ size) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  label[i] = d[(size_t)i * 3 + 2] ? i : -1;
-  size[i] = 0;
-}
-__global__ void cc_union_kernel(int* label, int w, int h) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-  if (x >= w || y >= h) return;
-  const int i = y * w + x;
-  if (label[i] < 0) return;
-  if (x > 0 && label[i - 1] >= 0) cc_unite(label, i, i - 1);
-  if (y > 0) {
-    if (label[i - w] >= 0) cc_unite(label, i, i - w);
-    if (x > 0 && label[i - w - 1] >= 0) cc_unite(label, i, i - w - 1);
-    if (x + 1 < w && label[i - w + 1] >= 0) cc_unite(label, i, i - w + 1);
-  }
-}
-// the forest is final after the union kernel: read-only root walks (a compressing find here would race with the readers)
-__device__ __forceinline__ int cc_root(const int* L, int x) {
-  int p = L[x];
-  while (p != x) { x = p; p = L[x]; }
-  return x;
-}
-__global__ void cc_count_kernel(const int* __restrict__ label, int n, int* __restrict__ size) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || label[i] < 0) return;
-  atomicAdd(&size[cc_root(label, i)], 1);
-}
-__global__ void cc_erase_kernel(int32_t* __restrict__ d, const int* __restrict__ label, const int* __restrict__ size, int n, int area) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || label[i] < 0) return;
-  if (size[cc_root(label, i)] <= area) { d[(size_t)i * 3] = 0; d[(size_t)i * 3 + 1] = 0; d[(size_t)i * 3 + 2] = 0; }
 }
 
 // SGM result: sub-pixel view + search.min, invalid where the filtered integer disparity is (CorrelationView.cc:862-875)
@@ -478,65 +262,6 @@ struct DevImg { float* p = nullptr; int w = 0, h = 0; };
 struct DevMask { uint8_t* p = nullptr; int w = 0, h = 0; };
 
 }  // namespace
-
-int vwgpu_launch_disparity_filter(vwgpu_ctx* ctx, const int32_t* src, int w, int h, int hh, int hv, double pthr, double rthr,
-                                  bool cleanup, int32_t* tmp_padded, int32_t* dst, bool inner_only, int tiles, size_t tile_ints) {
-  // tiles > 1 (the tile groups of vwgpu_pyramid_group_impl): the same filter over `tiles` images at a fixed stride of tile_ints ints, for the
-  // source, the padded intermediate and the destination alike — one launch (blockIdx.z); the second pass is the caller's (inner_only)
-  if (hh < 0 || hv < 0) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "disparity filter: negative half kernel");
-  const size_t rm_lds = (size_t)(32 + 2 * hh) * (8 + 2 * hv) * 13;
-  const bool direct = rm_lds > 64 * 1024;
-  if (tiles > 1 && (direct || (cleanup && !inner_only))) return vwgpu_fail(ctx, VWGPU_ERR_LOGIC, "disparity filter: this form is not built for tile groups");
-  const size_t ts = tiles > 1 ? tile_ints : 0;
-  // fabs((double)int32 difference) <= pthr  <=>  |difference| <= floor(pthr)
-  const int never = !(pthr >= 0.0);                                   // negative or NaN: nothing matches
-  const unsigned thr = never ? 0u : (pthr >= 4294967295.0 ? 0xffffffffu : (unsigned)std::floor(pthr));
-  auto rm_grid = [tiles](int ww, int hh2) { return dim3((unsigned)((ww + 31) / 32), (unsigned)((hh2 + 7) / 8), (unsigned)std::max(tiles, 1)); };
-  if (!cleanup) {
-    vwgpu_prof_scope ps(ctx, "rm_outliers");
-    if (direct) hipLaunchKernelGGL(rm_outliers_direct_kernel, grid2(w, h), kBlk, 0, ctx->stream, src, w, h, hh, hv, pthr, rthr, dst, w, h, 0, 0);
-    else if (hh == 5 && hv == 5) hipLaunchKernelGGL(rm_outliers_kernel<5>, rm_grid(w, h), dim3(32, 8), rm_lds, ctx->stream, src, w, h, hh, hv, thr, never, rthr, dst, w, h, 0, 0, ts, ts);
-    else hipLaunchKernelGGL(rm_outliers_kernel<0>, rm_grid(w, h), dim3(32, 8), rm_lds, ctx->stream, src, w, h, hh, hv, thr, never, rthr, dst, w, h, 0, 0, ts, ts);
-  } else {
-    {
-      vwgpu_prof_scope ps(ctx, "rm_outliers");
-      if (direct) hipLaunchKernelGGL(rm_outliers_direct_kernel, grid2(w + 2, h + 2), kBlk, 0, ctx->stream, src, w, h, hh, hv, pthr, rthr,
-                                     tmp_padded, w + 2, h + 2, -1, -1);
-      else if (hh == 5 && hv == 5) hipLaunchKernelGGL(rm_outliers_kernel<5>, rm_grid(w + 2, h + 2), dim3(32, 8), rm_lds, ctx->stream, src, w, h, hh, hv, thr, never, rthr,
-                                                      tmp_padded, w + 2, h + 2, -1, -1, ts, ts);
-      else hipLaunchKernelGGL(rm_outliers_kernel<0>, rm_grid(w + 2, h + 2), dim3(32, 8), rm_lds, ctx->stream, src, w, h, hh, hv, thr, never, rthr,
-                              tmp_padded, w + 2, h + 2, -1, -1, ts, ts);
-    }
-    if (!inner_only) {                                              // (inner_only: the caller applies the second pass itself, see zone_extent_fused_kernel)
-      vwgpu_prof_scope ps(ctx, "disparity_cleanup_outer");
-      hipLaunchKernelGGL(cleanup_outer_kernel, grid2(w, h), kBlk, 0, ctx->stream, tmp_padded, w, h, dst);
-    }
-  }
-  VWGPU_HIP(ctx, hipGetLastError());
-  return VWGPU_OK;
-}
-
-// scratch: 2 x w*h ints
-int vwgpu_launch_blob_filter(vwgpu_ctx* ctx, int32_t* d, int w, int h, int area, int* scratch) {
-  if (area < 1) return VWGPU_OK;
-  const int n = w * h;
-  int* label = scratch; int* size = scratch + n;
-  vwgpu_prof_scope ps(ctx, "blob_filter");
-  const dim3 g1((n + 255) / 256), b1(256);
-  hipLaunchKernelGGL(cc_init_kernel, g1, b1, 0, ctx->stream, d, n, label, size);
-  hipLaunchKernelGGL(cc_union_kernel, grid2(w, h), kBlk, 0, ctx->stream, label, w, h);
-  hipLaunchKernelGGL(cc_count_kernel, g1, b1, 0, ctx->stream, label, n, size);
-  hipLaunchKernelGGL(cc_erase_kernel, g1, b1, 0, ctx->stream, d, label, size, n, area);
-  VWGPU_HIP(ctx, hipGetLastError());
-  return VWGPU_OK;
-}
-
-int vwgpu_launch_disparity_mask(vwgpu_ctx* ctx, int32_t* d, int w, int h, const uint8_t* m1, const uint8_t* m2, int m2w, int m2h) {
-  vwgpu_prof_scope ps(ctx, "disparity_mask");
-  hipLaunchKernelGGL(disparity_mask_kernel, grid2(w, h), kBlk, 0, ctx->stream, d, w, h, m1, m2, m2w, m2h);
-  VWGPU_HIP(ctx, hipGetLastError());
-  return VWGPU_OK;
-}
 
 // Zone scheduler, device part: one wave per leaf box of the quad tree measures the element-wise min / max of the VALID
 // disparities inside the box and inside the box grown by 1 px (clipped to the image) — what subdivide_regions reads
@@ -628,6 +353,282 @@ zone_extent_fused_kernel(const int32_t* __restrict__ inner, int w, int h, const 
   }
 }
 
+// ---- what the single-tile and the tile-group level loops share (the rules themselves: pyramid_plan.h) ------------------
+namespace {
+
+using vwgpu::EdgeMargins;
+using vwgpu::LevelClass;
+using vwgpu::PyrLayout;
+using vwgpu::TileGeom;
+using vwgpu::ZoneLevel;
+using vwgpu::ZoneTasks;
+constexpr int CS = vwgpu::PYR_CS, NB = vwgpu::PYR_NB;
+
+// development aid (VWGPU_OPT_TRACE bit 0): host-side timeline of a tile (n == 0) or of a group of n tiles on stderr
+struct Stamp {
+  bool on; int n;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  void operator()(const char* what, int level) const {
+    if (!on) return;
+    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    if (n) fprintf(stderr, "  [%8.1f us] group of %d, level %d: %s\n", us, n, level, what);
+    else fprintf(stderr, "  [%8.1f us] level %d %s\n", us, level, what);
+  }
+};
+
+// the tiles' slices of the arena: tile t's buffer at offset `off` of the layout
+struct Slices {
+  char* base; size_t slice;
+  char* at(int t, size_t off) const { return base + (size_t)t * slice + off; }
+  float* f(int t, size_t off) const { return reinterpret_cast<float*>(at(t, off)); }
+  uint8_t* b(int t, size_t off) const { return reinterpret_cast<uint8_t*>(at(t, off)); }
+  int32_t* i(int t, size_t off) const { return reinterpret_cast<int32_t*>(at(t, off)); }
+};
+
+struct PyrSource {       // the image pair and its masks (device pointers; masks may be null)
+  const float* left; int lw, lh; ptrdiff_t ls;
+  const float* right; int rw, rh; ptrdiff_t rs;
+  const uint8_t* lmask; ptrdiff_t lms;
+  const uint8_t* rmask; ptrdiff_t rms;
+};
+
+// build_image_pyramids (CorrelationView.cc:67-239) for n tiles of equal size in slices laid out by Y: base crops, nodata mean fill,
+// smoothing + decimation chain with the masks, the prefiltered copies (where Y has them) and, with `classes`, the class of every level
+// of every tile (cls[t * (Y.L + 1) + level]) in ONE read-back.  alive[t] = false: a fully masked image, the tile has no data (:318-327);
+// stop_if_dead: return as soon as no tile is alive (the single-tile path: nothing else is queued for such a tile).
+int build_pyramids(vwgpu_ctx* ctx, const PyrSource& I, const vwgpu_pyramid_params* P, int n, const TileGeom* G, const PyrLayout& Y, const Slices& S,
+                   bool classes, bool stop_if_dead, const Stamp* stamp, bool* alive, LevelClass* cls) {
+  hipStream_t st = ctx->stream;
+  const int L = Y.L, bw = Y.lmw[0], bh = Y.lmh[0];
+  int rc;
+  // ---- base crops, nodata mean fill (:67-149) ----
+  for (int t = 0; t < n; ++t) {
+    const TileGeom& g = G[t];
+    vwgpu_prof_scope ps(ctx, "pyramid_base_crops");
+    CropJobs cj;
+    cj.j[0] = CropJob{I.left, I.ls, I.lw, I.lh, g.lg.x0, g.lg.y0, S.f(t, Y.lp[0]), Y.lpw[0], Y.lph[0], 1, 0};
+    cj.j[1] = CropJob{I.right, I.rs, I.rw, I.rh, g.rg.x0, g.rg.y0, S.f(t, Y.rp[0]), Y.rpw[0], Y.rph[0], 1, 0};
+    cj.j[2] = CropJob{I.lmask, I.lms, I.lw, I.lh, g.lg.x0, g.lg.y0, S.b(t, Y.lmx), Y.lpw[0], Y.lph[0], 0, 0};
+    cj.j[3] = CropJob{I.rmask, I.rms, I.rw, I.rh, g.rg.x0, g.rg.y0, S.b(t, Y.rmx), Y.rpw[0], Y.rph[0], 0, 0};
+    cj.j[4] = CropJob{I.lmask, I.lms, I.lw, I.lh, g.bbox.x0, g.bbox.y0, S.b(t, Y.lmp[0]), bw, bh, 0, 1};
+    cj.j[5] = CropJob{I.rmask, I.rms, I.rw, I.rh, g.rmb.x0, g.rmb.y0, S.b(t, Y.rmp[0]), Y.rmw[0], Y.rmh[0], 0, 1};
+    const int cmw = std::max(std::max(Y.lpw[0], Y.rpw[0]), std::max(bw, Y.rmw[0])), cmh = std::max(std::max(Y.lph[0], Y.rph[0]), std::max(bh, Y.rmh[0]));
+    hipLaunchKernelGGL(crop_jobs_kernel, dim3((cmw + 63) / 64, (cmh + 3) / 4, 6), kBlk, 0, st, cj);
+    alive[t] = true;
+  }
+  // nodata mean fill (:130-149).  Without a user mask the mask of an image crop is all-valid (it is edge-extended like the image — only the
+  // bbox crops lmp / rmp are zero outside the image): its mean is not needed and nothing is filled; when that is true of both images the two
+  // reductions, the read-back and its host round trip are skipped altogether.
+  const bool l_all = !I.lmask, r_all = !I.rmask;
+  const size_t nl = (size_t)Y.lpw[0] * Y.lph[0], nr = (size_t)Y.rpw[0] * Y.rph[0];
+  if (!(l_all && r_all)) {
+    // the reductions of every tile are queued, ONE synchronisation brings all partial sums back
+    double part1[4 * NB];                          // (a single tile: no heap)
+    std::vector<double> partn;
+    double* part = part1;
+    if (n > 1) { partn.resize((size_t)n * 4 * NB); part = partn.data(); }
+    int cell[VWGPU_MAX_GROUP * 8];
+    double acc[VWGPU_MAX_GROUP * 4], got[VWGPU_MAX_GROUP * 4];
+    bool serial[VWGPU_MAX_GROUP * 2];
+    const int init[8] = {INT_MAX, INT_MIN, 0, 0, INT_MAX, INT_MIN, 0, 0};
+    for (int t = 0; t < n; ++t) {
+      double* d_part = reinterpret_cast<double*>(S.at(t, Y.d_part));
+      int* d_cell = reinterpret_cast<int*>(S.at(t, Y.d_cell));
+      VWGPU_HIP(ctx, hipMemcpyAsync(d_cell, init, sizeof init, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(masked_mean_kernel, dim3(16, 16), kBlk, 0, st, S.f(t, Y.lp[0]), S.b(t, Y.lmx), Y.lpw[0], Y.lph[0], d_part, d_cell);
+      hipLaunchKernelGGL(masked_mean_kernel, dim3(16, 16), kBlk, 0, st, S.f(t, Y.rp[0]), S.b(t, Y.rmx), Y.rpw[0], Y.rph[0], d_part + 2 * NB, d_cell + 4);
+      VWGPU_HIP(ctx, hipMemcpyAsync(part + (size_t)t * 4 * NB, d_part, 4 * NB * sizeof(double), hipMemcpyDeviceToHost, st));
+      VWGPU_HIP(ctx, hipMemcpyAsync(cell + t * 8, d_cell, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    VWGPU_HIP(ctx, hipStreamSynchronize(st));
+    bool any_serial = false;
+    for (int t = 0; t < n; ++t)
+      for (int im = 0; im < 2; ++im) {
+        double s_ = 0.0, n_ = 0.0;
+        for (int b = 0; b < NB; ++b) { s_ += part[(size_t)t * 4 * NB + (im * NB + b) * 2]; n_ += part[(size_t)t * 4 * NB + (im * NB + b) * 2 + 1]; }
+        acc[t * 4 + 2 * im] = s_; acc[t * 4 + 2 * im + 1] = n_;
+        const int lo = cell[t * 8 + 4 * im], hi = cell[t * 8 + 4 * im + 1];
+        int lgn = 0;
+        while ((1LL << lgn) < (long long)n_ + 1) ++lgn;
+        // every partial sum of <= n pixels < 2^(hi+1), all multiples of 2^lo, is exact iff it needs <= 53 bits
+        serial[t * 2 + im] = cell[t * 8 + 4 * im + 2] != 0 || (lo != INT_MAX && (long long)hi + 1 + lgn - lo > 53);
+        any_serial = any_serial || serial[t * 2 + im];
+      }
+    if (any_serial) {
+      for (int t = 0; t < n; ++t) {
+        double* d_acc = reinterpret_cast<double*>(S.at(t, Y.d_acc));
+        if (serial[t * 2]) hipLaunchKernelGGL(masked_mean_serial_kernel, dim3(1), dim3(64), 0, st, S.f(t, Y.lp[0]), S.b(t, Y.lmx), Y.lpw[0], Y.lph[0], d_acc);
+        if (serial[t * 2 + 1]) hipLaunchKernelGGL(masked_mean_serial_kernel, dim3(1), dim3(64), 0, st, S.f(t, Y.rp[0]), S.b(t, Y.rmx), Y.rpw[0], Y.rph[0], d_acc + 2);
+        if (serial[t * 2] || serial[t * 2 + 1]) VWGPU_HIP(ctx, hipMemcpyAsync(got + t * 4, d_acc, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+      }
+      VWGPU_HIP(ctx, hipStreamSynchronize(st));
+      for (int t = 0; t < n; ++t) {
+        if (serial[t * 2]) { acc[t * 4] = got[t * 4]; acc[t * 4 + 1] = got[t * 4 + 1]; }
+        if (serial[t * 2 + 1]) { acc[t * 4 + 2] = got[t * 4 + 2]; acc[t * 4 + 3] = got[t * 4 + 3]; }
+      }
+    }
+    // A fully masked image.  Only an image with a user mask is asked: without one its crop mask is all 255 and its count is the number
+    // of sampled pixels, never zero — which is why "either count is zero" and this test agree.
+    bool any_alive = false;
+    for (int t = 0; t < n; ++t) {
+      alive[t] = !((!l_all && acc[t * 4 + 1] == 0.0) || (!r_all && acc[t * 4 + 3] == 0.0));
+      any_alive = any_alive || alive[t];
+    }
+    if (stop_if_dead && !any_alive) return VWGPU_OK;
+    for (int t = 0; t < n; ++t) {
+      if (!alive[t]) continue;
+      if (!l_all) hipLaunchKernelGGL(fill_masked_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st, S.f(t, Y.lp[0]), S.b(t, Y.lmx), nl, (float)(acc[t * 4] / acc[t * 4 + 1]));
+      if (!r_all) hipLaunchKernelGGL(fill_masked_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st, S.f(t, Y.rp[0]), S.b(t, Y.rmx), nr, (float)(acc[t * 4 + 2] / acc[t * 4 + 3]));
+    }
+  }
+  // ---- smoothing + decimation chain, mask decimation (:205-216): the four jobs of every tile of a level, VWGPU_MAX_IMG_JOBS per launch ----
+  const float k5[5] = {(float)(1.0 / 16.0), (float)(4.0 / 16.0), (float)(6.0 / 16.0), (float)(4.0 / 16.0), (float)(1.0 / 16.0)};
+  for (int i = 1; i <= L; ++i) {
+    vwgpu_img_job jobs[4 * VWGPU_MAX_GROUP];
+    for (int t = 0; t < n; ++t) {
+      jobs[4 * t + 0] = {S.f(t, Y.lp[i - 1]), Y.lpw[i - 1], Y.lpw[i - 1], Y.lph[i - 1], S.f(t, Y.lp[i]), Y.lpw[i], Y.lpw[i], Y.lph[i], 0, 0, nullptr, 0};
+      jobs[4 * t + 1] = {S.f(t, Y.rp[i - 1]), Y.rpw[i - 1], Y.rpw[i - 1], Y.rph[i - 1], S.f(t, Y.rp[i]), Y.rpw[i], Y.rpw[i], Y.rph[i], 0, 0, nullptr, 0};
+      jobs[4 * t + 2] = {S.b(t, Y.lmp[i - 1]), Y.lmw[i - 1], Y.lmw[i - 1], Y.lmh[i - 1], S.b(t, Y.lmp[i]), Y.lmw[i], Y.lmw[i], Y.lmh[i], 0, 0, nullptr, VWGPU_JOB_MASK_BY_TWO};
+      jobs[4 * t + 3] = {S.b(t, Y.rmp[i - 1]), Y.rmw[i - 1], Y.rmw[i - 1], Y.rmh[i - 1], S.b(t, Y.rmp[i]), Y.rmw[i], Y.rmw[i], Y.rmh[i], 0, 0, nullptr, VWGPU_JOB_MASK_BY_TWO};
+    }
+    for (int j0 = 0; j0 < 4 * n; j0 += VWGPU_MAX_IMG_JOBS)
+      if ((rc = vwgpu_launch_sepconv_jobs(ctx, jobs + j0, std::min(VWGPU_MAX_IMG_JOBS, 4 * n - j0), k5, 5, 2, k5, 5, 2, 0, 2))) return rc;
+  }
+  // ---- prefilter every level into copies (:232-236; the levels stay the unfiltered sources of the next level): every level of both
+  // images of every tile through the same two launches (gaussian, then laplacian / subtraction), level by level ----
+  if (Y.filtered) {
+    std::vector<const float*> fs; std::vector<float*> fd; std::vector<int> fw, fh;
+    for (int i = 0; i <= L; ++i)
+      for (int t = 0; t < n; ++t) {
+        fs.push_back(S.f(t, Y.lp[i])); fd.push_back(S.f(t, Y.lpf[i])); fw.push_back(Y.lpw[i]); fh.push_back(Y.lph[i]);
+        fs.push_back(S.f(t, Y.rp[i])); fd.push_back(S.f(t, Y.rpf[i])); fw.push_back(Y.rpw[i]); fh.push_back(Y.rph[i]);
+      }
+    if ((rc = vwgpu_prefilter_images_dev(ctx, (int)fs.size(), fs.data(), fw.data(), fh.data(), P->prefilter_mode, P->prefilter_width, fd.data()))) return rc;
+  }
+  // ---- class of every level of every tile (pyramid_plan.h, level_class), measured on the device: ONE read-back ----
+  if (classes) {
+    std::vector<int> cells((size_t)n * CS * (L + 1), 0);
+    for (int t = 0; t < n; ++t)
+      for (int i = 0; i <= L; ++i) { int* c = cells.data() + ((size_t)t * (L + 1) + i) * CS; c[0] = INT_MAX; c[1] = INT_MIN; }
+    std::vector<const float*> gi; std::vector<int> gw, gh; std::vector<ptrdiff_t> gs; std::vector<int*> gc;
+    for (int t = 0; t < n; ++t)
+      VWGPU_HIP(ctx, hipMemcpyAsync(S.at(t, Y.d_cells), cells.data() + (size_t)t * (L + 1) * CS, (size_t)(L + 1) * CS * sizeof(int), hipMemcpyHostToDevice, st));
+    for (int i = 0; i <= L; ++i)
+      for (int t = 0; t < n; ++t) {
+        int* d_cells = reinterpret_cast<int*>(S.at(t, Y.d_cells));
+        gi.push_back(S.f(t, Y.lpf[i])); gw.push_back(Y.lpw[i]); gh.push_back(Y.lph[i]); gs.push_back(Y.lpw[i]); gc.push_back(d_cells + CS * i);
+        gi.push_back(S.f(t, Y.rpf[i])); gw.push_back(Y.rpw[i]); gh.push_back(Y.rph[i]); gs.push_back(Y.rpw[i]); gc.push_back(d_cells + CS * i);
+      }
+    vwgpu_launch_float_grain(ctx, (int)gi.size(), gi.data(), gw.data(), gh.data(), gs.data(), gc.data());
+    for (int t = 0; t < n; ++t)
+      VWGPU_HIP(ctx, hipMemcpyAsync(cells.data() + (size_t)t * (L + 1) * CS, S.at(t, Y.d_cells), (size_t)(L + 1) * CS * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (stamp) (*stamp)("pyramids queued, waiting for the level classes", L);
+    VWGPU_HIP(ctx, hipStreamSynchronize(st));
+    if (stamp) (*stamp)("level classes on the host", L);
+    for (int t = 0; t < n; ++t)
+      for (int i = 0; i <= L; ++i)
+        cls[(size_t)t * (L + 1) + i] = vwgpu::level_class(P->cost_type, P->kernel_x, P->kernel_y, cells.data() + ((size_t)t * (L + 1) + i) * CS, ctx->certify != 0);
+  }
+  return VWGPU_OK;
+}
+
+// The leaf boxes of a level size on the device: the quad tree of boxes is fixed by (dw, dh), so its leaves go up once per context.
+int leaf_rects_on_device(vwgpu_ctx* ctx, int dw, int dh, const int4** d_rects, size_t* nleaf) {
+  const std::vector<vwgpu::IBox>& leaves = vwgpu::cached_leaves(dw, dh);
+  const size_t nl = leaves.size();
+  static_assert(sizeof(vwgpu::IBox) == sizeof(int4), "leaf boxes upload as int4");
+  *nleaf = nl; *d_rects = nullptr;
+  for (auto& lr : ctx->leaf_rects)
+    if (lr.w == dw && lr.h == dh && lr.n == nl) *d_rects = static_cast<const int4*>(lr.d_rects);
+  if (*d_rects) return VWGPU_OK;
+  void* p = nullptr;
+  VWGPU_HIP(ctx, hipMalloc(&p, std::max<size_t>(nl, 1) * sizeof(int4)));
+  VWGPU_HIP(ctx, hipMemcpyAsync(p, leaves.data(), nl * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
+  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));                 // the host list may be evicted from its cache later
+  if (ctx->leaf_rects.size() >= 64) { (void)hipFree(ctx->leaf_rects.front().d_rects); ctx->leaf_rects.erase(ctx->leaf_rects.begin()); }
+  ctx->leaf_rects.push_back({dw, dh, nl, p});
+  *d_rects = static_cast<const int4*>(p);
+  return VWGPU_OK;
+}
+
+// Zone refinement, device part (:754-799): the leaves of the quad tree are measured on the device (box + 1-px neighbourhood) for n tiles
+// in one launch, only that table comes back — to the pinned ring, or to `own` when it does not fit — and the host waits for it: the one
+// synchronisation of a level.  fused: `img` is the first pass of the clean-up filter (padded) and the second pass and the mask (m1, m2)
+// are applied as the kernel reads; otherwise `img` is the finished disparity image.  img_tile (ints) / mask_tile (bytes): the stride
+// from a tile to the next (0 for a single tile).
+int read_leaf_extents(vwgpu_ctx* ctx, int n, bool fused, const int32_t* img, size_t img_tile, int dw, int dh, const uint8_t* m1, const uint8_t* m2,
+                      size_t mask_tile, int m2w, int m2h, const Stamp& stamp, int level, std::vector<vwgpu::LeafExtent>* own,
+                      const vwgpu::LeafExtent** h_ext, size_t* nleaf) {
+  hipStream_t st = ctx->stream;
+  const int4* d_rects = nullptr;
+  int rc = leaf_rects_on_device(ctx, dw, dh, &d_rects, nleaf);
+  if (rc) return rc;
+  const size_t ext_bytes = (size_t)n * *nleaf * sizeof(vwgpu::LeafExtent);
+  if ((rc = vwgpu_arena_reserve(ctx, &ctx->zext, ext_bytes + 256))) return rc;
+  int32_t* d_ext = static_cast<int32_t*>(ctx->zext.base);
+  {
+    vwgpu_prof_scope ps(ctx, "zone_extents");
+    const dim3 grid((unsigned)*nleaf, (unsigned)n);
+    if (fused)
+      hipLaunchKernelGGL(zone_extent_fused_kernel, grid, dim3(64), 0, st, img, dw, dh, m1, m2, m2w, m2h, d_rects, (int)*nleaf, d_ext, img_tile, mask_tile);
+    else
+      hipLaunchKernelGGL(zone_extent_kernel, grid, dim3(64), 0, st, img, dw, dh, d_rects, (int)*nleaf, d_ext, img_tile);
+  }
+  *h_ext = static_cast<const vwgpu::LeafExtent*>(vwgpu_host_ring(ctx, ext_bytes));
+  if (!*h_ext) { own->resize((size_t)n * *nleaf); *h_ext = own->data(); }
+  VWGPU_HIP(ctx, hipMemcpyAsync(const_cast<vwgpu::LeafExtent*>(*h_ext), d_ext, ext_bytes, hipMemcpyDeviceToHost, st));
+  stamp("level queued, waiting", level);
+  VWGPU_HIP(ctx, hipStreamSynchronize(st));
+  stamp("leaf extents on the host", level);
+  return VWGPU_OK;
+}
+
+// One direction of a matching pass: image A matched against image B.
+struct MatchPair { const float* a; int aw, ah; const float* b; int bw, bh; };
+
+// Behind a certified pass: the zones of `tz` that the tile kernels flagged (hflag, on the host) — those of tile `img` only, or all with
+// img < 0 — are redone in the reference's order.  The launch is sized by the flagged zones: gated launches over all 2000 zones of a
+// border tile spent 0.1 ms each on workgroups that read a zero and left.  trace_level >= 0: say what was redone (VWGPU_OPT_TRACE bit 2).
+int redo_flagged_zones(vwgpu_ctx* ctx, const vwgpu_pyramid_params* P, const MatchPair& m, const std::vector<vwgpu_zone_task>& tz, const int* hflag, int img,
+                       int32_t* dst, int trace_level, size_t pass) {
+  std::vector<vwgpu_zone_task> redo;
+  for (size_t i = 0; i < tz.size(); ++i) if (hflag[i] && (img < 0 || tz[i].img == img)) redo.push_back(tz[i]);
+  if (redo.empty()) return VWGPU_OK;
+  if (trace_level >= 0 && (ctx->trace & 4)) {
+    size_t px = 0, ev = 0;
+    for (auto const& zt : redo) { px += (size_t)zt.zw * zt.zh; ev += (size_t)zt.zw * zt.zh * zt.sx * zt.sy; }
+    fprintf(stderr, "  level %d pass %zu: %zu of %zu zones to the exact-order kernels, %zu px, %zu evaluations; largest:", trace_level, pass, redo.size(), tz.size(), px, ev);
+    std::vector<vwgpu_zone_task> big(redo);
+    std::sort(big.begin(), big.end(), [](vwgpu_zone_task const& a2, vwgpu_zone_task const& b2) { return (size_t)a2.zw * a2.zh * a2.sx * a2.sy > (size_t)b2.zw * b2.zh * b2.sx * b2.sy; });
+    for (size_t i = 0; i < std::min<size_t>(4, big.size()); ++i) fprintf(stderr, " %dx%d x %dx%d", big[i].zw, big[i].zh, big[i].sx, big[i].sy);
+    fprintf(stderr, "\n");
+  }
+  return vwgpu_launch_bm_exact(ctx, P->cost_type, m.a, m.aw, m.ah, m.aw, m.b, m.bw, m.bh, m.bw, P->kernel_x, P->kernel_y, redo.data(), (int)redo.size(), dst);
+}
+
+// certification statistics (VWGPU_OPT_TRACE bit 2), the end of a call: into the context's counters, and on stderr with `print`
+int read_cert_stats(vwgpu_ctx* ctx, const unsigned long long* d_cert_stats, bool print) {
+  if (!d_cert_stats) return VWGPU_OK;
+  unsigned long long got[4] = {0, 0, 0, 0};
+  VWGPU_HIP(ctx, hipMemcpyAsync(got, d_cert_stats, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
+  VWGPU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->cert_px[0] += got[0]; ctx->cert_px[1] += got[1]; ctx->cert_px[2] += got[2];
+  if (print)
+    fprintf(stderr, "certification: %llu pixels in certified tiles, %llu in tiles that sent their zone to the exact-order kernels (%.2f %%); %llu in tiles "
+            "the fp32 tier passed on to float64 (%.2f %%)\n",
+            got[0], got[1], got[0] + got[1] ? 100.0 * (double)got[1] / (double)(got[0] + got[1]) : 0.0, got[2],
+            got[0] + got[1] ? 100.0 * (double)got[2] / (double)(got[0] + got[1]) : 0.0);
+  return VWGPU_OK;
+}
+
+const char* zone_err_text(vwgpu::ZoneErr e, bool group) {
+  if (e == vwgpu::ZONE_TOO_LARGE) return "pyramid_correlate: zone too large";
+  if (e == vwgpu::ZONE_TABLES_TOO_LARGE) return "pyramid_correlate: tile group too large for the zone tables";
+  return group ? "pyramid_correlate: tile group too large for the L/R check buffers" : "pyramid_correlate: tile too large for the L/R check buffers";
+}
+
+}  // namespace
+
 // All pointers are device pointers (masks may be null).  out: bw x bh x 3 floats.
 int vwgpu_pyramid_correlate_impl(vwgpu_ctx* ctx, const float* left, int lw, int lh, ptrdiff_t ls,
                                  const float* right, int rw, int rh, ptrdiff_t rs,
@@ -639,29 +640,23 @@ int vwgpu_pyramid_correlate_impl(vwgpu_ctx* ctx, const float* left, int lw, int 
   const ptrdiff_t lr_stride = P->lr_disp_diff_stride ? P->lr_disp_diff_stride : P->lr_disp_diff_cols;
   const int lr_ulx = bx - P->region_ul_x, lr_uly = by - P->region_ul_y;       // tile origin inside the diff image
   const IBox search(P->search_min_x, P->search_min_y, P->search_max_x, P->search_max_y);
-  const IBox bbox(bx, by, bx + bw, by + bh);
   hipStream_t st = ctx->stream;
 
-  // constructor + 1.0): number of levels (CorrelationView.h:99-105, CorrelationView.cc:301-310)
-  const int largest_search = std::max(search.dx(), search.dy());
-  int by_search = (int)(std::floor(std::log(float(largest_search)) / std::log(2.0f)) - 1);
-  by_search = std::max(0, std::min(by_search, P->max_pyramid_levels));
-  int L = (int)std::floor(std::log((double)std::min(bw, bh)) / std::log(2.0f) - std::log((double)std::max(kx, ky)) / std::log(2.0f));
-  L = std::min(L, by_search);
-  if (L < 1) L = 0;
+  const int L = vwgpu::pyramid_levels(P, bw, bh);
   const int hkx = kx / 2, hky = ky / 2, up = 1 << L;
-
-  // geometry of level 0
-  IBox lg = bbox; lg.x0 -= hkx * up; lg.x1 += hkx * up; lg.y0 -= hky * up; lg.y1 += hky * up;
-  const IBox rg(lg.x0 + search.x0, lg.y0 + search.y0, lg.x1 + search.x0 + search.dx(), lg.y1 + search.y0 + search.dy());
-  const IBox rmb(bbox.x0 + search.x0, bbox.y0 + search.y0, bbox.x1 + search.x0 + search.dx(), bbox.y1 + search.y0 + search.dy());
+  const TileGeom G = vwgpu::tile_geom(bx, by, bw, bh, search, hkx, hky, up);
+  const IBox &lg = G.lg, &rg = G.rg, &rmb = G.rmb;
+  const bool use_sgm = P->algorithm != 0;
+  // SGM/MGM run without a prefilter (CorrelationView.h:96-97) and without level classes
+  const bool filtered = !use_sgm && (P->prefilter_mode == VWGPU_PREFILTER_LOG || P->prefilter_mode == VWGPU_PREFILTER_MEANSUB);
+  const PyrLayout Y = vwgpu::pyr_layout(G, L, filtered);
 
   // arena: pyramids (4/3 of the bases, twice for the prefiltered copies), masks, disparities, scratch
   const size_t nl = (size_t)lg.dx() * lg.dy(), nr = (size_t)rg.dx() * rg.dy();
   const size_t need = 4 * (nl + nr) * 3 + (nl + nr) * 2 + (size_t)rmb.dx() * rmb.dy() * 2 + (size_t)bw * bh * (12 * 3 + 2) +
                       (size_t)(bw + 2) * (bh + 2) * 12 + (nl + nr) * 4 * 2 + (size_t)(rg.dx() + 2 * search.dx()) * (rg.dy() + 2 * search.dy()) * 20 +
                       (size_t)(lg.dx() + 2 * search.dx() + 2) * (lg.dy() + 2 * search.dy() + 2) * 4 + (1 << 20) +
-                      // per-level tables taken inside the level loop (ADVICE r4): zone flags of both passes and the R->L need records (8 ints per
+                      // per-level tables taken inside the level loop: zone flags of both passes and the R->L need records (8 ints per
                       // zone; zones <= 4 per 16 x 16 px of the tile + 64) with one cell flag per 16 x 16 px of every zone's R->L image (a zone widened
                       // by its search range: at most (sdx / 16 + 3)(sdy / 16 + 3) cells for a leaf-sized zone)
                       (size_t)(L + 1) * ((size_t)bw * bh / 64 + 64) * (48 + (size_t)(search.dx() / 16 + 3) * (search.dy() / 16 + 3)) + 4096;
@@ -673,143 +668,26 @@ int vwgpu_pyramid_correlate_impl(vwgpu_ctx* ctx, const float* left, int lw, int 
   int rc = vwgpu_arena_reserve(ctx, &ctx->pyr, need + need_sgm + need_blob);
   if (rc) return rc;
   Bump A{static_cast<char*>(ctx->pyr.base), ctx->pyr.cap};
-  std::vector<DevImg> lp(L + 1), rp(L + 1);
-  std::vector<DevMask> lmp(L + 1), rmp(L + 1);
   auto fail_mem = [&]() { return vwgpu_fail(ctx, VWGPU_ERR_LOGIC, "pyramid_correlate: internal arena too small"); };
-
-  lp[0].w = lg.dx(); lp[0].h = lg.dy(); lp[0].p = A.take<float>(nl);
-  rp[0].w = rg.dx(); rp[0].h = rg.dy(); rp[0].p = A.take<float>(nr);
-  uint8_t* lmx = A.take<uint8_t>(nl);
-  uint8_t* rmx = A.take<uint8_t>(nr);
-  lmp[0].w = bw; lmp[0].h = bh; lmp[0].p = A.take<uint8_t>((size_t)bw * bh);
-  rmp[0].w = rmb.dx(); rmp[0].h = rmb.dy(); rmp[0].p = A.take<uint8_t>((size_t)rmb.dx() * rmb.dy());
-  double* d_acc = A.take<double>(4);
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  if (!lp[0].p || !rp[0].p || !lmx || !rmx || !lmp[0].p || !rmp[0].p || !d_acc) return fail_mem();
-  {
-    vwgpu_prof_scope ps(ctx, "pyramid_base_crops");
-    CropJobs cj;
-    cj.j[0] = CropJob{left, ls, lw, lh, lg.x0, lg.y0, lp[0].p, lp[0].w, lp[0].h, 1, 0};
-    cj.j[1] = CropJob{right, rs, rw, rh, rg.x0, rg.y0, rp[0].p, rp[0].w, rp[0].h, 1, 0};
-    cj.j[2] = CropJob{lmask, lms, lw, lh, lg.x0, lg.y0, lmx, lp[0].w, lp[0].h, 0, 0};
-    cj.j[3] = CropJob{rmask, rms, rw, rh, rg.x0, rg.y0, rmx, rp[0].w, rp[0].h, 0, 0};
-    cj.j[4] = CropJob{lmask, lms, lw, lh, bbox.x0, bbox.y0, lmp[0].p, bw, bh, 0, 1};
-    cj.j[5] = CropJob{rmask, rms, rw, rh, rmb.x0, rmb.y0, rmp[0].p, rmp[0].w, rmp[0].h, 0, 1};
-    const int cmw = std::max(std::max(lp[0].w, rp[0].w), std::max(bw, rmp[0].w)), cmh = std::max(std::max(lp[0].h, rp[0].h), std::max(bh, rmp[0].h));
-    dim3 cgrd((cmw + 63) / 64, (cmh + 3) / 4, 6);
-    hipLaunchKernelGGL(crop_jobs_kernel, cgrd, kBlk, 0, st, cj);
-  }
-  // nodata mean fill (:130-149).  Without a user mask the mask of an image crop is all-valid (it is edge-extended like the image — only the
-  // bbox crops lmp / rmp are zero outside the image): its mean is not needed and nothing is filled; when that is true of both images the two
-  // reductions, the read-back and its host round trip are skipped altogether.
-  const bool l_all = !lmask, r_all = !rmask;
-  if (l_all && r_all) {
-    acc[0] = acc[1] = acc[2] = acc[3] = 1.0;
-  } else {
-    constexpr int NB = 256;                         // workgroups per image
-    double* d_part = A.take<double>(2 * 2 * NB);
-    int* d_cell = A.take<int>(8);
-    if (!d_part || !d_cell) return fail_mem();
-    const int init[8] = {INT_MAX, INT_MIN, 0, 0, INT_MAX, INT_MIN, 0, 0};
-    VWGPU_HIP(ctx, hipMemcpyAsync(d_cell, init, sizeof init, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(masked_mean_kernel, dim3(16, 16), kBlk, 0, st, lp[0].p, lmx, lp[0].w, lp[0].h, d_part, d_cell);
-    hipLaunchKernelGGL(masked_mean_kernel, dim3(16, 16), kBlk, 0, st, rp[0].p, rmx, rp[0].w, rp[0].h, d_part + 2 * NB, d_cell + 4);
-    double part[2 * 2 * NB];
-    int cell[8];
-    VWGPU_HIP(ctx, hipMemcpyAsync(part, d_part, sizeof part, hipMemcpyDeviceToHost, st));
-    VWGPU_HIP(ctx, hipMemcpyAsync(cell, d_cell, sizeof cell, hipMemcpyDeviceToHost, st));
-    VWGPU_HIP(ctx, hipStreamSynchronize(st));
-    bool serial[2];
-    for (int im = 0; im < 2; ++im) {
-      double s = 0.0, n = 0.0;
-      for (int b = 0; b < NB; ++b) { s += part[(im * NB + b) * 2]; n += part[(im * NB + b) * 2 + 1]; }
-      acc[2 * im] = s; acc[2 * im + 1] = n;
-      const int lo = cell[4 * im], hi = cell[4 * im + 1];
-      int lgn = 0;
-      while ((1LL << lgn) < (long long)n + 1) ++lgn;
-      // every partial sum of <= n pixels < 2^(hi+1), all multiples of 2^lo, is exact iff it needs <= 53 bits
-      serial[im] = cell[4 * im + 2] != 0 || (lo != INT_MAX && (long long)hi + 1 + lgn - lo > 53);
-    }
-    if (serial[0] || serial[1]) {
-      if (serial[0]) hipLaunchKernelGGL(masked_mean_serial_kernel, dim3(1), dim3(64), 0, st, lp[0].p, lmx, lp[0].w, lp[0].h, d_acc);
-      if (serial[1]) hipLaunchKernelGGL(masked_mean_serial_kernel, dim3(1), dim3(64), 0, st, rp[0].p, rmx, rp[0].w, rp[0].h, d_acc + 2);
-      double got[4];
-      VWGPU_HIP(ctx, hipMemcpyAsync(got, d_acc, sizeof got, hipMemcpyDeviceToHost, st));
-      VWGPU_HIP(ctx, hipStreamSynchronize(st));
-      if (serial[0]) { acc[0] = got[0]; acc[1] = got[1]; }
-      if (serial[1]) { acc[2] = got[2]; acc[3] = got[3]; }
-    }
-  }
-  if (acc[1] == 0.0 || acc[3] == 0.0) {            // a fully masked image: the tile has no data (:318-327)
+  // the tile's slice (pyramids, masks, disparity images) comes first; the scratch of the level loop follows it
+  const Slices S{A.take<char>(Y.slice), Y.slice};
+  if (!S.base) return fail_mem();
+  bool alive = true;
+  LevelClass cls[vwgpu::PYR_MAX_LEVELS];
+  const PyrSource src{left, lw, lh, ls, right, rw, rh, rs, lmask, lms, rmask, rms};
+  if ((rc = build_pyramids(ctx, src, P, 1, &G, Y, S, !use_sgm, true, nullptr, &alive, cls))) return rc;
+  if (!alive) {                                    // a fully masked image: the tile has no data (:318-327)
     hipLaunchKernelGGL(zero_out_kernel, grid2(bw, bh), kBlk, 0, st, out, os, bw, bh);
     VWGPU_HIP(ctx, hipGetLastError());
     return VWGPU_OK;
   }
-  if (!l_all) hipLaunchKernelGGL(fill_masked_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st, lp[0].p, lmx, nl, (float)(acc[0] / acc[1]));
-  if (!r_all) hipLaunchKernelGGL(fill_masked_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st, rp[0].p, rmx, nr, (float)(acc[2] / acc[3]));
-
-  // smoothing + decimation chain and mask decimation (:205-216)
-  const float k5[5] = {(float)(1.0 / 16.0), (float)(4.0 / 16.0), (float)(6.0 / 16.0), (float)(4.0 / 16.0), (float)(1.0 / 16.0)};
-  for (int i = 1; i <= L; ++i) {
-    lp[i].w = 1 + (lp[i - 1].w - 1) / 2; lp[i].h = 1 + (lp[i - 1].h - 1) / 2; lp[i].p = A.take<float>((size_t)lp[i].w * lp[i].h);
-    rp[i].w = 1 + (rp[i - 1].w - 1) / 2; rp[i].h = 1 + (rp[i - 1].h - 1) / 2; rp[i].p = A.take<float>((size_t)rp[i].w * rp[i].h);
-    lmp[i].w = 1 + (lmp[i - 1].w - 1) / 2; lmp[i].h = 1 + (lmp[i - 1].h - 1) / 2; lmp[i].p = A.take<uint8_t>((size_t)lmp[i].w * lmp[i].h);
-    rmp[i].w = 1 + (rmp[i - 1].w - 1) / 2; rmp[i].h = 1 + (rmp[i - 1].h - 1) / 2; rmp[i].p = A.take<uint8_t>((size_t)rmp[i].w * rmp[i].h);
-    if (!lp[i].p || !rp[i].p || !lmp[i].p || !rmp[i].p) return fail_mem();
-    // both images of the level in one launch, both masks in another (four launches of ~12 us on these sizes otherwise)
-    const vwgpu_img_job sj[4] = {{lp[i - 1].p, lp[i - 1].w, lp[i - 1].w, lp[i - 1].h, lp[i].p, lp[i].w, lp[i].w, lp[i].h, 0, 0, nullptr, 0},
-                                 {rp[i - 1].p, rp[i - 1].w, rp[i - 1].w, rp[i - 1].h, rp[i].p, rp[i].w, rp[i].w, rp[i].h, 0, 0, nullptr, 0},
-                                 {lmp[i - 1].p, lmp[i - 1].w, lmp[i - 1].w, lmp[i - 1].h, lmp[i].p, lmp[i].w, lmp[i].w, lmp[i].h, 0, 0, nullptr, VWGPU_JOB_MASK_BY_TWO},
-                                 {rmp[i - 1].p, rmp[i - 1].w, rmp[i - 1].w, rmp[i - 1].h, rmp[i].p, rmp[i].w, rmp[i].w, rmp[i].h, 0, 0, nullptr, VWGPU_JOB_MASK_BY_TWO}};
-    if ((rc = vwgpu_launch_sepconv_jobs(ctx, sj, 4, k5, 5, 2, k5, 5, 2, 0, 2))) return rc;      // both images and both masks of the level in one launch
-  }
-  // prefilter every level (:232-236); levels stay unfiltered sources of the next level, so filter into copies
-  const bool use_sgm = P->algorithm != 0;
-  // SGM/MGM run without a prefilter (CorrelationView.h:96-97)
-  const bool filtered = !use_sgm && (P->prefilter_mode == VWGPU_PREFILTER_LOG || P->prefilter_mode == VWGPU_PREFILTER_MEANSUB);
-  if (filtered) {
-    // every level of both images through the same two launches (gaussian, then laplacian / subtraction)
-    std::vector<const float*> fs; std::vector<float*> fd; std::vector<int> fw, fh;
-    for (int i = 0; i <= L; ++i) {
-      float* lf = A.take<float>((size_t)lp[i].w * lp[i].h);
-      float* rf = A.take<float>((size_t)rp[i].w * rp[i].h);
-      if (!lf || !rf) return fail_mem();
-      fs.push_back(lp[i].p); fd.push_back(lf); fw.push_back(lp[i].w); fh.push_back(lp[i].h);
-      fs.push_back(rp[i].p); fd.push_back(rf); fw.push_back(rp[i].w); fh.push_back(rp[i].h);
-      lp[i].p = lf; rp[i].p = rf;
-    }
-    if ((rc = vwgpu_prefilter_images_dev(ctx, (int)fs.size(), fs.data(), fw.data(), fh.data(), P->prefilter_mode, P->prefilter_width, fd.data()))) return rc;
-  }
-
-  // Class of every level: when the box sums of a level could round, its zones are matched in the reference's own
-  // summation order (bm_exact.hip); integer imagery and most float imagery are order free and take the tile kernels.
-  std::vector<char> exact_level(L + 1, 0), f32_level(L + 1, 0);      // f32_level: the window sums are exact in float32 as well (bm_zones.hip)
-  // cert_hi[level] != INT_MIN: the level is not order free but finite — its zones go through the tile kernels first, which certify every pixel
-  // against a bound on the difference to the reference's running sums (bm_zones.hip) and flag the zones that hold a pixel they cannot
-  // certify; only those are redone in the reference's order (VWGPU_OPT_CERTIFY = 0: every zone of such a level, as in round 3)
-  std::vector<int> cert_hi(L + 1, INT_MIN);
-  if (!use_sgm) {
-    constexpr int CS = 16;                                          // a cache line per level: same-line atomics queue up at the L2
-    int* d_cells = A.take<int>(CS * (size_t)(L + 1));
-    if (!d_cells) return fail_mem();
-    std::vector<int> cells(CS * (size_t)(L + 1), 0);
-    for (int i = 0; i <= L; ++i) { cells[CS * i] = INT_MAX; cells[CS * i + 1] = INT_MIN; cells[CS * i + 2] = 0; cells[CS * i + 3] = 0; }
-    VWGPU_HIP(ctx, hipMemcpyAsync(d_cells, cells.data(), cells.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    {
-      std::vector<const float*> gi; std::vector<int> gw, gh; std::vector<ptrdiff_t> gs; std::vector<int*> gc;
-      for (int i = 0; i <= L; ++i)
-        for (DevImg const* im : {&lp[i], &rp[i]}) { gi.push_back(im->p); gw.push_back(im->w); gh.push_back(im->h); gs.push_back(im->w); gc.push_back(d_cells + CS * i); }
-      vwgpu_launch_float_grain(ctx, (int)gi.size(), gi.data(), gw.data(), gh.data(), gs.data(), gc.data());
-    }
-    VWGPU_HIP(ctx, hipMemcpyAsync(cells.data(), d_cells, cells.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-    VWGPU_HIP(ctx, hipStreamSynchronize(st));
-    for (int i = 0; i <= L; ++i) {
-      exact_level[i] = !vwgpu_sums_order_free(P->cost_type, kx, ky, cells[CS * i], cells[CS * i + 1], cells[CS * i + 2]);
-      f32_level[i] = vwgpu_sums_bits(P->cost_type, kx, ky, cells[CS * i], cells[CS * i + 1], cells[CS * i + 2]) <= 24;      // (byte imagery under SAD)
-      if (exact_level[i] && ctx->certify && (cells[CS * i + 2] & 1) == 0 && cells[CS * i] != INT_MAX      // (bit 0: a non-finite pixel; bit 1 only says "negative pixels")
-          && cells[CS * i + 1] < 60 && cells[CS * i + 1] > -60)
-        cert_hi[i] = cells[CS * i + 1];
-    }
+  std::vector<DevImg> lp(L + 1), rp(L + 1);        // the levels the matchers read: the prefiltered copies where there are any
+  std::vector<DevMask> lmp(L + 1), rmp(L + 1);
+  for (int i = 0; i <= L; ++i) {
+    lp[i].p = S.f(0, Y.lpf[i]); lp[i].w = Y.lpw[i]; lp[i].h = Y.lph[i];
+    rp[i].p = S.f(0, Y.rpf[i]); rp[i].w = Y.rpw[i]; rp[i].h = Y.rph[i];
+    lmp[i].p = S.b(0, Y.lmp[i]); lmp[i].w = Y.lmw[i]; lmp[i].h = Y.lmh[i];
+    rmp[i].p = S.b(0, Y.rmp[i]); rmp[i].w = Y.rmw[i]; rmp[i].h = Y.rmh[i];
   }
 
   // certification statistics (VWGPU_OPT_TRACE bit 2): pixels in certified tiles / in tiles that flagged their zone
@@ -820,16 +698,16 @@ int vwgpu_pyramid_correlate_impl(vwgpu_ctx* ctx, const float* left, int lw, int 
     VWGPU_HIP(ctx, hipMemsetAsync(d_cert_stats, 0, 32, st));
   }
   // level loop
-  int32_t* disp = A.take<int32_t>((size_t)bw * bh * 3);
-  int32_t* disp2 = A.take<int32_t>((size_t)bw * bh * 3);
-  int32_t* padded = A.take<int32_t>((size_t)(bw + 2) * (bh + 2) * 3);
+  int32_t* disp = S.i(0, Y.disp);
+  int32_t* disp2 = S.i(0, Y.disp2);
+  int32_t* padded = S.i(0, Y.padded);
   int32_t* rl = A.take<int32_t>((size_t)(rg.dx() + 2 * search.dx()) * (rg.dy() + 2 * search.dy()) * 3 + 64);
   // tmp_a also receives the edge-extended LEFT crop of an R->L run: (zone + 2 * search - 1) per axis, at most the level size + 2 * search
   const size_t tmp_a_px = std::max(nl + nr, (size_t)(lg.dx() + 2 * search.dx() + 2) * (lg.dy() + 2 * search.dy() + 2));
   const size_t tmp_b_px = (size_t)(rg.dx() + 2 * search.dx()) * (rg.dy() + 2 * search.dy());
   float* tmp_a = A.take<float>(tmp_a_px);
   float* tmp_b = A.take<float>(tmp_b_px);
-  if (!disp || !disp2 || !padded || !rl || !tmp_a || !tmp_b) return fail_mem();
+  if (!rl || !tmp_a || !tmp_b) return fail_mem();
   int* blob_scratch = nullptr;
   if (P->blob_filter_area > 0) {
     blob_scratch = A.take<int>((size_t)(bw + search.dx() + 8) * (bh + search.dy() + 8) * 2);
@@ -858,11 +736,8 @@ int vwgpu_pyramid_correlate_impl(vwgpu_ctx* ctx, const float* left, int lw, int 
   // replaced by the wall clock whenever it has advanced by more than measure_spacing (2 s) since the last measurement
   // (std::time: whole seconds), so a seconds_per_op calibrated for the CPU cannot make the GPU quit after milliseconds.
   double estim = 0.0, prev_estim = 0.0;
-  const auto t_start = std::chrono::steady_clock::now();
-  const bool dbg_time = (ctx->trace & 1) != 0;     // development aid: host-side timeline of a tile on stderr
-  auto stamp = [&](const char* what, int level) {
-    if (dbg_time) fprintf(stderr, "  [%8.1f us] level %d %s\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count(), level, what);
-  };
+  const Stamp stamp{(ctx->trace & 1) != 0, 0};
+  const auto t_start = stamp.t0;
   auto remeasure = [&]() {
     if (P->corr_timeout > 0 && estim - prev_estim > 2.0) {
       estim = std::floor(std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count());
@@ -885,7 +760,7 @@ int vwgpu_pyramid_correlate_impl(vwgpu_ctx* ctx, const float* left, int lw, int 
       std::stable_sort(zones.begin(), zones.end(), [](SearchZone const& a, SearchZone const& b) { return a.volume() < b.volume(); });
     // dyadic / prefiltered data is not integer-valued: go straight to the float64 matcher there, or to the exact-order
     // kernels when the level's sums could round
-    const int level_path = exact_level[level] ? VWGPU_PATH_EXACT_ORDER : ((level > 0 || filtered) ? VWGPU_PATH_GENERIC_F64 : VWGPU_PATH_NONE);
+    const int level_path = cls[level].exact ? VWGPU_PATH_EXACT_ORDER : ((level > 0 || filtered) ? VWGPU_PATH_GENERIC_F64 : VWGPU_PATH_NONE);
     ctx->forced_path = (saved_force != VWGPU_PATH_NONE) ? saved_force : level_path;
     const DevImg Lv = lp[level], Rv = rp[level];
     const bool lr_active = P->consistency_threshold >= 0 && last;
@@ -935,40 +810,34 @@ int vwgpu_pyramid_correlate_impl(vwgpu_ctx* ctx, const float* left, int lw, int 
     if (batched && zones.size() == 1 && (double)zones[0].region.dx() * zones[0].region.dy() * zones[0].range.dx() * zones[0].range.dy() > 3.2e7)
       batched = false;
     if (batched) {
-      std::vector<vwgpu_zone_task> t1, t2, t3;
+      ZoneTasks zt;
+      std::vector<vwgpu_zone_task>&t1 = zt.a, &t2 = zt.b, &t3 = zt.c;
       t1.reserve(zones.size());
       if (lr_active) { t2.reserve(zones.size()); t3.reserve(zones.size()); }
-      size_t rl_pixels = 0;
+      const ZoneLevel zl{rox, roy, hkx, hky, kx, ky, dw};
+      const int diff_ul[2] = {lr_ulx, lr_uly};
       for (SearchZone const& z : zones) {
-        const IBox lr(z.region.x0 + rox - hkx, z.region.y0 + roy - hky, z.region.x1 + rox + hkx, z.region.y1 + roy + hky);
-        const IBox rr(lr.x0 + z.range.x0, lr.y0 + z.range.y0, lr.x1 + z.range.x0 + z.range.dx(), lr.y1 + z.range.y0 + z.range.dy());
+        // the time budget (see above): a zone's L->R run and its R->L run are accounted one after the other, and either may end the list
+        IBox lr, rr;
+        vwgpu::zone_boxes(z, zl, &lr, &rr);
         const double next = P->seconds_per_op * ((double)lr.width() * lr.height() * z.range.width() * z.range.height());
         if (P->corr_timeout > 0 && estim + next > P->corr_timeout) break;
         estim += next;
         remeasure();
-        const int zw = z.region.dx(), zh = z.region.dy(), sx = z.range.dx(), sy = z.range.dy();
-        if (zw <= 0 || zh <= 0 || sx <= 0 || sy <= 0) continue;
-        if (zw > 65535 * 32 || zh > 65535 * 32) { ctx->forced_path = saved_force; return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "pyramid_correlate: zone too large"); }
-        vwgpu_zone_task a{lr.x0, lr.y0, rr.x0, rr.y0, zw, zh, sx, sy, z.region.y0 * dw + z.region.x0, dw,
-                          lr_active ? 0 : z.range.x0, lr_active ? 0 : z.range.y0};
-        t1.push_back(a);
-        if (lr_active) {
+        bool cut = false;
+        if (lr_active && !vwgpu::zone_is_empty(z)) {
           const double next2 = P->seconds_per_op * ((double)rr.width() * rr.height() * z.range.width() * z.range.height());
-          if (P->corr_timeout > 0 && estim + next2 > P->corr_timeout) break;
-          estim += next2;
-          const int rlw = rr.dx() - kx + 1, rlh = rr.dy() - ky + 1;
-          vwgpu_zone_task b{rr.x0, rr.y0, lr.x0 - sx, lr.y0 - sy, rlw, rlh, sx, sy, (int)rl_pixels, rlw, -sx, -sy};
-          t2.push_back(b);
-          // (sx, sy) slots of an lr task = the zone's origin in the lr_disp_diff image (ul_corner_offset, :683-687)
-          vwgpu_zone_task c{(int)rl_pixels, 0, rlw, rlh, zw, zh, z.region.x0 + lr_ulx, z.region.y0 + lr_uly, a.out_off, dw, z.range.x0, z.range.y0};
-          t3.push_back(c);
-          rl_pixels += (size_t)rlw * rlh;
-          if (rl_pixels > (size_t)INT32_MAX / 2) { ctx->forced_path = saved_force; return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "pyramid_correlate: tile too large for the L/R check buffers"); }
+          cut = P->corr_timeout > 0 && estim + next2 > P->corr_timeout;
+          if (!cut) estim += next2;
         }
+        const vwgpu::ZoneErr ze = vwgpu::zone_tasks(z, zl, lr_active, !cut, 0, 0, diff_ul, &zt);
+        if (ze) { ctx->forced_path = saved_force; return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "%s", zone_err_text(ze, false)); }
+        if (cut) break;
       }
+      const size_t rl_pixels = zt.rl;
       ctx->forced_path = saved_force;
       stamp("zone tables built", level);
-      bool exact = exact_level[level] != 0;
+      bool exact = cls[level].exact;
       for (vwgpu_zone_task const& z : t1) exact = exact && vwgpu_bm_exact_supported(z.sx, z.sy);
       if (ctx->trace & 2) {           // development aid: the shape of a level's work
         size_t px = 0, ev = 0; int maxd = 0, maxw = 0, maxh = 0;
@@ -989,34 +858,19 @@ int vwgpu_pyramid_correlate_impl(vwgpu_ctx* ctx, const float* left, int lw, int 
       // The exact-order launches behind a certified pass are queued only if some zone was flagged: the two directions' "any zone
       // flagged" words come back in one small copy (one more host round trip per certified level, hidden by the other tile threads;
       // twelve gated launches of ~6 us that find nothing to do are not — measured 0.25 ms of a 2 ms LoG + NCC tile).
-      struct Pending { const float* a; int aw, ah; const float* b; int bw, bh; const std::vector<vwgpu_zone_task>* tz; int32_t* dst; int* zflag; };
+      struct Pending { MatchPair m; const std::vector<vwgpu_zone_task>* tz; int32_t* dst; int* zflag; };
       std::vector<Pending> pending;
       int* d_any = nullptr;
       const unsigned char* need_cells = nullptr;
-      // The "cannot matter" certificate of the certified passes (bm_zones.hip, ZEdge) and its premises.  L->R: a mask pass follows the
-      // clean-up filter (both sit behind filter_half_kernel > 0, CorrelationView.cc:702-744) and erases a pixel that points outside the
-      // right image; the filters before it compare disparities within 3 px over +- half kernel, hence the margin; no lr_disp_diff image
-      // (its entries keep the discrepancy of pixels the filters removed).  R->L: read by the L/R check alone.
+      // the "cannot matter" certificate of the certified passes (pyramid_plan.h, edge_margins)
       const int edge_k = rox - hkx;
-      // Margin.  Last level: ONE filter pass (rm_outliers, hk x hk, 3 px) — a far pixel M must not be counted by a pixel that
-      // can survive the mask, i.e. |dx(M) - dx(N)| > 3 for every N within hk columns whose target lies inside: hk + 3 + 1.  Intermediate
-      // levels: disparity_cleanup_using_thresh is TWO passes (inner (hk, hk, 3, 0.5), then outer (1, 1, 3, 0.2) on the inner pass's output,
-      // DisparityMap.h:427-441): a kept pixel K (target inside) has an outer-pass neighbour N within 1 column and 3 px — N's target up to 4
-      // columns outside — whose inner-pass count sees M within hk columns and 3 px: M's target up to hk + 7 columns outside must still be
-      // treated as "can matter", so far starts at hk + 8.
-      const int edge_m_lr = (P->filter_half_kernel > 0 && !(last && lr_diff)) ? P->filter_half_kernel + (last ? 4 : 8) : 0;
-      const int edge_m_rl = (P->consistency_threshold >= 0 && P->consistency_threshold < 1e6) ? (int)std::floor(P->consistency_threshold) + 2 : 0;
-      // columns of the right mask of this level that can be non-zero: the part of the crop inside the right image, halved per level the way
-      // subsample_mask_by_two does (a column is kept when one of its two source columns is)
-      const int rv0 = std::max(0, -rmb.x0) >> level, rv1 = (std::min(rmp[0].w, rw - rmb.x0) + (1 << level) - 1) >> level;
-      const int lr_lo = rv0 - edge_m_lr + 1, lr_hi = rv1 + edge_m_lr - 2;
-      const int rl_lo = -edge_m_rl + 1, rl_hi = dw + edge_m_rl - 2;           // the left pixels of the check lie in the tile: [0, dw)
-      auto match = [&](const float* a, int aw_, int ah_, const float* b, int bw_, int bh_, std::vector<vwgpu_zone_task> const& tz, int32_t* dst,
-                       const int* need, int edge_m, int edge_lo, int edge_hi) -> int {
+      const EdgeMargins em = vwgpu::edge_margins(P, last, lr_diff != nullptr, level, rmb.x0, rmp[0].w, rw, dw);
+      const int cert_hi = cls[level].cert_hi;
+      auto match = [&](const MatchPair& m, std::vector<vwgpu_zone_task> const& tz, int32_t* dst, const int* need, int edge_m, int edge_lo, int edge_hi) -> int {
         if (tz.empty()) return VWGPU_OK;
-        if (!exact) return vwgpu_launch_bm_zones(ctx, P->cost_type, a, aw_, ah_, b, bw_, bh_, kx, ky, tz.data(), (int)tz.size(), dst, f32_level[level],
+        if (!exact) return vwgpu_launch_bm_zones(ctx, P->cost_type, m.a, m.aw, m.ah, m.b, m.bw, m.bh, kx, ky, tz.data(), (int)tz.size(), dst, cls[level].f32,
                                                  INT_MIN, nullptr, nullptr, nullptr, need, need ? need_cells : nullptr);
-        if (cert_hi[level] != INT_MIN) {
+        if (cert_hi != INT_MIN) {
           if (!d_any) {                                            // the two "any zone flagged" words and the zone flags of both passes: one block, one fill
             const size_t nflag = 64 + t1.size() + t2.size();
             d_any = A.take<int>(nflag);
@@ -1024,22 +878,23 @@ int vwgpu_pyramid_correlate_impl(vwgpu_ctx* ctx, const float* left, int lw, int 
             VWGPU_HIP(ctx, hipMemsetAsync(d_any, 0, nflag * sizeof(int), st));
           }
           int* zflag = d_any + 64 + (pending.empty() ? 0 : t1.size());
-          int rc2 = vwgpu_launch_bm_zones(ctx, P->cost_type, a, aw_, ah_, b, bw_, bh_, kx, ky, tz.data(), (int)tz.size(), dst, 0, cert_hi[level], zflag, d_cert_stats,
+          int rc2 = vwgpu_launch_bm_zones(ctx, P->cost_type, m.a, m.aw, m.ah, m.b, m.bw, m.bh, kx, ky, tz.data(), (int)tz.size(), dst, 0, cert_hi, zflag, d_cert_stats,
                                           d_any + pending.size(), need, need ? need_cells : nullptr, edge_m, edge_k, edge_lo, edge_hi);
           if (rc2) return rc2;
-          pending.push_back(Pending{a, aw_, ah_, b, bw_, bh_, &tz, dst, zflag});
+          pending.push_back(Pending{m, &tz, dst, zflag});
           return VWGPU_OK;
         }
-        return vwgpu_launch_bm_exact(ctx, P->cost_type, a, aw_, ah_, aw_, b, bw_, bh_, bw_, kx, ky, tz.data(), (int)tz.size(), dst);
+        return vwgpu_launch_bm_exact(ctx, P->cost_type, m.a, m.aw, m.ah, m.aw, m.b, m.bw, m.bh, m.bw, kx, ky, tz.data(), (int)tz.size(), dst);
       };
       int32_t* rlbuf = static_cast<int32_t*>(ctx->zrl.base);
-      if ((rc = match(Lv.p, Lv.w, Lv.h, Rv.p, Rv.w, Rv.h, t1, disp, nullptr, edge_m_lr, lr_lo, lr_hi))) return rc;
+      const MatchPair l2r{Lv.p, Lv.w, Lv.h, Rv.p, Rv.w, Rv.h}, r2l{Rv.p, Rv.w, Rv.h, Lv.p, Lv.w, Lv.h};
+      if ((rc = match(l2r, t1, disp, nullptr, em.m_lr, em.lr_lo, em.lr_hi))) return rc;
       if (lr_active && !t2.empty()) {
         // The R->L pass only has to cover what the L/R check will look at: the positions the L->R disparities point to — about the zone
         // itself instead of the zone widened by its search range (3x the pixels for a 16 x 16 leaf with 32 disparities).  Only where the
         // tile kernels match (their pixels are independent of each other); the exact-order kernels need the whole zone for their sums.
         int* need = nullptr;
-        if (!exact || cert_hi[level] != INT_MIN) {
+        if (!exact || cert_hi != INT_MIN) {
           const size_t ncells = vwgpu_zone_need_cells(t3.data(), (int)t3.size());
           need = A.take<int>(8 * t3.size() + (ncells + 16 + 3) / 4);      // records, then the cell flags: one block, one fill
           if (!need) return fail_mem();
@@ -1047,15 +902,13 @@ int vwgpu_pyramid_correlate_impl(vwgpu_ctx* ctx, const float* left, int lw, int 
           if ((rc = vwgpu_launch_zone_need(ctx, t3.data(), (int)t3.size(), disp, pending.empty() ? nullptr : pending[0].zflag, need, cells, ncells))) return rc;
           need_cells = cells;
         }
-        if ((rc = match(Rv.p, Rv.w, Rv.h, Lv.p, Lv.w, Lv.h, t2, rlbuf, need, edge_m_rl, rl_lo, rl_hi))) return rc;
+        if ((rc = match(r2l, t2, rlbuf, need, em.m_rl, em.rl_lo, em.rl_hi))) return rc;
       }
       if (!pending.empty()) {
         int any[2] = {0, 0};
         VWGPU_HIP(ctx, hipMemcpyAsync(any, d_any, sizeof any, hipMemcpyDeviceToHost, st));
         VWGPU_HIP(ctx, hipStreamSynchronize(st));
-        // The flagged zones of a pass as a list of their own (their flags come back in a second small copy, only when there are any): the
-        // exact-order launches are then sized by the flagged zones — gated launches over all 2000 zones of a border tile spent 0.1 ms
-        // each on workgroups that read a zero and left (18 launches, 2 ms for 3 % of the tile's pixels).
+        // the flags of a pass come back in a second small copy, only when there are any
         std::vector<int> hflag;
         for (size_t k = 0; k < pending.size(); ++k) {
           if (!any[k]) continue;
@@ -1063,19 +916,7 @@ int vwgpu_pyramid_correlate_impl(vwgpu_ctx* ctx, const float* left, int lw, int 
           hflag.resize(q.tz->size());
           VWGPU_HIP(ctx, hipMemcpyAsync(hflag.data(), q.zflag, hflag.size() * sizeof(int), hipMemcpyDeviceToHost, st));
           VWGPU_HIP(ctx, hipStreamSynchronize(st));
-          std::vector<vwgpu_zone_task> redo;
-          for (size_t i = 0; i < hflag.size(); ++i) if (hflag[i]) redo.push_back((*q.tz)[i]);
-          if (redo.empty()) continue;
-          if (ctx->trace & 4) {
-            size_t px = 0, ev = 0;
-            for (auto const& zt : redo) { px += (size_t)zt.zw * zt.zh; ev += (size_t)zt.zw * zt.zh * zt.sx * zt.sy; }
-            fprintf(stderr, "  level %d pass %zu: %zu of %zu zones to the exact-order kernels, %zu px, %zu evaluations; largest:", level, k, redo.size(), q.tz->size(), px, ev);
-            std::vector<vwgpu_zone_task> big(redo);
-            std::sort(big.begin(), big.end(), [](vwgpu_zone_task const& a2, vwgpu_zone_task const& b2) { return (size_t)a2.zw * a2.zh * a2.sx * a2.sy > (size_t)b2.zw * b2.zh * b2.sx * b2.sy; });
-            for (size_t i = 0; i < std::min<size_t>(4, big.size()); ++i) fprintf(stderr, " %dx%d x %dx%d", big[i].zw, big[i].zh, big[i].sx, big[i].sy);
-            fprintf(stderr, "\n");
-          }
-          if ((rc = vwgpu_launch_bm_exact(ctx, P->cost_type, q.a, q.aw, q.ah, q.aw, q.b, q.bw, q.bh, q.bw, kx, ky, redo.data(), (int)redo.size(), q.dst))) return rc;
+          if ((rc = redo_flagged_zones(ctx, P, q.m, *q.tz, hflag.data(), -1, q.dst, level, k))) return rc;
         }
       }
       if (lr_active && (rc = vwgpu_launch_zone_lr(ctx, t3.data(), (int)t3.size(), disp, rlbuf, P->consistency_threshold, lr_diff, lr_stride))) return rc;
@@ -1166,53 +1007,15 @@ int vwgpu_pyramid_correlate_impl(vwgpu_ctx* ctx, const float* left, int lw, int 
     }
     // zone refinement (:754-799): the scheduler is data dependent host logic
     if (!last && !use_sgm) {
-      // The quad tree of boxes is fixed by (dw, dh): its leaves are measured on the device (box + 1-px neighbourhood),
-      // only that table comes back, and the accept / retry / merge recursion runs on it (zones.hip).
-      const std::vector<vwgpu::IBox>& leaves = vwgpu::cached_leaves(dw, dh);
-      const size_t nleaf = leaves.size();
-      static_assert(sizeof(vwgpu::IBox) == sizeof(int4), "leaf boxes upload as int4");
-      // the leaf boxes of a level size go to the device once per context
-      int4* d_rects = nullptr;
-      for (auto& lr : ctx->leaf_rects)
-        if (lr.w == dw && lr.h == dh && lr.n == nleaf) d_rects = static_cast<int4*>(lr.d_rects);
-      if (!d_rects) {
-        void* p = nullptr;
-        VWGPU_HIP(ctx, hipMalloc(&p, std::max<size_t>(nleaf, 1) * sizeof(int4)));
-        VWGPU_HIP(ctx, hipMemcpyAsync(p, leaves.data(), nleaf * sizeof(int4), hipMemcpyHostToDevice, st));
-        VWGPU_HIP(ctx, hipStreamSynchronize(st));                 // the host list may be evicted from its cache later
-        if (ctx->leaf_rects.size() >= 64) { (void)hipFree(ctx->leaf_rects.front().d_rects); ctx->leaf_rects.erase(ctx->leaf_rects.begin()); }
-        ctx->leaf_rects.push_back({dw, dh, nleaf, p});
-        d_rects = static_cast<int4*>(p);
-      }
-      const size_t ext_bytes = nleaf * sizeof(vwgpu::LeafExtent);
-      if ((rc = vwgpu_arena_reserve(ctx, &ctx->zext, ext_bytes + 256))) return rc;
-      int32_t* d_ext = static_cast<int32_t*>(ctx->zext.base);
-      {
-        vwgpu_prof_scope ps(ctx, "zone_extents");
-        if (fused_extents)
-          hipLaunchKernelGGL(zone_extent_fused_kernel, dim3((unsigned)nleaf), dim3(64), 0, st, padded, dw, dh, lmp[level].p, rmp[level].p, rmp[level].w, rmp[level].h,
-                             d_rects, (int)nleaf, d_ext);
-        else
-          hipLaunchKernelGGL(zone_extent_kernel, dim3((unsigned)nleaf), dim3(64), 0, st, disp, dw, dh, d_rects, (int)nleaf, d_ext);
-      }
-      const vwgpu::LeafExtent* h_ext = static_cast<const vwgpu::LeafExtent*>(vwgpu_host_ring(ctx, ext_bytes));
-      if (!h_ext) { leaf_ext.resize(nleaf); h_ext = leaf_ext.data(); }
-      VWGPU_HIP(ctx, hipMemcpyAsync(const_cast<vwgpu::LeafExtent*>(h_ext), d_ext, ext_bytes, hipMemcpyDeviceToHost, st));
-      stamp("level queued, waiting", level);
-      VWGPU_HIP(ctx, hipStreamSynchronize(st));
-      stamp("leaf extents on the host", level);
+      // the accept / retry / merge recursion runs on the leaf table the device measured (zones.hip)
+      const vwgpu::LeafExtent* h_ext = nullptr;
+      size_t nleaf = 0;
+      if ((rc = read_leaf_extents(ctx, 1, fused_extents, fused_extents ? padded : disp, 0, dw, dh, lmp[level].p, rmp[level].p, 0, rmp[level].w, rmp[level].h,
+                                  stamp, level, &leaf_ext, &h_ext, &nleaf))) return rc;
       zones.clear();
       vwgpu::subdivide_regions_from_leaves(dw, dh, kx, ky, h_ext, nleaf, zones);
-      const IBox scale_search(0, 0, rp[level - 1].w - lp[level - 1].w, rp[level - 1].h - lp[level - 1].h);
-      const IBox next_size(0, 0, lmp[level - 1].w, lmp[level - 1].h);
-      for (SearchZone& z : zones) {
-        z.region.scale(2);
-        z.region.clip(next_size);
-        z.range.scale(2);
-        z.range.expand(2);
-        z.range.clip(scale_search);
-        if (z.range.empty()) z.range = IBox(0, 0, search.width(), search.height());
-      }
+      vwgpu::rescale_zones(zones, IBox(0, 0, lmp[level - 1].w, lmp[level - 1].h),
+                           IBox(0, 0, rp[level - 1].w - lp[level - 1].w, rp[level - 1].h - lp[level - 1].h), search);
       stamp("zones of the next level ready", level);
     }
   }
@@ -1225,95 +1028,7 @@ int vwgpu_pyramid_correlate_impl(vwgpu_ctx* ctx, const float* left, int lw, int 
   else
     hipLaunchKernelGGL(finish_kernel, grid2(bw, bh), kBlk, 0, st, disp, bw, bh, search.x0, search.y0, out, os);
   VWGPU_HIP(ctx, hipGetLastError());
-  if (d_cert_stats) {
-    unsigned long long got[4] = {0, 0, 0, 0};
-    VWGPU_HIP(ctx, hipMemcpyAsync(got, d_cert_stats, sizeof got, hipMemcpyDeviceToHost, st));
-    VWGPU_HIP(ctx, hipStreamSynchronize(st));
-    ctx->cert_px[0] += got[0]; ctx->cert_px[1] += got[1]; ctx->cert_px[2] += got[2];
-    fprintf(stderr, "certification: %llu pixels in certified tiles, %llu in tiles that sent their zone to the exact-order kernels (%.2f %%); %llu in tiles "
-            "the fp32 tier passed on to float64 (%.2f %%)\n",
-            got[0], got[1], got[0] + got[1] ? 100.0 * (double)got[1] / (double)(got[0] + got[1]) : 0.0, got[2],
-            got[0] + got[1] ? 100.0 * (double)got[2] / (double)(got[0] + got[1]) : 0.0);
-  }
-  return VWGPU_OK;
-}
-
-// ---- helper threads of a context ----------------------------------------------------------------------------------------
-// The host side of a tile group is per-tile work on tables the device sent back (the zone scheduler's accept / retry / merge walk, the zone
-// task lists of the next level: ~30 000 zones for 16 tiles at level 0, milliseconds on one thread with the device idle).  A context keeps a
-// few helper threads for it: persistent (the zone scheduler caches its trees per thread), parked on a condition variable between jobs.
-namespace {
-struct HostPool {
-  std::vector<std::thread> workers;
-  std::mutex m;
-  std::condition_variable wake, done;
-  void (*fn)(void*, int) = nullptr;
-  void* arg = nullptr;
-  int n = 0;
-  std::atomic<int> next{0};
-  int running = 0;                   // workers still inside the current job
-  unsigned long long job = 0;        // generation counter
-  bool quit = false;
-  void work() {
-    for (;;) {
-      const int i = next.fetch_add(1);
-      if (i >= n) return;
-      fn(arg, i);
-    }
-  }
-  void loop() {
-    unsigned long long seen = 0;
-    for (;;) {
-      {
-        std::unique_lock<std::mutex> lk(m);
-        wake.wait(lk, [&] { return quit || job != seen; });
-        if (quit) return;
-        seen = job;
-      }
-      work();
-      {
-        std::lock_guard<std::mutex> lk(m);
-        if (--running == 0) done.notify_one();
-      }
-    }
-  }
-};
-}  // namespace
-
-void vwgpu_pool_run(vwgpu_ctx* ctx, int n, void (*fn)(void*, int), void* arg) {
-  if (n <= 0) return;
-  HostPool* P = static_cast<HostPool*>(ctx->host_pool);
-  if (!P && n >= 4) {
-    P = new HostPool();
-    const unsigned hc = std::thread::hardware_concurrency();
-    const int nw = hc >= 32 ? 7 : (hc >= 8 ? 3 : 0);               // + the calling thread
-    for (int i = 0; i < nw; ++i) P->workers.emplace_back([P] { P->loop(); });
-    ctx->host_pool = P;
-  }
-  if (!P || P->workers.empty() || n < 4) { for (int i = 0; i < n; ++i) fn(arg, i); return; }
-  {
-    std::lock_guard<std::mutex> lk(P->m);
-    P->fn = fn; P->arg = arg; P->n = n; P->next.store(0);
-    P->running = (int)P->workers.size();
-    ++P->job;
-  }
-  P->wake.notify_all();
-  P->work();
-  std::unique_lock<std::mutex> lk(P->m);
-  P->done.wait(lk, [&] { return P->running == 0; });
-}
-
-void vwgpu_pool_destroy(vwgpu_ctx* ctx) {
-  HostPool* P = static_cast<HostPool*>(ctx->host_pool);
-  if (!P) return;
-  {
-    std::lock_guard<std::mutex> lk(P->m);
-    P->quit = true;
-  }
-  P->wake.notify_all();
-  for (std::thread& t : P->workers) t.join();
-  delete P;
-  ctx->host_pool = nullptr;
+  return read_cert_stats(ctx, d_cert_stats, true);
 }
 
 // ---- tile groups (round 5) ------------------------------------------------------------------------------------------
@@ -1327,25 +1042,6 @@ void vwgpu_pool_destroy(vwgpu_ctx* ctx) {
 // Every tile's result is what vwgpu_pyramid_correlate_impl computes for it alone: same kernels, same arithmetic, same zone lists — the tiles
 // never read each other's data.  Eligible: block matching without an lr_disp_diff image, blob filter or time budget; anything else runs
 // tile by tile through vwgpu_pyramid_correlate_impl.
-namespace {
-
-struct GroupLayout {                       // offsets (bytes) inside a tile's slice of the arena; sizes per level
-  std::vector<size_t> lp, rp, lpf, rpf, lmp, rmp;
-  std::vector<int> lpw, lph, rpw, rph, lmw, lmh, rmw, rmh;
-  size_t lmx = 0, rmx = 0, d_acc = 0, d_part = 0, d_cell = 0, d_cells = 0, disp = 0, disp2 = 0, padded = 0;
-  size_t slice = 0;
-};
-
-struct GroupTile {
-  IBox bbox, lg, rg, rmb;
-  bool alive = true;                       // false: a fully masked image (the tile is zeros, CorrelationView.cc:318-327)
-  std::vector<SearchZone> zones;
-  std::vector<char> exact_level, f32_level;
-  std::vector<int> cert_hi;
-};
-
-}  // namespace
-
 namespace {
 template <class F> void pool_for(vwgpu_ctx* ctx, int n, F& f) {
   vwgpu_pool_run(ctx, n, [](void* a, int i) { (*static_cast<F*>(a))(i); }, &f);
@@ -1368,193 +1064,28 @@ int vwgpu_pyramid_group_impl(vwgpu_ctx* ctx, const float* left, int lw, int lh, 
   const int kx = P->kernel_x, ky = P->kernel_y;
   const IBox search(P->search_min_x, P->search_min_y, P->search_max_x, P->search_max_y);
   hipStream_t st = ctx->stream;
-  // number of levels (CorrelationView.h:99-105, CorrelationView.cc:301-310): the same for every tile of the group
-  const int largest_search = std::max(search.dx(), search.dy());
-  int by_search = (int)(std::floor(std::log(float(largest_search)) / std::log(2.0f)) - 1);
-  by_search = std::max(0, std::min(by_search, P->max_pyramid_levels));
-  int L = (int)std::floor(std::log((double)std::min(bw, bh)) / std::log(2.0f) - std::log((double)std::max(kx, ky)) / std::log(2.0f));
-  L = std::min(L, by_search);
-  if (L < 1) L = 0;
+  // levels, geometry and slice layout: the same for every tile of the group but for the tile's place in the images
+  const int L = vwgpu::pyramid_levels(P, bw, bh);
   const int hkx = kx / 2, hky = ky / 2, up = 1 << L;
   const bool filtered = P->prefilter_mode == VWGPU_PREFILTER_LOG || P->prefilter_mode == VWGPU_PREFILTER_MEANSUB;
-  constexpr int CS = 16, NB = 256;
-
-  const auto t_start = std::chrono::steady_clock::now();
-  const bool dbg_time = (ctx->trace & 1) != 0;     // development aid: host-side timeline of a group on stderr
-  auto stamp = [&](const char* what, int level) {
-    if (dbg_time) fprintf(stderr, "  [%8.1f us] group of %d, level %d: %s\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count(), n, level, what);
-  };
-  std::vector<GroupTile> T((size_t)n);
-  for (int t = 0; t < n; ++t) {
-    GroupTile& g = T[t];
-    g.bbox = IBox(bxs[t], bys[t], bxs[t] + bw, bys[t] + bh);
-    g.lg = g.bbox; g.lg.x0 -= hkx * up; g.lg.x1 += hkx * up; g.lg.y0 -= hky * up; g.lg.y1 += hky * up;
-    g.rg = IBox(g.lg.x0 + search.x0, g.lg.y0 + search.y0, g.lg.x1 + search.x0 + search.dx(), g.lg.y1 + search.y0 + search.dy());
-    g.rmb = IBox(g.bbox.x0 + search.x0, g.bbox.y0 + search.y0, g.bbox.x1 + search.x0 + search.dx(), g.bbox.y1 + search.y0 + search.dy());
-    g.exact_level.assign(L + 1, 0); g.f32_level.assign(L + 1, 0); g.cert_hi.assign(L + 1, INT_MIN);
-  }
-  // the layout of a tile's slice: the geometry of tile 0 is every tile's
-  GroupLayout Y;
-  {
-    Bump A{nullptr, SIZE_MAX};
-    auto off = [&](void* p) { return (size_t)reinterpret_cast<uintptr_t>(p); };
-    const IBox &lg = T[0].lg, &rg = T[0].rg, &rmb = T[0].rmb;
-    Y.lp.resize(L + 1); Y.rp.resize(L + 1); Y.lpf.resize(L + 1); Y.rpf.resize(L + 1); Y.lmp.resize(L + 1); Y.rmp.resize(L + 1);
-    Y.lpw.resize(L + 1); Y.lph.resize(L + 1); Y.rpw.resize(L + 1); Y.rph.resize(L + 1); Y.lmw.resize(L + 1); Y.lmh.resize(L + 1); Y.rmw.resize(L + 1); Y.rmh.resize(L + 1);
-    Y.lpw[0] = lg.dx(); Y.lph[0] = lg.dy(); Y.rpw[0] = rg.dx(); Y.rph[0] = rg.dy();
-    Y.lmw[0] = bw; Y.lmh[0] = bh; Y.rmw[0] = rmb.dx(); Y.rmh[0] = rmb.dy();
-    const size_t nl = (size_t)lg.dx() * lg.dy(), nr = (size_t)rg.dx() * rg.dy();
-    A.take<char>(256);                                            // (offset 0 stays unused: a null offset means "not there")
-    Y.lp[0] = off(A.take<float>(nl)); Y.rp[0] = off(A.take<float>(nr));
-    Y.lmx = off(A.take<uint8_t>(nl)); Y.rmx = off(A.take<uint8_t>(nr));
-    Y.lmp[0] = off(A.take<uint8_t>((size_t)bw * bh)); Y.rmp[0] = off(A.take<uint8_t>((size_t)rmb.dx() * rmb.dy()));
-    Y.d_acc = off(A.take<double>(4)); Y.d_part = off(A.take<double>(2 * 2 * NB)); Y.d_cell = off(A.take<int>(8));
-    for (int i = 1; i <= L; ++i) {
-      Y.lpw[i] = 1 + (Y.lpw[i - 1] - 1) / 2; Y.lph[i] = 1 + (Y.lph[i - 1] - 1) / 2; Y.rpw[i] = 1 + (Y.rpw[i - 1] - 1) / 2; Y.rph[i] = 1 + (Y.rph[i - 1] - 1) / 2;
-      Y.lmw[i] = 1 + (Y.lmw[i - 1] - 1) / 2; Y.lmh[i] = 1 + (Y.lmh[i - 1] - 1) / 2; Y.rmw[i] = 1 + (Y.rmw[i - 1] - 1) / 2; Y.rmh[i] = 1 + (Y.rmh[i - 1] - 1) / 2;
-      Y.lp[i] = off(A.take<float>((size_t)Y.lpw[i] * Y.lph[i])); Y.rp[i] = off(A.take<float>((size_t)Y.rpw[i] * Y.rph[i]));
-      Y.lmp[i] = off(A.take<uint8_t>((size_t)Y.lmw[i] * Y.lmh[i])); Y.rmp[i] = off(A.take<uint8_t>((size_t)Y.rmw[i] * Y.rmh[i]));
-    }
-    for (int i = 0; i <= L; ++i) {
-      Y.lpf[i] = filtered ? off(A.take<float>((size_t)Y.lpw[i] * Y.lph[i])) : Y.lp[i];
-      Y.rpf[i] = filtered ? off(A.take<float>((size_t)Y.rpw[i] * Y.rph[i])) : Y.rp[i];
-    }
-    Y.d_cells = off(A.take<int>(CS * (size_t)(L + 1)));
-    Y.disp = off(A.take<int32_t>((size_t)bw * bh * 3)); Y.disp2 = off(A.take<int32_t>((size_t)bw * bh * 3));
-    Y.padded = off(A.take<int32_t>((size_t)(bw + 2) * (bh + 2) * 3));
-    Y.slice = vwgpu_align_up(A.off + 256, 768);                  // a multiple of 12 (a disparity pixel), of 8 and of 256
-  }
+  const Stamp stamp{(ctx->trace & 1) != 0, n};
+  TileGeom G[VWGPU_MAX_GROUP];
+  for (int t = 0; t < n; ++t) G[t] = vwgpu::tile_geom(bxs[t], bys[t], bw, bh, search, hkx, hky, up);
+  const PyrLayout Y = vwgpu::pyr_layout(G[0], L, filtered);
   // group-level tables behind the slices: the certified passes' flag words, the R->L need records and cells (bounds as in the single-tile arena)
   const size_t tables = (size_t)n * ((size_t)(L + 1) * ((size_t)bw * bh / 64 + 64) * (48 + (size_t)(search.dx() / 16 + 3) * (search.dy() / 16 + 3)) + 8192) + (1 << 16);
   int rc = vwgpu_arena_reserve(ctx, &ctx->pyr, (size_t)n * Y.slice + tables);
   if (rc) return rc;
-  char* base = static_cast<char*>(ctx->pyr.base);
-  Bump GA{base + (size_t)n * Y.slice, tables};
+  const Slices S{static_cast<char*>(ctx->pyr.base), Y.slice};
+  Bump GA{S.base + (size_t)n * Y.slice, tables};
   auto fail_mem = [&]() { return vwgpu_fail(ctx, VWGPU_ERR_LOGIC, "pyramid_correlate (group): internal arena too small"); };
-  auto at = [&](int t, size_t off) -> char* { return base + (size_t)t * Y.slice + off; };
-  auto fimg = [&](int t, size_t off) { return reinterpret_cast<float*>(at(t, off)); };
-  auto bimg = [&](int t, size_t off) { return reinterpret_cast<uint8_t*>(at(t, off)); };
   const size_t slice_f = Y.slice / 4, slice_i = Y.slice / 4, slice_px = Y.slice / 12;
 
-  // ---- base crops, nodata mean fill (CorrelationView.cc:67-149) ----
-  for (int t = 0; t < n; ++t) {
-    const GroupTile& g = T[t];
-    vwgpu_prof_scope ps(ctx, "pyramid_base_crops");
-    CropJobs cj;
-    cj.j[0] = CropJob{left, ls, lw, lh, g.lg.x0, g.lg.y0, fimg(t, Y.lp[0]), Y.lpw[0], Y.lph[0], 1, 0};
-    cj.j[1] = CropJob{right, rs, rw, rh, g.rg.x0, g.rg.y0, fimg(t, Y.rp[0]), Y.rpw[0], Y.rph[0], 1, 0};
-    cj.j[2] = CropJob{lmask, lms, lw, lh, g.lg.x0, g.lg.y0, bimg(t, Y.lmx), Y.lpw[0], Y.lph[0], 0, 0};
-    cj.j[3] = CropJob{rmask, rms, rw, rh, g.rg.x0, g.rg.y0, bimg(t, Y.rmx), Y.rpw[0], Y.rph[0], 0, 0};
-    cj.j[4] = CropJob{lmask, lms, lw, lh, g.bbox.x0, g.bbox.y0, bimg(t, Y.lmp[0]), bw, bh, 0, 1};
-    cj.j[5] = CropJob{rmask, rms, rw, rh, g.rmb.x0, g.rmb.y0, bimg(t, Y.rmp[0]), Y.rmw[0], Y.rmh[0], 0, 1};
-    const int cmw = std::max(std::max(Y.lpw[0], Y.rpw[0]), std::max(bw, Y.rmw[0])), cmh = std::max(std::max(Y.lph[0], Y.rph[0]), std::max(bh, Y.rmh[0]));
-    hipLaunchKernelGGL(crop_jobs_kernel, dim3((cmw + 63) / 64, (cmh + 3) / 4, 6), kBlk, 0, st, cj);
-  }
-  const bool l_all = !lmask, r_all = !rmask;
-  const size_t nl = (size_t)Y.lpw[0] * Y.lph[0], nr = (size_t)Y.rpw[0] * Y.rph[0];
-  if (!(l_all && r_all)) {
-    // the reductions of every tile are queued, ONE synchronisation brings all partial sums back (pinned ring; the pageable fallback waits per copy)
-    std::vector<double> part((size_t)n * 4 * NB);
-    std::vector<int> cell((size_t)n * 8);
-    const int init[8] = {INT_MAX, INT_MIN, 0, 0, INT_MAX, INT_MIN, 0, 0};
-    for (int t = 0; t < n; ++t) {
-      double* d_part = reinterpret_cast<double*>(at(t, Y.d_part));
-      int* d_cell = reinterpret_cast<int*>(at(t, Y.d_cell));
-      VWGPU_HIP(ctx, hipMemcpyAsync(d_cell, init, sizeof init, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(masked_mean_kernel, dim3(16, 16), kBlk, 0, st, fimg(t, Y.lp[0]), bimg(t, Y.lmx), Y.lpw[0], Y.lph[0], d_part, d_cell);
-      hipLaunchKernelGGL(masked_mean_kernel, dim3(16, 16), kBlk, 0, st, fimg(t, Y.rp[0]), bimg(t, Y.rmx), Y.rpw[0], Y.rph[0], d_part + 2 * NB, d_cell + 4);
-      VWGPU_HIP(ctx, hipMemcpyAsync(part.data() + (size_t)t * 4 * NB, d_part, 4 * NB * sizeof(double), hipMemcpyDeviceToHost, st));
-      VWGPU_HIP(ctx, hipMemcpyAsync(cell.data() + (size_t)t * 8, d_cell, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
-    }
-    VWGPU_HIP(ctx, hipStreamSynchronize(st));
-    std::vector<double> acc((size_t)n * 4, 0.0);
-    std::vector<char> serial((size_t)n * 2, 0);
-    bool any_serial = false;
-    for (int t = 0; t < n; ++t)
-      for (int im = 0; im < 2; ++im) {
-        double s_ = 0.0, n_ = 0.0;
-        for (int b = 0; b < NB; ++b) { s_ += part[(size_t)t * 4 * NB + (im * NB + b) * 2]; n_ += part[(size_t)t * 4 * NB + (im * NB + b) * 2 + 1]; }
-        acc[t * 4 + 2 * im] = s_; acc[t * 4 + 2 * im + 1] = n_;
-        const int lo = cell[t * 8 + 4 * im], hi = cell[t * 8 + 4 * im + 1];
-        int lgn = 0;
-        while ((1LL << lgn) < (long long)n_ + 1) ++lgn;
-        serial[t * 2 + im] = cell[t * 8 + 4 * im + 2] != 0 || (lo != INT_MAX && (long long)hi + 1 + lgn - lo > 53);
-        any_serial = any_serial || serial[t * 2 + im];
-      }
-    if (any_serial) {
-      std::vector<double> got((size_t)n * 4, 0.0);
-      for (int t = 0; t < n; ++t) {
-        double* d_acc = reinterpret_cast<double*>(at(t, Y.d_acc));
-        if (serial[t * 2]) hipLaunchKernelGGL(masked_mean_serial_kernel, dim3(1), dim3(64), 0, st, fimg(t, Y.lp[0]), bimg(t, Y.lmx), Y.lpw[0], Y.lph[0], d_acc);
-        if (serial[t * 2 + 1]) hipLaunchKernelGGL(masked_mean_serial_kernel, dim3(1), dim3(64), 0, st, fimg(t, Y.rp[0]), bimg(t, Y.rmx), Y.rpw[0], Y.rph[0], d_acc + 2);
-        if (serial[t * 2] || serial[t * 2 + 1]) VWGPU_HIP(ctx, hipMemcpyAsync(got.data() + (size_t)t * 4, d_acc, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-      }
-      VWGPU_HIP(ctx, hipStreamSynchronize(st));
-      for (int t = 0; t < n; ++t) {
-        if (serial[t * 2]) { acc[t * 4] = got[t * 4]; acc[t * 4 + 1] = got[t * 4 + 1]; }
-        if (serial[t * 2 + 1]) { acc[t * 4 + 2] = got[t * 4 + 2]; acc[t * 4 + 3] = got[t * 4 + 3]; }
-      }
-    }
-    for (int t = 0; t < n; ++t) {
-      // (without a mask an image's crop mask is all valid: its mean is not needed, as in the single-tile path)
-      if ((!l_all && acc[t * 4 + 1] == 0.0) || (!r_all && acc[t * 4 + 3] == 0.0)) { T[t].alive = false; continue; }
-      if (!l_all) hipLaunchKernelGGL(fill_masked_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st, fimg(t, Y.lp[0]), bimg(t, Y.lmx), nl, (float)(acc[t * 4] / acc[t * 4 + 1]));
-      if (!r_all) hipLaunchKernelGGL(fill_masked_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st, fimg(t, Y.rp[0]), bimg(t, Y.rmx), nr, (float)(acc[t * 4 + 2] / acc[t * 4 + 3]));
-    }
-  }
-  // ---- smoothing + decimation chain, mask decimation (:205-216): the four jobs of every tile of a level, VWGPU_MAX_IMG_JOBS per launch ----
-  const float k5[5] = {(float)(1.0 / 16.0), (float)(4.0 / 16.0), (float)(6.0 / 16.0), (float)(4.0 / 16.0), (float)(1.0 / 16.0)};
-  for (int i = 1; i <= L; ++i) {
-    std::vector<vwgpu_img_job> jobs;
-    for (int t = 0; t < n; ++t) {
-      jobs.push_back({fimg(t, Y.lp[i - 1]), Y.lpw[i - 1], Y.lpw[i - 1], Y.lph[i - 1], fimg(t, Y.lp[i]), Y.lpw[i], Y.lpw[i], Y.lph[i], 0, 0, nullptr, 0});
-      jobs.push_back({fimg(t, Y.rp[i - 1]), Y.rpw[i - 1], Y.rpw[i - 1], Y.rph[i - 1], fimg(t, Y.rp[i]), Y.rpw[i], Y.rpw[i], Y.rph[i], 0, 0, nullptr, 0});
-      jobs.push_back({bimg(t, Y.lmp[i - 1]), Y.lmw[i - 1], Y.lmw[i - 1], Y.lmh[i - 1], bimg(t, Y.lmp[i]), Y.lmw[i], Y.lmw[i], Y.lmh[i], 0, 0, nullptr, VWGPU_JOB_MASK_BY_TWO});
-      jobs.push_back({bimg(t, Y.rmp[i - 1]), Y.rmw[i - 1], Y.rmw[i - 1], Y.rmh[i - 1], bimg(t, Y.rmp[i]), Y.rmw[i], Y.rmw[i], Y.rmh[i], 0, 0, nullptr, VWGPU_JOB_MASK_BY_TWO});
-    }
-    for (size_t j0 = 0; j0 < jobs.size(); j0 += VWGPU_MAX_IMG_JOBS)
-      if ((rc = vwgpu_launch_sepconv_jobs(ctx, jobs.data() + j0, (int)std::min<size_t>(VWGPU_MAX_IMG_JOBS, jobs.size() - j0), k5, 5, 2, k5, 5, 2, 0, 2))) return rc;
-  }
-  // ---- prefilter every level into copies (:232-236), level by level so that a launch holds images of one size ----
-  if (filtered) {
-    std::vector<const float*> fs; std::vector<float*> fd; std::vector<int> fw, fh;
-    for (int i = 0; i <= L; ++i)
-      for (int t = 0; t < n; ++t) {
-        fs.push_back(fimg(t, Y.lp[i])); fd.push_back(fimg(t, Y.lpf[i])); fw.push_back(Y.lpw[i]); fh.push_back(Y.lph[i]);
-        fs.push_back(fimg(t, Y.rp[i])); fd.push_back(fimg(t, Y.rpf[i])); fw.push_back(Y.rpw[i]); fh.push_back(Y.rph[i]);
-      }
-    if ((rc = vwgpu_prefilter_images_dev(ctx, (int)fs.size(), fs.data(), fw.data(), fh.data(), P->prefilter_mode, P->prefilter_width, fd.data()))) return rc;
-  }
-  // ---- class of every level of every tile: ONE read-back for the group ----
-  {
-    std::vector<int> cells((size_t)n * CS * (L + 1), 0);
-    for (int t = 0; t < n; ++t)
-      for (int i = 0; i <= L; ++i) { int* c = cells.data() + ((size_t)t * (L + 1) + i) * CS; c[0] = INT_MAX; c[1] = INT_MIN; }
-    std::vector<const float*> gi; std::vector<int> gw, gh; std::vector<ptrdiff_t> gs; std::vector<int*> gc;
-    for (int t = 0; t < n; ++t) {
-      int* d_cells = reinterpret_cast<int*>(at(t, Y.d_cells));
-      VWGPU_HIP(ctx, hipMemcpyAsync(d_cells, cells.data() + (size_t)t * (L + 1) * CS, (size_t)(L + 1) * CS * sizeof(int), hipMemcpyHostToDevice, st));
-    }
-    for (int i = 0; i <= L; ++i)
-      for (int t = 0; t < n; ++t) {
-        int* d_cells = reinterpret_cast<int*>(at(t, Y.d_cells));
-        gi.push_back(fimg(t, Y.lpf[i])); gw.push_back(Y.lpw[i]); gh.push_back(Y.lph[i]); gs.push_back(Y.lpw[i]); gc.push_back(d_cells + CS * i);
-        gi.push_back(fimg(t, Y.rpf[i])); gw.push_back(Y.rpw[i]); gh.push_back(Y.rph[i]); gs.push_back(Y.rpw[i]); gc.push_back(d_cells + CS * i);
-      }
-    vwgpu_launch_float_grain(ctx, (int)gi.size(), gi.data(), gw.data(), gh.data(), gs.data(), gc.data());
-    for (int t = 0; t < n; ++t)
-      VWGPU_HIP(ctx, hipMemcpyAsync(cells.data() + (size_t)t * (L + 1) * CS, at(t, Y.d_cells), (size_t)(L + 1) * CS * sizeof(int), hipMemcpyDeviceToHost, st));
-    stamp("pyramids queued, waiting for the level classes", L);
-    VWGPU_HIP(ctx, hipStreamSynchronize(st));
-    stamp("level classes on the host", L);
-    for (int t = 0; t < n; ++t)
-      for (int i = 0; i <= L; ++i) {
-        const int* c = cells.data() + ((size_t)t * (L + 1) + i) * CS;
-        T[t].exact_level[i] = !vwgpu_sums_order_free(P->cost_type, kx, ky, c[0], c[1], c[2]);
-        T[t].f32_level[i] = vwgpu_sums_bits(P->cost_type, kx, ky, c[0], c[1], c[2]) <= 24;
-        if (T[t].exact_level[i] && ctx->certify && (c[2] & 1) == 0 && c[0] != INT_MAX && c[1] < 60 && c[1] > -60) T[t].cert_hi[i] = c[1];
-      }
-  }
+  bool alive[VWGPU_MAX_GROUP];             // false: a fully masked image (the tile is zeros, CorrelationView.cc:318-327)
+  std::vector<LevelClass> cls((size_t)n * (L + 1));
+  const PyrSource src{left, lw, lh, ls, right, rw, rh, rs, lmask, lms, rmask, rms};
+  if ((rc = build_pyramids(ctx, src, P, n, G, Y, S, true, false, &stamp, alive, cls.data()))) return rc;
+  std::vector<SearchZone> zones[VWGPU_MAX_GROUP];
   unsigned long long* d_cert_stats = nullptr;
   if (ctx->trace & 4) {
     d_cert_stats = GA.take<unsigned long long>(4);
@@ -1562,7 +1093,7 @@ int vwgpu_pyramid_group_impl(vwgpu_ctx* ctx, const float* left, int lw, int lh, 
     VWGPU_HIP(ctx, hipMemsetAsync(d_cert_stats, 0, 32, st));
   }
   for (int t = 0; t < n; ++t)
-    if (T[t].alive) T[t].zones.push_back(SearchZone{IBox(0, 0, Y.lmw[L], Y.lmh[L]), IBox(0, 0, search.width() / up + 1, search.height() / up + 1)});
+    if (alive[t]) zones[t].push_back(SearchZone{IBox(0, 0, Y.lmw[L], Y.lmh[L]), IBox(0, 0, search.width() / up + 1, search.height() / up + 1)});
 
   // ---- level loop ----
   size_t disp_off = Y.disp, disp2_off = Y.disp2;                   // (the two disparity buffers of every tile swap together)
@@ -1574,66 +1105,49 @@ int vwgpu_pyramid_group_impl(vwgpu_ctx* ctx, const float* left, int lw, int lh, 
     {
       const size_t words = ((size_t)dw * dh * 12 + 15) / 16;      // (the buffers are 256-byte aligned and sized for the largest level; rounding up stays inside)
       hipLaunchKernelGGL(zero_tiles_kernel, dim3((unsigned)std::min<size_t>(512, (words + 255) / 256), (unsigned)n), dim3(256), 0, st,
-                         reinterpret_cast<uint4*>(at(0, disp_off)), Y.slice / 16, words);
+                         reinterpret_cast<uint4*>(S.at(0, disp_off)), Y.slice / 16, words);
     }
-    int32_t* disp0 = reinterpret_cast<int32_t*>(at(0, disp_off));
+    int32_t* disp0 = S.i(0, disp_off);
     const int rox = up * hkx / scaling, roy = up * hky / scaling;
     const bool lr_active = P->consistency_threshold >= 0 && last;
     const int aw_ = Y.lpw[level], ah_ = Y.lph[level], bw_ = Y.rpw[level], bh_ = Y.rph[level];
-    const float* A0 = fimg(0, Y.lpf[level]);
-    const float* B0 = fimg(0, Y.rpf[level]);
+    const float* A0 = S.f(0, Y.lpf[level]);
+    const float* B0 = S.f(0, Y.rpf[level]);
     // zone tasks of every tile, sorted into the kernel classes of this level: 0 = order free with float32 sums, 1 = order free, 2 = certified,
     // 3 = the reference's order only (a non-finite pixel, or VWGPU_OPT_CERTIFY = 0)
     std::vector<vwgpu_zone_task> t1[4], t2[4], t3[4];
-    std::vector<int> cls((size_t)n, -1);
+    int kcls[VWGPU_MAX_GROUP];
+    std::fill(kcls, kcls + n, -1);
     size_t rl_pixels = 0;
     // per tile on the helper threads (R->L offsets local to the tile), then strung together per class
-    struct TileTasks { std::vector<vwgpu_zone_task> a, b, c; size_t rl = 0; int err = 0; };
+    struct TileTasks : ZoneTasks { vwgpu::ZoneErr err = vwgpu::ZONE_OK; };
     std::vector<TileTasks> TT((size_t)n);
+    const ZoneLevel zl{rox, roy, hkx, hky, kx, ky, dw};
     auto build_tile = [&](int t) {
-      GroupTile& g = T[t];
       TileTasks& tt = TT[t];
-      if (!g.alive) return;
-      bool exact = g.exact_level[level] != 0;
-      for (SearchZone const& z : g.zones)
+      if (!alive[t]) return;
+      const LevelClass& lc = cls[(size_t)t * (L + 1) + level];
+      bool exact = lc.exact;
+      for (SearchZone const& z : zones[t])
         if (z.range.dx() > 0 && z.range.dy() > 0) exact = exact && vwgpu_bm_exact_supported(z.range.dx(), z.range.dy());      // (as the single-tile path: the tile kernels otherwise)
-      cls[t] = exact ? (g.cert_hi[level] != INT_MIN ? 2 : 3) : (g.f32_level[level] ? 0 : 1);
-      tt.a.reserve(g.zones.size());
-      if (lr_active) { tt.b.reserve(g.zones.size()); tt.c.reserve(g.zones.size()); }
-      for (SearchZone const& z : g.zones) {
-        const IBox lr(z.region.x0 + rox - hkx, z.region.y0 + roy - hky, z.region.x1 + rox + hkx, z.region.y1 + roy + hky);
-        const IBox rr(lr.x0 + z.range.x0, lr.y0 + z.range.y0, lr.x1 + z.range.x0 + z.range.dx(), lr.y1 + z.range.y0 + z.range.dy());
-        const int zw = z.region.dx(), zh = z.region.dy(), sx = z.range.dx(), sy = z.range.dy();
-        if (zw <= 0 || zh <= 0 || sx <= 0 || sy <= 0) continue;
-        if (zw > 65535 * 32 || zh > 65535 * 32) { tt.err = 1; return; }
-        const long long out_off = (long long)t * (long long)slice_px + (long long)z.region.y0 * dw + z.region.x0;
-        if (out_off > INT32_MAX) { tt.err = 2; return; }
-        vwgpu_zone_task a{lr.x0, lr.y0, rr.x0, rr.y0, zw, zh, sx, sy, (int)out_off, dw, lr_active ? 0 : z.range.x0, lr_active ? 0 : z.range.y0, t};
-        tt.a.push_back(a);
-        if (lr_active) {
-          const int rlw = rr.dx() - kx + 1, rlh = rr.dy() - ky + 1;
-          vwgpu_zone_task b{rr.x0, rr.y0, lr.x0 - sx, lr.y0 - sy, rlw, rlh, sx, sy, (int)tt.rl, rlw, -sx, -sy, t};
-          tt.b.push_back(b);
-          vwgpu_zone_task cc{(int)tt.rl, 0, rlw, rlh, zw, zh, 0, 0, a.out_off, dw, z.range.x0, z.range.y0, t};
-          tt.c.push_back(cc);
-          tt.rl += (size_t)rlw * rlh;
-          if (tt.rl > (size_t)INT32_MAX / 2) { tt.err = 3; return; }
-        }
-      }
+      kcls[t] = exact ? (lc.cert_hi != INT_MIN ? 2 : 3) : (lc.f32 ? 0 : 1);
+      tt.a.reserve(zones[t].size());
+      if (lr_active) { tt.b.reserve(zones[t].size()); tt.c.reserve(zones[t].size()); }
+      for (SearchZone const& z : zones[t])
+        if ((tt.err = vwgpu::zone_tasks(z, zl, lr_active, true, (long long)t * (long long)slice_px, t, nullptr, &tt))) return;
     };
     {
       size_t nz = 0;
-      for (int t = 0; t < n; ++t) nz += T[t].zones.size();
+      for (int t = 0; t < n; ++t) nz += zones[t].size();
       if (nz >= 1024) pool_for(ctx, n, build_tile);                 // (waking the helpers costs tens of microseconds: not for the coarse levels)
       else for (int t = 0; t < n; ++t) build_tile(t);
     }
     for (int t = 0; t < n; ++t) {
       TileTasks& tt = TT[t];
-      if (tt.err == 1) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "pyramid_correlate: zone too large");
-      if (tt.err == 2) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "pyramid_correlate: tile group too large for the zone tables");
-      if (tt.err == 3 || rl_pixels + tt.rl > (size_t)INT32_MAX / 2) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "pyramid_correlate: tile group too large for the L/R check buffers");
-      if (cls[t] < 0) continue;
-      const int c = cls[t], base = (int)rl_pixels;
+      if (tt.err) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "%s", zone_err_text(tt.err, true));
+      if (rl_pixels + tt.rl > (size_t)INT32_MAX / 2) return vwgpu_fail(ctx, VWGPU_ERR_NOIMPL, "%s", zone_err_text(vwgpu::ZONE_LR_TOO_LARGE, true));
+      if (kcls[t] < 0) continue;
+      const int c = kcls[t], base = (int)rl_pixels;
       t1[c].insert(t1[c].end(), tt.a.begin(), tt.a.end());
       for (vwgpu_zone_task& b : tt.b) b.out_off += base;
       for (vwgpu_zone_task& cc : tt.c) cc.ax += base;
@@ -1644,16 +1158,18 @@ int vwgpu_pyramid_group_impl(vwgpu_ctx* ctx, const float* left, int lw, int lh, 
     stamp("zone tasks built", level);
     if (lr_active && rl_pixels) { if ((rc = vwgpu_arena_reserve(ctx, &ctx->zrl, rl_pixels * 12))) return rc; }
     int32_t* rlbuf = static_cast<int32_t*>(ctx->zrl.base);
-    // the "cannot matter" certificate (see vwgpu_pyramid_correlate_impl): margins per level, bounds per tile
+    // the "cannot matter" certificate (pyramid_plan.h, edge_margins): margins per level, bounds per tile
     const int edge_k = rox - hkx;
-    const int edge_m_lr = P->filter_half_kernel > 0 ? P->filter_half_kernel + (last ? 4 : 8) : 0;
-    const int edge_m_rl = (P->consistency_threshold >= 0 && P->consistency_threshold < 1e6) ? (int)std::floor(P->consistency_threshold) + 2 : 0;
-    std::vector<int> lr_lo((size_t)n), lr_hi((size_t)n), rl_lo((size_t)n, -edge_m_rl + 1), rl_hi((size_t)n, dw + edge_m_rl - 2), hi_img((size_t)n, INT_MIN);
+    int edge_m_lr = 0, edge_m_rl = 0;
+    int lr_lo[VWGPU_MAX_GROUP], lr_hi[VWGPU_MAX_GROUP], rl_lo[VWGPU_MAX_GROUP], rl_hi[VWGPU_MAX_GROUP], hi_img[VWGPU_MAX_GROUP];
     for (int t = 0; t < n; ++t) {
-      const int rv0 = std::max(0, -T[t].rmb.x0) >> level, rv1 = (std::min(Y.rmw[0], rw - T[t].rmb.x0) + (1 << level) - 1) >> level;
-      lr_lo[t] = rv0 - edge_m_lr + 1; lr_hi[t] = rv1 + edge_m_lr - 2;
-      hi_img[t] = T[t].cert_hi[level];
+      const EdgeMargins em = vwgpu::edge_margins(P, last, false, level, G[t].rmb.x0, Y.rmw[0], rw, dw);
+      edge_m_lr = em.m_lr; edge_m_rl = em.m_rl;
+      lr_lo[t] = em.lr_lo; lr_hi[t] = em.lr_hi; rl_lo[t] = em.rl_lo; rl_hi[t] = em.rl_hi;
+      hi_img[t] = cls[(size_t)t * (L + 1) + level].cert_hi;
     }
+    const MatchPair l2r{A0, aw_, ah_, B0, bw_, bh_}, r2l{B0, bw_, bh_, A0, aw_, ah_};      // tile 0's; tile t's images lie t slices on
+    auto of_tile = [&](MatchPair m, int t) { m.a += (size_t)t * slice_f; m.b += (size_t)t * slice_f; return m; };
     vwgpu_zone_group grp;
     grp.n_img = n; grp.a_stride = slice_f; grp.b_stride = slice_f;
     // certified classes: flag words {any per pass and tile: 2 n} + zone flags of both passes, one block, one fill
@@ -1669,19 +1185,19 @@ int vwgpu_pyramid_group_impl(vwgpu_ctx* ctx, const float* left, int lw, int lh, 
       if (t1[c].empty()) continue;
       if (c == 3) {                                              // the reference's order: tile by tile (zones of one image pair per call)
         for (int t = 0; t < n; ++t) {
-          if (cls[t] != 3) continue;
+          if (kcls[t] != 3) continue;
           std::vector<vwgpu_zone_task> za, zb;
           for (auto const& z : t1[3]) if (z.img == t) za.push_back(z);
           for (auto const& z : t2[3]) if (z.img == t) zb.push_back(z);
-          const float* At = A0 + (size_t)t * slice_f; const float* Bt = B0 + (size_t)t * slice_f;
-          if (!za.empty() && (rc = vwgpu_launch_bm_exact(ctx, P->cost_type, At, aw_, ah_, aw_, Bt, bw_, bh_, bw_, kx, ky, za.data(), (int)za.size(), disp0))) return rc;
-          if (!zb.empty() && (rc = vwgpu_launch_bm_exact(ctx, P->cost_type, Bt, bw_, bh_, bw_, At, aw_, ah_, aw_, kx, ky, zb.data(), (int)zb.size(), rlbuf))) return rc;
+          const MatchPair m = of_tile(l2r, t);
+          if (!za.empty() && (rc = vwgpu_launch_bm_exact(ctx, P->cost_type, m.a, aw_, ah_, aw_, m.b, bw_, bh_, bw_, kx, ky, za.data(), (int)za.size(), disp0))) return rc;
+          if (!zb.empty() && (rc = vwgpu_launch_bm_exact(ctx, P->cost_type, m.b, bw_, bh_, bw_, m.a, aw_, ah_, aw_, kx, ky, zb.data(), (int)zb.size(), rlbuf))) return rc;
         }
         continue;
       }
       const bool cert = c == 2;
-      grp.cert_hi = cert ? hi_img.data() : nullptr;
-      grp.edge_lo = lr_lo.data(); grp.edge_hi = lr_hi.data();
+      grp.cert_hi = cert ? hi_img : nullptr;
+      grp.edge_lo = lr_lo; grp.edge_hi = lr_hi;
       rc = vwgpu_launch_bm_zones(ctx, P->cost_type, A0, aw_, ah_, B0, bw_, bh_, kx, ky, t1[c].data(), (int)t1[c].size(), disp0, c == 0 ? 1 : 0,
                                  cert ? 0 : INT_MIN, cert ? zflag1 : nullptr, cert ? d_cert_stats : nullptr, cert ? d_any : nullptr, nullptr, nullptr,
                                  cert ? edge_m_lr : 0, edge_k, 0, 0, 0, 0, &grp);
@@ -1693,7 +1209,7 @@ int vwgpu_pyramid_group_impl(vwgpu_ctx* ctx, const float* left, int lw, int lh, 
         unsigned char* cells = reinterpret_cast<unsigned char*>(need + 8 * t3[c].size());
         if ((rc = vwgpu_launch_zone_need(ctx, t3[c].data(), (int)t3[c].size(), disp0, cert ? zflag1 : nullptr, need, cells, ncells))) return rc;
         std::swap(grp.a_stride, grp.b_stride);                    // (equal anyway: the R->L pass matches the right image against the left)
-        grp.edge_lo = rl_lo.data(); grp.edge_hi = rl_hi.data();
+        grp.edge_lo = rl_lo; grp.edge_hi = rl_hi;
         rc = vwgpu_launch_bm_zones(ctx, P->cost_type, B0, bw_, bh_, A0, aw_, ah_, kx, ky, t2[c].data(), (int)t2[c].size(), rlbuf, c == 0 ? 1 : 0,
                                    cert ? 0 : INT_MIN, cert ? zflag2 : nullptr, cert ? d_cert_stats : nullptr, cert ? d_any + n : nullptr, need, cells,
                                    cert ? edge_m_rl : 0, edge_k, 0, 0, 0, 0, &grp);
@@ -1714,24 +1230,16 @@ int vwgpu_pyramid_group_impl(vwgpu_ctx* ctx, const float* left, int lw, int lh, 
         std::vector<int> hflag(tz.size());
         VWGPU_HIP(ctx, hipMemcpyAsync(hflag.data(), pass ? zflag2 : zflag1, hflag.size() * sizeof(int), hipMemcpyDeviceToHost, st));
         VWGPU_HIP(ctx, hipStreamSynchronize(st));
-        for (int t = 0; t < n; ++t) {
-          if (!any[pass * n + t]) continue;
-          std::vector<vwgpu_zone_task> redo;
-          for (size_t i = 0; i < tz.size(); ++i) if (hflag[i] && tz[i].img == t) redo.push_back(tz[i]);
-          if (redo.empty()) continue;
-          const float* At = A0 + (size_t)t * slice_f; const float* Bt = B0 + (size_t)t * slice_f;
-          if (pass == 0) rc = vwgpu_launch_bm_exact(ctx, P->cost_type, At, aw_, ah_, aw_, Bt, bw_, bh_, bw_, kx, ky, redo.data(), (int)redo.size(), disp0);
-          else rc = vwgpu_launch_bm_exact(ctx, P->cost_type, Bt, bw_, bh_, bw_, At, aw_, ah_, aw_, kx, ky, redo.data(), (int)redo.size(), rlbuf);
-          if (rc) return rc;
-        }
+        for (int t = 0; t < n; ++t)
+          if (any[pass * n + t] && (rc = redo_flagged_zones(ctx, P, of_tile(pass ? r2l : l2r, t), tz, hflag.data(), t, pass ? rlbuf : disp0, -1, pass))) return rc;
       }
     }
     if (lr_active)
       for (int c = 0; c < 4; ++c)
         if (!t3[c].empty() && (rc = vwgpu_launch_zone_lr(ctx, t3[c].data(), (int)t3[c].size(), disp0, rlbuf, P->consistency_threshold, nullptr, 0))) return rc;
     // ---- clean-up filters (:702-744) ----
-    int32_t* disp2_0 = reinterpret_cast<int32_t*>(at(0, disp2_off));
-    int32_t* padded0 = reinterpret_cast<int32_t*>(at(0, Y.padded));
+    int32_t* disp2_0 = S.i(0, disp2_off);
+    int32_t* padded0 = S.i(0, Y.padded);
     const bool fused_extents = !last && P->filter_half_kernel > 0;       // second filter pass + mask applied by the zone scheduler's kernel as it reads
     if (P->filter_half_kernel > 0) {
       rc = vwgpu_launch_disparity_filter(ctx, disp0, dw, dh, P->filter_half_kernel, P->filter_half_kernel, 3.0, 0.5, !last, padded0, disp2_0, true, n, slice_i);
@@ -1740,53 +1248,18 @@ int vwgpu_pyramid_group_impl(vwgpu_ctx* ctx, const float* left, int lw, int lh, 
     }
     // ---- zone refinement (:754-799): leaf extents of every tile in one launch, one copy, one synchronisation ----
     if (!last) {
-      const std::vector<vwgpu::IBox>& leaves = vwgpu::cached_leaves(dw, dh);
-      const size_t nleaf = leaves.size();
-      int4* d_rects = nullptr;
-      for (auto& lr : ctx->leaf_rects)
-        if (lr.w == dw && lr.h == dh && lr.n == nleaf) d_rects = static_cast<int4*>(lr.d_rects);
-      if (!d_rects) {
-        void* p = nullptr;
-        VWGPU_HIP(ctx, hipMalloc(&p, std::max<size_t>(nleaf, 1) * sizeof(int4)));
-        VWGPU_HIP(ctx, hipMemcpyAsync(p, leaves.data(), nleaf * sizeof(int4), hipMemcpyHostToDevice, st));
-        VWGPU_HIP(ctx, hipStreamSynchronize(st));
-        if (ctx->leaf_rects.size() >= 64) { (void)hipFree(ctx->leaf_rects.front().d_rects); ctx->leaf_rects.erase(ctx->leaf_rects.begin()); }
-        ctx->leaf_rects.push_back({dw, dh, nleaf, p});
-        d_rects = static_cast<int4*>(p);
-      }
-      const size_t ext_bytes = (size_t)n * nleaf * sizeof(vwgpu::LeafExtent);
-      if ((rc = vwgpu_arena_reserve(ctx, &ctx->zext, ext_bytes + 256))) return rc;
-      int32_t* d_ext = static_cast<int32_t*>(ctx->zext.base);
-      {
-        vwgpu_prof_scope ps(ctx, "zone_extents");
-        if (fused_extents)
-          hipLaunchKernelGGL(zone_extent_fused_kernel, dim3((unsigned)nleaf, (unsigned)n), dim3(64), 0, st, padded0, dw, dh, bimg(0, Y.lmp[level]), bimg(0, Y.rmp[level]),
-                             Y.rmw[level], Y.rmh[level], d_rects, (int)nleaf, d_ext, slice_i, Y.slice);
-        else
-          hipLaunchKernelGGL(zone_extent_kernel, dim3((unsigned)nleaf, (unsigned)n), dim3(64), 0, st, reinterpret_cast<const int32_t*>(at(0, disp_off)), dw, dh, d_rects, (int)nleaf, d_ext, slice_i);
-      }
       std::vector<vwgpu::LeafExtent> own;
-      const vwgpu::LeafExtent* h_ext = static_cast<const vwgpu::LeafExtent*>(vwgpu_host_ring(ctx, ext_bytes));
-      if (!h_ext) { own.resize((size_t)n * nleaf); h_ext = own.data(); }
-      VWGPU_HIP(ctx, hipMemcpyAsync(const_cast<vwgpu::LeafExtent*>(h_ext), d_ext, ext_bytes, hipMemcpyDeviceToHost, st));
-      stamp("level queued, waiting", level);
-      VWGPU_HIP(ctx, hipStreamSynchronize(st));
-      stamp("leaf extents on the host", level);
+      const vwgpu::LeafExtent* h_ext = nullptr;
+      size_t nleaf = 0;
+      if ((rc = read_leaf_extents(ctx, n, fused_extents, fused_extents ? padded0 : S.i(0, disp_off), slice_i, dw, dh, S.b(0, Y.lmp[level]), S.b(0, Y.rmp[level]),
+                                  Y.slice, Y.rmw[level], Y.rmh[level], stamp, level, &own, &h_ext, &nleaf))) return rc;
       const IBox scale_search(0, 0, Y.rpw[level - 1] - Y.lpw[level - 1], Y.rph[level - 1] - Y.lph[level - 1]);
       const IBox next_size(0, 0, Y.lmw[level - 1], Y.lmh[level - 1]);
       auto refine_tile = [&](int t) {                               // (helper threads: the scheduler keeps its tree of boxes per thread)
-        if (!T[t].alive) return;
-        std::vector<SearchZone>& zones = T[t].zones;
-        zones.clear();
-        vwgpu::subdivide_regions_from_leaves(dw, dh, kx, ky, h_ext + (size_t)t * nleaf, nleaf, zones);
-        for (SearchZone& z : zones) {
-          z.region.scale(2);
-          z.region.clip(next_size);
-          z.range.scale(2);
-          z.range.expand(2);
-          z.range.clip(scale_search);
-          if (z.range.empty()) z.range = IBox(0, 0, search.width(), search.height());
-        }
+        if (!alive[t]) return;
+        zones[t].clear();
+        vwgpu::subdivide_regions_from_leaves(dw, dh, kx, ky, h_ext + (size_t)t * nleaf, nleaf, zones[t]);
+        vwgpu::rescale_zones(zones[t], next_size, scale_search, search);
       };
       if (nleaf * (size_t)n >= 2048) pool_for(ctx, n, refine_tile);
       else for (int t = 0; t < n; ++t) refine_tile(t);
@@ -1798,18 +1271,12 @@ int vwgpu_pyramid_group_impl(vwgpu_ctx* ctx, const float* left, int lw, int lh, 
   {
     GroupOuts go;
     for (int t = 0; t < VWGPU_MAX_GROUP; ++t) { go.out[t] = nullptr; go.os[t] = 0; go.mode[t] = 0; }
-    for (int t = 0; t < n; ++t) { go.out[t] = outs[t]; go.os[t] = oss[t]; go.mode[t] = !T[t].alive ? 3 : (P->filter_half_kernel > 0 ? 2 : 1); }
-    hipLaunchKernelGGL(finish_group_kernel, dim3((bw + 63) / 64, (bh + 3) / 4, (unsigned)n), kBlk, 0, st, go, reinterpret_cast<const int32_t*>(at(0, disp_off)), slice_i, bw, bh,
-                       bimg(0, Y.lmp[0]), bimg(0, Y.rmp[0]), Y.slice, Y.rmw[0], Y.rmh[0], search.x0, search.y0);
+    for (int t = 0; t < n; ++t) { go.out[t] = outs[t]; go.os[t] = oss[t]; go.mode[t] = !alive[t] ? 3 : (P->filter_half_kernel > 0 ? 2 : 1); }
+    hipLaunchKernelGGL(finish_group_kernel, dim3((bw + 63) / 64, (bh + 3) / 4, (unsigned)n), kBlk, 0, st, go, S.i(0, disp_off), slice_i, bw, bh,
+                       S.b(0, Y.lmp[0]), S.b(0, Y.rmp[0]), Y.slice, Y.rmw[0], Y.rmh[0], search.x0, search.y0);
   }
   VWGPU_HIP(ctx, hipGetLastError());
-  if (d_cert_stats) {
-    unsigned long long got[4] = {0, 0, 0, 0};
-    VWGPU_HIP(ctx, hipMemcpyAsync(got, d_cert_stats, sizeof got, hipMemcpyDeviceToHost, st));
-    VWGPU_HIP(ctx, hipStreamSynchronize(st));
-    ctx->cert_px[0] += got[0]; ctx->cert_px[1] += got[1]; ctx->cert_px[2] += got[2];
-  }
-  return VWGPU_OK;
+  return read_cert_stats(ctx, d_cert_stats, false);
 }
 
 // ---- extern "C" entry points ------------------------------------------------------------------------------------
@@ -1832,81 +1299,26 @@ int vwgpu_subdivide_regions(const int32_t* disp, int w, int h, int kx, int ky, i
   return n;
 }
 
-int vwgpu_disparity_filter_dev(vwgpu_ctx* ctx, const int32_t* d_src, int w, int h, int hh, int hv,
-                               double pthr, double rthr, int cleanup, int32_t* d_dst) {
-  if (!ctx) return VWGPU_ERR_ARGUMENT;
-  ctx->err.clear();
-  if (!d_src || !d_dst || w <= 0 || h <= 0 || d_src == d_dst) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "rm_outliers_using_thresh: bad image arguments");
-  if (hh <= 0 || hv <= 0) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "RmOutliersFunc: half kernel sizes must be non-zero.");
-  VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  int32_t* padded = nullptr;
-  if (cleanup) {
-    int rc = vwgpu_arena_reserve(ctx, &ctx->pyr, (size_t)(w + 2) * (h + 2) * 12);
-    if (rc) return rc;
-    padded = static_cast<int32_t*>(ctx->pyr.base);
-  }
-  return vwgpu_launch_disparity_filter(ctx, d_src, w, h, hh, hv, pthr, rthr, cleanup != 0, padded, d_dst);
+// a row stride of 0 stands for dense rows
+static void default_strides(int lw, int rw, ptrdiff_t* ls, ptrdiff_t* rs, ptrdiff_t* lms, ptrdiff_t* rms) {
+  if (*ls == 0) *ls = lw;
+  if (*rs == 0) *rs = rw;
+  if (*lms == 0) *lms = lw;
+  if (*rms == 0) *rms = rw;
 }
 
-int vwgpu_disparity_filter(vwgpu_ctx* ctx, const int32_t* src, int w, int h, int hh, int hv,
-                           double pthr, double rthr, int cleanup, int32_t* dst) {
-  if (!ctx) return VWGPU_ERR_ARGUMENT;
-  ctx->err.clear();
-  if (!src || !dst || w <= 0 || h <= 0) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "rm_outliers_using_thresh: bad image arguments");
-  VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  vwgpu_stage st(ctx);
-  const int ps = st.add(src, w, h, 12, w, VWGPU_STAGE_IN), pd = st.add(dst, w, h, 12, w, VWGPU_STAGE_OUT);
-  int rc = st.commit();
-  if (rc) return rc;
-  rc = vwgpu_disparity_filter_dev(ctx, st.dev<int32_t>(ps), w, h, hh, hv, pthr, rthr, cleanup, st.dev<int32_t>(pd));
-  if (rc) return rc;
-  return st.finish();
+// CorrelationView.cc:277-283
+static const char kLrDiffDomain[] = "The L-R to R-L difference image domain does not contain the current tile.";
+static bool tile_outside_lr_diff(const vwgpu_pyramid_params* P, int bx, int by, int bw, int bh) {
+  return P->lr_disp_diff && (bx < P->region_ul_x || by < P->region_ul_y || bx + bw > P->region_ul_x + P->lr_disp_diff_cols ||
+                             by + bh > P->region_ul_y + P->lr_disp_diff_rows);
 }
 
-int vwgpu_disparity_mask_dev(vwgpu_ctx* ctx, int32_t* d_disp, int w, int h, const uint8_t* m1, const uint8_t* m2, int rmw, int rmh) {
-  if (!ctx) return VWGPU_ERR_ARGUMENT;
-  ctx->err.clear();
-  if (!d_disp || !m1 || !m2 || w <= 0 || h <= 0 || rmw <= 0 || rmh <= 0) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "disparity_mask: bad image arguments");
-  VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  return vwgpu_launch_disparity_mask(ctx, d_disp, w, h, m1, m2, rmw, rmh);
-}
-
-int vwgpu_disparity_mask(vwgpu_ctx* ctx, int32_t* disp, int w, int h, const uint8_t* m1, const uint8_t* m2, int rmw, int rmh) {
-  if (!ctx) return VWGPU_ERR_ARGUMENT;
-  ctx->err.clear();
-  if (!disp || !m1 || !m2 || w <= 0 || h <= 0 || rmw <= 0 || rmh <= 0) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "disparity_mask: bad image arguments");
-  VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  vwgpu_stage st(ctx);
-  const int pd = st.add(disp, w, h, 12, w, VWGPU_STAGE_INOUT), pa = st.add(m1, w, h, 1, w, VWGPU_STAGE_IN), pb = st.add(m2, rmw, rmh, 1, rmw, VWGPU_STAGE_IN);
-  int rc = st.commit();
-  if (rc) return rc;
-  rc = vwgpu_launch_disparity_mask(ctx, st.dev<int32_t>(pd), w, h, st.dev<uint8_t>(pa), st.dev<uint8_t>(pb), rmw, rmh);
-  if (rc) return rc;
-  return st.finish();
-}
-
-int vwgpu_disparity_blob_filter_dev(vwgpu_ctx* ctx, int32_t* d_disp, int w, int h, int max_blob_area) {
-  if (!ctx) return VWGPU_ERR_ARGUMENT;
-  ctx->err.clear();
-  if (!d_disp || w <= 0 || h <= 0 || (long long)w * h > 0x7fffffffLL) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "disparity_blob_filter: bad image arguments");
-  VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = vwgpu_arena_reserve(ctx, &ctx->pyr, (size_t)w * h * 8);
-  if (rc) return rc;
-  return vwgpu_launch_blob_filter(ctx, d_disp, w, h, max_blob_area, static_cast<int*>(ctx->pyr.base));
-}
-
-int vwgpu_disparity_blob_filter(vwgpu_ctx* ctx, int32_t* disp, int w, int h, int max_blob_area) {
-  if (!ctx) return VWGPU_ERR_ARGUMENT;
-  ctx->err.clear();
-  if (!disp || w <= 0 || h <= 0) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "disparity_blob_filter: bad image arguments");
-  VWGPU_HIP(ctx, hipSetDevice(ctx->device));
-  vwgpu_stage st(ctx);
-  const int pd = st.add(disp, w, h, 12, w, VWGPU_STAGE_INOUT);
-  int rc = st.commit();
-  if (rc) return rc;
-  rc = vwgpu_disparity_blob_filter_dev(ctx, st.dev<int32_t>(pd), w, h, max_blob_area);
-  if (rc) return rc;
-  return st.finish();
+// the end of the run of consecutive tiles of equal size that begins at t0, at most `cap` tiles: what one group can take
+static int equal_tiles_run(const int* bw, const int* bh, int t0, int n_tiles, int cap) {
+  int t1 = t0 + 1;
+  while (t1 < n_tiles && t1 - t0 < cap && bw[t1] == bw[t0] && bh[t1] == bh[t0]) ++t1;
+  return t1;
 }
 
 static int check_pyramid_args(vwgpu_ctx* ctx, const void* l, int lw, int lh, const void* r, int rw, int rh,
@@ -1946,15 +1358,10 @@ int vwgpu_pyramid_correlate_dev(vwgpu_ctx* ctx, const float* d_left, int lw, int
                                 const vwgpu_pyramid_params* P, int bx, int by, int bw, int bh, float* d_out, ptrdiff_t os) {
   int rc = check_pyramid_args(ctx, d_left, lw, lh, d_right, rw, rh, P, bw, bh, d_out);
   if (rc) return rc;
-  if (ls == 0) ls = lw;
-  if (rs == 0) rs = rw;
-  if (lms == 0) lms = lw;
-  if (rms == 0) rms = rw;
+  default_strides(lw, rw, &ls, &rs, &lms, &rms);
   if (os == 0) os = bw;
   if (ls < lw || rs < rw || lms < lw || rms < rw || os < bw) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "pyramid_correlate: row stride smaller than row width");
-  if (P->lr_disp_diff && (bx < P->region_ul_x || by < P->region_ul_y || bx + bw > P->region_ul_x + P->lr_disp_diff_cols ||
-                          by + bh > P->region_ul_y + P->lr_disp_diff_rows))
-    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "The L-R to R-L difference image domain does not contain the current tile.");
+  if (tile_outside_lr_diff(P, bx, by, bw, bh)) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, kLrDiffDomain);
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
   return vwgpu_pyramid_correlate_impl(ctx, d_left, lw, lh, ls, d_right, rw, rh, rs, d_lmask, lms, d_rmask, rms, P, bx, by, bw, bh, d_out, os,
                                       P->lr_disp_diff);
@@ -1968,10 +1375,7 @@ int vwgpu_pyramid_correlate_batch_dev(vwgpu_ctx* ctx, const float* d_left, int l
   if (!ctx) return VWGPU_ERR_ARGUMENT;
   ctx->err.clear();
   if (n_tiles < 0 || (n_tiles > 0 && (!bx || !by || !bw || !bh || !d_outs))) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "pyramid_correlate_batch: null tile table");
-  if (ls == 0) ls = lw;
-  if (rs == 0) rs = rw;
-  if (lms == 0) lms = lw;
-  if (rms == 0) rms = rw;
+  default_strides(lw, rw, &ls, &rs, &lms, &rms);
   for (int t = 0; t < n_tiles; ++t) {
     int rc = check_pyramid_args(ctx, d_left, lw, lh, d_right, rw, rh, P, bw[t], bh[t], d_outs[t]);
     if (rc) return rc;
@@ -1984,8 +1388,7 @@ int vwgpu_pyramid_correlate_batch_dev(vwgpu_ctx* ctx, const float* d_left, int l
   // filter, time budget, a forced kernel family) and lone tiles go through the single-tile entry — same results either way
   int t0 = 0, cap = VWGPU_MAX_GROUP;                   // cap: halved when a group's arena does not fit the device
   while (t0 < n_tiles) {
-    int t1 = t0 + 1;
-    while (t1 < n_tiles && t1 - t0 < cap && bw[t1] == bw[t0] && bh[t1] == bh[t0]) ++t1;
+    const int t1 = equal_tiles_run(bw, bh, t0, n_tiles, cap);
     const int m = t1 - t0;
     if (m > 1 && vwgpu_pyramid_group_eligible(ctx, P, m, bw + t0, bh + t0)) {
       ptrdiff_t oss[VWGPU_MAX_GROUP];
@@ -2001,9 +1404,7 @@ int vwgpu_pyramid_correlate_batch_dev(vwgpu_ctx* ctx, const float* d_left, int l
       if (rc) return rc;
     } else {
       for (int t = t0; t < t1; ++t) {
-        if (P->lr_disp_diff && (bx[t] < P->region_ul_x || by[t] < P->region_ul_y || bx[t] + bw[t] > P->region_ul_x + P->lr_disp_diff_cols ||
-                                by[t] + bh[t] > P->region_ul_y + P->lr_disp_diff_rows))
-          return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "The L-R to R-L difference image domain does not contain the current tile.");
+        if (tile_outside_lr_diff(P, bx[t], by[t], bw[t], bh[t])) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, kLrDiffDomain);
         int rc = vwgpu_pyramid_correlate_impl(ctx, d_left, lw, lh, ls, d_right, rw, rh, rs, d_lmask, lms, d_rmask, rms, P, bx[t], by[t], bw[t], bh[t], d_outs[t],
                                               (os && os[t]) ? os[t] : bw[t], P->lr_disp_diff);
         if (rc) return rc;
@@ -2094,18 +1495,14 @@ int vwgpu_pyramid_correlate_batch(vwgpu_ctx* ctx, const float* left, int lw, int
     int rc = check_pyramid_args(ctx, left, lw, lh, right, rw, rh, P, bw[t], bh[t], outs[t]);
     if (rc) return rc;
   }
-  if (ls == 0) ls = lw;
-  if (rs == 0) rs = rw;
-  if (lms == 0) lms = lw;
-  if (rms == 0) rms = rw;
+  default_strides(lw, rw, &ls, &rs, &lms, &rms);
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
   // Staged per RUN of tiles (consecutive tiles of equal size, at most VWGPU_MAX_GROUP: what one device group takes), not per call: tiles
   // scattered over a large pair would otherwise upload nearly the whole pair.  A run whose union window is more than three
   // times the windows of its tiles taken one by one (tiles far apart inside the run) goes through the single-tile entry.
   int t0 = 0;
   while (t0 < n_tiles) {
-    int t1 = t0 + 1;
-    while (t1 < n_tiles && t1 - t0 < VWGPU_MAX_GROUP && bw[t1] == bw[t0] && bh[t1] == bh[t0]) ++t1;
+    const int t1 = equal_tiles_run(bw, bh, t0, n_tiles, VWGPU_MAX_GROUP);
     long long ux0 = LLONG_MAX, uy0 = LLONG_MAX, ux1 = LLONG_MIN, uy1 = LLONG_MIN;
     for (int t = t0; t < t1; ++t) {
       ux0 = std::min<long long>(ux0, bx[t]); uy0 = std::min<long long>(uy0, by[t]);
@@ -2134,18 +1531,13 @@ int vwgpu_pyramid_correlate(vwgpu_ctx* ctx, const float* left, int lw, int lh, p
                             const vwgpu_pyramid_params* P, int bx, int by, int bw, int bh, float* out, ptrdiff_t os) {
   int rc = check_pyramid_args(ctx, left, lw, lh, right, rw, rh, P, bw, bh, out);
   if (rc) return rc;
-  if (ls == 0) ls = lw;
-  if (rs == 0) rs = rw;
-  if (lms == 0) lms = lw;
-  if (rms == 0) rms = rw;
+  default_strides(lw, rw, &ls, &rs, &lms, &rms);
   if (os == 0) os = bw;
   VWGPU_HIP(ctx, hipSetDevice(ctx->device));
   const pyr_window W = pyramid_window(P, bx, by, (long long)bx + bw, (long long)by + bh, lw, lh, rw, rh);
   if (W.lww <= 0 || W.lwh <= 0 || W.rww <= 0 || W.rwh <= 0)
     return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "pyramid_correlate: the tile lies outside the images");
-  if (P->lr_disp_diff && (bx < P->region_ul_x || by < P->region_ul_y || bx + bw > P->region_ul_x + P->lr_disp_diff_cols ||
-                          by + bh > P->region_ul_y + P->lr_disp_diff_rows))
-    return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, "The L-R to R-L difference image domain does not contain the current tile.");
+  if (tile_outside_lr_diff(P, bx, by, bw, bh)) return vwgpu_fail(ctx, VWGPU_ERR_ARGUMENT, kLrDiffDomain);
   // The discrepancy image is shared by the tile threads (each writes its own pixels, CorrelationView.cc:683-694): only the
   // tile's rectangle of it is staged, so that concurrent tiles never write back each other's stale pixels.
   const ptrdiff_t hdst = P->lr_disp_diff_stride ? P->lr_disp_diff_stride : P->lr_disp_diff_cols;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "vwgpu.h"
+#include "zone_task.h"
 
 struct vwgpu_prof_rec {
   const char* name;
@@ -91,7 +92,7 @@ struct vwgpu_ctx {
   vwgpu_arena hole_tab;  // hole filling: per-blob statistics, the kept-blob numbering, the internal label image and table of fill_holes_grass
   int inpaint_overlap = 1;    // VWGPU_OPT_INPAINT_OVERLAP
   int num_cu = 256;
-  void* host_pool = nullptr;  // helper threads for the per-tile host work of tile groups (pyramid.hip), created on first use
+  void* host_pool = nullptr;  // helper threads for the per-tile host work of tile groups (host_pool.hip), created on first use
 };
 // fn(i) for i in [0, n) on the context's helper threads and the calling thread; returns when all are done.  fn must not throw.
 void vwgpu_pool_run(vwgpu_ctx* ctx, int n, void (*fn)(void*, int), void* arg);
@@ -284,26 +285,7 @@ int vwgpu_pyramid_subpixel_tiles(vwgpu_ctx* ctx, const float* d_disp, int w, int
                                  int mode, float width, int kx, int ky, int levels, int algorithm, const vwgpu_pyr_refiner* refiner,
                                  const int* tiles, int ntiles, float* d_out, ptrdiff_t ostride, long long* stats);
 
-// bm_zones.hip — one row per search zone (or per R->L zone image); see the kernels for the field meaning
-struct vwgpu_zone_task {
-  int ax, ay;          // origin of the zone's input crop in image A (may lie outside: coordinates are clamped)
-  int bx, by;          // origin in image B of the window for disparity (0,0)
-  int zw, zh;          // output size
-  int sx, sy;          // search volume
-  int out_off;         // pixel offset of the zone's first output pixel in the output buffer
-  int out_stride;      // pixels
-  int addx, addy;      // added to the winning disparity index of every pixel
-  int img = 0;         // zone-matcher groups (vwgpu_zone_group): which image pair of the group the zone belongs to
-};
-// A launch sequence of the zone matcher over several image pairs of EQUAL geometry laid out at a fixed stride (the tiles of a
-// pyramid_correlate group, pyramid.hip): image pair i = (A + i * a_stride, B + i * b_stride); zones name theirs in vwgpu_zone_task::img.
-struct vwgpu_zone_group {
-  int n_img = 1;
-  size_t a_stride = 0, b_stride = 0;       // floats
-  const int* cert_hi = nullptr;            // n_img largest exponents (certified passes; overrides the cert_hi argument)
-  const int* edge_lo = nullptr;            // n_img bounds of the "cannot matter" certificate (override edge_lo / edge_hi)
-  const int* edge_hi = nullptr;
-};
+// bm_zones.hip — the zone tables (vwgpu_zone_task, vwgpu_zone_group, vwgpu_zone_row_flags) are in zone_task.h
 bool vwgpu_bm_zones_supported(int kx, int ky);
 // f32_sums: vwgpu_sums_bits <= 24 for BOTH images.  cert_hi != INT_MIN: certify against the reference's summation order (bm_zones.hip),
 // d_zflag[n] (zeroed by the caller) receives the zones that need vwgpu_launch_bm_exact; d_stats (optional): {pixels in certified tiles, in flagged tiles}
@@ -316,11 +298,6 @@ int vwgpu_launch_bm_zones(vwgpu_ctx* ctx, int cost_type, const float* A, int aw,
                           ptrdiff_t as = 0, ptrdiff_t bs = 0,                                      // row strides of A / B in floats (0: the widths)
                           const vwgpu_zone_group* grp = nullptr,                                   // several image pairs in one launch sequence; d_any then has n_img words
                           int* d_tflag = nullptr);                                                 // certified passes without d_need: one int per 32-row band of every zone (vwgpu_zone_row_flags of them, zeroed by the caller; zone i's begin where the bands of zones 0 .. i-1 end), set for bands with an unproven pixel
-inline size_t vwgpu_zone_row_flags(const vwgpu_zone_task* zones, int n) {
-  size_t r = 0;
-  for (int i = 0; i < n; ++i) r += (size_t)(zones[i].zh + 31) / 32;
-  return r;
-}
 // The flagged bands of one zone as row ranges {begin, end}, ... for vwgpu_launch_bm_exact; returns the number of flagged rows.
 inline int vwgpu_zone_flagged_rows(const int* bands, int zh, std::vector<int>* rows) {
   int flagged = 0;
@@ -343,12 +320,13 @@ int vwgpu_launch_zone_need(vwgpu_ctx* ctx, const vwgpu_zone_task* zones, int n, 
 int vwgpu_launch_zone_lr(vwgpu_ctx* ctx, const vwgpu_zone_task* zones, int n, int32_t* l2r, const int32_t* r2l, float thr,
                          float* diff2, ptrdiff_t dstride);
 
-// pyramid.hip
+// pyramid_filters.hip
 int vwgpu_launch_disparity_filter(vwgpu_ctx* ctx, const int32_t* src, int w, int h, int hh, int hv, double pthr, double rthr,
                                   bool cleanup, int32_t* tmp_padded, int32_t* dst, bool inner_only = false,      // inner_only: stop after the first pass (tmp_padded)
                                   int tiles = 1, size_t tile_ints = 0);                                        // tile groups: `tiles` images at a stride of tile_ints ints
 int vwgpu_launch_blob_filter(vwgpu_ctx* ctx, int32_t* d, int w, int h, int area, int* scratch);
 int vwgpu_launch_disparity_mask(vwgpu_ctx* ctx, int32_t* d, int w, int h, const uint8_t* m1, const uint8_t* m2, int m2w, int m2h);
+// pyramid.hip
 int vwgpu_pyramid_correlate_impl(vwgpu_ctx* ctx, const float* left, int lw, int lh, ptrdiff_t ls,
                                  const float* right, int rw, int rh, ptrdiff_t rs,
                                  const uint8_t* lmask, ptrdiff_t lms, const uint8_t* rmask, ptrdiff_t rms,

@@ -922,6 +922,170 @@ int vwgpu_composite_mask(vwgpu_ctx* ctx, vwgpu_composite* c, int index, float* o
 int vwgpu_composite_generate_patch_dev(vwgpu_ctx* ctx, vwgpu_composite* c, int x0, int y0, int w, int h, float* d_out, ptrdiff_t ostride);
 int vwgpu_composite_generate_patch(vwgpu_ctx* ctx, vwgpu_composite* c, int x0, int y0, int w, int h, float* out, ptrdiff_t ostride);
 
+/* ---- Image/Statistics.h, ImageThresh.h, Algorithms.h, AutoNormalize.h: image statistics and intensity scaling ---------- */
+
+/* Common to the entries of this block (tests/refimpl/image_stats_ref.cc, csrc/image_stats.hip):
+ * images are single-channel float, `mask` is an optional uint8 validity image of the same size (non-zero = valid, NULL =
+ * every pixel valid: the PixelMask of the reference); strides are in PIXELS, 0 = packed; the _dev form takes device
+ * pointers and works on the context's stream, the other form host pointers.  sample_cols, sample_rows: 0, 0 = every
+ * pixel, else the pass visits only the sampling grid of the second otsu_threshold overload (src/vw/Image/ImageThresh.h:
+ * 156-166): rows round(i * (rows - 1) / (sample_rows - 1)), columns likewise, computed on the host in double; a pixel that
+ * two grid points name counts twice, as it does there.  Null pointers, sizes <= 0, a stride below the width, one sampling
+ * count zero and the other not, a sampling count < 2 (the reference divides by n - 1) and the argument ranges named at the
+ * entries give VWGPU_ERR_ARGUMENT before any device work.  Integer and multi-channel pixels and alpha weighting are not
+ * covered. */
+
+typedef struct vwgpu_image_range { double min, max; long long count, nan_count; } vwgpu_image_range;
+/*   VWGPU_MIN_MAX_FIND   find_image_min_max (src/vw/Image/Statistics.h:113-127): min = DBL_MAX, max = -DBL_MAX, then
+ *                        `if (val < min) min = val; if (val > max) max = val;` in double over the valid pixels: a NaN never
+ *                        enters, and with no valid (non-NaN) pixel the two stay DBL_MAX and -DBL_MAX.
+ *   VWGPU_MIN_MAX_ACCUM  min_max_channel_values (:98-108) with MinMaxAccumulator<float> (src/vw/Math/Functors.h:355-372):
+ *                        the first valid pixel in raster order sets both, later ones enter through `arg < min`,
+ *                        `max < arg`: a NaN is admitted only as that first pixel (both extrema are then NaN for good), the
+ *                        rule of vwgpu_get_disparity_range.  No valid pixel: the accumulator throws "no valid samples";
+ *                        here min = max = 0, count = 0, and the call returns VWGPU_ERR_ARGUMENT where it hands the result
+ *                        to the host.
+ * count: the valid pixels visited, nan_count: those of them that are NaN.  The sign of a zero extremum is not pinned. */
+typedef enum vwgpu_min_max_mode { VWGPU_MIN_MAX_FIND = 0, VWGPU_MIN_MAX_ACCUM = 1 } vwgpu_min_max_mode;
+/* _dev: d_result (device) and host_result are both optional, one of them must be given; only host_result synchronises. */
+int vwgpu_image_min_max_dev(vwgpu_ctx* ctx, const float* d_in, int w, int h, ptrdiff_t istride, const uint8_t* d_mask, ptrdiff_t mstride,
+                            int sample_cols, int sample_rows, int mode, vwgpu_image_range* d_result, vwgpu_image_range* host_result);
+int vwgpu_image_min_max(vwgpu_ctx* ctx, const float* in, int w, int h, ptrdiff_t istride, const uint8_t* mask, ptrdiff_t mstride,
+                        int sample_cols, int sample_rows, int mode, vwgpu_image_range* result);
+
+/* moments = {count, sum of x, sum of (double)x * x} in double over the valid pixels: what Accumulator, MeanAccumulator and
+ * StdDevAccumulator (src/vw/Math/Functors.h:469-518) hold after sum_of_channel_values, mean_channel_value and
+ * stddev_channel_value (src/vw/Image/Statistics.h:129-172); vwgpu_moments_mean / vwgpu_moments_stddev apply their value()
+ * formulas.  The reference adds in raster order; here every lane adds its pixels in a fixed order, a workgroup folds its lanes
+ * in a fixed order into one row of a slab and a second kernel folds the slab, with no float atomics: two calls on the same
+ * pixels return the same bits, whichever form is called and wherever the image lies in memory, and on imagery whose partial
+ * sums are exact (integer-valued pixels below 2^53 in sum) they are the reference's bits.  Otherwise sum and sum of squares
+ * are within 2 (N - 1) u / (1 - (N - 1) u) * sum |term|, u = 2^-53, of the raster-order sums.
+ * _dev: d_result (device double[3]) and host_result (host double[3]) as above. */
+int vwgpu_image_moments_dev(vwgpu_ctx* ctx, const float* d_in, int w, int h, ptrdiff_t istride, const uint8_t* d_mask, ptrdiff_t mstride,
+                            int sample_cols, int sample_rows, double* d_result, double* host_result);
+int vwgpu_image_moments(vwgpu_ctx* ctx, const float* in, int w, int h, ptrdiff_t istride, const uint8_t* mask, ptrdiff_t mstride,
+                        int sample_cols, int sample_rows, double* result);
+/* MeanAccumulator::value (Functors.h:483-486) and StdDevAccumulator::value (:509-512); count 0 ("no valid samples") or a
+ * null pointer: VWGPU_ERR_ARGUMENT.  Host functions, no context. */
+int vwgpu_moments_mean(const double* moments, double* mean);
+int vwgpu_moments_stddev(const double* moments, double* stddev);
+
+#define VWGPU_HISTOGRAM_MAX_BINS 4096
+/* Replaces vw::histogram (src/vw/Image/ImageThresh.h:53-73) over math::Histogram::initialize / add_value with saturate =
+ * true (src/vw/Math/Statistics.cc:34-76): max == min becomes min + 1; a valid pixel v goes to bin
+ * (int)round(max_bin * ((v - min) / range)) in IEEE double, round half away from zero, max_bin = num_bins - 1, range =
+ * max - min; negative bins saturate to 0 and bins >= num_bins to max_bin.
+ * counts: uint64[num_bins + 2]: the bins, then counts[num_bins] = the total (get_total_num_values) and
+ * counts[num_bins + 1] = nan_count.  The one deliberate deviation: a pixel whose bin argument is NaN (a NaN pixel, or any
+ * pixel when min / max are not finite) makes the reference convert NaN to int, which is undefined; here it is counted in
+ * nan_count and in no bin, nor in the total.  An argument beyond the int range (also undefined there) saturates by its sign.
+ * accumulate != 0 adds into the counts that are already there, so that the tiles or row strips of a larger image give
+ * exactly the counts of the whole image; 0 zeroes them first.  bin_width: optional HOST double, range / num_bins
+ * (get_bin_width).  num_bins outside [1, VWGPU_HISTOGRAM_MAX_BINS], NaN min / max: VWGPU_ERR_ARGUMENT.
+ * The _dev form does not synchronise. */
+int vwgpu_image_histogram_dev(vwgpu_ctx* ctx, const float* d_in, int w, int h, ptrdiff_t istride, const uint8_t* d_mask, ptrdiff_t mstride,
+                              int sample_cols, int sample_rows, int num_bins, double min, double max, int accumulate,
+                              uint64_t* d_counts, double* bin_width);
+int vwgpu_image_histogram(vwgpu_ctx* ctx, const float* in, int w, int h, ptrdiff_t istride, const uint8_t* mask, ptrdiff_t mstride,
+                          int sample_cols, int sample_rows, int num_bins, double min, double max, int accumulate,
+                          uint64_t* counts, double* bin_width);
+
+/* Host functions on counts (the first num_bins words of the above), no context.
+ * vwgpu_histogram_percentile: Histogram::get_percentile (src/vw/Math/Statistics.cc:85-104): the first bin at which the
+ * running sum of counts[i] / (double)total reaches `percentile`.  percentile outside [0, 1] (or NaN): VWGPU_ERR_ARGUMENT;
+ * no bin reaches it ("Illegal histogram encountered", e.g. total == 0): VWGPU_ERR_LOGIC.
+ * vwgpu_otsu_from_histogram: what otsu_threshold does after its histogram is built.  overload 1 (ImageThresh.h:97-144): the
+ * between-class variance per bin, the indices of its maximum averaged when it is reached more than once, threshold = min +
+ * mean_index / (num_bins - 1) * (max - min); overload 2 (:204-238): the mu1 *= q1 recurrence, the FLT_EPSILON skip, the first
+ * strict maximum, threshold = (max - min) * (pos / (num_bins - 1)) + min.  min, max are the values the histogram was built
+ * with after `if (max == min) max++`.  total == 0 gives 0.0 in both.  Another overload number, num_bins < 1: ARGUMENT. */
+int vwgpu_histogram_percentile(const uint64_t* counts, int num_bins, uint64_t total, double percentile, int* bin);
+int vwgpu_otsu_from_histogram(const uint64_t* counts, int num_bins, uint64_t total, double min, double max, int overload,
+                              double* threshold);
+/* otsu_threshold(view) (overload 1: num_bins must be 256 and the sampling counts 0) and otsu_threshold(view,
+ * num_sample_rows, num_sample_cols, num_bins) (overload 2; sampling counts 0, 0 = cols, rows, which is every pixel once):
+ * vwgpu_image_min_max (FIND), `if (max == min) max++`, vwgpu_image_histogram, vwgpu_otsu_from_histogram.  A NaN pixel is
+ * left out (in the reference it would be converted to int).  threshold is a HOST double; both forms synchronise. */
+int vwgpu_otsu_threshold_dev(vwgpu_ctx* ctx, const float* d_in, int w, int h, ptrdiff_t istride, const uint8_t* d_mask, ptrdiff_t mstride,
+                             int sample_cols, int sample_rows, int num_bins, int overload, double* threshold);
+int vwgpu_otsu_threshold(vwgpu_ctx* ctx, const float* in, int w, int h, ptrdiff_t istride, const uint8_t* mask, ptrdiff_t mstride,
+                         int sample_cols, int sample_rows, int num_bins, int overload, double* threshold);
+
+/* The k-th smallest valid pixel, exactly, without sorting: a radix select over the order-preserving 32-bit key of a float,
+ * three digits (12, 12 and 8 bits) counted by the histogram kernel, the digit choice made on the device.
+ *   VWGPU_ORDER_RANK        arg = k, 0-based, clamped to the last valid pixel: sorted[k]
+ *   VWGPU_ORDER_MEDIAN      destructive_median (src/vw/Math/Functors.h:393-398), what median_channel_value returns: with len
+ *                           valid pixels sorted[len / 2] for odd len, else (sorted[len / 2 - 1] + sorted[len / 2]) / 2.0 —
+ *                           the sum of two floats, as written there, divided in double
+ *   VWGPU_ORDER_PERCENTILE  destructive_percentile (:424-444), arg = percentile in [0, 100]: sorted[ceil(arg / 100 * len) - 1],
+ *                           the index clamped to [0, len - 1]
+ * -0.0 and +0.0 compare equal in std::sort: the sign of a zero result is not pinned.  A NaN among the valid pixels
+ * (std::sort has no defined result) or no valid pixel ("no valid samples"): the device result is NaN and the call returns
+ * VWGPU_ERR_ARGUMENT where it hands the result to the host.  w * h above INT_MAX (the reference's int len), a NaN or
+ * negative arg, a percentile above 100: VWGPU_ERR_ARGUMENT.
+ * _dev: d_result (device double[1]) and host_result (host double[1]), one of them must be given; only host_result
+ * synchronises. */
+typedef enum vwgpu_order_kind { VWGPU_ORDER_RANK = 0, VWGPU_ORDER_MEDIAN = 1, VWGPU_ORDER_PERCENTILE = 2 } vwgpu_order_kind;
+int vwgpu_image_order_statistic_dev(vwgpu_ctx* ctx, const float* d_in, int w, int h, ptrdiff_t istride, const uint8_t* d_mask,
+                                    ptrdiff_t mstride, int kind, double arg, double* d_result, double* host_result);
+int vwgpu_image_order_statistic(vwgpu_ctx* ctx, const float* in, int w, int h, ptrdiff_t istride, const uint8_t* mask, ptrdiff_t mstride,
+                                int kind, double arg, double* result);
+
+/* The per-pixel pass of src/vw/Image/Algorithms.h, params a HOST double array:
+ *   VWGPU_RESCALE_CLAMP            clamp(image, low, high) (:30-61), params {low, high}: v > high ? high : v < low ? low : v
+ *   VWGPU_RESCALE_NORMALIZE        normalize(image, old_low, old_high, new_low, new_high) (:105-126, :171-188), params in that
+ *                                  order: (float)((v - old_low) * ratio + new_low), v - old_low in float, ratio the double
+ *                                  (new_high - new_low) / (double)(old_high - old_low) with both differences in float, 0 when
+ *                                  old_high == old_low
+ *   VWGPU_RESCALE_CLAMP_NORMALIZE  normalize(clamp(image, low, high), old_low, ...) in one pass, params {low, high, old_low,
+ *                                  old_high, new_low, new_high}
+ *   VWGPU_RESCALE_THRESHOLD        threshold(image, thresh, low, high) (:192-208), params {thresh, low, high}: v > thresh ?
+ *                                  high : low
+ * Every parameter is cast to float first (the functors hold channel_type), nothing is contracted.  out_type (what `out`
+ * holds): VWGPU_PIXEL_F32 the float result; VWGPU_PIXEL_U8 pixel_cast<uint8> of it, the C truncation; VWGPU_PIXEL_U8_AS_F32
+ * that uint8 value as a float (integer-valued imagery for vwgpu_calc_disparity).  Where the C conversion is undefined this
+ * one is defined: a NaN becomes 0, values below 0 become 0 and values of 256 and above 255.  in == out is allowed for the two
+ * float outputs.  There is no mask operand: UnaryCompoundFunctor applies the functor to the value of an invalid PixelMask
+ * pixel too and only carries the validity over (src/vw/Image/PixelMask.h:514-523), so the caller's mask stays as it is.
+ * A NaN parameter, an unknown mode or out_type: VWGPU_ERR_ARGUMENT. */
+typedef enum vwgpu_rescale_mode {
+  VWGPU_RESCALE_CLAMP = 0, VWGPU_RESCALE_NORMALIZE = 1, VWGPU_RESCALE_CLAMP_NORMALIZE = 2, VWGPU_RESCALE_THRESHOLD = 3
+} vwgpu_rescale_mode;
+typedef enum vwgpu_rescale_pixel { VWGPU_PIXEL_F32 = 0, VWGPU_PIXEL_U8 = 1, VWGPU_PIXEL_U8_AS_F32 = 2 } vwgpu_rescale_pixel;
+int vwgpu_image_rescale_dev(vwgpu_ctx* ctx, const float* d_in, int w, int h, ptrdiff_t istride, int mode, const double* params,
+                            int out_type, void* d_out, ptrdiff_t ostride);
+int vwgpu_image_rescale(vwgpu_ctx* ctx, const float* in, int w, int h, ptrdiff_t istride, int mode, const double* params,
+                        int out_type, void* out, ptrdiff_t ostride);
+
+/* percentile_scale_convert (src/vw/Image/ImageThresh.h:243-270): find_image_min_max, histogram(num_bins), low_bin / high_bin
+ * = get_percentile(low / high percentile), low_value = (low_bin + 1) * bin_width + min and high_value likewise, then
+ * pixel_cast<uint8>(normalize(clamp(image, low_value, high_value), low_value, high_value, 0.0, 255.0)).
+ * u8_convert (:274-286): min, max, `if (max == min) max = min + 1`, the same stretch between them.
+ * auto_normalize: normalize(image, low, high) of src/vw/Image/AutoNormalize.h:33-49: min_max_channel_values, then
+ * normalize(image, old_min, old_max, low, high) into floats (normalize(image) is low = 0, high = 1).
+ * The mask serves the statistics only; every pixel of the image is converted.  The _dev forms make NO host
+ * synchronisation: a one-workgroup kernel computes the percentile bins and the stretch on the device, in the double
+ * arithmetic of vwgpu_histogram_percentile, and hands them to the convert pass through device memory.  host_params:
+ * optional HOST double[4] {min, max, low_value, high_value} ({old_min, old_max, low, high} for auto_normalize); asking
+ * for it synchronises.  With no valid pixel, or no bin reaching a percentile, the reference throws: here every output
+ * pixel is new_low (0), and the call returns VWGPU_ERR_ARGUMENT where host_params is asked for or the form is the host one.
+ * Percentiles outside [0, 1], num_bins outside [1, VWGPU_HISTOGRAM_MAX_BINS], a NaN low / high: VWGPU_ERR_ARGUMENT. */
+int vwgpu_percentile_scale_convert_dev(vwgpu_ctx* ctx, const float* d_in, int w, int h, ptrdiff_t istride, const uint8_t* d_mask,
+                                       ptrdiff_t mstride, double low_percentile, double high_percentile, int num_bins, int out_type,
+                                       void* d_out, ptrdiff_t ostride, double* host_params);
+int vwgpu_percentile_scale_convert(vwgpu_ctx* ctx, const float* in, int w, int h, ptrdiff_t istride, const uint8_t* mask,
+                                   ptrdiff_t mstride, double low_percentile, double high_percentile, int num_bins, int out_type,
+                                   void* out, ptrdiff_t ostride, double* host_params);
+int vwgpu_u8_convert_dev(vwgpu_ctx* ctx, const float* d_in, int w, int h, ptrdiff_t istride, const uint8_t* d_mask, ptrdiff_t mstride,
+                         int out_type, void* d_out, ptrdiff_t ostride, double* host_params);
+int vwgpu_u8_convert(vwgpu_ctx* ctx, const float* in, int w, int h, ptrdiff_t istride, const uint8_t* mask, ptrdiff_t mstride,
+                     int out_type, void* out, ptrdiff_t ostride, double* host_params);
+int vwgpu_auto_normalize_dev(vwgpu_ctx* ctx, const float* d_in, int w, int h, ptrdiff_t istride, const uint8_t* d_mask, ptrdiff_t mstride,
+                             double low, double high, float* d_out, ptrdiff_t ostride, double* host_params);
+int vwgpu_auto_normalize(vwgpu_ctx* ctx, const float* in, int w, int h, ptrdiff_t istride, const uint8_t* mask, ptrdiff_t mstride,
+                         double low, double high, float* out, ptrdiff_t ostride, double* host_params);
+
 /* ---- Stereo/StereoModel.{h,cc} and Stereo/StereoView.h: triangulation and the universe radius ---------- */
 
 /* The part of vw::camera that triangulation needs (tests/refimpl/triangulate_ref.cc): a flat

@@ -40,6 +40,12 @@ SYMBOLS = [
     "vwgpu_composite_set_draft_mode", "vwgpu_composite_set_fill_holes", "vwgpu_composite_prepare", "vwgpu_composite_cols",
     "vwgpu_composite_rows", "vwgpu_composite_levels", "vwgpu_composite_bbox", "vwgpu_composite_mask",
     "vwgpu_composite_generate_patch_dev", "vwgpu_composite_generate_patch",
+    "vwgpu_image_min_max_dev", "vwgpu_image_min_max", "vwgpu_image_moments_dev", "vwgpu_image_moments", "vwgpu_moments_mean",
+    "vwgpu_moments_stddev", "vwgpu_image_histogram_dev", "vwgpu_image_histogram", "vwgpu_histogram_percentile",
+    "vwgpu_otsu_from_histogram", "vwgpu_otsu_threshold_dev", "vwgpu_otsu_threshold",
+    "vwgpu_image_order_statistic_dev", "vwgpu_image_order_statistic", "vwgpu_image_rescale_dev", "vwgpu_image_rescale",
+    "vwgpu_percentile_scale_convert_dev", "vwgpu_percentile_scale_convert", "vwgpu_u8_convert_dev", "vwgpu_u8_convert",
+    "vwgpu_auto_normalize_dev", "vwgpu_auto_normalize",
     "vwgpu_pinhole_camera", "vwgpu_stereo_triangulate_dev", "vwgpu_stereo_triangulate",
     "vwgpu_convergence_angle_dev", "vwgpu_convergence_angle", "vwgpu_universe_radius_dev", "vwgpu_universe_radius",
     "vwgpu_pinhole_camera_matrix", "vwgpu_epipolar_pinhole", "vwgpu_epipolar_cahv",
@@ -106,6 +112,11 @@ class IpDetectParams(ctypes.Structure):
 class IpPoints(ctypes.Structure):
     """struct vwgpu_ip_points (include/vwgpu.h)."""
     _fields_ = [(name, ctypes.c_void_p) for name in ("x", "y", "ix", "iy", "orientation", "scale", "interest")]
+
+
+class ImageRange(ctypes.Structure):
+    """struct vwgpu_image_range (include/vwgpu.h)."""
+    _fields_ = [("min", ctypes.c_double), ("max", ctypes.c_double), ("count", ctypes.c_longlong), ("nan_count", ctypes.c_longlong)]
 
 
 class TriangulateStats(ctypes.Structure):
@@ -297,6 +308,35 @@ def load():
     cgp = [P, P, I, I, I, I, P, PD]
     lib.vwgpu_composite_generate_patch_dev.argtypes = cgp
     lib.vwgpu_composite_generate_patch.argtypes = cgp
+    img = [P, P, I, I, PD, P, PD]      # ctx, image, w, h, stride, mask, mask stride
+    lib.vwgpu_image_min_max_dev.argtypes = img + [I, I, I, P, ctypes.POINTER(ImageRange)]
+    lib.vwgpu_image_min_max.argtypes = img + [I, I, I, ctypes.POINTER(ImageRange)]
+    lib.vwgpu_image_moments_dev.argtypes = img + [I, I, P, P]
+    lib.vwgpu_image_moments.argtypes = img + [I, I, P]
+    lib.vwgpu_moments_mean.argtypes = [P, ctypes.POINTER(D)]
+    lib.vwgpu_moments_stddev.argtypes = [P, ctypes.POINTER(D)]
+    ihs = img + [I, I, I, D, D, I, P, ctypes.POINTER(D)]
+    lib.vwgpu_image_histogram_dev.argtypes = ihs
+    lib.vwgpu_image_histogram.argtypes = ihs
+    lib.vwgpu_histogram_percentile.argtypes = [P, I, ctypes.c_uint64, D, ctypes.POINTER(ctypes.c_int)]
+    lib.vwgpu_otsu_from_histogram.argtypes = [P, I, ctypes.c_uint64, D, D, I, ctypes.POINTER(D)]
+    ots = img + [I, I, I, I, ctypes.POINTER(D)]
+    lib.vwgpu_otsu_threshold_dev.argtypes = ots
+    lib.vwgpu_otsu_threshold.argtypes = ots
+    lib.vwgpu_image_order_statistic_dev.argtypes = img + [I, D, P, ctypes.POINTER(D)]
+    lib.vwgpu_image_order_statistic.argtypes = img + [I, D, ctypes.POINTER(D)]
+    irs = [P, P, I, I, PD, I, P, I, P, PD]
+    lib.vwgpu_image_rescale_dev.argtypes = irs
+    lib.vwgpu_image_rescale.argtypes = irs
+    psc = img + [D, D, I, I, P, PD, P]
+    lib.vwgpu_percentile_scale_convert_dev.argtypes = psc
+    lib.vwgpu_percentile_scale_convert.argtypes = psc
+    u8c = img + [I, P, PD, P]
+    lib.vwgpu_u8_convert_dev.argtypes = u8c
+    lib.vwgpu_u8_convert.argtypes = u8c
+    anm = img + [D, D, P, PD, P]
+    lib.vwgpu_auto_normalize_dev.argtypes = anm
+    lib.vwgpu_auto_normalize.argtypes = anm
     CP = ctypes.POINTER(Camera)
     lib.vwgpu_pinhole_camera.argtypes = [P, P, D, D, D, D, P, P, P, D, I, P, CP]
     tri = [P, I, P, I, I, PD, I, I, CP, CP, D, I, P, PD, P, PD, P, PD, P]

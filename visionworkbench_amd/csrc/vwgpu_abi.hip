@@ -206,7 +206,7 @@ int vwgpu_create(vwgpu_ctx** out, int device) {
 static size_t free_arenas(vwgpu_ctx* ctx) {
   size_t freed = ctx->graveyard_bytes;
   vwgpu_arena* all[] = {&ctx->scratch, &ctx->flags, &ctx->filt, &ctx->misc, &ctx->pyr, &ctx->ztab, &ctx->zrl, &ctx->zext, &ctx->sgm,
-                        &ctx->sgm_main, &ctx->sgm_bnd, &ctx->xvol, &ctx->xtab, &ctx->xcarry, &ctx->staging, &ctx->hole, &ctx->hole_tab};
+                        &ctx->sgm_main, &ctx->sgm_bnd, &ctx->xvol, &ctx->xtab, &ctx->xcarry, &ctx->staging, &ctx->hole, &ctx->hole_tab, &ctx->istats};
   for (vwgpu_arena* a : all) {
     if (a->base) { (void)hipFree(a->base); freed += a->cap; }
     a->base = nullptr; a->cap = 0;

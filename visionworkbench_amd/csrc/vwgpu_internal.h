@@ -91,6 +91,7 @@ struct vwgpu_ctx {
   vwgpu_arena hole;      // hole filling (hole_fill.hip): union-find parents, roots and scan partials of one labelling
   vwgpu_arena hole_tab;  // hole filling: per-blob statistics, the kept-blob numbering, the internal label image and table of fill_holes_grass
   int inpaint_overlap = 1;    // VWGPU_OPT_INPAINT_OVERLAP
+  vwgpu_arena istats;    // image statistics (image_stats.hip): results, histogram bins, reduction slabs, sampling tables of one call
   int num_cu = 256;
   void* host_pool = nullptr;  // helper threads for the per-tile host work of tile groups (host_pool.hip), created on first use
 };

@@ -7,12 +7,18 @@ Masked images are numpy arrays or torch CUDA tensors of one of four pixel kinds:
     (rows, cols, 2) float32         PixelMask<float> as {value, valid}
     (rows, cols, 3) int32 / float32 PixelMask<Vector2i> / PixelMask<Vector2f> as {dx, dy, valid}
 A view whose rows are further apart than its width (a crop of a wider image) is passed as it is, with its row stride.
+
+Input conditioning, on (rows, cols) float32 images with an optional `mask` (any dtype, non-zero =
+valid: the PixelMask of the reference): min_max, moments, mean, stddev, median, percentile (src/vw/Image/Statistics.h,
+src/vw/Math/Functors.h), histogram, otsu_threshold, percentile_scale_convert, u8_convert (src/vw/Image/ImageThresh.h),
+clamp, normalize, threshold (src/vw/Image/Algorithms.h, AutoNormalize.h).
 """
 import ctypes
 
 import numpy as np
 
-from .core import ArgumentErr, CapacityErr
+from . import _lib
+from .core import ArgumentErr, CapacityErr, LogicErr
 from ._operands import Operands
 
 MASK_U8, MASKED_F32, DISPARITY_I32, DISPARITY_F32 = 0, 1, 2, 3      # vwgpu_pixel_kind
@@ -213,3 +219,279 @@ def fill_nodata_with_avg(img, kernel_size, ctx=None):
     out = ops.empty((h, w, 2), np.float32)
     ops.call("fill_nodata_with_avg", ops.ptr(a), w, h, stride, int(kernel_size), ops.ptr(out), 0)
     return out
+
+
+# ---- image statistics and intensity scaling (include/vwgpu.h) ------------------------------
+
+HISTOGRAM_MAX_BINS = 4096                                            # VWGPU_HISTOGRAM_MAX_BINS
+MIN_MAX_MODES = {"find": 0, "accumulator": 1}                        # vwgpu_min_max_mode
+ORDER_RANK, ORDER_MEDIAN, ORDER_PERCENTILE = 0, 1, 2                 # vwgpu_order_kind
+RESCALE_CLAMP, RESCALE_NORMALIZE, RESCALE_CLAMP_NORMALIZE, RESCALE_THRESHOLD = 0, 1, 2, 3      # vwgpu_rescale_mode
+PIXEL_F32, PIXEL_U8, PIXEL_U8_AS_F32 = 0, 1, 2                       # vwgpu_rescale_pixel
+
+
+def _gray(ops, name, img, mask=None, sample=None):
+    """The leading arguments of a statistics entry: image, cols, rows, row stride, mask, mask stride, and the sampling
+    counts (sample = (num_sample_rows, num_sample_cols) as otsu_threshold orders them, None = every pixel)."""
+    a = ops.image(img, np.float32, rows=True)
+    if a.ndim != 2 or a.shape[0] <= 0 or a.shape[1] <= 0:
+        raise ArgumentErr("%s: a non-empty (rows, cols) float32 image expected" % name)
+    h, w = int(a.shape[0]), int(a.shape[1])
+    m = ops.nonzero_u8(mask)
+    if m is not None and tuple(m.shape) != (h, w):
+        raise ArgumentErr("%s: the mask must have the image's shape" % name)
+    sr, sc = (0, 0) if sample is None else (int(sample[0]), int(sample[1]))
+    return a, (ops.ptr(a), w, h, ops.row_stride(a), ops.ptr(m), 0), (sc, sr), m
+
+
+def min_max(img, mask=None, mode="find", sample=None, ctx=None):
+    """(min, max, count, nan_count) over the valid pixels.  mode 'find': find_image_min_max (src/vw/Image/Statistics.h:
+    113-127; DBL_MAX, -DBL_MAX when nothing is valid); 'accumulator': min_max_channel_values (:98-108), which raises
+    ArgumentErr without a valid sample and keeps a NaN that is the first valid pixel."""
+    if mode not in MIN_MAX_MODES:
+        raise ArgumentErr("min_max: mode must be 'find' or 'accumulator', not %r" % (mode,))
+    ops = Operands("min_max", img, ctx)
+    a, lead, samp, m = _gray(ops, "min_max", img, mask, sample)
+    r = _lib.ImageRange()
+    if ops.tensor:
+        ops.call("image_min_max", *(lead + samp + (MIN_MAX_MODES[mode], None, ctypes.byref(r))))
+    else:
+        ops.call("image_min_max", *(lead + samp + (MIN_MAX_MODES[mode], ctypes.byref(r))))
+    return r.min, r.max, r.count, r.nan_count
+
+
+def moments(img, mask=None, sample=None, ctx=None):
+    """(count, sum, sum of squares) of the valid pixels in double (vwgpu_image_moments): reproducible bit for bit, the
+    raster-order sums of the reference exactly on integer-valued imagery."""
+    ops = Operands("moments", img, ctx)
+    a, lead, samp, m = _gray(ops, "moments", img, mask, sample)
+    r = (ctypes.c_double * 3)()
+    if ops.tensor:
+        ops.call("image_moments", *(lead + samp + (None, ctypes.addressof(r))))
+    else:
+        ops.call("image_moments", *(lead + samp + (ctypes.addressof(r),)))
+    return r[0], r[1], r[2]
+
+
+def _from_moments(name, entry, m):
+    r, mom = ctypes.c_double(0), (ctypes.c_double * 3)(*m)
+    if getattr(_lib.load(), entry)(ctypes.addressof(mom), ctypes.byref(r)):
+        raise ArgumentErr("%s: no valid samples" % name)
+    return r.value
+
+
+def sum_of_channel_values(img, mask=None, ctx=None):
+    """sum_of_channel_values (src/vw/Image/Statistics.h:129-137)."""
+    return moments(img, mask, ctx=ctx)[1]
+
+
+def mean(img, mask=None, ctx=None):
+    """mean_channel_value (src/vw/Image/Statistics.h:139-148, MeanAccumulator)."""
+    return _from_moments("mean", "vwgpu_moments_mean", moments(img, mask, ctx=ctx))
+
+
+def stddev(img, mask=None, ctx=None):
+    """stddev_channel_value (src/vw/Image/Statistics.h:166-172, StdDevAccumulator): normalised by the sample count."""
+    return _from_moments("stddev", "vwgpu_moments_stddev", moments(img, mask, ctx=ctx))
+
+
+def _order(name, img, mask, kind, arg, ctx):
+    ops = Operands(name, img, ctx)
+    a, lead, samp, m = _gray(ops, name, img, mask)
+    r = ctypes.c_double(0)
+    if ops.tensor:
+        ops.call("image_order_statistic", *(lead + (kind, float(arg), None, ctypes.byref(r))))
+    else:
+        ops.call("image_order_statistic", *(lead + (kind, float(arg), ctypes.byref(r))))
+    return r.value
+
+
+def median(img, mask=None, ctx=None):
+    """median_channel_value (src/vw/Image/Statistics.h:179-186, destructive_median) by an exact radix select, no sort."""
+    return _order("median", img, mask, ORDER_MEDIAN, 0.0, ctx)
+
+
+def percentile(img, p, mask=None, ctx=None):
+    """destructive_percentile (src/vw/Math/Functors.h:424-444) of the valid pixels, p in [0, 100] (nearest rank)."""
+    return _order("percentile", img, mask, ORDER_PERCENTILE, p, ctx)
+
+
+def kth_smallest(img, k, mask=None, ctx=None):
+    """sorted(valid pixels)[k], k clamped to the last one."""
+    return _order("kth_smallest", img, mask, ORDER_RANK, k, ctx)
+
+
+class Histogram(object):
+    """vw::math::Histogram as vw::histogram fills it (saturating).  counts: num_bins + 2 words on the image's side (an
+    int64 CUDA tensor or a uint64 numpy array): the bins, the total, the NaN count."""
+    __slots__ = ("counts", "num_bins", "min_value", "max_value")
+
+    def __init__(self, counts, num_bins, min_value, max_value):
+        self.counts, self.num_bins = counts, int(num_bins)
+        self.min_value = float(min_value)
+        self.max_value = float(max_value) if max_value != min_value else float(min_value) + 1.0      # ImageThresh.h:61-62
+
+    def host_counts(self):
+        c = self.counts.cpu().numpy() if hasattr(self.counts, "cpu") else self.counts
+        return np.ascontiguousarray(c).view(np.uint64)
+
+    @property
+    def bin_width(self):
+        return (self.max_value - self.min_value) / self.num_bins      # Statistics.cc:48-49
+
+    @property
+    def total(self):
+        return int(self.host_counts()[self.num_bins])
+
+    @property
+    def nan_count(self):
+        return int(self.host_counts()[self.num_bins + 1])
+
+    def bin_value(self, i):
+        return float(self.host_counts()[:self.num_bins][i])
+
+    def bin_center(self, i):
+        return self.min_value + i * self.bin_width + self.bin_width / 2.0      # Statistics.cc:52
+
+    def get_percentile(self, percentile):
+        c = self.host_counts()
+        b = ctypes.c_int(0)
+        rc = _lib.load().vwgpu_histogram_percentile(c.ctypes.data, self.num_bins, int(c[self.num_bins]), float(percentile), ctypes.byref(b))
+        if rc == -1:
+            raise ArgumentErr("get_histogram_percentile: illegal percentile request: %r" % (percentile,))
+        if rc:
+            raise LogicErr("get_histogram_percentile: Illegal histogram encountered!")
+        return b.value
+
+
+def otsu_from_histogram(hist, overload=1):
+    """The threshold either otsu_threshold overload derives from its histogram (vwgpu_otsu_from_histogram)."""
+    c = hist.host_counts()
+    t = ctypes.c_double(0)
+    rc = _lib.load().vwgpu_otsu_from_histogram(c.ctypes.data, hist.num_bins, int(c[hist.num_bins]), hist.min_value, hist.max_value,
+                                               int(overload), ctypes.byref(t))
+    if rc:
+        raise ArgumentErr("otsu_from_histogram: overload must be 1 or 2")
+    return t.value
+
+
+def histogram(img, num_bins, min_val, max_val, mask=None, sample=None, into=None, ctx=None):
+    """vw::histogram(view, num_bins, min_val, max_val, hist) (src/vw/Image/ImageThresh.h:53-73).  into: a Histogram of the
+    same bins and bounds to add to (the tiles or row strips of a larger image give the counts of the whole image)."""
+    if not 1 <= int(num_bins) <= HISTOGRAM_MAX_BINS:
+        raise ArgumentErr("histogram: num_bins %d is outside [1, %d]" % (num_bins, HISTOGRAM_MAX_BINS))
+    ops = Operands("histogram", img, ctx)
+    a, lead, samp, m = _gray(ops, "histogram", img, mask, sample)
+    if into is None:
+        counts = ops.zeros((int(num_bins) + 2,), np.int64 if ops.tensor else np.uint64)
+    else:
+        same = Histogram(None, num_bins, min_val, max_val)
+        if into.num_bins != same.num_bins or (into.min_value, into.max_value) != (same.min_value, same.max_value):
+            raise ArgumentErr("histogram: `into` has other bins or bounds")
+        counts = ops.image(into.counts, np.int64 if ops.tensor else np.uint64, in_place=True)
+    ops.call("image_histogram", *(lead + samp + (int(num_bins), float(min_val), float(max_val), 1, ops.ptr(counts), None)))
+    return Histogram(counts, num_bins, min_val, max_val)
+
+
+def otsu_threshold(img, num_sample_rows=None, num_sample_cols=None, num_bins=None, mask=None, ctx=None):
+    """otsu_threshold(view) with no further argument, otsu_threshold(view, num_sample_rows, num_sample_cols, num_bins)
+    with all three (src/vw/Image/ImageThresh.h:80-145, :151-239)."""
+    given = [x is not None for x in (num_sample_rows, num_sample_cols, num_bins)]
+    if any(given) and not all(given):
+        raise ArgumentErr("otsu_threshold: num_sample_rows, num_sample_cols and num_bins go together")
+    ops = Operands("otsu_threshold", img, ctx)
+    sample = (num_sample_rows, num_sample_cols) if all(given) else None
+    a, lead, samp, m = _gray(ops, "otsu_threshold", img, mask, sample)
+    t = ctypes.c_double(0)
+    ops.call("otsu_threshold", *(lead + samp + (int(num_bins) if all(given) else 256, 2 if all(given) else 1, ctypes.byref(t))))
+    return t.value
+
+
+def _out_type(name, dtype, as_u8):
+    dt = np.dtype(dtype)
+    if dt == np.uint8:
+        return PIXEL_U8, np.uint8
+    if dt == np.float32:
+        return (PIXEL_U8_AS_F32 if as_u8 else PIXEL_F32), np.float32
+    raise ArgumentErr("%s: dtype must be float32 or uint8" % name)
+
+
+def _rescale(name, img, mode, params, dtype, out, ctx):
+    ops = Operands(name, img, ctx)
+    a, lead, samp, m = _gray(ops, name, img)
+    out_type, dt = _out_type(name, dtype, False)
+    if out is None:
+        out = ops.empty(tuple(a.shape), dt)
+    else:
+        out = ops.image(out, dt, in_place=True)
+        if tuple(out.shape) != tuple(a.shape):
+            raise ArgumentErr("%s: out must have the image's shape" % name)
+    p = (ctypes.c_double * len(params))(*[float(x) for x in params])
+    ops.call("image_rescale", *(lead[:4] + (mode, ctypes.addressof(p), out_type, ops.ptr(out), 0)))
+    return out
+
+
+def clamp(img, low, high, dtype=np.float32, out=None, ctx=None):
+    """clamp(image, low, high) (src/vw/Image/Algorithms.h:50-61).  dtype uint8: pixel_cast<uint8> of the result."""
+    return _rescale("clamp", img, RESCALE_CLAMP, (low, high), dtype, out, ctx)
+
+
+def threshold(img, thresh=0.0, low=0.0, high=1.0, dtype=np.float32, out=None, ctx=None):
+    """threshold(image, thresh, low, high) (src/vw/Image/Algorithms.h:192-208): high where the pixel is above thresh."""
+    return _rescale("threshold", img, RESCALE_THRESHOLD, (thresh, low, high), dtype, out, ctx)
+
+
+def _converted(ops, name, a, dtype, as_u8):
+    out_type, dt = _out_type(name, dtype, as_u8)
+    return out_type, ops.empty(tuple(a.shape), dt)
+
+
+def normalize(img, *bounds, **kw):
+    """normalize(image, old_low, old_high, new_low, new_high) (src/vw/Image/Algorithms.h:171-188) with four bounds;
+    normalize(image, low, high) and normalize(image) = (image, 0, 1) of src/vw/Image/AutoNormalize.h:33-86 with two or
+    none: old_low, old_high are min_max_channel_values of the valid pixels (mask=), found on the device without a host
+    round trip.  Every pixel is converted, the invalid ones too (src/vw/Image/PixelMask.h:514-523).  Keywords: mask, dtype,
+    out (four bounds only), clamp=(low, high) to clamp first in the same pass, params=True to return (image, {old_low,
+    old_high, low, high}) from the automatic form, ctx."""
+    mask, ctx, out, dtype = kw.pop("mask", None), kw.pop("ctx", None), kw.pop("out", None), kw.pop("dtype", np.float32)
+    pre, want_params = kw.pop("clamp", None), kw.pop("params", False)
+    if kw:
+        raise TypeError("normalize: unexpected keyword %s" % sorted(kw)[0])
+    if len(bounds) == 4:
+        if pre is not None:
+            return _rescale("normalize", img, RESCALE_CLAMP_NORMALIZE, tuple(pre) + bounds, dtype, out, ctx)
+        return _rescale("normalize", img, RESCALE_NORMALIZE, bounds, dtype, out, ctx)
+    if len(bounds) not in (0, 2) or pre is not None or out is not None or np.dtype(dtype) != np.float32:
+        raise ArgumentErr("normalize: (image), (image, low, high) or (image, old_low, old_high, new_low, new_high)")
+    low, high = bounds if bounds else (0.0, 1.0)
+    ops = Operands("normalize", img, ctx)
+    a, lead, samp, m = _gray(ops, "normalize", img, mask)
+    res = ops.empty(tuple(a.shape), np.float32)
+    p = (ctypes.c_double * 4)()
+    ops.call("auto_normalize", *(lead + (float(low), float(high), ops.ptr(res), 0, ctypes.addressof(p) if want_params else None)))
+    return (res, tuple(p)) if want_params else res
+
+
+def percentile_scale_convert(img, low_percentile=0.02, high_percentile=0.98, num_bins=256, mask=None, dtype=np.uint8, params=False,
+                             ctx=None):
+    """percentile_scale_convert (src/vw/Image/ImageThresh.h:243-270): the stretch between the histogram bins at the two
+    percentiles (fractions in [0, 1]) to 0..255.  dtype uint8 as the reference, or float32 for the same integer values as
+    floats (what stereo.calc_disparity takes on its packed-u8 path).  A tensor call makes no host synchronisation unless
+    params=True, which returns (image, (min, max, low_value, high_value))."""
+    ops = Operands("percentile_scale_convert", img, ctx)
+    a, lead, samp, m = _gray(ops, "percentile_scale_convert", img, mask)
+    out_type, res = _converted(ops, "percentile_scale_convert", a, dtype, True)
+    p = (ctypes.c_double * 4)()
+    ops.call("percentile_scale_convert", *(lead + (float(low_percentile), float(high_percentile), int(num_bins), out_type, ops.ptr(res), 0,
+                                                   ctypes.addressof(p) if params else None)))
+    return (res, tuple(p)) if params else res
+
+
+def u8_convert(img, mask=None, dtype=np.uint8, params=False, ctx=None):
+    """u8_convert (src/vw/Image/ImageThresh.h:274-286): the stretch between the minimum and the maximum to 0..255."""
+    ops = Operands("u8_convert", img, ctx)
+    a, lead, samp, m = _gray(ops, "u8_convert", img, mask)
+    out_type, res = _converted(ops, "u8_convert", a, dtype, True)
+    p = (ctypes.c_double * 4)()
+    ops.call("u8_convert", *(lead + (out_type, ops.ptr(res), 0, ctypes.addressof(p) if params else None)))
+    return (res, tuple(p)) if params else res

@@ -638,10 +638,28 @@ def describe_interest_points(image, generator, ip, ctx=None):
     return InterestPoints(ip.x, ip.y, desc, **{name: getattr(ip, name) for name, _ in _FIELDS[2:] if getattr(ip, name) is not None})
 
 
-def ipfind(image, detector="iagd", descriptor="sgrad", ip_per_tile=250, gain=1, ctx=None):
+def normalized_input(image, nodata=None, ctx=None):
+    """The image tools/ipfind.cc hands its detectors (:286-295): normalize(raw_image) to [0, 1], or with a nodata value
+    apply_mask(normalize(create_mask(raw_image, nodata))): the range is taken over the pixels that differ from nodata, and
+    those that equal it become 0.  On the side of `image`; a tensor never leaves the device."""
+    from . import image as _image
+    if nodata is None:
+        return _image.normalize(image, ctx=ctx)
+    valid = image != float(np.float32(nodata))
+    out = _image.normalize(image, mask=valid, ctx=ctx)
+    out[~valid] = 0
+    return out
+
+
+def ipfind(image, detector="iagd", descriptor="sgrad", ip_per_tile=250, gain=1, ctx=None, normalize=False, nodata=None):
     """What tools/ipfind.cc does to one float image without OpenCV (:328-339, :395-400): detect with "iagd" (the default) or
     "obalog", whose threshold is IDEAL_OBALOG_THRESHOLD / gain, ip_per_tile points per 1024 x 1024 tile, then describe with
-    "sgrad" or "sgrad2".  The result goes to match() and write_binary_ip_file()."""
+    "sgrad" or "sgrad2".  The result goes to match() and write_binary_ip_file().  normalize=True first applies
+    normalized_input(image, nodata), as the tool always does (:286-295); the default takes the image as it is."""
+    if normalize:
+        image = normalized_input(image, nodata, ctx)
+    elif nodata is not None:
+        raise ArgumentErr("ipfind: nodata is used by normalize=True only")
     if _code(DETECTORS, detector, "detector") == DETECTORS["obalog"]:
         det = IntegralInterestPointDetector(OBALoGInterestOperator(float(IDEAL_OBALOG_THRESHOLD / np.float32(gain))), max_points=ip_per_tile)
     else:
@@ -652,7 +670,7 @@ def ipfind(image, detector="iagd", descriptor="sgrad", ip_per_tile=250, gain=1, 
 
 __all__ = ["integral_image", "assign_orientation", "OBALoGInterestOperator", "IntegralInterestPointDetector", "IntegralAutoGainDetector", "detect_interest_points",
            "detection_tiles", "cull_order", "SGradDescriptorGenerator", "SGrad2DescriptorGenerator", "description_crop",
-           "describe_interest_points", "ipfind",
+           "describe_interest_points", "ipfind", "normalized_input",
            "InterestPoints", "match", "matched_pairs", "remove_duplicates", "remove_duplicates_mask", "NullConstraint",
            "ScaleOrientationConstraint", "PositionConstraint", "fit_similarity", "fit_affine", "fit_homography", "ransac", "ransac_samples",
            "iplist_to_vectorlist", "read_binary_ip_file", "write_binary_ip_file", "read_binary_match_file", "write_binary_match_file",

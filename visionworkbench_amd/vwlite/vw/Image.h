@@ -17,6 +17,13 @@
 //                                                  src/vw/Image/BlobIndex.h:385-500, :507-615
 //   applyErodeView                                 src/vw/Image/ErodeView.h:157-162
 //   inpaint, fill_holes_grass, fill_nodata_with_avg   src/vw/Image/InpaintView.h:231-237, :307-311, :381-387
+//
+// Image statistics and intensity scaling on the engine, on float, PixelGray<float> and
+// PixelMask<float> images:
+//   find_image_min_max, min_max_channel_values, sum_of_channel_values, mean_channel_value, stddev_channel_value,
+//   median_channel_value                           src/vw/Image/Statistics.h:98-186
+//   histogram, otsu_threshold (both overloads), percentile_scale_convert, u8_convert   src/vw/Image/ImageThresh.h:53-286
+//   clamp, normalize, threshold                    src/vw/Image/Algorithms.h:50-61, :171-188, :210-, AutoNormalize.h:33-86
 #ifndef VWLITE_IMAGE_H
 #define VWLITE_IMAGE_H
 
@@ -516,6 +523,202 @@ ImageView<PixelMask<float>> fill_nodata_with_avg(ImageViewBase<ImgT> const& img,
                                                 reinterpret_cast<float*>(out.data()), 0));
   return out;
 }
+
+// ---- image statistics and intensity scaling on the engine ----------------------------------------------------------
+namespace detail {
+/// A single-channel float image as the engine takes it: the values and, for PixelMask<float>, the validity as uint8.
+struct GrayOperand {
+  ImageView<float> values;
+  ImageView<uint8> mask;
+  bool masked = false;
+  const uint8* mask_ptr() const { return masked ? mask.data() : nullptr; }
+  int32 cols() const { return values.cols(); }
+  int32 rows() const { return values.rows(); }
+};
+inline float gray_value(float p) { return p; }
+inline float gray_value(PixelGray<float> const& p) { return p.v(); }
+template <class PixelT> struct gray_pixel { static const bool masked = false; static float value(PixelT const& p) { return gray_value(p); } };
+template <class ChildT> struct gray_pixel<PixelMask<ChildT>> {
+  static const bool masked = true;
+  static float value(PixelMask<ChildT> const& p) { return gray_value(p.child()); }
+};
+template <class ViewT>
+GrayOperand gray_operand(ImageViewBase<ViewT> const& view) {
+  typedef typename ViewT::pixel_type pixel_type;
+  ImageView<pixel_type> in = view.impl();
+  GrayOperand g;
+  g.values.set_size(in.cols(), in.rows());
+  g.masked = gray_pixel<pixel_type>::masked;
+  if (g.masked) g.mask.set_size(in.cols(), in.rows());
+  for (int32 r = 0; r < in.rows(); ++r)
+    for (int32 c = 0; c < in.cols(); ++c) {
+      g.values(c, r) = gray_pixel<pixel_type>::value(in(c, r));
+      if (g.masked) g.mask(c, r) = is_valid(in(c, r)) ? 1 : 0;
+    }
+  return g;
+}
+/// The values of `out` under the validity of `like` (UnaryCompoundFunctor carries the validity over, PixelMask.h:514-523).
+inline void gray_store(float v, float const&, float& dst) { dst = v; }
+inline void gray_store(float v, PixelGray<float> const&, PixelGray<float>& dst) { dst = PixelGray<float>(v); }
+template <class ChildT> void gray_store(float v, PixelMask<ChildT> const& like, PixelMask<ChildT>& dst) {
+  ChildT c;
+  gray_store(v, like.child(), c);
+  dst = PixelMask<ChildT>(c);
+  if (!is_valid(like)) dst.invalidate();
+}
+template <class ViewT>
+ImageView<typename ViewT::pixel_type> rescaled(ImageViewBase<ViewT> const& view, int mode, const double* params) {
+  typedef typename ViewT::pixel_type pixel_type;
+  ImageView<pixel_type> in = view.impl(), out(in.cols(), in.rows());
+  if (in.cols() == 0 || in.rows() == 0) return out;
+  GrayOperand g = gray_operand(in);
+  vwgpu_ctx* ctx = engine::thread_context();
+  engine::check(ctx, vwgpu_image_rescale(ctx, g.values.data(), g.cols(), g.rows(), 0, mode, params, VWGPU_PIXEL_F32, g.values.data(), 0));
+  for (int32 r = 0; r < in.rows(); ++r)
+    for (int32 c = 0; c < in.cols(); ++c) gray_store(g.values(c, r), in(c, r), out(c, r));
+  return out;
+}
+inline void moments_of(GrayOperand const& g, double* m) {
+  m[0] = m[1] = m[2] = 0;
+  if (g.cols() == 0 || g.rows() == 0) return;
+  vwgpu_ctx* ctx = engine::thread_context();
+  engine::check(ctx, vwgpu_image_moments(ctx, g.values.data(), g.cols(), g.rows(), 0, g.mask_ptr(), 0, 0, 0, m));
+}
+}  // namespace detail
+
+/// find_image_min_max(view, min_val, max_val) (Statistics.h:113-127).
+template <class ViewT>
+void find_image_min_max(ImageViewBase<ViewT> const& view, double& min_val, double& max_val) {
+  max_val = -std::numeric_limits<double>::max();
+  min_val = -max_val;
+  detail::GrayOperand g = detail::gray_operand(view);
+  if (g.cols() == 0 || g.rows() == 0) return;
+  vwgpu_ctx* ctx = engine::thread_context();
+  vwgpu_image_range r;
+  engine::check(ctx, vwgpu_image_min_max(ctx, g.values.data(), g.cols(), g.rows(), 0, g.mask_ptr(), 0, 0, 0, VWGPU_MIN_MAX_FIND, &r));
+  min_val = r.min; max_val = r.max;
+}
+/// min_max_channel_values(view, min, max) (Statistics.h:98-108): ArgumentErr without a valid sample.
+template <class ViewT>
+void min_max_channel_values(ImageViewBase<ViewT> const& view, float& min, float& max) {
+  detail::GrayOperand g = detail::gray_operand(view);
+  VW_ASSERT(g.cols() > 0 && g.rows() > 0, ArgumentErr() << "MinMaxAccumulator: no valid samples");
+  vwgpu_ctx* ctx = engine::thread_context();
+  vwgpu_image_range r;
+  engine::check(ctx, vwgpu_image_min_max(ctx, g.values.data(), g.cols(), g.rows(), 0, g.mask_ptr(), 0, 0, 0, VWGPU_MIN_MAX_ACCUM, &r));
+  min = (float)r.min; max = (float)r.max;
+}
+/// sum_of_channel_values (Statistics.h:129-137), mean_channel_value (:139-148), stddev_channel_value (:166-172).
+template <class ViewT> double sum_of_channel_values(ImageViewBase<ViewT> const& view) {
+  double m[3];
+  detail::moments_of(detail::gray_operand(view), m);
+  return m[1];
+}
+template <class ViewT> double mean_channel_value(ImageViewBase<ViewT> const& view) {
+  double m[3], r = 0;
+  detail::moments_of(detail::gray_operand(view), m);
+  VW_ASSERT(vwgpu_moments_mean(m, &r) == VWGPU_OK, ArgumentErr() << "MeanAccumulator: no valid samples");
+  return r;
+}
+template <class ViewT> double stddev_channel_value(ImageViewBase<ViewT> const& view) {
+  double m[3], r = 0;
+  detail::moments_of(detail::gray_operand(view), m);
+  VW_ASSERT(vwgpu_moments_stddev(m, &r) == VWGPU_OK, ArgumentErr() << "StdDevAccumulator(): no valid samples.");
+  return r;
+}
+/// median_channel_value (Statistics.h:179-186): an exact selection on the engine, nothing is sorted.
+template <class ViewT> double median_channel_value(ImageViewBase<ViewT> const& view) {
+  detail::GrayOperand g = detail::gray_operand(view);
+  VW_ASSERT(g.cols() > 0 && g.rows() > 0, ArgumentErr() << "median: no valid samples.");
+  vwgpu_ctx* ctx = engine::thread_context();
+  double r = 0;
+  engine::check(ctx, vwgpu_image_order_statistic(ctx, g.values.data(), g.cols(), g.rows(), 0, g.mask_ptr(), 0, VWGPU_ORDER_MEDIAN, 0.0, &r));
+  return r;
+}
+
+/// histogram(view, num_bins, min_val, max_val, hist) (ImageThresh.h:53-73).
+template <class ViewT>
+void histogram(ImageViewBase<ViewT> const& view, int num_bins, double min_val, double max_val, math::Histogram& hist) {
+  VW_ASSERT(num_bins > 0, ArgumentErr() << "histogram: number of input bins must be positive");
+  if (max_val == min_val) max_val = min_val + 1.0;
+  hist.initialize(num_bins, min_val, max_val);
+  detail::GrayOperand g = detail::gray_operand(view);
+  if (g.cols() == 0 || g.rows() == 0) return;
+  vwgpu_ctx* ctx = engine::thread_context();
+  std::vector<uint64_t> counts((size_t)num_bins + 2);
+  engine::check(ctx, vwgpu_image_histogram(ctx, g.values.data(), g.cols(), g.rows(), 0, g.mask_ptr(), 0, 0, 0, num_bins, min_val, max_val, 0,
+                                           counts.data(), nullptr));
+  hist.set_counts(counts.data());
+}
+
+/// otsu_threshold(view) (ImageThresh.h:80-145) and otsu_threshold(view, num_sample_rows, num_sample_cols, num_bins) (:151-239).
+template <class ViewT> double otsu_threshold(ImageViewBase<ViewT> const& view) {
+  detail::GrayOperand g = detail::gray_operand(view);
+  if (g.cols() == 0 || g.rows() == 0) return 0.0;
+  vwgpu_ctx* ctx = engine::thread_context();
+  double t = 0;
+  engine::check(ctx, vwgpu_otsu_threshold(ctx, g.values.data(), g.cols(), g.rows(), 0, g.mask_ptr(), 0, 0, 0, 256, 1, &t));
+  return t;
+}
+template <class ViewT> double otsu_threshold(ImageViewBase<ViewT> const& view, int num_sample_rows, int num_sample_cols, int num_bins) {
+  detail::GrayOperand g = detail::gray_operand(view);
+  if (g.cols() == 0 || g.rows() == 0) return 0.0;
+  vwgpu_ctx* ctx = engine::thread_context();
+  double t = 0;
+  engine::check(ctx, vwgpu_otsu_threshold(ctx, g.values.data(), g.cols(), g.rows(), 0, g.mask_ptr(), 0, num_sample_cols, num_sample_rows,
+                                          num_bins, 2, &t));
+  return t;
+}
+
+/// percentile_scale_convert(input_image, output_image, low_percentile, high_percentile, num_bins) (ImageThresh.h:243-270).
+template <class ViewT>
+void percentile_scale_convert(ImageViewBase<ViewT> const& input_image, ImageView<uint8>& output_image, double low_percentile = 0.02,
+                              double high_percentile = 0.98, int num_bins = 256) {
+  detail::GrayOperand g = detail::gray_operand(input_image);
+  output_image.set_size(g.cols(), g.rows());
+  if (g.cols() == 0 || g.rows() == 0) return;
+  vwgpu_ctx* ctx = engine::thread_context();
+  engine::check(ctx, vwgpu_percentile_scale_convert(ctx, g.values.data(), g.cols(), g.rows(), 0, g.mask_ptr(), 0, low_percentile,
+                                                    high_percentile, num_bins, VWGPU_PIXEL_U8, output_image.data(), 0, nullptr));
+}
+/// u8_convert(input_image, output_image) (ImageThresh.h:274-286).
+template <class ViewT>
+void u8_convert(ImageViewBase<ViewT> const& input_image, ImageView<PixelGray<uint8>>& output_image) {
+  static_assert(sizeof(PixelGray<uint8>) == 1, "PixelGray<uint8> is one byte");
+  detail::GrayOperand g = detail::gray_operand(input_image);
+  output_image.set_size(g.cols(), g.rows());
+  if (g.cols() == 0 || g.rows() == 0) return;
+  vwgpu_ctx* ctx = engine::thread_context();
+  engine::check(ctx, vwgpu_u8_convert(ctx, g.values.data(), g.cols(), g.rows(), 0, g.mask_ptr(), 0, VWGPU_PIXEL_U8,
+                                      reinterpret_cast<uint8*>(output_image.data()), 0, nullptr));
+}
+
+/// clamp(image, low, high) (Algorithms.h:50-61), threshold(image, thresh, low, high) (:210-), normalize(image, old_low, old_high,
+/// new_low, new_high) (:171-188), normalize(image, low, high) and normalize(image) (AutoNormalize.h:33-86); rasterised at once.
+template <class ViewT>
+ImageView<typename ViewT::pixel_type> clamp(ImageViewBase<ViewT> const& image, double low, double high) {
+  const double p[2] = {low, high};
+  return detail::rescaled(image, VWGPU_RESCALE_CLAMP, p);
+}
+template <class ViewT>
+ImageView<typename ViewT::pixel_type> threshold(ImageViewBase<ViewT> const& image, double thresh = 0.0, double low = 0.0, double high = 1.0) {
+  const double p[3] = {thresh, low, high};
+  return detail::rescaled(image, VWGPU_RESCALE_THRESHOLD, p);
+}
+template <class ViewT>
+ImageView<typename ViewT::pixel_type> normalize(ImageViewBase<ViewT> const& image, double old_low, double old_high, double new_low,
+                                                double new_high) {
+  const double p[4] = {old_low, old_high, new_low, new_high};
+  return detail::rescaled(image, VWGPU_RESCALE_NORMALIZE, p);
+}
+template <class ViewT>
+ImageView<typename ViewT::pixel_type> normalize(ImageViewBase<ViewT> const& image, double low, double high) {
+  float old_min, old_max;
+  min_max_channel_values(image, old_min, old_max);
+  return normalize(image, old_min, old_max, low, high);
+}
+template <class ViewT>
+ImageView<typename ViewT::pixel_type> normalize(ImageViewBase<ViewT> const& image) { return normalize(image, 0.0, 1.0); }
 
 }  // namespace vw
 #endif

@@ -1,11 +1,15 @@
 // vw/Math.h — Vector2i/Vector2f and the half-open integer box BBox2i with the semantics of
 // src/vw/Math/BBox.tcc:82-197,268-290; Matrix3x3 and HomographyTransform
-// (src/vw/Math/Transform.h:365-389).
+// (src/vw/Math/Transform.h:365-389); math::Histogram (src/vw/Math/Statistics.h, Statistics.cc:34-104), the container that
+// vw::histogram of vw/Image.h fills on the engine.
 #ifndef VWLITE_MATH_H
 #define VWLITE_MATH_H
 
 #include <algorithm>
+#include <cmath>
+#include <cstdint>
 #include <ostream>
+#include <vector>
 
 #include "Core.h"
 
@@ -122,6 +126,59 @@ public:
   Matrix3x3 const& matrix() const { return m_H; }
   Matrix3x3 const& inverse_matrix() const { return m_H_inverse; }
 };
+
+namespace math {
+/// math::Histogram (src/vw/Math/Statistics.cc:34-104) with integer counts.  vw::histogram (vw/Image.h) fills it on the engine;
+/// add_value is the host form of the same binning (saturate = true), a NaN bin argument is dropped.
+class Histogram {
+  int m_num_bins, m_max_bin;
+  uint64_t m_num_values;
+  double m_min_value, m_max_value, m_range, m_bin_width;
+  std::vector<uint64_t> m_bin_values;
+public:
+  Histogram() : m_num_bins(0), m_max_bin(0), m_num_values(0), m_min_value(0), m_max_value(0), m_range(0), m_bin_width(0) {}
+  Histogram(size_t num_bins, double min_value, double max_value) { initialize(num_bins, min_value, max_value); }
+  void initialize(size_t num_bins, double min_value, double max_value) {
+    if (num_bins == 0) vw_throw(ArgumentErr() << "Can't create a Histogram with zero bins!");
+    m_num_bins = (int)num_bins; m_max_bin = (int)num_bins - 1; m_num_values = 0;
+    m_min_value = min_value; m_max_value = max_value;
+    m_range = max_value - min_value;
+    m_bin_width = m_range / num_bins;
+    m_bin_values.assign(num_bins, 0);
+  }
+  void add_value(double value) {
+    const double r = std::round(m_max_bin * ((value - m_min_value) / m_range));
+    if (r != r) return;
+    m_bin_values[r < 0 ? 0 : r >= m_num_bins ? m_max_bin : (int)r] += 1;
+    ++m_num_values;
+  }
+  void operator()(double value) { add_value(value); }
+  /// The counts as the engine returns them: num_bins bins, then the total.
+  void set_counts(const uint64_t* counts) {
+    m_bin_values.assign(counts, counts + m_num_bins);
+    m_num_values = counts[m_num_bins];
+  }
+  int get_num_bins() const { return m_num_bins; }
+  uint64_t get_total_num_values() const { return m_num_values; }
+  double get_bin_value(int i) const { return (double)m_bin_values[i]; }
+  double get_bin_width() const { return m_bin_width; }
+  double get_bin_center(int i) const { return m_min_value + i * m_bin_width + m_bin_width / 2.0; }
+  double get_min_value() const { return m_min_value; }
+  double get_max_value() const { return m_max_value; }
+  const uint64_t* counts() const { return m_bin_values.data(); }
+  size_t get_percentile(double percentile) const {
+    if ((percentile < 0) || (percentile > 1.0)) vw_throw(ArgumentErr() << "get_histogram_percentile: illegal percentile request: " << percentile << "\n");
+    const double sum = static_cast<double>(m_num_values);
+    double running_percentile = 0;
+    for (int i = 0; i < m_num_bins; ++i) {
+      running_percentile += get_bin_value(i) / sum;
+      if (running_percentile >= percentile) return i;
+    }
+    vw_throw(LogicErr() << "get_histogram_percentile: Illegal histogram encountered!");
+    return 0;
+  }
+};
+}  // namespace math
 
 }  // namespace vw
 #endif
